@@ -195,7 +195,7 @@ def _bench(args):
 def test_bench_two_ranks_over_gloo_on_one_gpu():
     """`python bench.py --gpus 2` starts two ranks by itself, defaults to the sharded sweep (C4 shape, small here) and gets
     the single-process sweep's global log-likelihood"""
-    common = ["--particles", "4000", "--T", "25", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    common = ["--particles", "4000", "--T", "25", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"]
     two = _bench(["--gpus", "2", "--dist-backend", "gloo", "--filters-per-gpu", "3"] + common)
     one = _bench(["--gpus", "1", "--workload", "bank", "--filters-per-gpu", "6"] + common)
     assert two["n_gpus"] == 2 and two["ranks_seen"] == [0, 1] and one["n_gpus"] == 1

@@ -14,12 +14,15 @@ from llpf_amd import _capi, _structs as S
 
 
 def test_snippets_compile_for_gfx950_without_a_device():
+    # ids are handed out per process in the order of first compilation, and a suite run in one process may have compiled these
+    # snippets before: with a comment of this test's own they are new sources, and their ids the next two
+    quadtank, pendulum = (src + "\n// test_snippets_compile_for_gfx950_without_a_device\n" for src in (UM.QUADTANK_SRC, UM.PENDULUM_SRC))
     os.environ["LLPF_JIT_COMPILE_ONLY"] = "1"
     try:
-        a = _capi.model_compile(UM.QUADTANK_SRC, 4, 2)
-        b = _capi.model_compile(UM.PENDULUM_SRC, 2, 1)
+        a = _capi.model_compile(quadtank, 4, 2)
+        b = _capi.model_compile(pendulum, 2, 1)
         assert a >= 1000 and b == a + 1
-        assert _capi.model_compile(UM.QUADTANK_SRC, 4, 2) == a                 # the same (source, nx, ny) again: the same id, no recompilation
+        assert _capi.model_compile(quadtank, 4, 2) == a                        # the same (source, nx, ny) again: the same id, no recompilation
         ids = [_capi.model_compile(src, 2, 1) for src in (UM.LAPLACE_SRC, UM.STUDENT_T_SRC, UM.LAPLACE_NO_BOUND_SRC)]   # likelihood hooks
         assert len(set(ids)) == 3 and "loglik_bound" not in UM.LAPLACE_NO_BOUND_SRC
         # what a snippet defines is reported without running anything (the template argument of a tag kernel's lowered name)

@@ -9,6 +9,6 @@ for lib in "$@"; do
   echo "   bank thr 1.0: $(python tools/bench_bank.py --thr 1.0 | grep -E -o '"us_per_timestep": [0-9.]+' | head -1)"
   echo "   bank thr 0.1: $(python tools/bench_bank.py | grep -E -o '"us_per_timestep": [0-9.]+' | head -1)"
   for thr in 0.1 1.0; do
-  echo "   single 1.6e7 thr $thr: $(python bench.py --particles 16000000 --T 100 --threshold $thr --no-cpu-baseline --no-other-configs --steps 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['roofline']['whole_timestep']['us'],1), d['config'].get('resamples_per_pass'))")"
+  echo "   single 1.6e7 thr $thr: $(python bench.py --full --particles 16000000 --T 100 --threshold $thr --no-cpu-baseline --no-other-configs --steps 2 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['roofline']['whole_timestep']['us'],1), d['config'].get('resamples_per_pass'))")"
   done
 done; done

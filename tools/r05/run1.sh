@@ -2,7 +2,7 @@
 # round 5, GPU lease 1: suite on the new build, driver-style bench, k_norm one-wave-per-tile A/B, exp scaling through v_ldexp_f64 A/B
 O=gpurun_out/r05a; mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/gputests.log 2>&1; echo "gpu tests rc=$?" >> $O/gputests.log
-( time python bench.py --steps 20 --warmup 5 ) > $O/bench_default.json 2> $O/bench_default.err
+( time python bench.py --full --steps 20 --warmup 5 ) > $O/bench_default.json 2> $O/bench_default.err
 for rep in 1 2; do for v in 0 1; do
   echo "norm_wave_tile=$v rep$rep $(LLPF_NORM_WAVE_TILE=$v python tools/bench_bank.py 2>/dev/null | tail -1)" >> $O/norm_ab.txt
 done; done

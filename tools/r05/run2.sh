@@ -5,7 +5,7 @@ timeout 600 python -m pytest tests/test_gpu_rbfull.py -x -q > $O/rbfull_tests.lo
 if grep -q "rc=0" $O/rbfull_tests.log; then
 for rep in 1 2; do for v in 0 auto; do
   if [ $v = 0 ]; then export LLPF_RBF_TAIL=0; else unset LLPF_RBF_TAIL; fi
-  echo "tail=$v rep$rep $(timeout 300 python bench.py --workload rbpf_full --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+  echo "tail=$v rep$rep $(timeout 300 python bench.py --full --workload rbpf_full --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.4e us/timestep %.2f k_rbfull %.2f' % (d['value'], d['roofline']['whole_timestep']['us'], d['roofline']['avg_launch_us']))")" >> $O/c5_tail_ab.txt
 done; done
 unset LLPF_RBF_TAIL

@@ -4,7 +4,7 @@ O=gpurun_out/r05d; mkdir -p $O
 run() { # lib particles tail
   if [ "$3" = "-" ] || [ "$3" = "auto" ]; then unset LLPF_RBF_TAIL; else export LLPF_RBF_TAIL=$3; fi
   if [ "$1" = "old" ]; then export LLPF_LIB=$PWD/lib_oldrbf.so; else unset LLPF_LIB; fi
-  timeout 300 python bench.py --workload rbpf_full --particles $2 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --workload rbpf_full --particles $2 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.4e us/timestep %.2f k_rbfull %.2f' % (d['value'], d['roofline']['whole_timestep']['us'], d['roofline']['avg_launch_us']))"
 }
 for rep in 1 2; do

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # name lib [env]
   name=$1; lib=$2; shift 2
   for rep in 1 2; do
-    env LLPF_LIB=$lib "$@" timeout 300 python $R/bench.py --workload bank --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+    env LLPF_LIB=$lib "$@" timeout 300 python $R/bench.py --full --workload bank --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$name rep$rep %.4e part-steps/s  %.2f us/timestep' % (d['value'], d['roofline']['whole_timestep']['us']))" >> $R/$O/bank_ab.txt
   done
   env LLPF_LIB=$lib "$@" timeout 300 rocprofv3 --kernel-trace -d $R/$O/kt_$name -o kt -- python $R/bench.py --workload bank --steps 2 --warmup 1 --no-cpu-baseline > $R/$O/kt_$name.log 2>&1
