@@ -28,17 +28,27 @@ static int fail(int code, const std::string& msg) noexcept {
     try { g_err = msg; } catch (...) { g_err.clear(); }
     return code;
 }
+static int fail(int code, const char* msg) noexcept {
+    try { g_err = msg; } catch (...) { g_err.clear(); }
+    return code;
+}
 
 // The barrier include/llpf.h promises ("no C++ exception crosses the ABI"; SURVEY §8(b) Errors row; the reference turns a throw
 // inside the likelihood into -Inf, src/smoothing.jl:275-279, never into a dead session).  Every export is a function-try-block
 //     int llpf_name(...) LLPF_TRY { ... } LLPF_GUARD (llpf_name)
 // whose handler maps what the host code can throw (std::vector / std::string / std::thread / the hiprtc cache) to a status.
+// Building the message can itself run out of memory: then the status stands with a static message.
 static int guard_catch(const char* fn) noexcept {
-    try { throw; }
-    catch (const std::bad_alloc&) { return fail(LLPF_ERR_ALLOC, std::string(fn) + ": out of host memory"); }
-    catch (const std::length_error& e) { return fail(LLPF_ERR_ALLOC, std::string(fn) + ": a size beyond what can be allocated (" + e.what() + ")"); }
-    catch (const std::exception& e) { return fail(LLPF_ERR_INTERNAL, std::string(fn) + ": " + e.what()); }
-    catch (...) { return fail(LLPF_ERR_INTERNAL, std::string(fn) + ": unknown exception"); }
+    int code = LLPF_ERR_INTERNAL;
+    try {
+        try { throw; }
+        catch (const std::bad_alloc&) { code = LLPF_ERR_ALLOC; return fail(code, std::string(fn) + ": out of host memory"); }
+        catch (const std::length_error& e) { code = LLPF_ERR_ALLOC; return fail(code, std::string(fn) + ": a size beyond what can be allocated (" + e.what() + ")"); }
+        catch (const std::exception& e) { return fail(code, std::string(fn) + ": " + e.what()); }
+        catch (...) { return fail(code, std::string(fn) + ": unknown exception"); }
+    } catch (...) {
+        return fail(code, code == LLPF_ERR_ALLOC ? "out of host memory" : "internal error");
+    }
 }
 #define LLPF_TRY try
 #define LLPF_GUARD(name) catch (...) { return guard_catch(#name); }
@@ -104,19 +114,13 @@ int llpf_device_count(int32_t* n) LLPF_TRY {
 int llpf_create(const llpf_config* cfg, llpf_filter** out) LLPF_TRY {
     if (!out) return fail(LLPF_ERR_ARG, "null out pointer");
     *out = nullptr;
-    llpf_filter* f = new (std::nothrow) llpf_filter();
+    std::unique_ptr<llpf_filter> f(new (std::nothrow) llpf_filter());
     if (!f) return fail(LLPF_ERR_ALLOC, "out of host memory");
-    int rc = bank_create(cfg, nullptr, 1, f->bank);
-    if (rc != LLPF_OK) { free_bank(f->bank); delete f; return rc; }
-    *out = f;
+    CHK(bank_create(cfg, nullptr, 1, f->bank));
+    *out = f.release();
     return LLPF_OK;
 } LLPF_GUARD(llpf_create)
-int llpf_destroy(llpf_filter* f) LLPF_TRY {
-    if (!f) return LLPF_OK;
-    free_bank(f->bank);
-    delete f;
-    return LLPF_OK;
-} LLPF_GUARD(llpf_destroy)
+int llpf_destroy(llpf_filter* f) LLPF_TRY { delete f; return LLPF_OK; } LLPF_GUARD(llpf_destroy)
 #define NEEDF(f) if (!(f)) return fail(LLPF_ERR_ARG, "null handle")
 
 int llpf_reset(llpf_filter* f) LLPF_TRY { NEEDF(f); CHK(use_device(f->bank)); return bank_init_particles(f->bank, true); } LLPF_GUARD(llpf_reset)
@@ -342,7 +346,7 @@ int llpf_weighted_quantile(llpf_filter* f, const double* q, int32_t nq, double* 
     CHK(ensure_wq(b, q, nq));
     HIPC(hipStreamSynchronize(b.stream));                                     // q is the caller's (pageable) memory
     HIPC(launch_materialize(d, nullptr, b.d_wq_we, b.stream));               // we = expweights(pf), [N]
-    CHK(ensure(&b.d_xquant, &b.cap_xq, (size_t)nq * b.nx));
+    CHK(b.d_xquant.ensure((size_t)nq * b.nx));
     HIPC(launch_wquantile(d.xcur, b.Ns, b.nx, b.d_wq_we, b.N, b.d_wq_p, nq, b.d_xquant, b.nx, 1, b.d_wq, b.stream));      // [nq][nx]
     HIPC(hipMemcpyAsync(out, b.d_xquant, sizeof(double) * (size_t)nq * b.nx, hipMemcpyDeviceToHost, b.stream));
     HIPC(hipStreamSynchronize(b.stream));
@@ -398,19 +402,13 @@ int llpf_bank_create(const llpf_config* base, const llpf_model* models, int32_t 
     if (!out) return fail(LLPF_ERR_ARG, "null out pointer");
     *out = nullptr;
     // models == NULL: every filter uses base->model (Monte-Carlo replicas; seeds differ: seed + k)
-    llpf_bank* b = new (std::nothrow) llpf_bank();
+    std::unique_ptr<llpf_bank> b(new (std::nothrow) llpf_bank());
     if (!b) return fail(LLPF_ERR_ALLOC, "out of host memory");
-    int rc = bank_create(base, models, n_filters, b->bank);
-    if (rc != LLPF_OK) { free_bank(b->bank); delete b; return rc; }
-    *out = b;
+    CHK(bank_create(base, models, n_filters, b->bank));
+    *out = b.release();
     return LLPF_OK;
 } LLPF_GUARD(llpf_bank_create)
-int llpf_bank_destroy(llpf_bank* b) LLPF_TRY {
-    if (!b) return LLPF_OK;
-    free_bank(b->bank);
-    delete b;
-    return LLPF_OK;
-} LLPF_GUARD(llpf_bank_destroy)
+int llpf_bank_destroy(llpf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_bank_destroy)
 int llpf_bank_reset(llpf_bank* b) LLPF_TRY { NEEDF(b); CHK(use_device(b->bank)); return bank_init_particles(b->bank, true); } LLPF_GUARD(llpf_bank_reset)
 int llpf_bank_seed(llpf_bank* b, uint64_t seed) LLPF_TRY { NEEDF(b); return bank_seed(b->bank, seed); } LLPF_GUARD(llpf_bank_seed)
 int llpf_bank_set_models(llpf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return bank_set_models(b->bank, models); } LLPF_GUARD(llpf_bank_set_models)
@@ -447,26 +445,21 @@ int llpf_mbank_create(const llpf_config* base, const llpf_model* models, int32_t
         if (devices[i] < 0 || devices[i] >= ndev) return fail(LLPF_ERR_ARG, "device ordinal out of range");
         for (int j = 0; j < i; ++j) if (devices[j] == devices[i]) distinct = false;
     }
-    llpf_mbank* m = new (std::nothrow) llpf_mbank();
+    std::unique_ptr<llpf_mbank> m(new (std::nothrow) llpf_mbank());
     if (!m) return fail(LLPF_ERR_ALLOC, "out of host memory");
-    int rc = mbank_build(m, base, models, n_filters, devices, n_devices, 0, n_devices);
-    if (rc == LLPF_OK) {
-        m->collective = mbank_env_collective(distinct, n_devices);
-        if (m->collective == MBANK_COLL_RCCL) {
-            rccl_dl::Api* R = rccl_dl::api();
-            if (!R->handle) rc = fail(LLPF_ERR_HIP, R->err);
-            else {
-                std::vector<rccl_dl::comm_t> comms((size_t)n_devices, nullptr);
-                std::vector<int> devs(devices, devices + n_devices);
-                (void)hipGetLastError();      // RCCL reads the runtime's sticky last-error after its own launches: start clean
-                rccl_dl::result_t r = R->CommInitAll(comms.data(), n_devices, devs.data());
-                if (r != rccl_dl::Success) rc = fail(LLPF_ERR_HIP, std::string("ncclCommInitAll: ") + R->GetErrorString(r));
-                else for (int i = 0; i < n_devices; ++i) m->shards[i]->comm = comms[i];
-            }
-        }
+    CHK(mbank_build(m.get(), base, models, n_filters, devices, n_devices, 0, n_devices));
+    m->collective = mbank_env_collective(distinct, n_devices);
+    if (m->collective == MBANK_COLL_RCCL) {
+        rccl_dl::Api* R = rccl_dl::api();
+        if (!R->handle) return fail(LLPF_ERR_HIP, R->err);
+        std::vector<rccl_dl::comm_t> comms((size_t)n_devices, nullptr);
+        std::vector<int> devs(devices, devices + n_devices);
+        (void)hipGetLastError();      // RCCL reads the runtime's sticky last-error after its own launches: start clean
+        rccl_dl::result_t r = R->CommInitAll(comms.data(), n_devices, devs.data());
+        if (r != rccl_dl::Success) return fail(LLPF_ERR_HIP, std::string("ncclCommInitAll: ") + R->GetErrorString(r));
+        for (int i = 0; i < n_devices; ++i) m->shards[i]->comm = comms[i];
     }
-    if (rc != LLPF_OK) { const std::string keep = g_err; mbank_free(m); g_err = keep; return rc; }
-    *out = m;
+    *out = m.release();
     return LLPF_OK;
 } LLPF_GUARD(llpf_mbank_create)
 int llpf_mbank_unique_id(uint8_t* id) LLPF_TRY {
@@ -495,33 +488,26 @@ int llpf_mbank_create_rank(const llpf_config* base, const llpf_model* models, in
     if (world < 1 || rank < 0 || rank >= world) return fail(LLPF_ERR_ARG, "rank / world out of range");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(LLPF_ERR_NO_DEVICE, "no HIP device visible; this engine has no CPU fallback");
-    llpf_mbank* m = new (std::nothrow) llpf_mbank();
+    std::unique_ptr<llpf_mbank> m(new (std::nothrow) llpf_mbank());
     if (!m) return fail(LLPF_ERR_ALLOC, "out of host memory");
     const int32_t dev = base->device;
-    int rc = mbank_build(m, base, models, n_filters, &dev, 1, rank, world);
-    if (rc == LLPF_OK) {
-        m->collective = id ? MBANK_COLL_RCCL : (world > 1 ? MBANK_COLL_EXTERNAL : mbank_env_collective(true, 1));
-        if (m->collective == MBANK_COLL_RCCL) {
-            rccl_dl::Api* R = rccl_dl::api();
-            if (!R->handle) rc = fail(LLPF_ERR_HIP, R->err);
-            else {
-                rccl_dl::unique_id u;
-                if (id) memcpy(u.internal, id, LLPF_MBANK_ID_BYTES);
-                else { rccl_dl::result_t r0 = R->GetUniqueId(&u); if (r0 != rccl_dl::Success) rc = fail(LLPF_ERR_HIP, std::string("ncclGetUniqueId: ") + R->GetErrorString(r0)); }
-                if (rc == LLPF_OK) {
-                    hipSetDevice(dev);
-                    (void)hipGetLastError();
-                    rccl_dl::result_t r = R->CommInitRank(&m->shards[0]->comm, world, u, rank);
-                    if (r != rccl_dl::Success) rc = fail(LLPF_ERR_HIP, std::string("ncclCommInitRank: ") + R->GetErrorString(r));
-                }
-            }
-        }
+    CHK(mbank_build(m.get(), base, models, n_filters, &dev, 1, rank, world));
+    m->collective = id ? MBANK_COLL_RCCL : (world > 1 ? MBANK_COLL_EXTERNAL : mbank_env_collective(true, 1));
+    if (m->collective == MBANK_COLL_RCCL) {
+        rccl_dl::Api* R = rccl_dl::api();
+        if (!R->handle) return fail(LLPF_ERR_HIP, R->err);
+        rccl_dl::unique_id u;
+        if (id) memcpy(u.internal, id, LLPF_MBANK_ID_BYTES);
+        else { rccl_dl::result_t r0 = R->GetUniqueId(&u); if (r0 != rccl_dl::Success) return fail(LLPF_ERR_HIP, std::string("ncclGetUniqueId: ") + R->GetErrorString(r0)); }
+        hipSetDevice(dev);
+        (void)hipGetLastError();
+        rccl_dl::result_t r = R->CommInitRank(&m->shards[0]->comm, world, u, rank);
+        if (r != rccl_dl::Success) return fail(LLPF_ERR_HIP, std::string("ncclCommInitRank: ") + R->GetErrorString(r));
     }
-    if (rc != LLPF_OK) { const std::string keep = g_err; mbank_free(m); g_err = keep; return rc; }
-    *out = m;
+    *out = m.release();
     return LLPF_OK;
 } LLPF_GUARD(llpf_mbank_create_rank)
-int llpf_mbank_destroy(llpf_mbank* m) LLPF_TRY { mbank_free(m); return LLPF_OK; } LLPF_GUARD(llpf_mbank_destroy)
+int llpf_mbank_destroy(llpf_mbank* m) LLPF_TRY { delete m; return LLPF_OK; } LLPF_GUARD(llpf_mbank_destroy)
 int llpf_mbank_reset(llpf_mbank* m) LLPF_TRY {
     NEEDF(m);
     return mbank_foreach(*m, [&](int s) -> int { Bank& b = m->shards[s]->bank; CHK(use_device(b)); return bank_init_particles(b, true); });
@@ -603,8 +589,8 @@ static int scratch_bank(int32_t device, int64_t n, int strategy, std::unique_ptr
     m.dynamics_density = g; m.measurement_density = g; m.initial_density = g;
     out.reset(new (std::nothrow) llpf_filter());
     if (!out) return fail(LLPF_ERR_ALLOC, "out of host memory");
-    int rc = bank_create(&c, nullptr, 1, out->bank);
-    if (rc != LLPF_OK) { free_bank(out->bank); out.reset(); }
+    const int rc = bank_create(&c, nullptr, 1, out->bank);
+    if (rc != LLPF_OK) out.reset();
     return rc;
 }
 
@@ -625,7 +611,6 @@ int llpf_logsumexp(int32_t device, double* w, double* we, int64_t n, double* ll)
         if (rc == LLPF_OK) rc = bank_get_w(b, w, false);
         if (rc == LLPF_OK && we) rc = bank_get_w(b, we, true);
     }
-    free_bank(b);
     return rc;
 } LLPF_GUARD(llpf_logsumexp)
 
@@ -635,39 +620,31 @@ int llpf_resample(int32_t device, int32_t strategy, const double* we, int64_t n,
     std::unique_ptr<llpf_filter> h;
     CHK(scratch_bank(device, n, strategy, h));
     Bank& b = h->bank;
-    int rc = LLPF_OK;
-    int32_t* d_j = nullptr;
-    double* d_U = nullptr;
-    auto body = [&]() -> int {
-        std::vector<double> stage((size_t)b.Ns, 0.0);
-        memcpy(stage.data(), we, sizeof(double) * n);
-        HIPC(hipMemcpyAsync(b.d_w, stage.data(), sizeof(double) * b.Ns, hipMemcpyHostToDevice, b.stream));
-        const int64_t cap = (m > b.Ns ? m : b.Ns);
-        std::vector<int32_t> j32((size_t)cap, 0);
-        for (int64_t i = 0; i < m; ++i) j32[i] = (int32_t)j[i];
-        HIPC(hipMalloc(&d_j, sizeof(int32_t) * cap));
-        HIPC(hipMemcpyAsync(d_j, j32.data(), sizeof(int32_t) * cap, hipMemcpyHostToDevice, b.stream));
-        const int64_t nU = (strategy == LLPF_RESAMPLE_SYSTEMATIC) ? 1 : m;
-        HIPC(hipMalloc(&d_U, sizeof(double) * nU));
-        HIPC(hipMemcpyAsync(d_U, U, sizeof(double) * nU, hipMemcpyHostToDevice, b.stream));
-        std::vector<FilterScal> s;
-        CHK(scal_download(b, s));
-        s[0].uniform = 0; s[0].anc_ident_s[0] = s[0].anc_ident_s[1] = 0; s[0].status = 0; s[0].do_resample = 1;
-        CHK(scal_upload(b, s));
-        // ancestors are written relative to a row of stride Ns; the scratch bank has one filter, so row 0
-        ResArgs ra{};
-        ra.mode = RES_RESAMPLE; ra.M = (int32_t)m; ra.Uexp = d_U; ra.anc_out = d_j; ra.force = 1; ra.src_values = 1;
-        HIPC(launch_resample(b.dev(), ra, b.stream));
-        HIPC(hipMemcpyAsync(j32.data(), d_j, sizeof(int32_t) * m, hipMemcpyDeviceToHost, b.stream));
-        HIPC(hipStreamSynchronize(b.stream));
-        for (int64_t i = 0; i < m; ++i) j[i] = j32[i];
-        return LLPF_OK;
-    };
-    rc = body();
-    if (d_j) hipFree(d_j);
-    if (d_U) hipFree(d_U);
-    free_bank(b);
-    return rc;
+    std::vector<double> stage((size_t)b.Ns, 0.0);
+    memcpy(stage.data(), we, sizeof(double) * n);
+    HIPC(hipMemcpyAsync(b.d_w, stage.data(), sizeof(double) * b.Ns, hipMemcpyHostToDevice, b.stream));
+    const int64_t cap = (m > b.Ns ? m : b.Ns);
+    std::vector<int32_t> j32((size_t)cap, 0);
+    for (int64_t i = 0; i < m; ++i) j32[i] = (int32_t)j[i];
+    DevBuf<int32_t> d_j;
+    CHK(d_j.ensure((size_t)cap));
+    HIPC(hipMemcpyAsync(d_j, j32.data(), sizeof(int32_t) * cap, hipMemcpyHostToDevice, b.stream));
+    const int64_t nU = (strategy == LLPF_RESAMPLE_SYSTEMATIC) ? 1 : m;
+    DevBuf<double> d_U;
+    CHK(d_U.ensure((size_t)nU));
+    HIPC(hipMemcpyAsync(d_U, U, sizeof(double) * nU, hipMemcpyHostToDevice, b.stream));
+    std::vector<FilterScal> s;
+    CHK(scal_download(b, s));
+    s[0].uniform = 0; s[0].anc_ident_s[0] = s[0].anc_ident_s[1] = 0; s[0].status = 0; s[0].do_resample = 1;
+    CHK(scal_upload(b, s));
+    // ancestors are written relative to a row of stride Ns; the scratch bank has one filter, so row 0
+    ResArgs ra{};
+    ra.mode = RES_RESAMPLE; ra.M = (int32_t)m; ra.Uexp = d_U; ra.anc_out = d_j; ra.force = 1; ra.src_values = 1;
+    HIPC(launch_resample(b.dev(), ra, b.stream));
+    HIPC(hipMemcpyAsync(j32.data(), d_j, sizeof(int32_t) * m, hipMemcpyDeviceToHost, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    for (int64_t i = 0; i < m; ++i) j[i] = j32[i];
+    return LLPF_OK;
 } LLPF_GUARD(llpf_resample)
 
 int llpf_resample_uniforms(int32_t strategy, int64_t m, uint64_t seed, uint32_t step, double* u) LLPF_TRY {
@@ -684,20 +661,14 @@ int llpf_selftest_math(int32_t device, int32_t which, const double* in, double* 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(LLPF_ERR_NO_DEVICE, "no HIP device visible");
     if (!in || !out || n < 1) return fail(LLPF_ERR_ARG, "bad arguments");
     HIPC(hipSetDevice(device));
-    double *di = nullptr, *dout = nullptr;
-    auto body = [&]() -> int {
-        HIPC(hipMalloc(&di, sizeof(double) * n));
-        HIPC(hipMalloc(&dout, sizeof(double) * n));
-        HIPC(hipMemcpy(di, in, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPC(launch_selftest_math(which, di, dout, n, nullptr));
-        HIPC(hipDeviceSynchronize());
-        HIPC(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
-        return LLPF_OK;
-    };
-    const int rc = body();
-    hipFree(di);
-    hipFree(dout);
-    return rc;
+    DevBuf<double> di, dout;
+    CHK(di.ensure((size_t)n));
+    CHK(dout.ensure((size_t)n));
+    HIPC(hipMemcpy(di, in, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPC(launch_selftest_math(which, di, dout, n, nullptr));
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return LLPF_OK;
 } LLPF_GUARD(llpf_selftest_math)
 int llpf_selftest_normals(int32_t device, uint64_t seed, uint32_t step, uint32_t stream, int32_t nd, double* out, int64_t n) LLPF_TRY {
     int ndev = 0;
@@ -705,17 +676,12 @@ int llpf_selftest_normals(int32_t device, uint64_t seed, uint32_t step, uint32_t
     if (nd < 1 || nd > MAXD) return fail(LLPF_ERR_ARG, "nd out of range");
     if (!out || n < 1) return fail(LLPF_ERR_ARG, "bad arguments");
     HIPC(hipSetDevice(device));
-    double* dout = nullptr;
-    auto body = [&]() -> int {
-        HIPC(hipMalloc(&dout, sizeof(double) * n * nd));
-        HIPC(launch_selftest_normals((uint32_t)seed, (uint32_t)(seed >> 32), step, stream, nd, dout, n, nullptr));
-        HIPC(hipDeviceSynchronize());
-        HIPC(hipMemcpy(out, dout, sizeof(double) * n * nd, hipMemcpyDeviceToHost));
-        return LLPF_OK;
-    };
-    const int rc = body();
-    hipFree(dout);
-    return rc;
+    DevBuf<double> dout;
+    CHK(dout.ensure((size_t)n * nd));
+    HIPC(launch_selftest_normals((uint32_t)seed, (uint32_t)(seed >> 32), step, stream, nd, dout, n, nullptr));
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(out, dout, sizeof(double) * n * nd, hipMemcpyDeviceToHost));
+    return LLPF_OK;
 } LLPF_GUARD(llpf_selftest_normals)
 
 }  // extern "C"

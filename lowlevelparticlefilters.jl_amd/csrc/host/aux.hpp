@@ -49,12 +49,7 @@ static int aux_launch_resprop(Bank& b, bool has_y1, double t, bool fast, int onl
     HIPC(launch_resprop(d, ra, st, 1, b.stream));
     return LLPF_OK;
 }
-static int aux_ensure_lam(Bank& b) {
-    if (b.d_lam) return LLPF_OK;
-    HIPC(hipMalloc(&b.d_lam, sizeof(double) * (size_t)b.F * b.Ns));
-    HIPC(hipMemsetAsync(b.d_lam, 0, sizeof(double) * (size_t)b.F * b.Ns, b.stream));
-    return LLPF_OK;
-}
+static int aux_ensure_lam(Bank& b) { return b.d_lam.ensure_zeroed((size_t)b.F * b.Ns, b.stream); }
 
 // Single-call correct!: synchronous.  Weights that do not come from an aux predict! (uniform after reset!, already
 // normalised, installed) are normalised in the exact-max form.
@@ -229,12 +224,12 @@ static int bank_aux_run(Bank& b, const double* U, const double* Y, int64_t T, in
     // refused HERE, before any state of the handle moves (the back-to-back epochs below never pass through aux_predict_dev's own check)
     if (is_rb(b) || is_rbfull(b)) return fail(LLPF_ERR_ARG, "the auxiliary filter is not defined for the Rao-Blackwellized model");
     if (b.nx > 8) return fail(LLPF_ERR_ARG, "the auxiliary filter is compiled for up to 8 states (this filter has " + std::to_string(b.nx) + ")");
-    CHK(ensure(&b.d_U, &b.capU, (size_t)T * (b.nu > 0 ? b.nu : 1)));
-    CHK(ensure(&b.d_Y, &b.capY, (size_t)T * b.ny));
+    CHK(b.d_U.ensure((size_t)T * (b.nu > 0 ? b.nu : 1)));
+    CHK(b.d_Y.ensure((size_t)T * b.ny));
     if (b.nu > 0) HIPC(hipMemcpyAsync(b.d_U, U, sizeof(double) * T * b.nu, hipMemcpyHostToDevice, b.stream));
     HIPC(hipMemcpyAsync(b.d_Y, Y, sizeof(double) * T * b.ny, hipMemcpyHostToDevice, b.stream));
-    CHK(ensure(&b.d_ll_steps, &b.cap_ll, (size_t)T * b.F));
-    if (xmean) CHK(ensure(&b.d_xmean, &b.cap_xm, (size_t)T * b.F * b.nx));
+    CHK(b.d_ll_steps.ensure((size_t)T * b.F));
+    if (xmean) CHK(b.d_xmean.ensure((size_t)T * b.F * b.nx));
     const bool residual = b.cfg.resampling_strategy == LLPF_RESAMPLE_RESIDUAL;     // balanced form, driven step by step (aux_predict_dev)
     CHK(aux_ensure_lam(b));
     const double Ts = b.cfg.model.Ts;

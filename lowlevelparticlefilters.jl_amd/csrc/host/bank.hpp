@@ -1,63 +1,140 @@
 // host/bank.hpp — the Bank (F filters on one device / stream), creation, initialisation, profiling helpers.  Part of capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
+// owning handles: a device buffer, the executable of a captured graph, a scope guard
+// ------------------------------------------------------------------------------------------------
+// A device allocation of `cap` elements, freed by its destructor.  ensure(n) grows it: while the capacity suffices nothing happens
+// (no free, allocation, memset or synchronisation), otherwise the old allocation is freed and n elements (at least one) are
+// allocated, the contents not kept.  Failures are statuses, through HIPC.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() {
+        if (p) hipFree(p);
+        p = nullptr; cap = 0;
+    }
+    int ensure(size_t n) {
+        if (p && cap >= n) return LLPF_OK;
+        reset();
+        HIPC(hipMalloc(&p, sizeof(T) * (n ? n : 1)));
+        cap = n;
+        return LLPF_OK;
+    }
+    // ... zero-filled on stream s when it is allocated
+    int ensure_zeroed(size_t n, hipStream_t s) {
+        if (p && cap >= n) return LLPF_OK;
+        CHK(ensure(n));
+        HIPC(hipMemsetAsync(p, 0, sizeof(T) * (n ? n : 1), s));
+        return LLPF_OK;
+    }
+    // ... and the form that does not fail: false (the runtime's last error cleared) when the allocation cannot be had
+    bool try_ensure(size_t n) {
+        if (p && cap >= n) return true;
+        reset();
+        if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+        cap = n;
+        return true;
+    }
+};
+// the executable of a captured graph, destroyed with its owner
+struct GraphExec {
+    hipGraphExec_t h = nullptr;
+    GraphExec() = default;
+    explicit GraphExec(hipGraphExec_t e) : h(e) {}
+    GraphExec(GraphExec&& o) noexcept { std::swap(h, o.h); }
+    GraphExec& operator=(GraphExec&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~GraphExec() { if (h) hipGraphExecDestroy(h); }
+};
+// runs fn when the scope is left, by whichever path: auto g = on_scope_exit([&] { ... });
+template <class Fn>
+struct ScopeExit {
+    Fn fn;
+    explicit ScopeExit(Fn f) : fn(f) {}
+    ScopeExit(const ScopeExit&) = delete;
+    ScopeExit& operator=(const ScopeExit&) = delete;
+    ~ScopeExit() { fn(); }
+};
+template <class Fn>
+static ScopeExit<Fn> on_scope_exit(Fn fn) { return ScopeExit<Fn>(fn); }
+
+// ------------------------------------------------------------------------------------------------
 // Bank: F independent filters of N particles on one device / one stream
 // ------------------------------------------------------------------------------------------------
-struct Bank {
+// The stream and the events recorded on it.  A base of Bank, so that they are destroyed after Bank's buffers.
+struct BankStream {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    struct Ev { hipEvent_t a, b; int cls; };
+    std::vector<Ev> pending;
+    std::vector<hipEvent_t> ev_pool;
+    hipEvent_t ev_run0 = nullptr, ev_run1 = nullptr;
+    BankStream() = default;
+    BankStream(const BankStream&) = delete;
+    BankStream& operator=(const BankStream&) = delete;
+    ~BankStream() {
+        for (auto e : ev_pool) hipEventDestroy(e);
+        for (auto& e : pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
+        if (ev_run0) hipEventDestroy(ev_run0);
+        if (ev_run1) hipEventDestroy(ev_run1);
+        if (stream) hipStreamDestroy(stream);
+    }
+};
+
+struct Bank : BankStream {
     llpf_config cfg{};
     int F = 0;
     int64_t N = 0, Ns = 0;
     int nx = 0, nu = 0, ny = 0, P1 = 0, P2 = 0;
     int xrows = 0;                   // rows of a particle plane: nx, or xn + xl + packed R for LLPF_MODEL_RB_BILINEAR
     int nxp = 0;                     // dimension of a particle as the accessors see it: nx, or nxn + nxl for LLPF_MODEL_RB_BILINEAR (RBParticle indexes like [xn; xl])
-    int device = 0;
-    hipStream_t stream = nullptr;
-    void* d_pool = nullptr;          // the one allocation the members below (up to d_tmp) point into
+    DevBuf<char> d_pool;             // the one allocation the members below (up to d_tmp) point into
     ModelD* d_models = nullptr;
     FilterScal* d_scal = nullptr;
     double* d_x[2] = {nullptr, nullptr};
     int cur = 0;
     double* d_w = nullptr;           // the weights (the CURRENT ones: a split-schedule run of fused steps alternates between this and d_w_spare, host/run.hpp)
     double* d_w_spare = nullptr;     // second weight buffer, allocated by the first such run
-    double* d_w_alloc = nullptr;     // the allocation behind whichever of the two is not part of the pool
+    DevBuf<double> d_w_alloc;        // the allocation behind whichever of the two is not part of the pool
     bool w_pingpong = false;         // inside such a run: the fused kernel writes the weights it forms to the other buffer
     int32_t* d_anc = nullptr;
     uint64_t* d_acc = nullptr;
     uint64_t* d_quanta[2] = {nullptr, nullptr};
     int qcur = 0;                    // quanta buffer that holds the quanta of the current weights
     uint64_t* d_tileq = nullptr;
-    void* d_wq = nullptr;            // weighted_quantile: selection state (k_quantile.hip), the exp-weights [N], the probabilities [cap_wqp]
-    double *d_wq_we = nullptr, *d_wq_p = nullptr, *d_xquant = nullptr;
-    size_t cap_wqp = 0, cap_xq = 0;
+    DevBuf<char> d_wq;               // weighted_quantile: selection state (k_quantile.hip), the exp-weights [N], the probabilities [nq]
+    DevBuf<double> d_wq_we, d_wq_p, d_xquant;
     uint64_t *d_tpre = nullptr, *d_gsum = nullptr;      // filters above 1024 tiles: k_tile_prefix (kernels/resample.hpp)
     uint32_t* d_flag = nullptr;
     int64_t last_run_launches = 0, last_run_fx_steps = 0;
     double last_run_surv = -1.0;
-    double* d_xmpart = nullptr;
+    DevBuf<double> d_xmpart;
     // Rao-Blackwellized model: host side of the shared covariance recursion (csrc/shared/llpf_rbkf.h)
     struct RBHost { double R[16], kfx[4], kfR[16]; };
     std::vector<RBHost> rb;           // per filter: x[1].R and the inner KalmanFilter object's fields
     std::vector<llpf_model> hmodels;  // the F model descriptors as given at create
     RBStep* d_rb = nullptr;           // device: parameters of the single-step API ([2][F]) ...
-    RBStep* d_rbseq = nullptr;        // ... and of a run ([2T+1][F]: corr_0, pred_0, corr_1, ...)
-    size_t cap_rbseq = 0;
+    DevBuf<RBStep> d_rbseq;           // ... and of a run ([2T+1][F]: corr_0, pred_0, corr_1, ...)
     uint64_t* d_rtile = nullptr;      // [F][2][P2] residual resampling: per-tile counts / residual sums and their prefixes
-    double* d_lam = nullptr;          // [F][Ns] lambda of the AuxiliaryParticleFilter predict! (allocated on first use)
+    DevBuf<double> d_lam;             // [F][Ns] lambda of the AuxiliaryParticleFilter predict! (allocated on first use)
     double surv_frac = -1.0;          // distinct ancestors per predict! / N over the last run of a model that can take the source-side form (-1: none yet)
     bool use_fx = true;               //   ... and the form the next run takes (hysteresis: host/run.hpp)
-    unsigned long long* d_surv = nullptr;   // [F][P2][4] survivor counters of a run (BankDev::surv)
-    int32_t* d_mark = nullptr;        // [F][Ns] run-start marks / [F][nx][Ns] f(x_j): resampling with source-side dynamics (kernels/resfx.hpp),
-    double* d_fxs = nullptr;          //   allocated on first use (ensure_fx)
+    DevBuf<unsigned long long> d_surv;      // [F][P2][4] survivor counters of a run (BankDev::surv)
+    DevBuf<int32_t> d_mark;           // [F][Ns] run-start marks / [F][nx][Ns] f(x_j): resampling with source-side dynamics (kernels/resfx.hpp),
+    DevBuf<double> d_fxs;             //   allocated on first use (ensure_fx)
     bool aux_pending = false;         // w holds lambda - log N of an aux predict!; their exp-sums wait in slot (parity+2)%3
     bool we_is_lambda = false;        // expweights(pf) returns lambda until the next correct! (the reference keeps it in `we`)
     int parity = 0;                  // accumulator slot (0..2) the NEXT weighting kernel writes (engine.hpp ACC_NSLOT)
     double* d_uy = nullptr;          // staging for single-step u / y (2 * MAXD)
-    double* d_U = nullptr;           // resident inputs of a run
-    double* d_Y = nullptr;
-    size_t capU = 0, capY = 0;
-    double* d_ll_steps = nullptr;
-    double* d_xmean = nullptr;
-    double* d_xcov = nullptr;         // [T][nx*nx] + a mean: the xcov output of a run
-    size_t cap_ll = 0, cap_xm = 0, cap_xc = 0;
+    DevBuf<double> d_U, d_Y;         // resident inputs of a run
+    DevBuf<double> d_ll_steps, d_xmean;
+    DevBuf<double> d_xcov;            // [T][nx*nx] + a mean: the xcov output of a run
     double* d_tmp = nullptr;         // F*N*max(nx,1) doubles (also reinterpreted as int64 / double staging)
     uint64_t seed = 0;
     uint64_t key_off = 0, key_stride = 1;   // filter f of this bank is filter key_off + f * key_stride of a sharded sweep (llpf_mbank): its
@@ -71,26 +148,28 @@ struct Bank {
         const void *dU, *dY, *dll, *dxm, *dxc, *drb, *dxq, *dqp, *dw, *dws;      // every device buffer a captured launch addresses that ensure() may reallocate
         int nq;
         uint64_t yhash;
-        hipGraphExec_t exec;
+        GraphExec exec;
         bool same(const RunGraph& o) const {
             return T == o.T && t_index0 == o.t_index0 && par0 == o.par0 && cur0 == o.cur0 && qcur0 == o.qcur0 && flags == o.flags &&
                    np_parity == o.np_parity && dU == o.dU && dY == o.dY && dll == o.dll && dxm == o.dxm && dxc == o.dxc && drb == o.drb && dxq == o.dxq && dqp == o.dqp && dw == o.dw && dws == o.dws && nq == o.nq && yhash == o.yhash;
         }
     };
     std::vector<RunGraph> graphs;
-    double* d_hist = nullptr;         // device staging of the forward_trajectory history ([T][N][nx] x, [T][N] w, [T][N] we)
-    size_t cap_hist = 0;
+    DevBuf<double> d_hist;            // device staging of the forward_trajectory history ([T][N][nx] x, [T][N] w, [T][N] we)
     int64_t t_index = 0;
     // measurement
     bool profiling = false;
     double prof_ms[LLPF_PROF_CLASSES] = {0, 0, 0, 0};
     int64_t prof_n[LLPF_PROF_CLASSES] = {0, 0, 0, 0};
-    struct Ev { hipEvent_t a, b; int cls; };
-    std::vector<Ev> pending;
-    std::vector<hipEvent_t> ev_pool;
-    hipEvent_t ev_run0 = nullptr, ev_run1 = nullptr;
     double last_run_ms = 0.0;
     int64_t run_resamples = 0;
+
+    Bank() = default;
+    ~Bank() {      // never touches g_err: a failed create reports its own message after this has run
+        hipSetDevice(device);
+        if (stream) hipStreamSynchronize(stream);
+        graphs.clear();
+    }                // ... then the members free the buffers, and ~BankStream destroys the events and the stream
 
     BankDev dev() const {
         BankDev b;
@@ -124,23 +203,6 @@ struct llpf_bank { Bank bank; };
 static int use_device(const Bank& b) {
     HIPC(hipSetDevice(b.device));
     return LLPF_OK;
-}
-
-static void free_bank(Bank& b) {
-    hipSetDevice(b.device);
-    if (b.stream) hipStreamSynchronize(b.stream);
-    for (auto& g : b.graphs) if (g.exec) hipGraphExecDestroy(g.exec);
-    b.graphs.clear();
-    hipFree(b.d_pool);               // models, scal, x, w, anc, acc, quanta, tileq, flag, rtile, rb, uy, tmp
-    hipFree(b.d_w_alloc);
-    hipFree(b.d_wq); hipFree(b.d_wq_we); hipFree(b.d_wq_p); hipFree(b.d_xquant);
-    hipFree(b.d_xmpart); hipFree(b.d_lam); hipFree(b.d_surv); hipFree(b.d_mark); hipFree(b.d_fxs); hipFree(b.d_rbseq); hipFree(b.d_hist); hipFree(b.d_U); hipFree(b.d_Y);
-    hipFree(b.d_ll_steps); hipFree(b.d_xmean); hipFree(b.d_xcov);
-    for (auto e : b.ev_pool) hipEventDestroy(e);
-    for (auto& e : b.pending) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
-    if (b.ev_run0) hipEventDestroy(b.ev_run0);
-    if (b.ev_run1) hipEventDestroy(b.ev_run1);
-    if (b.stream) hipStreamDestroy(b.stream);
 }
 
 static int scal_download(Bank& b, std::vector<FilterScal>& h) {
@@ -204,24 +266,13 @@ static void prof_collect(Bank& b) {
 // the scratch of the resampling with source-side dynamics: marks (zero between timesteps) and the plane of f(x_j)
 // per-block parts of the weighted mean, one set per accumulator slot: [ACC_NSLOT][F][P1][MAXD] — 400 MB for a filter near 2^29 particles,
 // so it is not part of every handle's pool but allocated by the first run that asks for the means (kernels touch it under want_xmean only)
-static int ensure_xmpart(Bank& b) {
-    if (b.d_xmpart) return LLPF_OK;
-    const size_t n = (size_t)ACC_NSLOT * b.F * b.P1 * MAXD;
-    HIPC(hipMalloc(&b.d_xmpart, sizeof(double) * n));
-    HIPC(hipMemsetAsync(b.d_xmpart, 0, sizeof(double) * n, b.stream));
-    return LLPF_OK;
-}
+static int ensure_xmpart(Bank& b) { return b.d_xmpart.ensure_zeroed((size_t)ACC_NSLOT * b.F * b.P1 * MAXD, b.stream); }
 
 // weighted_quantile state: allocated by the first call that asks for quantiles; p [nq] uploaded
 static int ensure_wq(Bank& b, const double* p, int nq) {
-    if (!b.d_wq) HIPC(hipMalloc(&b.d_wq, wquantile_workspace_bytes(b.nx)));
-    if (!b.d_wq_we) HIPC(hipMalloc(&b.d_wq_we, sizeof(double) * (size_t)b.N));
-    if (b.cap_wqp < (size_t)nq) {
-        if (b.d_wq_p) hipFree(b.d_wq_p);
-        b.d_wq_p = nullptr; b.cap_wqp = 0;
-        HIPC(hipMalloc(&b.d_wq_p, sizeof(double) * (size_t)nq));
-        b.cap_wqp = (size_t)nq;
-    }
+    CHK(b.d_wq.ensure(wquantile_workspace_bytes(b.nx)));
+    CHK(b.d_wq_we.ensure((size_t)b.N));
+    CHK(b.d_wq_p.ensure((size_t)nq));
     HIPC(hipMemcpyAsync(b.d_wq_p, p, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, b.stream));
     return LLPF_OK;
 }
@@ -229,8 +280,8 @@ static int ensure_wq(Bank& b, const double* p, int nq) {
 static int ensure_fx(Bank& b) {
     if (b.d_mark && b.d_fxs) return LLPF_OK;
     const size_t FN = (size_t)b.F * b.Ns;
-    if (!b.d_mark) { HIPC(hipMalloc(&b.d_mark, sizeof(int32_t) * FN)); HIPC(hipMemsetAsync(b.d_mark, 0, sizeof(int32_t) * FN, b.stream)); }
-    if (!b.d_fxs) { HIPC(hipMalloc(&b.d_fxs, sizeof(double) * FN * b.nx)); HIPC(hipMemsetAsync(b.d_fxs, 0, sizeof(double) * FN * b.nx, b.stream)); }
+    CHK(b.d_mark.ensure_zeroed(FN, b.stream));
+    CHK(b.d_fxs.ensure_zeroed(FN * b.nx, b.stream));
     HIPC(hipStreamSynchronize(b.stream));
     return LLPF_OK;
 }
@@ -383,9 +434,10 @@ static int bank_create(const llpf_config* cfg, const llpf_model* models, int F, 
         const size_t o_tpre = take(two_level ? sizeof(uint64_t) * (size_t)F * b.P2 : 0), o_gsum = take(two_level ? sizeof(uint64_t) * (size_t)F * ((b.P2 + 4 * BLOCK - 1) / (4 * BLOCK)) : 0);
         const size_t o_uy = take(sizeof(double) * 4 * MAXD);
         const size_t o_tmp = take(sizeof(double) * (size_t)F * b.N * (b.nxp > 1 ? b.nxp : 1) + 64);
-        HIPC(hipMalloc(&b.d_pool, off));
+        CHK(b.d_pool.ensure(off));
+        test_throw("pool");
         HIPC(hipMemsetAsync(b.d_pool, 0, off, b.stream));
-        char* base = static_cast<char*>(b.d_pool);
+        char* base = b.d_pool;
         b.d_models = reinterpret_cast<ModelD*>(base + o_models); b.d_scal = reinterpret_cast<FilterScal*>(base + o_scal);
         b.d_x[0] = reinterpret_cast<double*>(base + o_x0); b.d_x[1] = reinterpret_cast<double*>(base + o_x1);
         b.d_w = reinterpret_cast<double*>(base + o_w); b.d_anc = reinterpret_cast<int32_t*>(base + o_anc);
@@ -449,10 +501,7 @@ static int bank_set_models(Bank& b, const llpf_model* models) {
         const int rc = model_prepare(&mf, &hm[f]);
         if (rc) return fail(LLPF_ERR_ARG, "invalid density (covariance not positive definite or dimension mismatch), code " + std::to_string(rc) + ", in filter " + std::to_string(f));
     }
-    if (mm[0].Ts != m0.Ts) {          // the time of a step rides in launch arguments: captured run loops are of no use any more
-        for (auto& g : b.graphs) if (g.exec) hipGraphExecDestroy(g.exec);
-        b.graphs.clear();
-    }
+    if (mm[0].Ts != m0.Ts) b.graphs.clear();      // the time of a step rides in launch arguments: captured run loops are of no use any more
     b.hmodels = mm;
     b.cfg.model = mm[0];
     HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * F, hipMemcpyHostToDevice, b.stream));

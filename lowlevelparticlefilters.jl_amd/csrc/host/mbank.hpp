@@ -79,9 +79,12 @@ struct MShard {
     Bank bank;
     int device = 0;
     std::vector<int> owned;          // global filter indices, ascending: shard s owns s, s + S, s + 2S, ...
-    double* d_ll = nullptr;          // [n_filters] on the shard's device: this shard's slots filled, zero elsewhere
+    DevBuf<double> d_ll;             // [n_filters] on the shard's device: this shard's slots filled, zero elsewhere
     rccl_dl::comm_t comm = nullptr;
-    bool created = false;
+    ~MShard() {                      // the communicator first, then (the members, in reverse order) d_ll, then the bank
+        hipSetDevice(device);
+        if (comm && rccl_dl::api()->CommDestroy) rccl_dl::api()->CommDestroy(comm);
+    }
 };
 
 enum { MBANK_COLL_NONE = 0, MBANK_COLL_RCCL = 1, MBANK_COLL_HOST = 2, MBANK_COLL_EXTERNAL = 3 };
@@ -128,18 +131,6 @@ static int mbank_foreach(llpf_mbank& m, Fn fn) {
     return LLPF_OK;
 }
 
-static void mbank_free(llpf_mbank* m) {
-    if (!m) return;
-    for (auto& sp : m->shards) {
-        MShard& sh = *sp;
-        hipSetDevice(sh.device);
-        if (sh.comm && rccl_dl::api()->CommDestroy) rccl_dl::api()->CommDestroy(sh.comm);
-        if (sh.d_ll) hipFree(sh.d_ll);
-        if (sh.created) free_bank(sh.bank);
-    }
-    delete m;
-}
-
 // shard `gs` of `S` owns the filters k with k mod S == gs
 static void mbank_owned(int n_filters, int gs, int S, std::vector<int>& out) {
     out.clear();
@@ -155,7 +146,7 @@ static int mbank_build(llpf_mbank* m, const llpf_config* base, const llpf_model*
     m->first_shard = first_shard;
     m->h_ll.assign((size_t)n_filters, 0.0);
     for (int s = 0; s < n_local; ++s) {
-        m->shards.emplace_back(new MShard());
+        m->shards.push_back(std::make_unique<MShard>());
         MShard& sh = *m->shards.back();
         sh.device = devices[s];
         mbank_owned(n_filters, first_shard + s, n_shards_total, sh.owned);
@@ -166,9 +157,8 @@ static int mbank_build(llpf_mbank* m, const llpf_config* base, const llpf_model*
         c.device = sh.device;
         std::vector<llpf_model> mine;
         if (models) { mine.reserve(sh.owned.size()); for (int k : sh.owned) mine.push_back(models[k]); }
-        sh.created = true;
         CHK(bank_create(&c, models ? mine.data() : nullptr, (int)sh.owned.size(), sh.bank, (uint64_t)(first_shard + s), (uint64_t)n_shards_total));
-        HIPC(hipMalloc(&sh.d_ll, sizeof(double) * (size_t)n_filters));
+        CHK(sh.d_ll.ensure((size_t)n_filters));
         HIPC(hipMemset(sh.d_ll, 0, sizeof(double) * (size_t)n_filters));
         return LLPF_OK;
     }));

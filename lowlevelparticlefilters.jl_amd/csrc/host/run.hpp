@@ -1,15 +1,5 @@
 // host/run.hpp — the trajectory loop (forward_trajectory / loglik).  Part of capi.hip (one translation unit).
 // ---- the trajectory loop ------------------------------------------------------------------------
-static int ensure(double** p, size_t* cap, size_t n) {
-    if (*cap >= n && *p) return LLPF_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIPC(hipMalloc(p, sizeof(double) * (n ? n : 1)));
-    *cap = n;
-    return LLPF_OK;
-}
-
 // `multi`: every filter of the bank has its own inputs, U [F][T][nu] and Y [F][T][ny] (the Monte-Carlo loops of the
 // reference's own benchmark, examples/example_lineargaussian.jl:282-316, as one bank); missing measurements must coincide.
 static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double t_index0,
@@ -23,19 +13,19 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     test_throw("run");
     if ((x_hist || w_hist || we_hist) && b.F != 1) return fail(LLPF_ERR_ARG, "history outputs need a single filter");
     if (xcov && (b.F != 1 || is_rbfull(b))) return fail(LLPF_ERR_ARG, "the xcov output needs a single filter that is not LLPF_MODEL_RB_BILINEAR");
-    if (xcov) CHK(ensure(&b.d_xcov, &b.cap_xc, (size_t)T * b.nx * b.nx + MAXD));
+    if (xcov) CHK(b.d_xcov.ensure((size_t)T * b.nx * b.nx + MAXD));
     if (xquant) {      // weighted_quantile(sol, q) (src/filtering.jl:583-595) of the state the history would copy out, per timestep, on the device
         if (b.F != 1 || is_rbfull(b)) return fail(LLPF_ERR_ARG, "the xquant output needs a single filter that is not LLPF_MODEL_RB_BILINEAR");
         if (!quant_p || nq < 1 || nq > 1024) return fail(LLPF_ERR_ARG, "the xquant output needs 1 <= nq <= 1024 probabilities");
         for (int i = 0; i < nq; ++i) if (!(quant_p[i] >= 0.0 && quant_p[i] <= 1.0)) return fail(LLPF_ERR_ARG, "xquant: a probability outside [0, 1]");
         CHK(ensure_wq(b, quant_p, nq));
         HIPC(hipStreamSynchronize(b.stream));
-        CHK(ensure(&b.d_xquant, &b.cap_xq, (size_t)T * b.nx * nq));
+        CHK(b.d_xquant.ensure((size_t)T * b.nx * nq));
     }
     b.aux_pending = false; b.we_is_lambda = false;
     const int FM = multi ? b.F : 1;                      // input sets on the device, laid out [T][FM][nu | ny]
-    CHK(ensure(&b.d_U, &b.capU, (size_t)T * FM * (b.nu > 0 ? b.nu : 1)));
-    CHK(ensure(&b.d_Y, &b.capY, (size_t)T * FM * b.ny));
+    CHK(b.d_U.ensure((size_t)T * FM * (b.nu > 0 ? b.nu : 1)));
+    CHK(b.d_Y.ensure((size_t)T * FM * b.ny));
     std::vector<double> stageU, stageY;
     if (multi) {
         if (is_rb(b)) return fail(LLPF_ERR_ARG, "per-filter inputs are not provided for the Rao-Blackwellized model");
@@ -56,8 +46,8 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     if (b.nu > 0) HIPC(hipMemcpyAsync(b.d_U, multi ? stageU.data() : U, sizeof(double) * T * FM * b.nu, hipMemcpyHostToDevice, b.stream));
     HIPC(hipMemcpyAsync(b.d_Y, multi ? stageY.data() : Y, sizeof(double) * T * FM * b.ny, hipMemcpyHostToDevice, b.stream));
     if (multi) HIPC(hipStreamSynchronize(b.stream));     // the staging vectors are pageable host memory
-    if (ll_steps) CHK(ensure(&b.d_ll_steps, &b.cap_ll, (size_t)T * b.F));
-    if (xmean) CHK(ensure(&b.d_xmean, &b.cap_xm, (size_t)T * b.F * b.nxp));
+    if (ll_steps) CHK(b.d_ll_steps.ensure((size_t)T * b.F));
+    if (xmean) CHK(b.d_xmean.ensure((size_t)T * b.F * b.nxp));
     {   // zero the running log-likelihood and remember the resample counter
         std::vector<FilterScal> h;
         CHK(scal_download(b, h));
@@ -115,19 +105,14 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     const bool source_fx = fx_capable && (sfx_env ? atoi(sfx_env) != 0 : b.use_fx);
     const size_t n_surv = (size_t)b.F * b.P2 * 4;
     if (fx_capable) {
-        if (!b.d_surv) HIPC(hipMalloc(&b.d_surv, sizeof(unsigned long long) * n_surv));
+        CHK(b.d_surv.ensure(n_surv));
         HIPC(hipMemsetAsync(b.d_surv, 0, sizeof(unsigned long long) * n_surv, b.stream));
     }
     if (source_fx) CHK(ensure_fx(b));
     if (rbm) {
         // the whole gain schedule of the run (data independent): corr_0, pred_0, corr_1, pred_1, ..., [F] each
         const size_t need = (size_t)(2 * T + 1) * b.F;
-        if (b.cap_rbseq < need) {
-            if (b.d_rbseq) hipFree(b.d_rbseq);
-            b.d_rbseq = nullptr; b.cap_rbseq = 0;
-            HIPC(hipMalloc(&b.d_rbseq, sizeof(RBStep) * need));
-            b.cap_rbseq = need;
-        }
+        CHK(b.d_rbseq.ensure(need));
         std::vector<RBStep> seq(need);
         for (int64_t k = 0; k < T; ++k)
             for (int f = 0; f < b.F; ++f) {
@@ -164,12 +149,18 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     const bool lazy_run = !merged && !unfused && !no_bound && b.cfg.resample_threshold < 1.0 && !(lazy_s && atoi(lazy_s) == 0);
     if (lazy_run && !b.d_w_spare) {
         const size_t bytes = sizeof(double) * (size_t)b.F * b.Ns;
-        if (hipMalloc(&b.d_w_alloc, bytes) != hipSuccess) { (void)hipGetLastError(); b.d_w_alloc = nullptr; return fail(LLPF_ERR_ALLOC, "second weight buffer of the split schedule"); }
+        if (!b.d_w_alloc.try_ensure((size_t)b.F * b.Ns)) return fail(LLPF_ERR_ALLOC, "second weight buffer of the split schedule");
         b.d_w_spare = b.d_w_alloc;
         HIPC(hipMemcpyAsync(b.d_w_spare, b.d_w, bytes, hipMemcpyDeviceToDevice, b.stream));
     }
     double* const wbuf0 = b.d_w;
     double* const wbuf1 = lazy_run ? b.d_w_spare : b.d_w;
+    // however the run ends (a failed status or a throw included), the verbs after it weight in place, on the buffer it began in
+    auto restore_w = on_scope_exit([&] {
+        b.d_w = wbuf0;
+        if (lazy_run) b.d_w_spare = wbuf1;
+        b.w_pingpong = false;
+    });
     // The run ends in the buffer it began in (a handle's weights do not move between runs: one captured graph per shape, not two that
     // alternate): T - 1 steps have a weighting phase; when that number is odd, step 0 keeps the stored form and weights in place.
     const int64_t k_pp0 = (lazy_run && ((T - 1) & 1)) ? 1 : 0;
@@ -225,13 +216,8 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     const size_t hist_doubles = (x_hist ? hist_rows * b.nxp : 0) + (w_hist ? hist_rows : 0) + (we_hist ? hist_rows : 0);
     bool hist_dev = hist && hist_doubles * sizeof(double) <= ((size_t)16 << 30);
     double *dx_hist = nullptr, *dw_hist = nullptr, *dwe_hist = nullptr;
-    if (hist_dev && (b.cap_hist < hist_doubles || !b.d_hist)) {
-        // the staging buffer can be most of the device's memory: if it cannot be had, copy row by row instead of failing
-        if (b.d_hist) hipFree(b.d_hist);
-        b.d_hist = nullptr; b.cap_hist = 0;
-        if (hipMalloc(&b.d_hist, sizeof(double) * hist_doubles) == hipSuccess) b.cap_hist = hist_doubles;
-        else { (void)hipGetLastError(); b.d_hist = nullptr; hist_dev = false; }
-    }
+    // the staging buffer can be most of the device's memory: if it cannot be had, copy row by row instead of failing
+    if (hist_dev && !b.d_hist.try_ensure(hist_doubles)) hist_dev = false;
     if (hist_dev) {
         double* p = b.d_hist;
         if (x_hist) { dx_hist = p; p += hist_rows * b.nxp; }
@@ -287,9 +273,9 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
             st.only_fallback = only_fb;
             HIPC(launch_step(d, weight ? MODE_PROP_WEIGHT : MODE_PROP, st, b.stream));
         } else {
-            uint64_t* d_dbg = nullptr;
+            DevBuf<uint64_t> d_dbg;
             if (dbg_env && k == atoll(dbg_env)) {
-                HIPC(hipMalloc(&d_dbg, sizeof(uint64_t) * 8 * b.P2));
+                CHK(d_dbg.ensure((size_t)8 * b.P2));
                 HIPC(hipMemsetAsync(d_dbg, 0, sizeof(uint64_t) * 8 * b.P2, b.stream));
                 ra.dbg = d_dbg;
             }
@@ -309,7 +295,6 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
                     }
                     fclose(fp);
                 }
-                hipFree(d_dbg);
             }
         }
         return LLPF_OK;
@@ -347,23 +332,22 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
         // a run shape is captured the second time it is seen (capture + instantiation of ~T nodes costs several ms:
         // one-off shapes are simply enqueued)
         Bank::RunGraph* slot = nullptr;
-        for (auto& g : b.graphs) if (g.same(key)) { slot = &g; gexec = g.exec; break; }
+        for (auto& g : b.graphs) if (g.same(key)) { slot = &g; gexec = g.exec.h; break; }
         if (!slot) {
-            if (b.graphs.size() >= 4) { if (b.graphs.front().exec) hipGraphExecDestroy(b.graphs.front().exec); b.graphs.erase(b.graphs.begin()); }
-            key.exec = nullptr;
-            b.graphs.push_back(key);
+            if (b.graphs.size() >= 4) b.graphs.erase(b.graphs.begin());
+            b.graphs.push_back(std::move(key));
         } else if (!gexec) {
             hipGraph_t graph = nullptr;
+            auto drop_graph = on_scope_exit([&] { if (graph) hipGraphDestroy(graph); });
             HIPC(hipStreamBeginCapture(b.stream, hipStreamCaptureModeThreadLocal));
             int rc = first_weighting();
             for (int64_t k = 0; rc == LLPF_OK && k < T; ++k) rc = launch_timestep(k, !no_bound, 0);
             const hipError_t ee = hipStreamEndCapture(b.stream, &graph);
-            if (rc != LLPF_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+            CHK(rc);
             if (ee != hipSuccess) return fail(LLPF_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
             const hipError_t ei = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-            hipGraphDestroy(graph);
             if (ei != hipSuccess) return fail(LLPF_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
-            slot->exec = gexec;
+            slot->exec = GraphExec(gexec);
         }
     }
     HIPC(hipEventRecord(b.ev_run0, b.stream));
@@ -432,6 +416,7 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
             const int64_t k1 = replayed ? T : std::min(T, k0 + batch);
             if (!replayed) {
                 for (int64_t k = k0; k < k1; ++k) CHK(launch_timestep(k, !no_bound, 0));
+                test_throw("run_loop");
             }
             replayed = false;
             std::vector<int> fl;
@@ -446,8 +431,8 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
             batch = std::max<int64_t>(1, std::min(batch, T) / 4);
         }
     }
-    at_step(T);
-    b.w_pingpong = false;                                    // the verbs outside a run weight in place, on the buffer the run ended in
+    at_step(T);                                              // (back in wbuf0: a run ends in the buffer it began in)
+    b.w_pingpong = false;                                    // the launches below and every verb after the run weight in place
     b.qcur = qcur0 ^ (int)(T & 1);                           // the last step has no weighting phase: no quanta swap
     b.parity = (par0 + (int)(T % ACC_NSLOT)) % ACC_NSLOT;
     {
@@ -463,11 +448,10 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
         if (w_hist) HIPC(hipMemcpyAsync(w_hist, dw_hist, sizeof(double) * hist_rows, hipMemcpyDeviceToHost, b.stream));
         if (we_hist) HIPC(hipMemcpyAsync(we_hist, dwe_hist, sizeof(double) * hist_rows, hipMemcpyDeviceToHost, b.stream));
     }
-    if (hist_dev && b.cap_hist * sizeof(double) > ((size_t)256 << 20)) {
+    if (hist_dev && b.d_hist.cap * sizeof(double) > ((size_t)256 << 20)) {
         // a large history staging buffer is not kept for the lifetime of the handle (other filters / banks need the memory)
         HIPC(hipStreamSynchronize(b.stream));
-        hipFree(b.d_hist);
-        b.d_hist = nullptr; b.cap_hist = 0;
+        b.d_hist.reset();
     }
     if (ll_steps) HIPC(hipMemcpyAsync(ll_steps, b.d_ll_steps, sizeof(double) * T * b.F, hipMemcpyDeviceToHost, b.stream));
     if (xmean) HIPC(hipMemcpyAsync(xmean, b.d_xmean, sizeof(double) * T * b.F * b.nxp, hipMemcpyDeviceToHost, b.stream));

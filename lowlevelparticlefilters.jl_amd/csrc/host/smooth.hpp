@@ -28,46 +28,41 @@ static int bank_smooth(Bank& b, int64_t M, const double* U, int64_t T, const dou
         if (idx) idx[(size_t)(T - 1) * M + m] = j[m];
     }
     if (T == 1) return LLPF_OK;
-    double *d_xf = nullptr, *d_wf = nullptr, *d_fx = nullptr, *d_xb = nullptr, *d_u = nullptr;
-    int64_t* d_idx = nullptr;
-    auto body = [&]() -> int {
-        HIPC(hipMalloc(&d_xf, sizeof(double) * (size_t)T * N * nx));
-        HIPC(hipMalloc(&d_wf, sizeof(double) * (size_t)T * N));
-        HIPC(hipMalloc(&d_fx, sizeof(double) * (size_t)nx * b.Ns));
-        HIPC(hipMalloc(&d_xb, sizeof(double) * (size_t)T * M * nx));
-        HIPC(hipMalloc(&d_idx, sizeof(int64_t) * (size_t)T * M));
-        HIPC(hipMalloc(&d_u, sizeof(double) * (size_t)T * (b.nu > 0 ? b.nu : 1)));
-        HIPC(hipMemcpyAsync(d_xf, xf, sizeof(double) * (size_t)T * N * nx, hipMemcpyHostToDevice, b.stream));
-        HIPC(hipMemcpyAsync(d_wf, wf, sizeof(double) * (size_t)T * N, hipMemcpyHostToDevice, b.stream));
-        if (b.nu > 0) HIPC(hipMemcpyAsync(d_u, U, sizeof(double) * (size_t)T * b.nu, hipMemcpyHostToDevice, b.stream));
-        HIPC(hipMemcpyAsync(d_xb + (size_t)(T - 1) * M * nx, xb + (size_t)(T - 1) * M * nx, sizeof(double) * M * nx, hipMemcpyHostToDevice, b.stream));
-        HIPC(hipMemsetAsync(d_idx, 0, sizeof(int64_t) * (size_t)T * M, b.stream));
-        BankDev d = b.dev();
-        HIPC(hipEventRecord(b.ev_run0, b.stream));
-        for (int64_t t = T - 2; t >= 0; --t) {
-            SmoothArgs a{};
-            a.xf_t = d_xf + (size_t)t * N * nx; a.wf_t = d_wf + (size_t)t * N;
-            a.u = b.nu > 0 ? d_u + t * b.nu : nullptr; a.t = (double)t * b.cfg.model.Ts;
-            a.fx = d_fx; a.xb_next = d_xb + (size_t)(t + 1) * M * nx; a.xb_t = d_xb + (size_t)t * M * nx;
-            a.idx_t = d_idx + (size_t)t * M; a.M = (int32_t)M; a.step = (uint32_t)t;
-            HIPC(launch_smooth_fx(d, a, b.stream));
-            HIPC(launch_smooth_draw(d, a, b.stream));
-        }
-        HIPC(hipEventRecord(b.ev_run1, b.stream));
-        HIPC(hipMemcpyAsync(xb, d_xb, sizeof(double) * (size_t)(T - 1) * M * nx, hipMemcpyDeviceToHost, b.stream));
-        std::vector<int64_t> hidx;
-        if (idx) {
-            hidx.resize((size_t)(T - 1) * M);
-            HIPC(hipMemcpyAsync(hidx.data(), d_idx, sizeof(int64_t) * (size_t)(T - 1) * M, hipMemcpyDeviceToHost, b.stream));
-        }
-        HIPC(hipStreamSynchronize(b.stream));
-        if (idx) memcpy(idx, hidx.data(), sizeof(int64_t) * (size_t)(T - 1) * M);
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, b.ev_run0, b.ev_run1));
-        b.last_run_ms = ms;
-        return LLPF_OK;
-    };
-    const int rc = body();
-    hipFree(d_xf); hipFree(d_wf); hipFree(d_fx); hipFree(d_xb); hipFree(d_idx); hipFree(d_u);
-    return rc;
+    DevBuf<double> d_xf, d_wf, d_fx, d_xb, d_u;
+    DevBuf<int64_t> d_idx;
+    CHK(d_xf.ensure((size_t)T * N * nx));
+    CHK(d_wf.ensure((size_t)T * N));
+    CHK(d_fx.ensure((size_t)nx * b.Ns));
+    CHK(d_xb.ensure((size_t)T * M * nx));
+    CHK(d_idx.ensure((size_t)T * M));
+    CHK(d_u.ensure((size_t)T * (b.nu > 0 ? b.nu : 1)));
+    HIPC(hipMemcpyAsync(d_xf, xf, sizeof(double) * (size_t)T * N * nx, hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemcpyAsync(d_wf, wf, sizeof(double) * (size_t)T * N, hipMemcpyHostToDevice, b.stream));
+    if (b.nu > 0) HIPC(hipMemcpyAsync(d_u, U, sizeof(double) * (size_t)T * b.nu, hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemcpyAsync(d_xb + (size_t)(T - 1) * M * nx, xb + (size_t)(T - 1) * M * nx, sizeof(double) * M * nx, hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemsetAsync(d_idx, 0, sizeof(int64_t) * (size_t)T * M, b.stream));
+    BankDev d = b.dev();
+    HIPC(hipEventRecord(b.ev_run0, b.stream));
+    for (int64_t t = T - 2; t >= 0; --t) {
+        SmoothArgs a{};
+        a.xf_t = d_xf + (size_t)t * N * nx; a.wf_t = d_wf + (size_t)t * N;
+        a.u = b.nu > 0 ? d_u + t * b.nu : nullptr; a.t = (double)t * b.cfg.model.Ts;
+        a.fx = d_fx; a.xb_next = d_xb + (size_t)(t + 1) * M * nx; a.xb_t = d_xb + (size_t)t * M * nx;
+        a.idx_t = d_idx + (size_t)t * M; a.M = (int32_t)M; a.step = (uint32_t)t;
+        HIPC(launch_smooth_fx(d, a, b.stream));
+        HIPC(launch_smooth_draw(d, a, b.stream));
+    }
+    HIPC(hipEventRecord(b.ev_run1, b.stream));
+    HIPC(hipMemcpyAsync(xb, d_xb, sizeof(double) * (size_t)(T - 1) * M * nx, hipMemcpyDeviceToHost, b.stream));
+    std::vector<int64_t> hidx;
+    if (idx) {
+        hidx.resize((size_t)(T - 1) * M);
+        HIPC(hipMemcpyAsync(hidx.data(), d_idx, sizeof(int64_t) * (size_t)(T - 1) * M, hipMemcpyDeviceToHost, b.stream));
+    }
+    HIPC(hipStreamSynchronize(b.stream));
+    if (idx) memcpy(idx, hidx.data(), sizeof(int64_t) * (size_t)(T - 1) * M);
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, b.ev_run0, b.ev_run1));
+    b.last_run_ms = ms;
+    return LLPF_OK;
 }

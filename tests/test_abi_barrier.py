@@ -5,6 +5,7 @@ host threads of a multi-GPU bank catch inside the thread.  The reference's analo
 
 Faults are injected with LLPF_TEST_THROW="<alloc|error|other>:<site>" (capi.hip: test_throw)."""
 import ctypes as C
+import glob
 import os
 import re
 
@@ -36,6 +37,37 @@ def test_every_export_is_guarded():
     # no thread body without a handler of its own
     mb = open(os.path.join(os.path.dirname(CAPI), "host", "mbank.hpp")).read()
     assert mb.count("emplace_back([&") == 1 and "noexcept {" in mb and 'guard_catch("shard worker")' in mb
+
+
+def _struct_span(src, name):
+    m = re.search(r"\bstruct %s\b[^;{]*\{" % name, src)
+    assert m, name
+    depth, i = 1, m.end()
+    while depth:
+        depth += {"{": 1, "}": -1}.get(src[i], 0)
+        i += 1
+    return m.start(), i
+
+
+def test_device_resources_are_owned():
+    # device buffers, captured graphs and handles are owned by types (host/bank.hpp: DevBuf, GraphExec; std::unique_ptr for the
+    # handles): no hand-written cleanup that an early return or a throw can skip
+    d = os.path.dirname(CAPI)
+    srcs = {os.path.relpath(p, d): re.sub(r"//[^\n]*", "", open(p).read()) for p in [CAPI] + sorted(glob.glob(os.path.join(d, "host", "*.hpp")))}
+    bank = srcs["host/bank.hpp"]
+    for owner in ("DevBuf", "GraphExec"):
+        a, b = _struct_span(bank, owner)
+        assert "hip" in bank[a:b]
+        bank = bank[:a] + bank[b:]
+    srcs["host/bank.hpp"] = bank
+    for name, src in srcs.items():
+        for word in ("hipMalloc(", "hipFree(", "hipGraphExecDestroy(", "free_bank", "mbank_free"):
+            assert word not in src, (name, word)
+        for line in src.splitlines():
+            if "new (std::nothrow)" in line:
+                assert re.search(r"std::unique_ptr<\w+> \w+\(new \(std::nothrow\)|\w+\.reset\(new \(std::nothrow\)", line), (name, line)
+    a, b = _struct_span(bank, "Bank")
+    assert not re.search(r"\bcap(_\w+|[A-Z]\w*)\b", bank[a:b])
 
 
 class _Inject:
@@ -84,6 +116,59 @@ def test_a_throw_inside_a_run_leaves_a_usable_handle():
             assert ei.value.code == code
     g.seed(7); g.reset()          # (reset! alone keeps drawing fresh noise: the same seed again gives the same run)
     assert g.run(U, Y, 0.0)["ll"] == ref
+
+
+def _device_free_bytes():
+    # hipMemGetInfo of the HIP runtime the library is bound to (the lookup through its handle searches its dependencies)
+    free, total = C.c_size_t(), C.c_size_t()
+    assert _capi.lib()["hipMemGetInfo"](C.byref(free), C.byref(total)) == 0
+    return free.value
+
+
+@pytest.mark.gpu
+def test_a_failed_create_leaks_no_device_memory():
+    # a throw right after the pool of a handle is allocated (LLPF_TEST_THROW=alloc:pool): the half-built handle is freed
+    L = _capi.lib()
+    cfg = S.make_config(M.lg_test_model(), 1 << 24)      # a pool of ~1.3 GB (76 bytes per particle at nx = 2)
+    _capi.FilterHandle(cfg).close()                       # (the runtime's own first allocations are not counted)
+    free0 = _device_free_bytes()
+    with _Inject("alloc:pool"):
+        for _ in range(8):
+            h = C.c_void_p()
+            assert L.llpf_create(C.byref(cfg), C.byref(h)) == _capi.ERR_ALLOC
+            assert b"out of host memory" in L.llpf_last_error() and not h.value
+            hb = C.c_void_p()
+            assert L.llpf_bank_create(C.byref(cfg), None, 1, C.byref(hb)) == _capi.ERR_ALLOC
+            assert not hb.value
+    assert free0 - _device_free_bytes() < 1 << 30      # less than one pool; sixteen leaked pools would be ~20 GB
+
+
+@pytest.mark.gpu
+def test_a_throw_inside_a_split_schedule_run_leaves_a_usable_handle():
+    # N = 2e6 at threshold 0.1: the split schedule with two weight buffers (host/run.hpp).  The first run of its shape is enqueued, and
+    # the throw comes after all its steps are (LLPF_TEST_THROW=error:run_loop).  The buffers are back in place there, but the run is still
+    # marked as alternating between them (Bank::w_pingpong), and a verb whose fused kernel forms weights (the auxiliary predict!, through
+    # BankDev::w_next) would write them to the spare buffer: the run must clear that on every exit.
+    model = M.lg_test_model()
+    _, U, Y = M.simulate_lg(model, 12)
+    cfg = S.make_config(model, 2_000_000, S.PARTICLE_FILTER, S.RESAMPLE_SYSTEMATIC, 0.1, 7, 0)
+    g = _capi.FilterHandle(cfg)
+    with _Inject("error:run_loop"):
+        with pytest.raises(_capi.LLPFError) as ei:
+            g.run(U, Y, 0.0)
+        assert ei.value.code == _capi.ERR_INTERNAL
+    out = []
+    for h in (g, _capi.FilterHandle(cfg)):
+        h.seed(7); h.reset()
+        ll = h.correct(U[0], Y[0], 1.0)
+        h.predict(U[0], 1.0)
+        single = (h.particles(), h.weights(), h.expweights())
+        h.aux_predict(U[1], Y[2], 2.0)
+        aux = (h.particles(), h.weights(), h.expweights(), np.array([h.aux_correct()]))
+        r = h.run(U[2:], Y[2:], 3.0, ll_steps=True)
+        out.append([np.array([ll]), *single, *aux, r["ll_steps"], h.particles(), h.weights(), h.expweights()])
+    for a, b in zip(*out):
+        assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 @pytest.mark.gpu
