@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define LLPF_VERSION_MAJOR 0
-#define LLPF_VERSION_MINOR 6
+#define LLPF_VERSION_MINOR 7
 #define LLPF_MAX_DIM 16       /* states and outputs of a model (round 5: 8 -> 16; above 4 the linear-Gaussian model and every user model are compiled at run time) */
 #define LLPF_MAX_INPUTS 8     /* inputs u */
 #define LLPF_RB_MAX_LINEAR 8  /* linear states of LLPF_MODEL_RB_BILINEAR */
@@ -344,6 +344,29 @@ int  llpf_bank_run_multi(llpf_bank* b, const double* U, const double* Y, int64_t
 /* as llpf_aux_run for every filter of the bank (the ML sweep over AuxiliaryParticleFilters, test/runtests.jl:419-423) */
 int  llpf_bank_aux_run(llpf_bank* b, const double* U, const double* Y, int64_t T, int32_t mode,
                        double* ll_total, double* ll_steps);
+
+/* ---- simulation: data from the model of a filter (the reference's simulate(pf, T, du), src/filtering.jl:457-477) ---------------
+ * M trajectories of T steps, one per GPU thread; for trajectory m and step t, tau_t = (t_index0 + t) * Ts as llpf_run takes it:
+ *   x_0     = mean(initial_density); with LLPF_SIM_SAMPLE_INITIAL the draw reset! gives particle m (the model's own `initial` included)
+ *   y_t     = g(x_t, u_t, p, tau_t) + e_t,  e_t ~ measurement_density (Philox stream 4 at (m, step0 + t)); a model with a likelihood of
+ *             its own (`loglik`) still draws e_t from the Gaussian measurement_density: a likelihood has no sampler
+ *   x_{t+1} = f(x_t, u_t, p, tau_t) + w_t,  w_t the process noise predict! gives particle m at Philox step step0 + t (the model's own
+ *             `noise` included)
+ * The Philox key is derived from `seed` as the filter derives its own from its seed (filter k of a bank: seed + k): with step0 = 0 the
+ * initial draw equals the particles a handle draws in its constructor with that seed, or in the first llpf_reset after llpf_seed(seed)
+ * (reset! passes its reset count as the step), and x_{t+1} the particles of a filter that never resamples after predict! at step
+ * counter step0 + t.  Pass a seed other than the filter's own: data drawn with the filter's key
+ * share their noise with its particles.  The handle is not changed (particles, weights, step counters, captured runs).
+ * Linear-Gaussian, quad-tank and run-time compiled models; the Rao-Blackwellized kinds return LLPF_ERR_ARG. */
+enum { LLPF_SIM_DYNAMICS_NOISE = 1, LLPF_SIM_MEASUREMENT_NOISE = 2, LLPF_SIM_SAMPLE_INITIAL = 4 };
+/* U: [T][nu] shared by all trajectories (u_per_trajectory = 0) or [M][T][nu] (= 1); NULL when nu = 0.
+ * X (optional) [T][M][nx], Y (optional) [T][M][ny], time-major like the history outputs of llpf_run / llpf_smooth; at least one of them */
+int  llpf_simulate(llpf_filter* f, int64_t M, int64_t T, const double* U, int32_t u_per_trajectory, double t_index0,
+                   uint64_t seed, uint32_t step0, int32_t flags, double* X, double* Y);
+/* every filter of the bank, each with its own parameters and key seed + k: U [T][nu] or [n_filters][M][T][nu];
+ * X [n_filters][T][M][nx], Y [n_filters][T][M][ny] */
+int  llpf_bank_simulate(llpf_bank* b, int64_t M, int64_t T, const double* U, int32_t u_per_trajectory, double t_index0,
+                        uint64_t seed, uint32_t step0, int32_t flags, double* X, double* Y);
 
 /* ---- sweeps sharded over the GPUs of one node (multi-GPU banks) ------------------------------
  * The same sweep as llpf_bank_*, with filter k on shard k mod n_shards (one shard = one GPU, one stream): the reference's

@@ -37,6 +37,8 @@ SYMBOLS = {
     "llpf_aux_update": [_vp, _dp, _dp, C.c_double, _dp],
     "llpf_aux_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.RunOutputs)],
     "llpf_bank_aux_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, _dp],
+    "llpf_simulate": [_vp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_int32, _dp, _dp],
+    "llpf_bank_simulate": [_vp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_int32, _dp, _dp],
     "llpf_num_particles": [_vp, _ip],
     "llpf_index": [_vp, _ip],
     "llpf_get_particles": [_vp, _dp],
@@ -96,6 +98,7 @@ SYMBOLS = {
     "llpf_selftest_normals": [C.c_int32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, _dp, C.c_int64],
 }
 
+SIM_DYNAMICS_NOISE, SIM_MEASUREMENT_NOISE, SIM_SAMPLE_INITIAL = 1, 2, 4
 OK, ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_DEGENERATE, ERR_ALLOC, ERR_INTERNAL = 0, 1, 2, 3, 4, 5, 6
 PROF_CLASSES = 4
 
@@ -148,6 +151,20 @@ def iptr(a):
 
 def f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _simulate(fn, h, F, nx, nu, ny, M, T, U, u_per_trajectory, t_index0, seed, step0, flags, states, measurements):
+    """llpf_simulate / llpf_bank_simulate: returns X [F, T, M, nx] (or None), Y [F, T, M, ny] (or None)"""
+    M, T = int(M), int(T)
+    if nu > 0:
+        U = f64(U).reshape((F, M, T, nu) if u_per_trajectory else (T, nu))
+    else:
+        U = None
+    X = np.empty((F, T, M, nx)) if states else None
+    Y = np.empty((F, T, M, ny)) if measurements else None
+    check(fn(h, M, T, dptr(U), 1 if u_per_trajectory else 0, float(t_index0), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0) & 0xFFFFFFFF,
+             int(flags), dptr(X), dptr(Y)))
+    return X, Y
 
 
 def device_count():
@@ -252,6 +269,14 @@ class FilterHandle:
         check(self.L.llpf_run(self.h, dptr(U), dptr(Y), T, float(t_index0), C.byref(ll), C.byref(outs)))
         res["ll"] = ll.value
         return res
+
+    def simulate(self, M, T, U=None, u_per_trajectory=False, t_index0=0.0, seed=0, step0=0, flags=SIM_DYNAMICS_NOISE | SIM_MEASUREMENT_NOISE,
+                 states=True, measurements=True):
+        """llpf_simulate: M trajectories of T steps of this filter's model on the device.  U [T, nu] shared, or [M, T, nu] with
+        u_per_trajectory; returns X [T, M, nx] (or None), Y [T, M, ny] (or None).  The handle is not changed."""
+        X, Y = _simulate(self.L.llpf_simulate, self.h, 1, self.nx, self.nu, self.ny, M, T, U, u_per_trajectory, t_index0, seed, step0, flags,
+                         states, measurements)
+        return (None if X is None else X[0]), (None if Y is None else Y[0])
 
     def weighted_cov(self):
         """weighted_cov of the current particles under the current weights (reference src/filtering.jl:571-581), on the device"""
@@ -499,6 +524,13 @@ class BankHandle:
         lls = np.zeros((T, self.F)) if ll_steps else None
         check(self.L.llpf_bank_aux_run(self.h, dptr(U), dptr(Y), T, int(mode), dptr(ll), dptr(lls)))
         return {"ll": ll, "ll_steps": lls}
+
+    def simulate(self, M, T, U=None, u_per_trajectory=False, t_index0=0.0, seed=0, step0=0, flags=SIM_DYNAMICS_NOISE | SIM_MEASUREMENT_NOISE,
+                 states=True, measurements=True):
+        """llpf_bank_simulate: M trajectories of every filter's model, filter k with key seed + k.  U [T, nu] shared, or [F, M, T, nu] with
+        u_per_trajectory; returns X [F, T, M, nx] (or None), Y [F, T, M, ny] (or None)."""
+        return _simulate(self.L.llpf_bank_simulate, self.h, self.F, self.nx, self.nu, self.ny, M, T, U, u_per_trajectory, t_index0, seed, step0,
+                         flags, states, measurements)
 
     def last_run_ms(self):
         v = C.c_double(0)

@@ -32,7 +32,7 @@ __all__ = [
     "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
-    "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "parameters",
+    "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
     "dynamics", "measurement", "measurement_likelihood", "dynamics_density", "measurement_density",
     "initial_density", "resample_threshold", "resampling_strategy", "UserDynamics", "UserMeasurement", "UserLikelihood", "UserNoise", "UserInitial",
 ]
@@ -971,6 +971,55 @@ def simulate(pf, T_or_u, du=None, p=None, dynamics_noise=True, measurement_noise
     return x, u, y
 
 
+def _sim_inputs(nu, T_or_u, M, du, u_per_trajectory, rng, lead=()):
+    """the inputs of simulate_batch: (T, u) with u [T, nu], or lead + [M, T, nu] with u_per_trajectory"""
+    if np.isscalar(T_or_u):
+        T = int(T_or_u)
+        if nu == 0:
+            return T, np.zeros(lead + (M, T, 0) if u_per_trajectory else (T, 0))
+        if du is None:
+            raise ValueError("the model has inputs: pass du (their distribution) or the inputs themselves")
+        rng = np.random.default_rng(0) if rng is None else rng
+        if not u_per_trajectory:          # as simulate draws them
+            return T, np.stack([du.rand(rng) for _ in range(T)])
+        z = rng.standard_normal(lead + (M, T, nu))
+        return T, du.mean + z @ np.linalg.cholesky(du.cov).T
+    u = np.asarray(T_or_u, dtype=np.float64)
+    if u_per_trajectory:
+        if nu == 0:
+            T = u.shape[len(lead) + 1]
+            return T, np.zeros(lead + (M, T, 0))
+        u = u.reshape(lead + (M, -1, nu))
+        return u.shape[-2], u
+    u = u.reshape(u.shape[0], -1)
+    if u.shape[1] != nu:
+        raise ValueError("u must be [T, %d]" % nu)
+    return u.shape[0], u
+
+
+def _sim_flags(dynamics_noise, measurement_noise, sample_initial):
+    return ((_capi.SIM_DYNAMICS_NOISE if dynamics_noise else 0) | (_capi.SIM_MEASUREMENT_NOISE if measurement_noise else 0) |
+            (_capi.SIM_SAMPLE_INITIAL if sample_initial else 0))
+
+
+def simulate_batch(pf, T_or_u, M, du=None, *, seed=0, step0=0, dynamics_noise=True, measurement_noise=True, sample_initial=False, states=True,
+                   u_per_trajectory=False, t_index0=0.0, rng=None):
+    """x, u, y = simulate_batch(pf, T, M, du) / simulate_batch(pf, u, M): M trajectories of simulate(pf, T, du) (reference
+    src/filtering.jl:457-477) at once, on the device (llpf_simulate), for every model the filter can run — device snippets without a
+    host version, UserNoise / UserInitial included; not the Rao-Blackwellized filter.
+
+    x [T, M, nx] (None with states=False), y [T, M, ny].  u: [T, nu] shared by all trajectories, drawn on the host from du as simulate
+    draws them (rng: a numpy Generator, default seeded 0), or given; with u_per_trajectory [M, T, nu].  Step t runs at time
+    (t_index0 + t) * Ts.  The noise comes from the engine's own generator under the key `seed` (derived as the filter derives its own):
+    trajectory m is particle m of a filter with that seed that never resamples — its reset! draw for x_0 with sample_initial (else
+    x_0 = mean(initial_density)), its predict! noise at Philox step step0 + t.  Measurement noise is drawn from the Gaussian
+    measurement_density, also for a model with a likelihood of its own.  The filter itself is not changed."""
+    T, u = _sim_inputs(pf.nu, T_or_u, int(M), du, u_per_trajectory, rng)
+    x, y = pf._h.simulate(M, T, u, u_per_trajectory, t_index0, seed, step0, _sim_flags(dynamics_noise, measurement_noise, sample_initial),
+                          states=states)
+    return x, u, y
+
+
 # ---------------------------------------------------------------------------------------------------
 # banks of independent filters (parameter sweeps; reference test/runtests.jl:412-417)
 # ---------------------------------------------------------------------------------------------------
@@ -1000,3 +1049,12 @@ class FilterBank:
     def forward(self, u, y, ll_steps=False):
         self._h.reset()
         return self._h.run(u, y, t_index0=0.0, ll_steps=ll_steps)
+
+    def simulate(self, T_or_u, M, du=None, *, seed=0, step0=0, dynamics_noise=True, measurement_noise=True, sample_initial=False, states=True,
+                 u_per_trajectory=False, t_index0=0.0, rng=None):
+        """x, u, y = simulate_batch of every filter of the bank, filter k with its own parameters and the key seed + k (llpf_bank_simulate):
+        x [F, T, M, nx] (None with states=False), y [F, T, M, ny]; u [T, nu] shared, or [F, M, T, nu] with u_per_trajectory."""
+        T, u = _sim_inputs(self._h.nu, T_or_u, int(M), du, u_per_trajectory, rng, lead=(self.n_filters,) if u_per_trajectory else ())
+        x, y = self._h.simulate(M, T, u, u_per_trajectory, t_index0, seed, step0, _sim_flags(dynamics_noise, measurement_noise, sample_initial),
+                                states=states)
+        return x, u, y

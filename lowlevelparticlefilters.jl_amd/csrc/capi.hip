@@ -90,6 +90,7 @@ static void test_throw(const char* site) {
 #include "host/smooth.hpp"
 #include "host/access.hpp"
 #include "host/mbank.hpp"
+#include "host/simulate.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -190,6 +191,17 @@ int llpf_bank_aux_run(llpf_bank* b, const double* U, const double* Y, int64_t T,
     if (!b) return fail(LLPF_ERR_ARG, "null bank");
     return bank_aux_run(b->bank, U, Y, T, mode, ll_total, ll_steps, nullptr, nullptr, nullptr, nullptr);
 } LLPF_GUARD(llpf_bank_aux_run)
+
+int llpf_simulate(llpf_filter* f, int64_t M, int64_t T, const double* U, int32_t u_per_trajectory, double t_index0,
+                  uint64_t seed, uint32_t step0, int32_t flags, double* X, double* Y) LLPF_TRY {
+    NEEDF(f);
+    return bank_simulate(f->bank, M, T, U, u_per_trajectory, t_index0, seed, step0, flags, X, Y);
+} LLPF_GUARD(llpf_simulate)
+int llpf_bank_simulate(llpf_bank* b, int64_t M, int64_t T, const double* U, int32_t u_per_trajectory, double t_index0,
+                       uint64_t seed, uint32_t step0, int32_t flags, double* X, double* Y) LLPF_TRY {
+    if (!b) return fail(LLPF_ERR_ARG, "null bank");
+    return bank_simulate(b->bank, M, T, U, u_per_trajectory, t_index0, seed, step0, flags, X, Y);
+} LLPF_GUARD(llpf_bank_simulate)
 
 int llpf_rb_get_covariance(llpf_filter* f, double* R) LLPF_TRY {
     NEEDF(f);

@@ -259,6 +259,7 @@ struct ResArgs {
 };
 
 // ---- end of the part the run-time compiled user-model kernels see (tools/gen_jit_prelude.py cuts here) ----
+#include "kernels/sim_args.hpp"
 // launchers (kernels.hip)
 hipError_t launch_init(const BankDev& b, uint32_t step, int init_anc, hipStream_t s);
 hipError_t launch_init_user(const BankDev& b, const double* zero_u, uint32_t step, int init_anc, hipStream_t s);   // kernels/jit.hpp: UserModel::initial
@@ -312,5 +313,12 @@ int jit_compile_user_model(const char* device_src, int nx, int ny, std::string& 
 bool rbfull_supported(int fn_kind, int nn, int nl, int ny);
 int rbfull_rows(int nn, int nl);   // rows of the particle plane: xn, xl, packed R
 unsigned rbfull_grid_x(const BankDev& b, int nl, int mode);   // workgroups along x of a k_rbfull launch (persistent for the 8x8 form)
+// trajectories of a filter's model (k_simulate.hip; kernels/simulate.hpp): simulate_prepare compiles the k_simulate of a run-time compiled
+// model on its first use (0, or -1 with `err` set); launch_simulate runs one chunk of steps for F filters
+int simulate_prepare(int model_id, std::string& err);
+hipError_t launch_simulate(int model_id, int nx, int ny, const ModelD* models, int F, const SimArgs& a, hipStream_t s);
+// kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
+bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
+const char* jit_prelude();
 
 }  // namespace llpf

@@ -165,6 +165,13 @@ hipError_t launch_smooth_fx_user(const BankDev& b, const SmoothArgs& a, hipStrea
     void* args[] = {&bd, &models, &aa};
     return hipModuleLaunchKernel(fn, (unsigned)((b.N + BLOCK - 1) / BLOCK), 1, 1, BLOCK, 1, 1, 0, s, args, nullptr);
 }
+bool jit_model_source(int model_id, std::string& src, int& nx, int& ny) {
+    JitModel* jm = jit_model(model_id);
+    if (!jm) return false;
+    src = jm->src; nx = jm->nx; ny = jm->ny;
+    return true;
+}
+const char* jit_prelude() { return LLPF_JIT_PRELUDE; }
 int jit_model_traits(int model_id) { JitModel* jm = jit_model(model_id); return jm ? jm->traits : -1; }
 // reset! of a model with an initial density of its own (UserModel::initial)
 hipError_t launch_init_user(const BankDev& b, const double* zero_u, uint32_t step, int init_anc, hipStream_t s) {

@@ -35,7 +35,7 @@ import LowLevelParticleFilters: AbstractParticleFilter, ParticleFilteringSolutio
 export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter, GPURBPF, GPUFilterBank, GPUMultiBank,
        LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMeasurement, GaussianLikelihood,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
-       seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model
+       seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch
 
 const LIB = get(ENV, "LLPF_HIP_LIB", joinpath(@__DIR__, "..", "libllpf_hip.so"))
 const MAXD = 16          # LLPF_MAX_DIM: states / outputs
@@ -822,6 +822,47 @@ function loglik_multi(b::GPUFilterBank, U::Array{Float64,3}, Y::Array{Float64,3}
     check(ccall((:llpf_bank_run_multi, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                 b.h, U, Y, T, 1.0, ll, C_NULL, xm))
     ll, xm
+end
+
+# ---- data from the model on the device: M trajectories of the reference's simulate(pf, T, du) (src/filtering.jl:457-477), llpf_simulate ----
+sim_flags(dn, mn, si) = Int32((dn ? 1 : 0) | (mn ? 2 : 0) | (si ? 4 : 0))      # LLPF_SIM_DYNAMICS_NOISE | _MEASUREMENT_NOISE | _SAMPLE_INITIAL
+"""
+    x, u, y = simulate_batch(pf, U, M; seed = 0, step0 = 0, dynamics_noise = true, measurement_noise = true, sample_initial = false,
+                             states = true, t_index0 = 0.0)
+
+M trajectories of `simulate(pf, T, du)` at once on the device, for every model the filter runs (device snippets with their own `noise` /
+`initial` included; not the RBPF).  `U`: the inputs, nu x T shared by all trajectories or nu x T x M one sequence per trajectory (an
+integer T for a model without inputs).  x: nx x M x T (`nothing` with states = false), y: ny x M x T — column-major, the ABI's
+[T][M][n].  Step t runs at time (t_index0 + t) * Ts.  Trajectory m is particle m of a filter seeded `seed` that never resamples: its
+reset! draw for x_0 with sample_initial (else the mean of the initial density), its predict! noise at Philox step step0 + t; measurement
+noise comes from the Gaussian measurement density.  The filter is not changed.
+"""
+function simulate_batch(pf::GPF, U, M::Integer; seed = 0, step0 = 0, dynamics_noise = true, measurement_noise = true, sample_initial = false,
+                        states = true, t_index0 = 0.0)
+    Um = U isa Integer ? zeros(pf.nu, U) : Array{Float64}(U)
+    T = size(Um, 2)
+    x = states ? zeros(pf.nx, M, T) : nothing
+    y = zeros(pf.ny, M, T)
+    GC.@preserve Um x y check(ccall((:llpf_simulate, LIB), Cint,
+                                    (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int32, Float64, UInt64, UInt32, Int32, Ptr{Float64}, Ptr{Float64}),
+                                    pf.h, M, T, pf.nu > 0 ? pointer(Um) : C_NULL, Int32(ndims(Um) == 3), Float64(t_index0), UInt64(seed),
+                                    UInt32(step0), sim_flags(dynamics_noise, measurement_noise, sample_initial),
+                                    x === nothing ? C_NULL : pointer(x), pointer(y)))
+    x, Um, y
+end
+"as simulate_batch for every filter of the bank, filter k with its own parameters and the key seed + k: U nu x T or nu x T x M x F; x nx x M x T x F, y ny x M x T x F"
+function simulate_batch(b::GPUFilterBank, U, M::Integer; seed = 0, step0 = 0, dynamics_noise = true, measurement_noise = true,
+                        sample_initial = false, states = true, t_index0 = 0.0)
+    Um = U isa Integer ? zeros(b.nu, U) : Array{Float64}(U)
+    T = size(Um, 2)
+    x = states ? zeros(b.nx, M, T, b.F) : nothing
+    y = zeros(b.ny, M, T, b.F)
+    GC.@preserve Um x y check(ccall((:llpf_bank_simulate, LIB), Cint,
+                                    (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int32, Float64, UInt64, UInt32, Int32, Ptr{Float64}, Ptr{Float64}),
+                                    b.h, M, T, b.nu > 0 ? pointer(Um) : C_NULL, Int32(ndims(Um) == 4), Float64(t_index0), UInt64(seed),
+                                    UInt32(step0), sim_flags(dynamics_noise, measurement_noise, sample_initial),
+                                    x === nothing ? C_NULL : pointer(x), pointer(y)))
+    x, Um, y
 end
 
 # ---- the same sweep sharded over the GPUs of a node (llpf_mbank_*): filter k on shard k mod n_shards, one RCCL all-reduce
