@@ -368,6 +368,39 @@ int  llpf_simulate(llpf_filter* f, int64_t M, int64_t T, const double* U, int32_
 int  llpf_bank_simulate(llpf_bank* b, int64_t M, int64_t T, const double* U, int32_t u_per_trajectory, double t_index0,
                         uint64_t seed, uint32_t step0, int32_t flags, double* X, double* Y);
 
+/* ---- banks of Kalman filters (the reference's KalmanFilter(A, B, C, D, R1, R2, d0), src/kalman.jl) ----------------------------------
+ * n_filters independent Kalman filters with constant matrices, one GPU thread each, in the operation order of csrc/shared/llpf_kalman.h
+ * (that header is the definition: a host build of it gives the same bits):
+ *   x' = A x + B u + w, w ~ N(0, R1);  y = C x + D u + e, e ~ N(0, R2);  x_0 ~ d0;  alpha = 1, no cross-covariance R12.
+ * The descriptors are llpf_model with model_id LLPF_MODEL_LINEAR_GAUSSIAN (the ones a bank of particle filters is built from):
+ * A, B, C, R1 = cov(dynamics_density), R2 = cov(measurement_density), d0 = initial_density, every covariance kind; D [n_filters][ny][nu]
+ * or NULL (zero).  nx <= 8, ny <= 4, nu <= 8, the same for every filter.  LLPF_ERR_ARG: other dimensions, a noise density with a
+ * non-zero mean, an R2 or cov(d0) that is not positive definite.  A filter whose S = C R C' + R2 loses definiteness during a run is NaN
+ * from that step on; the run returns LLPF_OK and the other filters are unaffected.
+ * Step t of a run (forward_trajectory, src/filtering.jl:343-365): x[t], R[t] the prior; correct! (a row of Y whose first element is
+ * NaN is missing: skipped, ll 0, e NaN) gives ll[t], e[t] and the posterior xt[t], Rt[t]; predict! gives the prior of t + 1.  The state
+ * carries from run to run: run(a) then run(b) is run(a + b).  loglik and forward_trajectory reset first. */
+typedef struct llpf_kalman_bank llpf_kalman_bank;
+typedef struct llpf_kalman_outputs {     /* every output optional (NULL); time-major like llpf_bank_run_multi's xmean */
+    uint32_t struct_size;                /* sizeof(llpf_kalman_outputs): guards growth */
+    uint32_t pad;
+    double *ll_steps, *x, *xt, *R, *Rt, *e;   /* ll_steps [T][F]; x, xt [T][F][nx]; R, Rt [T][F][nx][nx]; e [T][F][ny] */
+} llpf_kalman_outputs;
+int  llpf_kalman_bank_create(int32_t device, const llpf_model* models, const double* D /* [F][ny][nu] or NULL */, int32_t n_filters,
+                             llpf_kalman_bank** out);
+int  llpf_kalman_bank_destroy(llpf_kalman_bank* b);
+/* reset!: x = mean(d0), R = cov(d0) */
+int  llpf_kalman_bank_reset(llpf_kalman_bank* b);
+/* new matrices for every filter (same dimensions, nothing reallocated; the state is left as it is, the next reset uses the new d0) */
+int  llpf_kalman_bank_set_models(llpf_kalman_bank* b, const llpf_model* models, const double* D);
+/* T steps of every filter.  per_filter bit 0: U is [F][T][nu] (else [T][nu] shared), bit 1: Y is [F][T][ny] (else [T][ny] shared).
+ * ll_total [F] (optional): the sum of this run's ll[t] in step order; out NULL: nothing per step is stored */
+int  llpf_kalman_bank_run(llpf_kalman_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter,
+                          double* ll_total, const llpf_kalman_outputs* out);
+/* state(kf), covariance(kf) of every filter: x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
+int  llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R);
+int  llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R);
+
 /* ---- sweeps sharded over the GPUs of one node (multi-GPU banks) ------------------------------
  * The same sweep as llpf_bank_*, with filter k on shard k mod n_shards (one shard = one GPU, one stream): the reference's
  * one-filter-per-thread layout (src/smoothing.jl:335-347, test/runtests.jl:412-417) with GPUs for threads.  Filters never

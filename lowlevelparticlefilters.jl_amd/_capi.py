@@ -39,6 +39,13 @@ SYMBOLS = {
     "llpf_bank_aux_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, _dp],
     "llpf_simulate": [_vp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_int32, _dp, _dp],
     "llpf_bank_simulate": [_vp, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_int32, _dp, _dp],
+    "llpf_kalman_bank_create": [C.c_int32, C.POINTER(S.Model), _dp, C.c_int32, C.POINTER(_vp)],
+    "llpf_kalman_bank_destroy": [_vp],
+    "llpf_kalman_bank_reset": [_vp],
+    "llpf_kalman_bank_set_models": [_vp, C.POINTER(S.Model), _dp],
+    "llpf_kalman_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_kalman_bank_get_state": [_vp, _dp, _dp],
+    "llpf_kalman_bank_set_state": [_vp, _dp, _dp],
     "llpf_num_particles": [_vp, _ip],
     "llpf_index": [_vp, _ip],
     "llpf_get_particles": [_vp, _dp],
@@ -447,6 +454,79 @@ class FilterHandle:
         n = np.zeros(PROF_CLASSES, dtype=np.int64)
         check(self.L.llpf_get_profile(self.h, dptr(ms), iptr(n)))
         return ms, n
+
+
+KALMAN_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+
+
+class KalmanBankHandle:
+    """RAII wrapper of an `llpf_kalman_bank*` (independent Kalman filters with constant matrices on one device)."""
+
+    def __init__(self, device, models, D=None):
+        self.L = lib()
+        self.h = _vp()
+        self.F = len(models)
+        m0 = models[0]
+        self.nx, self.nu, self.ny = m0.nx, m0.nu, m0.ny
+        arr = (S.Model * self.F)(*models)
+        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
+        check(self.L.llpf_kalman_bank_create(int(device), arr, dptr(D), self.F, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.llpf_kalman_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(self.L.llpf_kalman_bank_reset(self.h))
+
+    def set_models(self, models, D=None):
+        arr = (S.Model * self.F)(*models)
+        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
+        check(self.L.llpf_kalman_bank_set_models(self.h, arr, dptr(D)))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
+        """T steps of every filter: U [T, nu] or [F, T, nu] (u_per_filter), Y [T, ny] or [F, T, ny] (y_per_filter).  Returns
+        {"ll": [F], name: array} for every name of `outputs` (KALMAN_OUTPUTS), time-major: ll_steps [T, F], x / xt [T, F, nx],
+        R / Rt [T, F, nx, nx], e [T, F, ny]."""
+        F, nx, nu, ny = self.F, self.nx, self.nu, self.ny
+        Y = f64(Y)
+        T = Y.shape[1] if y_per_filter else Y.reshape(-1, ny).shape[0]
+        Y = Y.reshape((F, T, ny) if y_per_filter else (T, ny))
+        if nu > 0:
+            U = f64(U).reshape((F, T, nu) if u_per_filter else (T, nu))
+        else:
+            U, u_per_filter = None, False
+        shapes = {"ll_steps": (T, F), "x": (T, F, nx), "xt": (T, F, nx), "R": (T, F, nx, nx), "Rt": (T, F, nx, nx), "e": (T, F, ny)}
+        res = {k: np.empty(shapes[k]) for k in outputs}
+        out = None
+        if res:
+            out = S.KalmanOutputs()
+            out.struct_size = C.sizeof(S.KalmanOutputs)
+            for k, a in res.items():
+                setattr(out, k, dptr(a))
+        ll = np.empty(F)
+        check(self.L.llpf_kalman_bank_run(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
+                                          None if out is None else C.byref(out)))
+        res["ll"] = ll
+        return res
+
+    def get_state(self):
+        x = np.empty((self.F, self.nx))
+        R = np.empty((self.F, self.nx, self.nx))
+        check(self.L.llpf_kalman_bank_get_state(self.h, dptr(x), dptr(R)))
+        return x, R
+
+    def set_state(self, x, R):
+        x = f64(x).reshape(self.F, self.nx)
+        R = f64(R).reshape(self.F, self.nx, self.nx)
+        check(self.L.llpf_kalman_bank_set_state(self.h, dptr(x), dptr(R)))
 
 
 class BankHandle:

@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "covariance", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -372,14 +372,136 @@ _DESCRIPTORS = (LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMea
 
 
 class KalmanFilter:
-    """KalmanFilter(A, B, C, D, R1, R2, d0) — descriptor of the inner filter of an RBPF (reference src/kalman.jl; only
-    constant matrices and D = 0 are supported)."""
+    """KalmanFilter(A, B, C, D, R1, R2, d0; Ts, device) — the reference's Kalman filter with constant matrices (src/kalman.jl):
+    x' = A x + B u + w, w ~ N(0, R1);  y = C x + D u + e, e ~ N(0, R2);  x_0 ~ d0.  Runs on the device as a bank of one filter
+    (llpf_kalman_bank_*), created on first use: as the inner filter of an RBPF it is a descriptor only (D = 0 there).
+    R1, R2: matrices (a 1-D array: the diagonal; a float: sigma^2 I); d0: MvNormal.  nx <= 8, ny <= 4, nu <= 8."""
 
-    def __init__(self, A, B, C, D, R1, R2, d0):
-        if np.any(np.asarray(D) != 0):
-            raise NotImplementedError("D != 0")
+    def __init__(self, A, B, C, D, R1, R2, d0, *, Ts=1.0, device=0):
         self.A, self.B, self.C, self.D = np.atleast_2d(np.asarray(A, float)), B, C, D
         self.R1, self.R2, self.d0 = np.atleast_2d(np.asarray(R1, float)), np.atleast_2d(np.asarray(R2, float)), d0
+        self._R1_in, self._R2_in = R1, R2
+        self.Ts, self.device = float(Ts), int(device)
+        self._handle = None
+
+    def _model(self):
+        """(llpf_model, D [ny, nu]) of this filter"""
+        nx = self.A.shape[0]
+        Cm = np.atleast_2d(np.asarray(self.C, float))
+        ny = Cm.shape[0]
+        B = np.zeros((nx, 0)) if self.B is None else np.asarray(self.B, float).reshape(nx, -1)
+        nu = B.shape[1]
+        cov = lambda c, n: MvNormal(np.zeros(n), c if np.ndim(c) < 2 else np.atleast_2d(np.asarray(c, float))).struct()
+        d0 = self.d0.struct() if isinstance(self.d0, MvNormal) else self.d0
+        m = S.make_lg_model(self.A, B, Cm, cov(self._R1_in, nx), cov(self._R2_in, ny), d0, self.Ts)
+        D = np.broadcast_to(np.asarray(0.0 if self.D is None else self.D, float), (ny, nu)).copy()
+        return m, D
+
+    @property
+    def _h(self):
+        if self._handle is None:
+            m, D = self._model()
+            self._handle = _capi.KalmanBankHandle(self.device, [m], D[None])
+        return self._handle
+
+    @property
+    def nx(self):
+        return self.A.shape[0]
+
+    @property
+    def x(self):
+        """state(kf): the current estimate"""
+        return self._h.get_state()[0][0]
+
+    @property
+    def R(self):
+        """covariance(kf)"""
+        return self._h.get_state()[1][0]
+
+    def _run(self, u, y, outputs=()):
+        y = np.asarray(y, dtype=np.float64)
+        y = y.reshape(y.shape[0], -1) if y.ndim else y.reshape(1, 1)
+        r = self._h.run(None if self._h.nu == 0 else np.asarray(u, dtype=np.float64).reshape(y.shape[0], -1), y, outputs=outputs)
+        return r
+
+
+class KalmanFilteringSolution:
+    """Fields f, u, y, x, xt, R, Rt, ll, e, t of the reference's struct (src/solutions.jl): x, xt [T, nx] the prior and the posterior
+    estimate of every step, R, Rt [T, nx, nx] their covariances, e [T, ny] the innovations (NaN at a missing measurement), ll the sum."""
+
+    def __init__(self, f, u, y, x, xt, R, Rt, ll, e):
+        self.f, self.u, self.y, self.x, self.xt, self.R, self.Rt, self.ll, self.e = f, u, y, x, xt, R, Rt, ll, e
+        self.t = np.arange(x.shape[0]) * f.Ts
+
+
+def covariance(kf):
+    """covariance(kf) — the covariance R of the current estimate of a KalmanFilter"""
+    return kf.R
+
+
+class KalmanFilterBank:
+    """n independent Kalman filters with constant matrices of the same dimensions on one device, one GPU thread each
+    (llpf_kalman_bank_*): the exact log-likelihood of every parameter set of a linear-Gaussian sweep.  `filters_spec` is a list of
+    KalmanFilter or of (A, B, C, D, R1, R2, d0) tuples."""
+
+    def __init__(self, filters_spec, device=0):
+        models, Ds = self._models(filters_spec)
+        self.device = int(device)
+        self._h = _capi.KalmanBankHandle(self.device, models, Ds)
+        self.n_filters = len(models)
+        self.Ts = float(models[0].Ts)
+
+    @staticmethod
+    def _models(filters_spec):
+        kfs = [f if isinstance(f, KalmanFilter) else KalmanFilter(*f) for f in filters_spec]
+        md = [kf._model() for kf in kfs]
+        return [m for m, _ in md], np.stack([D for _, D in md])
+
+    @classmethod
+    def from_filter_bank(cls, bank, device=None):
+        """the Kalman twin of a FilterBank of linear-Gaussian filters: the same descriptors, D = 0"""
+        self = cls.__new__(cls)
+        models = list(bank._models)
+        if any(m.model_id != S.MODEL_LINEAR_GAUSSIAN for m in models):
+            raise TypeError("from_filter_bank: every filter of the bank must be linear-Gaussian")
+        self.device = int(bank._h.cfg.device if device is None else device)
+        self._h = _capi.KalmanBankHandle(self.device, models, None)
+        self.n_filters = len(models)
+        self.Ts = float(models[0].Ts)
+        return self
+
+    def set_parameters(self, filters_spec):
+        """new matrices for every filter (same dimensions, nothing reallocated: llpf_kalman_bank_set_models)"""
+        models, Ds = self._models(filters_spec)
+        self._h.set_models(models, Ds)
+
+    def reset(self):
+        self._h.reset()
+
+    def state(self):
+        """(x [F, nx], R [F, nx, nx]) of every filter"""
+        return self._h.get_state()
+
+    def _io(self, u, y):
+        y = np.asarray(y, dtype=np.float64)
+        y_per = y.ndim == 3
+        if self._h.nu == 0 or u is None:
+            return None, False, y, y_per
+        u = np.asarray(u, dtype=np.float64)
+        return u, u.ndim == 3, y, y_per
+
+    def loglik(self, u, y):
+        """[loglik(kf_k, u, y) for k]: reset, then T update! steps.  u [T, nu] / y [T, ny] shared, or [F, T, n] per filter (by ndim)."""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.run(u, y, up, yp)["ll"]
+
+    def forward(self, u, y, outputs=_capi.KALMAN_OUTPUTS):
+        """forward_trajectory of every filter: {"ll": [F], "ll_steps": [T, F], "x", "xt": [T, F, nx], "R", "Rt": [T, F, nx, nx],
+        "e": [T, F, ny]} for the names in `outputs`"""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.run(u, y, up, yp, outputs=outputs)
 
 
 class RBMeasurementModel:
@@ -414,6 +536,8 @@ class RBPF(_AbstractParticleFilter):
 
     def __init__(self, N, kf, dynamics, nl_measurement_model, R1n, d0n, *, An=None, nu=-1, Ts=1.0, p=None, rng=None,
                  resample_threshold=0.1, names=None, device=0):
+        if np.any(np.asarray(0.0 if kf.D is None else kf.D) != 0):
+            raise NotImplementedError("D != 0")
         as_g = lambda d: d.struct() if isinstance(d, MvNormal) else d
         as_cov = lambda d, n: d if not isinstance(d, (np.ndarray, list)) else MvNormal(np.zeros(n), np.atleast_2d(np.asarray(d, float)))
         nn = 4 if isinstance(dynamics, QuadTankDynamics) else np.atleast_2d(np.asarray(dynamics.A, float)).shape[0]
@@ -513,7 +637,7 @@ class ParticleFilteringSolution:
 # verbs
 # ---------------------------------------------------------------------------------------------------
 def reset(pf):
-    """reset!(pf) — reference src/filtering.jl:4-14."""
+    """reset!(pf) — reference src/filtering.jl:4-14 (src/kalman.jl:159-164 for a KalmanFilter)."""
     pf._h.reset()
 
 
@@ -549,7 +673,11 @@ def correct(pf, u, y, p=None, t=None):
 
 def update(pf, u, y, *args, **kw):
     """ll, 0 = update!(pf, u, y, p, t) — reference src/filtering.jl:181-185;
-    update!(pf::AuxiliaryParticleFilter, u, y, y1, p, t) — :187-191."""
+    update!(pf::AuxiliaryParticleFilter, u, y, y1, p, t) — :187-191.
+    ll, e = update!(kf::KalmanFilter, u, y): correct! then predict!, continuing the filter's state."""
+    if isinstance(pf, KalmanFilter):
+        r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], ("e",))
+        return float(r["ll"][0]), r["e"][0, 0]
     if isinstance(pf, AuxiliaryParticleFilter):
         y1 = args[0] if args else kw.get("y1")
         return pf._h.aux_update(u, y1, _t(pf, _pt(args, kw, 1)[1])), 0
@@ -561,7 +689,12 @@ def forward_trajectory(pf, u, y, p=None, quantiles=None):
     filter).  The whole T-step loop is enqueued on the device; callbacks of the reference signature are not
     supported (a fused on-device loop cannot call back into the host) — drive update() step by step if needed.
     quantiles=q (not for the auxiliary filter): weighted_quantile(sol, q) of every timestep is computed on the device inside the run loop
-    (llpf_run's xquant output) and kept in the solution; weighted_quantile(sol, q') with q' among q is then served from it."""
+    (llpf_run's xquant output) and kept in the solution; weighted_quantile(sol, q') with q' among q is then served from it.
+    For a KalmanFilter: the reference's KalmanFilteringSolution (src/filtering.jl forward_trajectory), computed on the device."""
+    if isinstance(pf, KalmanFilter):
+        reset(pf)
+        r = pf._run(u, y, _capi.KALMAN_OUTPUTS)
+        return KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
     reset(pf)
     if isinstance(pf, AuxiliaryParticleFilter):
         if quantiles is not None:
@@ -575,8 +708,10 @@ def forward_trajectory(pf, u, y, p=None, quantiles=None):
 def loglik(pf, u, y, p=None):
     """loglik(pf, u, y, p) — reference src/smoothing.jl:227-230 (reset!, then sum of update! with
     t = index(pf)*Ts, i.e. the first step is at t = 1*Ts); :232-236 for the auxiliary filter (t = (k-1)*Ts, the
-    last step is an update! of the wrapped filter)."""
+    last step is an update! of the wrapped filter).  For a KalmanFilter: reset!, then the sum of T update! steps (exact)."""
     reset(pf)
+    if isinstance(pf, KalmanFilter):
+        return float(pf._run(u, y)["ll"][0])
     if isinstance(pf, AuxiliaryParticleFilter):
         return pf._h.run_aux(u, y, mode=1)["ll"]
     return pf._h.run(u, y, t_index0=1.0)["ll"]
@@ -845,6 +980,8 @@ def expweights(pf):
 
 
 def state(pf):
+    if isinstance(pf, KalmanFilter):
+        return pf.x
     return pf.state
 
 
@@ -1035,11 +1172,13 @@ class FilterBank:
         self.rng = 0 if rng is None else int(rng)
         cfg = S.make_config(models[0], N, S.PARTICLE_FILTER, resampling_strategy.code, resample_threshold, self.rng, device)
         self._h = _capi.BankHandle(cfg, models)
+        self._models = models
         self.n_filters = len(models)
 
     def set_parameters(self, filters_spec):
         """new (dynamics, measurement, df, dg, d0) for every filter of the bank, nothing reallocated (llpf_bank_set_models)"""
-        self._h.set_models([_build_model(dy, me, df, dg, d0, self.Ts) for (dy, me, df, dg, d0) in filters_spec])
+        self._models = [_build_model(dy, me, df, dg, d0, self.Ts) for (dy, me, df, dg, d0) in filters_spec]
+        self._h.set_models(self._models)
 
     def loglik(self, u, y):
         """[loglik(pf_k, u, y) for k] — reference src/smoothing.jl:227-230 applied to every filter."""

@@ -15,6 +15,7 @@
 
 #include "engine.hpp"
 #include "shared/llpf_rbkf.h"
+#include "shared/llpf_kalman.h"
 
 using namespace llpf;
 
@@ -91,6 +92,7 @@ static void test_throw(const char* site) {
 #include "host/access.hpp"
 #include "host/mbank.hpp"
 #include "host/simulate.hpp"
+#include "host/kalman.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -202,6 +204,30 @@ int llpf_bank_simulate(llpf_bank* b, int64_t M, int64_t T, const double* U, int3
     if (!b) return fail(LLPF_ERR_ARG, "null bank");
     return bank_simulate(b->bank, M, T, U, u_per_trajectory, t_index0, seed, step0, flags, X, Y);
 } LLPF_GUARD(llpf_bank_simulate)
+
+// ---- banks of Kalman filters (host/kalman.hpp) ----
+int llpf_kalman_bank_create(int32_t device, const llpf_model* models, const double* D, int32_t n_filters, llpf_kalman_bank** out) LLPF_TRY {
+    if (!out) return fail(LLPF_ERR_ARG, "null out pointer");
+    *out = nullptr;
+    std::unique_ptr<llpf_kalman_bank> b(new (std::nothrow) llpf_kalman_bank());
+    if (!b) return fail(LLPF_ERR_ALLOC, "out of host memory");
+    CHK(kalman_create(device, models, D, n_filters, *b));
+    *out = b.release();
+    return LLPF_OK;
+} LLPF_GUARD(llpf_kalman_bank_create)
+int llpf_kalman_bank_destroy(llpf_kalman_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_kalman_bank_destroy)
+int llpf_kalman_bank_reset(llpf_kalman_bank* b) LLPF_TRY { NEEDF(b); return kalman_reset(*b); } LLPF_GUARD(llpf_kalman_bank_reset)
+int llpf_kalman_bank_set_models(llpf_kalman_bank* b, const llpf_model* models, const double* D) LLPF_TRY {
+    NEEDF(b);
+    return kalman_set_models(*b, models, D);
+} LLPF_GUARD(llpf_kalman_bank_set_models)
+int llpf_kalman_bank_run(llpf_kalman_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                         const llpf_kalman_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return kalman_run(*b, U, Y, T, per_filter, ll_total, out);
+} LLPF_GUARD(llpf_kalman_bank_run)
+int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kalman_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
+int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kalman_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
 
 int llpf_rb_get_covariance(llpf_filter* f, double* R) LLPF_TRY {
     NEEDF(f);

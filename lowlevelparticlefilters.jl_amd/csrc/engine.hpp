@@ -260,6 +260,21 @@ struct ResArgs {
 
 // ---- end of the part the run-time compiled user-model kernels see (tools/gen_jit_prelude.py cuts here) ----
 #include "kernels/sim_args.hpp"
+// arguments of k_kalman (kernels/kalman.hpp): one launch is one chunk of steps [t0, t0 + Tc) of F Kalman filters, one thread per filter.
+// Device arrays are SoA / time-major: a wave's 64 lanes read and write whole lines.
+struct KalmanArgs {
+    const double* par;       // [npar][F] the constant matrices (shared/llpf_kalman.h: LLPF_KF_OFF_*)
+    double* state;           // [nx + np + 1][F] x, packed R, the run's running ll_total: in at t0, out at t0 + Tc
+    const double* u;         // inputs of the chunk: [Tc][nu] shared, or [Tc][F][nu] (u_per = 1); unused when nu = 0
+    const double* y;         // measurements of the chunk: [Tc][ny] shared, or [Tc][F][ny] (y_per = 1)
+    double *ll, *x, *xt, *R, *Rt, *e;   // per-step outputs of the chunk, each optional: [Tc][F], [Tc][F][nx], [Tc][F][nx][nx], [Tc][F][ny]
+    int64_t F;
+    int32_t Tc, nu;
+    int32_t u_per, y_per;
+    int32_t first;           // 1: the first chunk of a run (ll_total starts at 0)
+    int32_t pad;
+    int64_t par_tstride;     // always 0 (kernels/kalman.hpp: KF_RELOAD)
+};
 // launchers (kernels.hip)
 hipError_t launch_init(const BankDev& b, uint32_t step, int init_anc, hipStream_t s);
 hipError_t launch_init_user(const BankDev& b, const double* zero_u, uint32_t step, int init_anc, hipStream_t s);   // kernels/jit.hpp: UserModel::initial
@@ -317,6 +332,8 @@ unsigned rbfull_grid_x(const BankDev& b, int nl, int mode);   // workgroups alon
 // model on its first use (0, or -1 with `err` set); launch_simulate runs one chunk of steps for F filters
 int simulate_prepare(int model_id, std::string& err);
 hipError_t launch_simulate(int model_id, int nx, int ny, const ModelD* models, int F, const SimArgs& a, hipStream_t s);
+// banks of Kalman filters (k_kalman.hip; kernels/kalman.hpp): one chunk of steps, nx in 1..8, ny in 1..4
+hipError_t launch_kalman(int nx, int ny, const KalmanArgs& a, hipStream_t s);
 // kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
 bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
 const char* jit_prelude();

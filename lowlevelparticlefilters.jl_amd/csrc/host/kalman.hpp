@@ -1,0 +1,256 @@
+// host/kalman.hpp — banks of Kalman filters with constant matrices (llpf_kalman_bank_*; kernel: kernels/kalman.hpp, step:
+// shared/llpf_kalman.h).  Part of capi.hip (one translation unit).
+// ------------------------------------------------------------------------------------------------
+// Device layout: the constants par [npar][F] and the state [nx + np + 1][F] (x, packed R, the running ll_total of a run), SoA so that
+// lane f of a wave reads column f.  A run drives T in chunks as host/simulate.hpp does: chunk c runs into device staging buffer c % 2, a
+// second stream copies it to pinned buffer c % 2 while chunk c + 1 runs, and the host moves it to the caller's arrays while chunk c + 2
+// runs.  The state carries from chunk to chunk (and from run to run) in the device buffer, so the prefix of a long run is a short run and
+// run(a) followed by run(b) is run(a + b), bit for bit.  A run that asks for ll_total only stages nothing per step.
+constexpr size_t KF_CHUNK_BYTES = (size_t)64 << 20;
+constexpr int64_t KF_CHUNK_STEPS = 256;
+
+struct llpf_kalman_bank : BankStream {
+    int F = 0, nx = 0, ny = 0, nu = 0;
+    int np = 0, npar = 0, nstate = 0;
+    DevBuf<double> d_par, d_state;
+    std::vector<double> h_init;       // [nstate][F] what reset loads: mean(d0), packed cov(d0), 0
+};
+
+// models (+ D [F][ny][nu] or NULL) -> the SoA constants and initial state; every check that needs no device
+static int kalman_pack(const llpf_model* models, const double* D, int32_t F, int& nx, int& ny, int& nu, std::vector<double>& par,
+                       std::vector<double>& init) {
+    if (!models) return fail(LLPF_ERR_ARG, "kalman: models is null");
+    if (F < 1) return fail(LLPF_ERR_ARG, "kalman: n_filters must be >= 1");
+    nx = models[0].nx; ny = models[0].ny; nu = models[0].nu;
+    if (nx < 1 || nx > LLPF_KF_MAXX || ny < 1 || ny > LLPF_KF_MAXY || nu < 0 || nu > LLPF_KF_MAXU)
+        return fail(LLPF_ERR_ARG, "kalman: nx must be in 1..8, ny in 1..4 and nu in 0..8");
+    const int np = LLPF_KF_NP(nx), npar = LLPF_KF_NPAR(nx, ny, nu), nstate = nx + np + 1;
+    par.assign((size_t)npar * F, 0.0);
+    init.assign((size_t)nstate * F, 0.0);
+    double S[MAXD * MAXD];
+    for (int f = 0; f < F; ++f) {
+        const llpf_model& m = models[f];
+        const std::string at = "kalman: filter " + std::to_string(f) + ": ";
+        if (m.model_id != LLPF_MODEL_LINEAR_GAUSSIAN) return fail(LLPF_ERR_ARG, at + "model_id must be LLPF_MODEL_LINEAR_GAUSSIAN");
+        if (m.nx != nx || m.ny != ny || m.nu != nu) return fail(LLPF_ERR_ARG, at + "dimensions differ from filter 0's");
+        const llpf_gaussian* g[3] = {&m.dynamics_density, &m.measurement_density, &m.initial_density};
+        const int dims[3] = {nx, ny, nx};
+        for (int k = 0; k < 3; ++k) {
+            if (g[k]->dim != dims[k]) return fail(LLPF_ERR_ARG, at + "a density's dimension does not match the model");
+            if (g[k]->kind != LLPF_COV_SCAL && g[k]->kind != LLPF_COV_DIAG && g[k]->kind != LLPF_COV_FULL)
+                return fail(LLPF_ERR_ARG, at + "unknown covariance kind");
+        }
+        for (int k = 0; k < 2; ++k)
+            for (int i = 0; i < dims[k]; ++i)
+                if (g[k]->mu[i] != 0.0) return fail(LLPF_ERR_ARG, at + "the noise densities must have zero mean");
+        GaussD gd;                                // positive definiteness of R2 and P0: the host Cholesky of gauss_prepare
+        if (gauss_prepare(&m.measurement_density, &gd) != 0) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
+        if (gauss_prepare(&m.initial_density, &gd) != 0) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
+        auto put = [&](int e, double v) { par[(size_t)e * F + f] = v; };
+        for (int i = 0; i < nx * nx; ++i) put(LLPF_KF_OFF_A + i, m.A[i]);
+        for (int i = 0; i < ny * nx; ++i) put(LLPF_KF_OFF_C(nx) + i, m.C[i]);
+        gauss_cov_dense(&m.dynamics_density, S);
+        for (int r = 0; r < nx; ++r) for (int c = 0; c <= r; ++c) put(LLPF_KF_OFF_R1(nx, ny) + llpf_kf_idx(r, c), S[r * nx + c]);
+        gauss_cov_dense(&m.measurement_density, S);
+        for (int r = 0; r < ny; ++r) for (int c = 0; c <= r; ++c) put(LLPF_KF_OFF_R2(nx, ny) + llpf_kf_idx(r, c), S[r * ny + c]);
+        for (int i = 0; i < nx * nu; ++i) put(LLPF_KF_OFF_B(nx, ny) + i, m.B[i]);
+        for (int i = 0; i < ny * nu; ++i) put(LLPF_KF_OFF_D(nx, ny, nu) + i, D ? D[(size_t)f * ny * nu + i] : 0.0);
+        gauss_cov_dense(&m.initial_density, S);
+        for (int i = 0; i < nx; ++i) init[(size_t)i * F + f] = m.initial_density.mu[i];
+        for (int r = 0; r < nx; ++r) for (int c = 0; c <= r; ++c) init[(size_t)(nx + llpf_kf_idx(r, c)) * F + f] = S[r * nx + c];
+    }
+    return LLPF_OK;
+}
+
+static int kalman_create(int32_t device, const llpf_model* models, const double* D, int32_t F, llpf_kalman_bank& b) {
+    std::vector<double> par;
+    CHK(kalman_pack(models, D, F, b.nx, b.ny, b.nu, par, b.h_init));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(LLPF_ERR_NO_DEVICE, "no HIP device visible; this engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(LLPF_ERR_ARG, "device ordinal out of range");
+    test_throw("kalman_create");
+    b.F = F;
+    b.np = LLPF_KF_NP(b.nx);
+    b.npar = LLPF_KF_NPAR(b.nx, b.ny, b.nu);
+    b.nstate = b.nx + b.np + 1;
+    b.device = device;
+    HIPC(hipSetDevice(device));
+    HIPC(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    CHK(b.d_par.ensure(par.size()));
+    CHK(b.d_state.ensure(b.h_init.size()));
+    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+static int kalman_reset(llpf_kalman_bank& b) {
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+static int kalman_set_models(llpf_kalman_bank& b, const llpf_model* models, const double* D) {
+    std::vector<double> par, init;
+    int nx = 0, ny = 0, nu = 0;
+    CHK(kalman_pack(models, D, b.F, nx, ny, nu, par, init));
+    if (nx != b.nx || ny != b.ny || nu != b.nu) return fail(LLPF_ERR_ARG, "kalman: set_models must keep the dimensions of the bank");
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    b.h_init.swap(init);
+    return LLPF_OK;
+}
+
+// x [F][nx], R [F][nx][nx] (either may be NULL) of the current state
+static int kalman_get_state(llpf_kalman_bank& b, double* x, double* R) {
+    std::vector<double> h((size_t)b.nstate * b.F);
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(h.data(), b.d_state, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    const size_t F = (size_t)b.F;
+    for (size_t f = 0; f < F; ++f) {
+        if (x) for (int i = 0; i < b.nx; ++i) x[f * b.nx + i] = h[i * F + f];
+        if (R) for (int r = 0; r < b.nx; ++r) for (int c = 0; c < b.nx; ++c) R[(f * b.nx + r) * b.nx + c] = h[(b.nx + llpf_kf_idx(r, c)) * F + f];
+    }
+    return LLPF_OK;
+}
+
+// the lower triangle of R is taken (R is a covariance: the upper one is not read)
+static int kalman_set_state(llpf_kalman_bank& b, const double* x, const double* R) {
+    if (!x || !R) return fail(LLPF_ERR_ARG, "kalman: x and R must both be given");
+    std::vector<double> h((size_t)b.nstate * b.F, 0.0);
+    const size_t F = (size_t)b.F;
+    for (size_t f = 0; f < F; ++f) {
+        for (int i = 0; i < b.nx; ++i) h[i * F + f] = x[f * b.nx + i];
+        for (int r = 0; r < b.nx; ++r) for (int c = 0; c <= r; ++c) h[(b.nx + llpf_kf_idx(r, c)) * F + f] = R[(f * b.nx + r) * b.nx + c];
+    }
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(b.d_state, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+static int kalman_run(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                      const llpf_kalman_outputs* out) {
+    if (T < 1) return fail(LLPF_ERR_ARG, "kalman: T must be >= 1");
+    if (!Y) return fail(LLPF_ERR_ARG, "kalman: Y is null");
+    if (b.nu > 0 && !U) return fail(LLPF_ERR_ARG, "kalman: U is null");
+    if (per_filter & ~3) return fail(LLPF_ERR_ARG, "kalman: per_filter has bits other than 0 and 1");
+    if (out && out->struct_size < sizeof(llpf_kalman_outputs)) return fail(LLPF_ERR_ARG, "kalman: llpf_kalman_outputs.struct_size too small (ABI)");
+    const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu;
+    const bool upf = nu > 0 && (per_filter & 1), ypf = (per_filter & 2) != 0;
+    // the outputs of one step, in staging order: ll, x, xt, R, Rt, e
+    double* dst[6] = {out ? out->ll_steps : nullptr, out ? out->x : nullptr, out ? out->xt : nullptr, out ? out->R : nullptr,
+                      out ? out->Rt : nullptr, out ? out->e : nullptr};
+    const uint64_t width[6] = {1, (uint64_t)nx, (uint64_t)nx, (uint64_t)nx * nx, (uint64_t)nx * nx, (uint64_t)ny};
+    uint64_t w = 0;
+    for (int k = 0; k < 6; ++k) if (dst[k]) w += width[k];
+    const uint64_t in_w = (upf ? (uint64_t)nu : 0) + (ypf ? (uint64_t)ny : 0);
+    uint64_t step_d = 0, total = 0, in_step = 0, in_total = 0;      // per-step outputs / per-filter inputs of all filters, in doubles
+    if (__builtin_mul_overflow((uint64_t)F, w, &step_d) || __builtin_mul_overflow(step_d, (uint64_t)T, &total) ||
+        __builtin_mul_overflow(total, (uint64_t)sizeof(double), &total) || total > (uint64_t)PTRDIFF_MAX ||
+        __builtin_mul_overflow((uint64_t)F, in_w, &in_step) ||
+        __builtin_mul_overflow(in_step, (uint64_t)T, &in_total) || __builtin_mul_overflow(in_total, (uint64_t)sizeof(double), &in_total) ||
+        in_total > (uint64_t)PTRDIFF_MAX)
+        return fail(LLPF_ERR_ARG, "kalman: the size of the outputs or of the inputs overflows");
+    test_throw("kalman_run");
+    HIPC(hipSetDevice(b.device));
+    const size_t step_bytes = (size_t)(step_d + in_step) * sizeof(double);
+    // (shared inputs and no per-step outputs: nothing per step scales with F, the chunk is KF_CHUNK_STEPS)
+    const int64_t Tc = std::min<int64_t>(T, std::min<int64_t>(KF_CHUNK_STEPS, step_bytes ? std::max<int64_t>(1, (int64_t)(KF_CHUNK_BYTES / step_bytes))
+                                                                                         : KF_CHUNK_STEPS));
+    const int64_t nchunk = (T + Tc - 1) / Tc;
+    const int nbuf = nchunk > 1 ? 2 : 1;
+    const size_t chunk_out = (size_t)step_d * Tc;
+    const size_t chunk_u = nu > 0 ? (upf ? (size_t)F * Tc * nu : (size_t)Tc * nu) : 0;
+    const size_t chunk_y = ypf ? (size_t)F * Tc * ny : (size_t)Tc * ny;
+    // device buffers first: destroyed after the pipe has waited for the streams
+    DevBuf<double> d_out[2], d_u[2], d_y[2];
+    std::vector<double> upack[2], ypack[2];     // per-filter inputs of a chunk, repacked time-major [Tc][F][n] for one copy
+    SimPipe pipe;
+    pipe.compute = b.stream;
+    HIPC(hipStreamCreateWithFlags(&pipe.copy, hipStreamNonBlocking));
+    for (int i = 0; i < nbuf; ++i) {
+        if (chunk_out) {
+            CHK(d_out[i].ensure(chunk_out));
+            HIPC(hipHostMalloc(reinterpret_cast<void**>(&pipe.pinned[i]), chunk_out * sizeof(double), hipHostMallocDefault));
+        }
+        if (chunk_u) CHK(d_u[i].ensure(chunk_u));
+        CHK(d_y[i].ensure(chunk_y));
+        if (upf) upack[i].resize(chunk_u);
+        if (ypf) ypack[i].resize(chunk_y);
+        HIPC(hipEventCreateWithFlags(&pipe.ev_k[i], hipEventDisableTiming));
+        HIPC(hipEventCreateWithFlags(&pipe.ev_c[i], hipEventDisableTiming));
+        HIPC(hipEventCreateWithFlags(&pipe.ev_u[i], hipEventDisableTiming));
+    }
+    // chunk c's outputs from pinned buffer c % 2 into the caller's time-major arrays: one contiguous range per output
+    auto drain = [&](int64_t c) -> int {
+        const int s = (int)(c & 1);
+        const int64_t t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
+        HIPC(hipEventSynchronize(pipe.ev_c[s]));
+        const double* src = reinterpret_cast<const double*>(pipe.pinned[s]);
+        for (int k = 0; k < 6; ++k) {
+            if (!dst[k]) continue;
+            const size_t n = (size_t)tc * F * width[k];
+            memcpy(dst[k] + (size_t)t0 * F * width[k], src, n * sizeof(double));
+            src += n;
+        }
+        return LLPF_OK;
+    };
+    // per-filter rows [F][T][n] of steps [t0, t0 + tc) -> [tc][F][n]
+    auto repack = [&](const double* A, int n, int64_t t0, int64_t tc, double* p) {
+        for (int64_t k = 0; k < tc; ++k)
+            for (int f = 0; f < F; ++f) memcpy(p + ((size_t)k * F + f) * n, A + ((size_t)f * T + t0 + k) * n, sizeof(double) * n);
+    };
+    for (int64_t c = 0; c < nchunk; ++c) {
+        const int s = (int)(c & 1);
+        const int64_t t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
+        if (c >= 2 && chunk_out) HIPC(hipStreamWaitEvent(b.stream, pipe.ev_c[s], 0));     // staging s has been copied out (chunk c - 2)
+        if (c >= 2 && (upf || ypf)) HIPC(hipEventSynchronize(pipe.ev_u[s]));              // the copies of chunk c - 2 have read the packs
+        if (nu > 0) {
+            if (upf) {
+                repack(U, nu, t0, tc, upack[s].data());
+                HIPC(hipMemcpyAsync(d_u[s], upack[s].data(), sizeof(double) * tc * F * nu, hipMemcpyHostToDevice, b.stream));
+            } else {
+                HIPC(hipMemcpyAsync(d_u[s], U + (size_t)t0 * nu, sizeof(double) * tc * nu, hipMemcpyHostToDevice, b.stream));
+            }
+        }
+        if (ypf) {
+            repack(Y, ny, t0, tc, ypack[s].data());
+            HIPC(hipMemcpyAsync(d_y[s], ypack[s].data(), sizeof(double) * tc * F * ny, hipMemcpyHostToDevice, b.stream));
+        } else {
+            HIPC(hipMemcpyAsync(d_y[s], Y + (size_t)t0 * ny, sizeof(double) * tc * ny, hipMemcpyHostToDevice, b.stream));
+        }
+        HIPC(hipEventRecord(pipe.ev_u[s], b.stream));
+        KalmanArgs a{};
+        a.par = b.d_par; a.state = b.d_state;
+        a.u = nu > 0 ? d_u[s].p : nullptr;
+        a.y = d_y[s].p;
+        double* o = d_out[s].p;
+        double** slot[6] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.e};
+        for (int k = 0; k < 6; ++k) {
+            *slot[k] = dst[k] ? o : nullptr;
+            if (dst[k]) o += (size_t)tc * F * width[k];
+        }
+        a.F = F; a.Tc = (int32_t)tc; a.nu = nu;
+        a.u_per = upf ? 1 : 0; a.y_per = ypf ? 1 : 0;
+        a.first = c == 0 ? 1 : 0;
+        a.par_tstride = 0;
+        HIPC(launch_kalman(nx, ny, a, b.stream));
+        if (chunk_out) {
+            HIPC(hipEventRecord(pipe.ev_k[s], b.stream));
+            HIPC(hipStreamWaitEvent(pipe.copy, pipe.ev_k[s], 0));
+            HIPC(hipMemcpyAsync(pipe.pinned[s], d_out[s], (size_t)step_d * tc * sizeof(double), hipMemcpyDeviceToHost, pipe.copy));
+            HIPC(hipEventRecord(pipe.ev_c[s], pipe.copy));
+            if (c >= 1) CHK(drain(c - 1));
+        }
+    }
+    if (chunk_out) CHK(drain(nchunk - 1));
+    if (ll_total)     // the running sum: row nx + np of the state
+        HIPC(hipMemcpyAsync(ll_total, b.d_state.p + (size_t)(nx + b.np) * F, sizeof(double) * F, hipMemcpyDeviceToHost, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}

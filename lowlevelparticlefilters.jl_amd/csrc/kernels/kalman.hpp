@@ -1,0 +1,81 @@
+// kernels/kalman.hpp — k_kalman: banks of Kalman filters with constant matrices (llpf_kalman_bank_run; host side: host/kalman.hpp).
+// Part of k_kalman.hip (namespace llpf).
+// ------------------------------------------------------------------------------------------------
+// One thread per filter, the time loop inside the kernel, x and the packed lower triangle of R in registers.  The step is
+// shared/llpf_kalman.h with literal NX, NY (every loop over the dimensions unrolls; nu is a run-time number), so a host build of that
+// header gives the same bits.  The constant matrices are read from the SoA [entry][F] each step (lane f at column f: a wave reads whole
+// lines); shared U / Y rows are one address for every lane, per-filter rows come time-major [Tc][F][n].  Outputs are time-major
+// [Tc][F][...], a lane's n doubles consecutive.
+// ------------------------------------------------------------------------------------------------
+constexpr int KF_BLOCK = 64;
+#ifndef KF_RELOAD
+#define KF_RELOAD(nx, ny) ((nx) >= 5)
+#endif        // one wave per workgroup: a bank of 10^3 filters still spreads over 16 CUs
+
+typedef double llpf_kf_d2 __attribute__((ext_vector_type(2)));
+template <int N>
+DEV void kf_store(double* p, const double* v) {
+    if constexpr (N % 2 == 0) {       // 16-byte stores: p is 16-byte aligned (N even, the buffer 256-byte aligned)
+#pragma unroll
+        for (int d = 0; d < N; d += 2) {
+            llpf_kf_d2 w;
+            w.x = v[d];
+            w.y = v[d + 1];
+            *reinterpret_cast<llpf_kf_d2*>(p + d) = w;
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < N; ++d) p[d] = v[d];
+    }
+}
+// the dense nx x nx form of the packed R, row by row
+template <int NX>
+DEV void kf_store_dense(double* p, const double* R) {
+    double row[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) {
+#pragma unroll
+        for (int c = 0; c < NX; ++c) row[c] = R[llpf_kf_idx(r, c)];
+        kf_store<NX>(p + r * NX, row);
+    }
+}
+
+template <int NX, int NY>
+__global__ __launch_bounds__(KF_BLOCK) void k_kalman(KalmanArgs a) {
+    constexpr int NP = LLPF_KF_NP(NX);
+    const int64_t F = a.F;
+    const int64_t f = (int64_t)blockIdx.x * KF_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int nu = a.nu;
+    const double* __restrict__ P0 = a.par + f;
+    double* st = a.state + f;
+    double x[NX], R[NP];
+#pragma unroll
+    for (int d = 0; d < NX; ++d) x[d] = st[d * F];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) R[i] = st[(NX + i) * F];
+    double llt = a.first ? 0.0 : st[(NX + NP) * F];
+#pragma unroll 1
+    for (int k = 0; k < a.Tc; ++k) {
+        const size_t kf = (size_t)k * F + f;
+        const double* u = nu > 0 ? a.u + (a.u_per ? kf : (size_t)k) * nu : a.u;
+        const double* y = a.y + (a.y_per ? kf : (size_t)k) * NY;
+        if (a.x) kf_store<NX>(a.x + kf * NX, x);
+        if (a.R) kf_store_dense<NX>(a.R + kf * NX * NX, R);
+        double e[NY];
+        // (KF_RELOAD: par_tstride is a run-time 0, so the constants' addresses look step-dependent and their loads stay inside the loop)
+        const double* P = KF_RELOAD(NX, NY) ? P0 + (size_t)k * a.par_tstride : P0;
+        const double ll = llpf_kf_correct(NX, NY, nu, P, F, u, y, x, R, e);
+        llt = llt + ll;
+        if (a.ll) a.ll[kf] = ll;
+        if (a.e) kf_store<NY>(a.e + kf * NY, e);
+        if (a.xt) kf_store<NX>(a.xt + kf * NX, x);
+        if (a.Rt) kf_store_dense<NX>(a.Rt + kf * NX * NX, R);
+        llpf_kf_predict(NX, NY, nu, P, F, u, x, R);
+    }
+#pragma unroll
+    for (int d = 0; d < NX; ++d) st[d * F] = x[d];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) st[(NX + i) * F] = R[i];
+    st[(NX + NP) * F] = llt;
+}

@@ -1,0 +1,214 @@
+/* llpf_kalman.h — the Kalman filter with constant matrices (reference src/kalman.jl, predict! / correct! of src/filtering.jl:52-128),
+ * in the one operation order that the device bank (kernels/kalman.hpp, one filter per thread) and a host build of this file share.
+ * This header IS the device-order definition: the GPU reproduces a host build of it (-ffp-contract=off) bit for bit.
+ *
+ * Plain C for host and device.  Every accumulation runs over its summation index in increasing order with explicit llpf_fma; sqrt and
+ * log are those of llpf_detmath.h.  On the device the dimensions nx, ny are literal constants at the call site and every loop over them
+ * unrolls; nu is a run-time number (loops over the inputs stay loops).
+ *
+ * Model: x' = A x + B u + w, w ~ N(0, R1);  y = C x + D u + e, e ~ N(0, R2).  alpha = 1, no cross-covariance R12.
+ *
+ * The form computed here.  With S = C R C' + R2 = L L' (lower Cholesky factor) and W = L^-1 (C R) (ny x nx):
+ *     K e            = R C' S^-1 e = W' z,  z = L^-1 e
+ *     (I - K C) R    = R - R C' S^-1 C R = R - W' W
+ *     logpdf(N(0, S), e) = -(ny/2) log(2 pi) - log(L11 ... Lnn) - z'z / 2
+ * — the reference's correct! (K = (R C')/S_chol, x += K e, R = symmetrize((I - K C) R)) term by term, without forming K.
+ * Choices of this order:
+ *   - R is symmetric by construction and only its lower triangle is formed and stored (packed, entry (r, c), c <= r, at r(r+1)/2 + c):
+ *     symmetrize() is then the identity.  The same holds for S (lower triangle of C R C' plus R2) and for A R A' + R1.
+ *   - the triangular solves multiply by 1 / L_ii (one division per diagonal entry);
+ *   - log det S / 2 is ONE log of the product of L's diagonal (ny <= 4 factors);
+ *   - the running sums of a matrix-vector product continue from the C (A) columns into the D (B) columns in one accumulator.
+ * A filter whose S is not positive definite (the Cholesky pivot is not > 0, or NaN) returns ll = NaN and NaN x, R: from that step on
+ * every result of that filter is NaN, and nothing else is touched.
+ *
+ * Parameters of one filter are entries P[e * ps] (host: ps = 1 and one filter's entries consecutive; device: the SoA [entry][F] of the
+ * bank with ps = F, P pointing at filter f's column), in the order of LLPF_KF_OFF_* below.  The state is x [nx] and the packed R [np]. */
+#ifndef LLPF_KALMAN_H
+#define LLPF_KALMAN_H
+
+#include "llpf_detmath.h"
+
+#define LLPF_KF_MAXX 8
+#define LLPF_KF_MAXY 4
+#define LLPF_KF_MAXU 8
+#define LLPF_KF_NP(n) ((n) * ((n) + 1) / 2)
+
+/* parameter entries: A [nx][nx], C [ny][nx], R1 packed, R2 packed, B [nx][nu], D [ny][nu] (the inputs last: A .. R2 sit at offsets that
+ * do not depend on the run-time nu) */
+#define LLPF_KF_OFF_A 0
+#define LLPF_KF_OFF_C(nx) ((nx) * (nx))
+#define LLPF_KF_OFF_R1(nx, ny) (LLPF_KF_OFF_C(nx) + (ny) * (nx))
+#define LLPF_KF_OFF_R2(nx, ny) (LLPF_KF_OFF_R1(nx, ny) + LLPF_KF_NP(nx))
+#define LLPF_KF_OFF_B(nx, ny) (LLPF_KF_OFF_R2(nx, ny) + LLPF_KF_NP(ny))
+#define LLPF_KF_OFF_D(nx, ny, nu) (LLPF_KF_OFF_B(nx, ny) + (nx) * (nu))
+#define LLPF_KF_NPAR(nx, ny, nu) (LLPF_KF_OFF_D(nx, ny, nu) + (ny) * (nu))
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LLPF_KF_UNROLL _Pragma("unroll")
+#else
+#define LLPF_KF_UNROLL
+#endif
+
+#define LLPF_KF_P(e) (P[(int64_t)(e) * ps])
+
+LLPF_HD int llpf_kf_idx(int r, int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
+LLPF_HD double llpf_kf_nan(void) { return llpf_u2d(0x7ff8000000000000ULL); }
+
+/* correct!(kf, u, y): the innovation e (ny), x and R updated in place; returns logpdf(N(0, S), e).
+ * A row whose first element is NaN is missing: x and R stay, e is NaN, the result is 0. */
+LLPF_HD double llpf_kf_correct(const int nx, const int ny, const int nu, const double* P, const int64_t ps, const double* u,
+                               const double* y, double* x, double* R, double* e) {
+    if (!(y[0] == y[0])) {
+        LLPF_KF_UNROLL
+        for (int r = 0; r < ny; ++r) e[r] = llpf_kf_nan();
+        return 0.0;
+    }
+    const int oC = LLPF_KF_OFF_C(nx), oR2 = LLPF_KF_OFF_R2(nx, ny), oD = LLPF_KF_OFF_D(nx, ny, nu);
+    /* e = y - (C x + D u) */
+    LLPF_KF_UNROLL
+    for (int r = 0; r < ny; ++r) {
+        double acc = LLPF_KF_P(oC + r * nx) * x[0];
+        LLPF_KF_UNROLL
+        for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(oC + r * nx + q), x[q], acc);
+        for (int c = 0; c < nu; ++c) acc = llpf_fma(LLPF_KF_P(oD + r * nu + c), u[c], acc);
+        e[r] = y[r] - acc;
+    }
+    /* CR = C R  (ny x nx) */
+    double CR[LLPF_KF_MAXY * LLPF_KF_MAXX];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < ny; ++r) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = LLPF_KF_P(oC + r * nx) * R[llpf_kf_idx(0, c)];
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(oC + r * nx + q), R[llpf_kf_idx(q, c)], acc);
+            CR[r * LLPF_KF_MAXX + c] = acc;
+        }
+    }
+    /* S = (C R) C' + R2, lower triangle, factored in place: L L' = S */
+    double L[LLPF_KF_NP(LLPF_KF_MAXY)], inv[LLPF_KF_MAXY];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < ny; ++r) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c <= r; ++c) {
+            double acc = CR[r * LLPF_KF_MAXX] * LLPF_KF_P(oC + c * nx);
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(CR[r * LLPF_KF_MAXX + q], LLPF_KF_P(oC + c * nx + q), acc);
+            L[llpf_kf_idx(r, c)] = acc + LLPF_KF_P(oR2 + llpf_kf_idx(r, c));
+        }
+    }
+    int ok = 1;
+    LLPF_KF_UNROLL
+    for (int i = 0; i < ny; ++i) {
+        LLPF_KF_UNROLL
+        for (int j = 0; j <= i; ++j) {
+            double acc = L[llpf_kf_idx(i, j)];
+            LLPF_KF_UNROLL
+            for (int k = 0; k < j; ++k) acc = llpf_fma(-L[llpf_kf_idx(i, k)], L[llpf_kf_idx(j, k)], acc);
+            if (i == j) {
+                ok = ok & (acc > 0.0);
+                const double d = llpf_sqrt(acc);
+                L[llpf_kf_idx(i, i)] = d;
+                inv[i] = 1.0 / d;
+            } else {
+                L[llpf_kf_idx(i, j)] = acc * inv[j];
+            }
+        }
+    }
+    /* W = L^-1 (C R)  (ny x nx),  z = L^-1 e */
+    double W[LLPF_KF_MAXY * LLPF_KF_MAXX], z[LLPF_KF_MAXY];
+    LLPF_KF_UNROLL
+    for (int i = 0; i < ny; ++i) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = CR[i * LLPF_KF_MAXX + c];
+            LLPF_KF_UNROLL
+            for (int q = 0; q < i; ++q) acc = llpf_fma(-L[llpf_kf_idx(i, q)], W[q * LLPF_KF_MAXX + c], acc);
+            W[i * LLPF_KF_MAXX + c] = acc * inv[i];
+        }
+        double acc = e[i];
+        LLPF_KF_UNROLL
+        for (int q = 0; q < i; ++q) acc = llpf_fma(-L[llpf_kf_idx(i, q)], z[q], acc);
+        z[i] = acc * inv[i];
+    }
+    /* ll = -(ny/2) log(2 pi) - log(L11 ... Lnn) - z'z / 2 */
+    double quad = z[0] * z[0], det = L[0];
+    LLPF_KF_UNROLL
+    for (int i = 1; i < ny; ++i) {
+        quad = llpf_fma(z[i], z[i], quad);
+        det = det * L[llpf_kf_idx(i, i)];
+    }
+    const double c0 = -((double)ny * llpf_log(6.283185307179586)) / 2.0;
+    double ll = (c0 - llpf_log(det)) - 0.5 * quad;
+    /* x += W' z ;  R -= W' W  (lower triangle) */
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        double acc = W[r] * z[0];
+        LLPF_KF_UNROLL
+        for (int i = 1; i < ny; ++i) acc = llpf_fma(W[i * LLPF_KF_MAXX + r], z[i], acc);
+        x[r] = x[r] + acc;
+    }
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c <= r; ++c) {
+            double acc = W[r] * W[c];
+            LLPF_KF_UNROLL
+            for (int i = 1; i < ny; ++i) acc = llpf_fma(W[i * LLPF_KF_MAXX + r], W[i * LLPF_KF_MAXX + c], acc);
+            R[llpf_kf_idx(r, c)] = R[llpf_kf_idx(r, c)] - acc;
+        }
+    }
+    if (!ok) {                              /* S not positive definite: this filter is NaN from here on */
+        ll = llpf_kf_nan();
+        LLPF_KF_UNROLL
+        for (int r = 0; r < nx; ++r) x[r] = llpf_kf_nan();
+        LLPF_KF_UNROLL
+        for (int i = 0; i < LLPF_KF_NP(nx); ++i) R[i] = llpf_kf_nan();
+    }
+    return ll;
+}
+
+/* predict!(kf, u): x = A x + B u, R = A R A' + R1 (lower triangle; A R formed one row at a time) */
+LLPF_HD void llpf_kf_predict(const int nx, const int ny, const int nu, const double* P, const int64_t ps, const double* u, double* x,
+                             double* R) {
+    const int oR1 = LLPF_KF_OFF_R1(nx, ny), oB = LLPF_KF_OFF_B(nx, ny);
+    double xn[LLPF_KF_MAXX], Rn[LLPF_KF_NP(LLPF_KF_MAXX)];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        double acc = LLPF_KF_P(r * nx) * x[0];
+        LLPF_KF_UNROLL
+        for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(r * nx + q), x[q], acc);
+        for (int c = 0; c < nu; ++c) acc = llpf_fma(LLPF_KF_P(oB + r * nu + c), u[c], acc);
+        xn[r] = acc;
+    }
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        double ar[LLPF_KF_MAXX];             /* row r of A R */
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = LLPF_KF_P(r * nx) * R[llpf_kf_idx(0, c)];
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(r * nx + q), R[llpf_kf_idx(q, c)], acc);
+            ar[c] = acc;
+        }
+        LLPF_KF_UNROLL
+        for (int c = 0; c <= r; ++c) {
+            double acc = ar[0] * LLPF_KF_P(c * nx);
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(ar[q], LLPF_KF_P(c * nx + q), acc);
+            Rn[llpf_kf_idx(r, c)] = acc + LLPF_KF_P(oR1 + llpf_kf_idx(r, c));
+        }
+    }
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) x[r] = xn[r];
+    LLPF_KF_UNROLL
+    for (int i = 0; i < LLPF_KF_NP(nx); ++i) R[i] = Rn[i];
+}
+
+/* One step t of forward_trajectory (reference src/filtering.jl:343-365): x, R on entry are the prior x[t], R[t]; correct! gives ll[t],
+ * e[t] and the posterior xt[t], Rt[t]; predict! gives the prior of t + 1.  update! is this step.  A run's ll_total starts at 0.0 and
+ * adds ll[t] in step order (ll_total = ll_total + ll[t]), a missing row adding 0. */
+#undef LLPF_KF_P
+
+#endif /* LLPF_KALMAN_H */

@@ -30,12 +30,13 @@ import LowLevelParticleFilters: AbstractParticleFilter, ParticleFilteringSolutio
     particles, weights, expweights, state, num_particles, index, particletype, parameters,
     effective_particles, shouldresample, weighted_mean, weighted_cov, weighted_quantile,
     dynamics, measurement, measurement_likelihood, dynamics_density, measurement_density, initial_density,
-    resample_threshold, resampling_strategy
+    resample_threshold, resampling_strategy, KalmanFilteringSolution, covariance
 
 export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter, GPURBPF, GPUFilterBank, GPUMultiBank,
        LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMeasurement, GaussianLikelihood,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
-       seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch
+       seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
+       GPUKalmanFilter, GPUKalmanFilterBank
 
 const LIB = get(ENV, "LLPF_HIP_LIB", joinpath(@__DIR__, "..", "libllpf_hip.so"))
 const MAXD = 16          # LLPF_MAX_DIM: states / outputs
@@ -935,5 +936,114 @@ function Base.show(io::IO, b::GPUMultiBank)
 end
 
 include(joinpath(@__DIR__, "tracing.jl"))      # closures -> device snippet (trace_dynamics, emit_user_model)
+
+# ---- banks of Kalman filters with constant matrices (the reference's KalmanFilter(A, B, C, D, R1, R2, d0), src/kalman.jl): llpf_kalman_bank_* ----
+struct CKalmanOutputs                 # llpf_kalman_outputs
+    struct_size::UInt32
+    pad::UInt32
+    ll_steps::Ptr{Float64}
+    x::Ptr{Float64}
+    xt::Ptr{Float64}
+    R::Ptr{Float64}
+    Rt::Ptr{Float64}
+    e::Ptr{Float64}
+end
+mutable struct GPUKalmanFilterBank
+    h::Ptr{Cvoid}
+    F::Int
+    nx::Int
+    nu::Int
+    ny::Int
+end
+kalman_model(A, B, C, R1, R2, d0, Ts) = cmodel(LinearDynamics(A, B), LinearMeasurement(C), GaussianSpec(zeros(size(A, 1)), Matrix{Float64}(R1)),
+                                              GaussianSpec(zeros(size(C, 1)), Matrix{Float64}(R2)), d0, Float64(Ts))
+kalman_D(Ds, ny, nu) = Float64[D[r, c] for D in Ds for r in 1:ny for c in 1:nu]        # [F][ny][nu] row-major
+"""
+    GPUKalmanFilterBank(filters; Ts = 1.0, device = 0)
+
+Independent Kalman filters with constant matrices on the device, one GPU thread each; `filters` is a vector of (A, B, C, D, R1, R2, d0)
+tuples of the same dimensions (nx <= 8, ny <= 4, nu <= 8).  `loglik(bank, u, y)` is the vector of every filter's log-likelihood.
+"""
+function GPUKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0)
+    cms = [kalman_model(f[1], f[2], f[3], f[5], f[6], f[7], Ts) for f in filters]
+    Dv = kalman_D([f[4] for f in filters], cms[1].ny, cms[1].nu)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_kalman_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Ptr{Float64}, Int32, Ref{Ptr{Cvoid}}), device, cms, Dv, length(cms), h))
+    b = GPUKalmanFilterBank(h[], length(cms), cms[1].nx, cms[1].nu, cms[1].ny)
+    finalizer(x -> ccall((:llpf_kalman_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    b
+end
+function set_parameters!(b::GPUKalmanFilterBank, filters::Vector; Ts = 1.0)
+    cms = [kalman_model(f[1], f[2], f[3], f[5], f[6], f[7], Ts) for f in filters]
+    length(cms) == b.F || throw(ArgumentError("set_parameters!: $(length(cms)) filters for a bank of $(b.F)"))
+    Dv = kalman_D([f[4] for f in filters], b.ny, b.nu)
+    check(ccall((:llpf_kalman_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}, Ptr{Float64}), b.h, cms, Dv))
+    b
+end
+reset!(b::GPUKalmanFilterBank) = check(ccall((:llpf_kalman_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+# u, y: vectors of T vectors shared by every filter (a missing y is `missing` / a NaN first element); returns ll_total and the outputs asked for
+function kalman_run(b::GPUKalmanFilterBank, u, y; outputs = false)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        check(ccall((:llpf_kalman_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{CKalmanOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+"loglik(bank, u, y): every filter's loglik(kf, u, y) (reset! first, then T update! steps)"
+loglik(b::GPUKalmanFilterBank, u, y) = (reset!(b); kalman_run(b, u, y)[1])
+"x (nx x F), R (nx x nx x F) of every filter"
+function state(b::GPUKalmanFilterBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_kalman_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, x, R))
+    x, R
+end
+covariance(b::GPUKalmanFilterBank) = state(b)[2]
+"set the estimate of every filter: x (nx x F), R (nx x nx x F; its lower triangle is read)"
+function set_state!(b::GPUKalmanFilterBank, x, R)
+    xm = Matrix{Float64}(reshape(x, b.nx, b.F)); Rm = Array{Float64}(reshape(R, b.nx, b.nx, b.F))
+    Rr = permutedims(Rm, (2, 1, 3))                  # column-major nx x nx = the row-major [nx][nx] of its transpose
+    check(ccall((:llpf_kalman_bank_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, xm, Rr))
+    b
+end
+
+"""
+    GPUKalmanFilter(A, B, C, D, R1, R2, d0; Ts = 1.0, device = 0)
+
+The reference's `KalmanFilter` with constant matrices, run on the device (a bank of one filter, llpf_kalman_bank_*):
+`forward_trajectory` returns the reference's `KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `state`, `covariance`.
+"""
+mutable struct GPUKalmanFilter
+    bank::GPUKalmanFilterBank
+    Ts::Float64
+end
+GPUKalmanFilter(A, B, C, D, R1, R2, d0; Ts = 1.0, device = 0) =
+    GPUKalmanFilter(GPUKalmanFilterBank([(A, B, C, D, R1, R2, d0)]; Ts = Ts, device = device), Float64(Ts))
+reset!(kf::GPUKalmanFilter) = reset!(kf.bank)
+loglik(kf::GPUKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
+"update!(kf, u, y): correct! then predict!; returns (ll, e)"
+function update!(kf::GPUKalmanFilter, u, y, p = NullParameters(), t = 0)
+    _, o = kalman_run(kf.bank, [u], [y]; outputs = true)
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+state(kf::GPUKalmanFilter) = state(kf.bank)[1][:, 1]
+covariance(kf::GPUKalmanFilter) = state(kf.bank)[2][:, :, 1]
+function forward_trajectory(kf::GPUKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o = kalman_run(kf.bank, u, y; outputs = true)
+    T = length(y)
+    KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                            [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+end
 
 end # module

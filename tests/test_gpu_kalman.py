@@ -1,0 +1,206 @@
+"""Banks of Kalman filters on the device (llpf_kalman_bank_*; kernels/kalman.hpp, host/kalman.hpp): the GPU reproduces the host build
+of csrc/shared/llpf_kalman.h bit for bit, whatever the shape, the bank, the chunking of T or the split of a run; and the Python API
+(KalmanFilter, KalmanFilterBank) computes the reference's Kalman filter."""
+import numpy as np
+import pytest
+
+import llpf_amd
+from llpf_amd import _capi
+import kalman_common as kc
+import models as M
+import oracle_binding as ob
+
+pytestmark = pytest.mark.gpu
+OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return kc.build_host(tmp_path_factory.mktemp("kalman_host"))
+
+
+def _bank(systems):
+    return _capi.KalmanBankHandle(0, [m for m, _ in systems], np.stack([D for _, D in systems]))
+
+
+def _data(rng, T, nu, ny, missing=()):
+    U = rng.standard_normal((T, nu))
+    Y = 2.0 * rng.standard_normal((T, ny))
+    for t in missing:
+        Y[t, 0] = np.nan
+    return U, Y
+
+
+def _same(g, h, keys=OUTS, what=""):
+    for k in keys:
+        assert kc.bits_equal(g[k], h[k]), (what, k)
+
+
+@pytest.mark.parametrize("nx", range(1, 9))
+def test_bit_identical_to_the_host_header_for_every_shape(host, nx):
+    """F = 1000 random filters, T = 200, every output; shared and per-filter inputs give the same bits"""
+    for ny in range(1, 5):
+        rng = np.random.default_rng(10 * nx + ny)
+        nu = int(rng.integers(0, 4))
+        systems = [kc.random_system(rng, nx, ny, nu, k % 3, D=k % 5 != 0) for k in range(1000)]
+        U, Y = _data(rng, 200, nu, ny, missing=(50, 51, 120))
+        b = _bank(systems)
+        g = b.run(U, Y, outputs=OUTS)
+        h, _ = kc.host_run(host, systems, U, Y, 200)
+        _same(g, h, OUTS + ("ll",), (nx, ny))
+        b.reset()
+        gp = b.run(np.broadcast_to(U, (1000,) + U.shape), np.broadcast_to(Y, (1000,) + Y.shape), u_per_filter=nu > 0, y_per_filter=True,
+                   outputs=OUTS)
+        _same(gp, g, OUTS + ("ll",), (nx, ny, "per-filter"))
+        b.close()
+
+
+def test_per_filter_inputs_of_their_own(host):
+    rng = np.random.default_rng(3)
+    systems = [kc.random_system(rng, 4, 2, 2, k % 3) for k in range(300)]
+    U = rng.standard_normal((300, 80, 2))
+    Y = rng.standard_normal((300, 80, 2))
+    Y[::7, 30, 0] = np.nan
+    g = _bank(systems).run(U, Y, True, True, outputs=OUTS)
+    h, _ = kc.host_run(host, systems, U, Y, 80, per_filter=3)
+    _same(g, h, OUTS + ("ll",))
+
+
+def test_a_filters_bits_do_not_depend_on_the_bank(host):
+    rng = np.random.default_rng(4)
+    systems = [kc.random_system(rng, 3, 2, 1, k % 3) for k in range(1000)]
+    U, Y = _data(rng, 60, 1, 2)
+    g = _bank(systems).run(U, Y, outputs=OUTS)
+    pick = [999, 0, 517, 64, 63, 65]
+    sub = _bank([systems[k] for k in pick][::-1]).run(U, Y, outputs=OUTS)
+    for j, k in enumerate(pick[::-1]):
+        for key in OUTS:
+            assert kc.bits_equal(sub[key][:, j], g[key][:, k]), (k, key)
+    one = _bank([systems[517]]).run(U, Y, outputs=OUTS)
+    for key in OUTS:
+        assert kc.bits_equal(one[key][:, 0], g[key][:, 517]), key
+
+
+def test_chunks_and_continuation(host):
+    rng = np.random.default_rng(5)
+    systems = [kc.random_system(rng, 4, 2, 2, k % 3) for k in range(1000)]
+    U, Y = _data(rng, 700, 2, 2, missing=(255, 256, 600))
+    b = _bank(systems)
+    long = b.run(U, Y, outputs=OUTS)                   # several chunks of at most 256 steps
+    b.reset()
+    short = b.run(U[:300], Y[:300], outputs=OUTS)
+    for k in OUTS:
+        assert kc.bits_equal(long[k][:300], short[k]), k
+    h, _ = kc.host_run(host, systems, U, Y, 700)
+    _same(long, h, OUTS + ("ll",), "T = 700")
+    b.reset()
+    whole = b.run(U[:50], Y[:50], outputs=OUTS)
+    b.reset()
+    first = b.run(U[:25], Y[:25], outputs=OUTS)
+    x, R = b.get_state()
+    second = b.run(U[25:50], Y[25:50], outputs=OUTS)
+    for k in OUTS:
+        assert kc.bits_equal(np.concatenate([first[k], second[k]]), whole[k]), k
+    fresh = _bank(systems)
+    fresh.set_state(x, R)
+    again = fresh.run(U[25:50], Y[25:50], outputs=OUTS)
+    _same(again, second, OUTS + ("ll",), "set_state")
+    llonly = fresh.run(U[:10], Y[:10])                 # a run without per-step outputs still continues the state
+    x2, _ = fresh.get_state()
+    b.set_state(x, R)
+    b.run(U[25:50], Y[25:50])
+    ref = b.run(U[:10], Y[:10], outputs=("ll_steps",))
+    assert kc.bits_equal(llonly["ll"], ref["ll"]) and kc.bits_equal(x2, b.get_state()[0])
+
+
+def test_missing_rows_and_a_filter_that_loses_definiteness(host):
+    rng = np.random.default_rng(6)
+    systems = [kc.random_system(rng, 2, 1, 0, k % 3) for k in range(130)]
+    U, Y = _data(rng, 40, 0, 1, missing=(5, 6, 30))
+    b = _bank(systems)
+    x, R = b.get_state()
+    ok = b.run(None, Y, outputs=OUTS)
+    assert np.all(ok["ll_steps"][[5, 6, 30]] == 0.0) and np.all(np.isnan(ok["e"][[5, 6, 30]]))
+    R[77] = -100.0 * np.eye(2)
+    b.set_state(x, R)
+    bad = b.run(None, Y, outputs=OUTS)
+    # NaN from the first step on; a missing row still adds 0 (correct! is skipped)
+    assert np.all(np.isnan(np.delete(bad["ll_steps"][:, 77], [5, 6, 30]))) and np.all(bad["ll_steps"][[5, 6, 30], 77] == 0.0)
+    assert np.isnan(bad["ll"][77]) and np.all(np.isnan(bad["xt"][:, 77])) and np.all(np.isnan(bad["R"][1:, 77]))
+    keep = [f for f in range(130) if f != 77]
+    for k in OUTS:
+        assert kc.bits_equal(bad[k][:, keep], ok[k][:, keep]), k
+    h, _ = kc.host_run(host, systems, None, Y, 40, state=(x, R))
+    _same(bad, h, OUTS + ("ll",), "NaN filter")
+
+
+def test_python_api():
+    rng = np.random.default_rng(7)
+    m, D = kc.random_system(rng, 3, 2, 1, 2)
+    mt = kc.matrices(m, D)
+    U, Y = kc.simulate(rng, mt, 50, missing=(9,))
+    kf = llpf_amd.KalmanFilter(mt["A"], mt["B"], mt["C"], mt["D"], mt["R1"], mt["R2"], llpf_amd.MvNormal(mt["x0"], mt["P0"]))
+    assert kf._handle is None
+    sol = llpf_amd.forward_trajectory(kf, U, Y)
+    assert sol.x.shape == (50, 3) and sol.xt.shape == (50, 3) and sol.R.shape == (50, 3, 3) and sol.Rt.shape == (50, 3, 3)
+    assert sol.e.shape == (50, 2) and np.isscalar(sol.ll) and sol.t.shape == (50,)
+    ref = kc.numpy_reference(mt, U, Y)
+    for k in ("x", "xt", "R", "Rt", "e"):
+        assert kc.close(getattr(sol, k), ref[k]), k
+    assert abs(sol.ll - ref["ll"]) <= 1e-10 * abs(ref["ll"])
+    assert llpf_amd.loglik(kf, U, Y) == sol.ll
+    llpf_amd.reset(kf)
+    lls = [llpf_amd.update(kf, U[t], Y[t])[0] for t in range(50)]
+    assert kc.close(np.array(lls), ref["ll_steps"]) and lls[9] == 0.0
+    assert np.allclose(llpf_amd.state(kf), kf.x) and kc.close(kf.x[None], (mt["A"] @ ref["xt"][-1] + mt["B"] @ U[-1])[None])
+    assert llpf_amd.covariance(kf).shape == (3, 3)
+    # log_likelihood_fun with a factory that returns a KalmanFilter
+    from scipy import stats
+    fac = lambda th: llpf_amd.KalmanFilter(mt["A"] * th[0], mt["B"], mt["C"], mt["D"], mt["R1"], mt["R2"], llpf_amd.MvNormal(mt["x0"], mt["P0"]))
+    f = llpf_amd.log_likelihood_fun(fac, [stats.uniform(0.5, 1.0)], U, Y)
+    assert abs(f(np.array([1.0])) - (stats.uniform(0.5, 1.0).logpdf(1.0) + sol.ll)) < 1e-9
+    assert f(np.array([0.8])) != f(np.array([1.0])) and f(np.array([3.0])) == -np.inf
+    # a bank of the same filter and of others: loglik with shared and per-filter arrays
+    kb = llpf_amd.KalmanFilterBank([kf, (mt["A"] * 0.5, mt["B"], mt["C"], mt["D"], mt["R1"], mt["R2"], llpf_amd.MvNormal(mt["x0"], mt["P0"]))])
+    ll = kb.loglik(U, Y)
+    assert ll[0] == sol.ll
+    assert kc.bits_equal(kb.loglik(np.stack([U, U]), np.stack([Y, Y])), ll)
+    kb.set_parameters([(mt["A"] * 0.5, mt["B"], mt["C"], mt["D"], mt["R1"], mt["R2"], llpf_amd.MvNormal(mt["x0"], mt["P0"]))] * 2)
+    ll2 = kb.loglik(U, Y)
+    assert ll2[0] == ll2[1] == ll[1]
+    fw = kb.forward(U, Y)
+    assert fw["x"].shape == (50, 2, 3) and kb.state()[0].shape == (2, 3)
+
+
+def test_from_filter_bank_agrees_with_the_oracle_and_the_particle_filter():
+    specs, models = [], []
+    for k in range(8):
+        model = M.lg_test_model(sigma_f=0.1 + 0.05 * k)
+        mt = kc.matrices(model, np.zeros((1, 1)))
+        specs.append((llpf_amd.LinearDynamics(mt["A"], mt["B"]), llpf_amd.LinearMeasurement(mt["C"]),
+                      llpf_amd.MvNormal(np.zeros(2), mt["R1"]), llpf_amd.MvNormal(np.zeros(1), mt["R2"]),
+                      llpf_amd.MvNormal(mt["x0"], mt["P0"])))
+        models.append(model)
+    _, U, Y = M.simulate_lg(models[0], 100)
+    pf = llpf_amd.FilterBank(100000, specs, rng=11)
+    kb = llpf_amd.KalmanFilterBank.from_filter_bank(pf)
+    ll = kb.loglik(U, Y)
+    for k, model in enumerate(models):
+        o = ob.kalman_loglik(model, U, Y)
+        assert abs(ll[k] - o) <= 1e-10 * abs(o), (k, ll[k], o)
+    llpf = pf.loglik(U, Y)
+    assert np.all(np.abs(llpf - ll) < 0.5), (llpf, ll)
+
+
+def test_a_large_bank(host):
+    """F = 10^5, T = 1000, (4, 2), ll only: every ll finite, 64 sampled filters equal to the host build"""
+    rng = np.random.default_rng(12)
+    base = [kc.random_system(rng, 4, 2, 2, k % 3) for k in range(500)]
+    systems = [base[k % 500] for k in range(100000)]
+    U, Y = _data(rng, 1000, 2, 2)
+    b = _bank(systems)
+    ll = b.run(U, Y)["ll"]
+    assert np.all(np.isfinite(ll))
+    pick = np.sort(rng.choice(100000, 64, replace=False))
+    h, _ = kc.host_run(host, [systems[k] for k in pick], U, Y, 1000)
+    assert kc.bits_equal(ll[pick], h["ll"])
