@@ -397,6 +397,19 @@ int  llpf_kalman_bank_set_models(llpf_kalman_bank* b, const llpf_model* models, 
  * ll_total [F] (optional): the sum of this run's ll[t] in step order; out NULL: nothing per step is stored */
 int  llpf_kalman_bank_run(llpf_kalman_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter,
                           double* ll_total, const llpf_kalman_outputs* out);
+/* smooth(kf, u, y): the Rauch-Tung-Striebel smoother (reference src/smoothing.jl:10-102) of every filter, in the operation order of
+ * llpf_kf_smooth (csrc/shared/llpf_kalman.h).  The forward pass is llpf_kalman_bank_run on the same arguments (the same ll_total, the
+ * same optional forward outputs, the same state afterwards: the prior of step T); the posterior of every step is kept on the device,
+ * (nx + np) * 8 bytes per filter-step with np = nx (nx + 1) / 2, in a buffer the bank keeps for its next call.  The backward pass gives
+ * xT[t], RT[t], the mean and covariance of state t given all T measurements; xT[T] = xt[T].  A filter whose prior covariance loses
+ * definiteness is NaN at that step and every earlier one.  LLPF_ERR_ALLOC when the memory cannot be had: the state is then untouched. */
+typedef struct llpf_kalman_smooth_outputs {
+    uint32_t struct_size;                /* sizeof(llpf_kalman_smooth_outputs): guards growth */
+    uint32_t pad;
+    double *xT, *RT;                     /* xT [T][F][nx], RT [T][F][nx][nx]; either NULL */
+} llpf_kalman_smooth_outputs;
+int  llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter,
+                             double* ll_total, const llpf_kalman_outputs* forward /* or NULL */, const llpf_kalman_smooth_outputs* out);
 /* state(kf), covariance(kf) of every filter: x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
 int  llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R);
 int  llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R);

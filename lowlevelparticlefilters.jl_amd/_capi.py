@@ -44,6 +44,7 @@ SYMBOLS = {
     "llpf_kalman_bank_reset": [_vp],
     "llpf_kalman_bank_set_models": [_vp, C.POINTER(S.Model), _dp],
     "llpf_kalman_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_kalman_bank_smooth": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.KalmanOutputs), C.POINTER(S.KalmanSmoothOutputs)],
     "llpf_kalman_bank_get_state": [_vp, _dp, _dp],
     "llpf_kalman_bank_set_state": [_vp, _dp, _dp],
     "llpf_num_particles": [_vp, _ip],
@@ -457,6 +458,7 @@ class FilterHandle:
 
 
 KALMAN_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+KALMAN_SMOOTH_OUTPUTS = ("xT", "RT")
 
 
 class KalmanBankHandle:
@@ -495,7 +497,16 @@ class KalmanBankHandle:
         """T steps of every filter: U [T, nu] or [F, T, nu] (u_per_filter), Y [T, ny] or [F, T, ny] (y_per_filter).  Returns
         {"ll": [F], name: array} for every name of `outputs` (KALMAN_OUTPUTS), time-major: ll_steps [T, F], x / xt [T, F, nx],
         R / Rt [T, F, nx, nx], e [T, F, ny]."""
-        F, nx, nu, ny = self.F, self.nx, self.nu, self.ny
+        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
+        res, out = self._forward_outputs(T, outputs)
+        ll = np.empty(self.F)
+        check(self.L.llpf_kalman_bank_run(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
+                                          None if out is None else C.byref(out)))
+        res["ll"] = ll
+        return res
+
+    def _inputs(self, U, Y, u_per_filter, y_per_filter):
+        F, nu, ny = self.F, self.nu, self.ny
         Y = f64(Y)
         T = Y.shape[1] if y_per_filter else Y.reshape(-1, ny).shape[0]
         Y = Y.reshape((F, T, ny) if y_per_filter else (T, ny))
@@ -503,6 +514,10 @@ class KalmanBankHandle:
             U = f64(U).reshape((F, T, nu) if u_per_filter else (T, nu))
         else:
             U, u_per_filter = None, False
+        return U, Y, T, u_per_filter
+
+    def _forward_outputs(self, T, outputs):
+        F, nx, ny = self.F, self.nx, self.ny
         shapes = {"ll_steps": (T, F), "x": (T, F, nx), "xt": (T, F, nx), "R": (T, F, nx, nx), "Rt": (T, F, nx, nx), "e": (T, F, ny)}
         res = {k: np.empty(shapes[k]) for k in outputs}
         out = None
@@ -511,9 +526,25 @@ class KalmanBankHandle:
             out.struct_size = C.sizeof(S.KalmanOutputs)
             for k, a in res.items():
                 setattr(out, k, dptr(a))
+        return res, out
+
+    def smooth(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=KALMAN_SMOOTH_OUTPUTS, forward=()):
+        """the forward pass of run() and the RTS smoother's backward pass (llpf_kalman_bank_smooth).  Returns {"ll": [F]} with xT [T, F, nx]
+        and RT [T, F, nx, nx] for the names in `outputs` (KALMAN_SMOOTH_OUTPUTS) and the forward outputs named in `forward`
+        (KALMAN_OUTPUTS); the state afterwards is the one run() leaves."""
+        F, nx = self.F, self.nx
+        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
+        res, fwd = self._forward_outputs(T, forward)
+        shapes = {"xT": (T, F, nx), "RT": (T, F, nx, nx)}
+        sm = {k: np.empty(shapes[k]) for k in outputs}
+        out = S.KalmanSmoothOutputs()
+        out.struct_size = C.sizeof(S.KalmanSmoothOutputs)
+        for k, a in sm.items():
+            setattr(out, k, dptr(a))
         ll = np.empty(F)
-        check(self.L.llpf_kalman_bank_run(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
-                                          None if out is None else C.byref(out)))
+        check(self.L.llpf_kalman_bank_smooth(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
+                                             None if fwd is None else C.byref(fwd), C.byref(out)))
+        res.update(sm)
         res["ll"] = ll
         return res
 

@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "covariance", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -434,6 +434,15 @@ class KalmanFilteringSolution:
         self.t = np.arange(x.shape[0]) * f.Ts
 
 
+class KalmanSmoothingSolution(KalmanFilteringSolution):
+    """The reference's KalmanSmoothingSolution (src/solutions.jl): the fields of the KalmanFilteringSolution it is built from, plus xT [T, nx]
+    and RT [T, nx, nx], the mean and covariance of every state given all T measurements (the Rauch-Tung-Striebel smoother)."""
+
+    def __init__(self, sol, xT, RT):
+        super().__init__(sol.f, sol.u, sol.y, sol.x, sol.xt, sol.R, sol.Rt, sol.ll, sol.e)
+        self.xT, self.RT = xT, RT
+
+
 def covariance(kf):
     """covariance(kf) — the covariance R of the current estimate of a KalmanFilter"""
     return kf.R
@@ -502,6 +511,13 @@ class KalmanFilterBank:
         u, up, y, yp = self._io(u, y)
         self._h.reset()
         return self._h.run(u, y, up, yp, outputs=outputs)
+
+    def smooth(self, u, y, outputs=_capi.KALMAN_SMOOTH_OUTPUTS, forward=()):
+        """smooth(kf_k, u, y) of every filter (reset, the forward pass, the RTS smoother on the device): {"ll": [F], "xT": [T, F, nx],
+        "RT": [T, F, nx, nx]} for the names in `outputs`, plus the forward outputs named in `forward` (as forward())"""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.smooth(u, y, up, yp, outputs=outputs, forward=forward)
 
 
 class RBMeasurementModel:
@@ -920,7 +936,18 @@ def mode_trajectory(x, we=None):
 
 def smooth(pf, *args):
     """xb, ll = smooth(pf, M, u, y, p) / smooth(pf, xf, wf, wef, ll, M, u, y, p) — forward filtering, backward
-    simulation (reference src/smoothing.jl:103-143).  xb is [T, M, nx]."""
+    simulation (reference src/smoothing.jl:103-143).  xb is [T, M, nx].
+    sol = smooth(kf::KalmanFilter, u, y, p) — reset!, forward_trajectory and the Rauch-Tung-Striebel smoother (src/smoothing.jl:10-102),
+    on the device: a KalmanSmoothingSolution."""
+    if isinstance(pf, KalmanFilter):
+        u, y = args[:2]
+        reset(pf)
+        yy = np.asarray(y, dtype=np.float64)
+        yy = yy.reshape(yy.shape[0], -1) if yy.ndim else yy.reshape(1, 1)
+        uu = None if pf._h.nu == 0 else np.asarray(u, dtype=np.float64).reshape(yy.shape[0], -1)
+        r = pf._h.smooth(uu, yy, forward=_capi.KALMAN_OUTPUTS)
+        sol = KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
+        return KalmanSmoothingSolution(sol, r["xT"][:, 0], r["RT"][:, 0])
     if len(args) >= 7:
         xf, wf, wef, ll, M, u, y = args[:7]
     else:

@@ -226,6 +226,11 @@ int llpf_kalman_bank_run(llpf_kalman_bank* b, const double* U, const double* Y, 
     NEEDF(b);
     return kalman_run(*b, U, Y, T, per_filter, ll_total, out);
 } LLPF_GUARD(llpf_kalman_bank_run)
+int llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                            const llpf_kalman_outputs* forward, const llpf_kalman_smooth_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return kalman_smooth(*b, U, Y, T, per_filter, ll_total, forward, out);
+} LLPF_GUARD(llpf_kalman_bank_smooth)
 int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kalman_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
 int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kalman_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
 

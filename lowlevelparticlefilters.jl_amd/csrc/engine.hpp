@@ -274,6 +274,22 @@ struct KalmanArgs {
     int32_t first;           // 1: the first chunk of a run (ll_total starts at 0)
     int32_t pad;
     int64_t par_tstride;     // always 0 (kernels/kalman.hpp: KF_RELOAD)
+    double* post;            // optional [Tc][nx + np][F]: the posterior xt, packed Rt of every step, SoA (what k_kalman_smooth reads);
+                             // null: k_kalman<..., false>, the kernel of a run
+};
+// arguments of k_kalman_smooth (kernels/kalman.hpp): one launch is the backward pass over one chunk of steps [t0, t0 + Tc), run from
+// t0 + Tc - 1 down to t0, one thread per filter
+struct KalmanSmoothArgs {
+    const double* par;       // [npar][F] the constant matrices
+    const double* post;      // [Tc][nx + np][F] the posterior of the chunk's steps (KalmanArgs::post of the forward pass)
+    double* carry;           // [nx + np][F] xT, packed RT: in, those of step t0 + Tc (unless init); out, those of step t0
+    const double* u;         // inputs of the chunk: [Tc][nu] shared, or [Tc][F][nu] (u_per = 1); unused when nu = 0
+    double *xT, *RT;         // per-step outputs of the chunk, each optional: [Tc][F][nx], [Tc][F][nx][nx]
+    int64_t F;
+    int32_t Tc, ny, nu, u_per;
+    int32_t init;            // 1: the chunk holds the run's last step, where xT = xt, RT = Rt (the carry is not read)
+    int32_t pad;
+    int64_t par_tstride;     // always 0 (kernels/kalman.hpp: KF_RELOAD)
 };
 // launchers (kernels.hip)
 hipError_t launch_init(const BankDev& b, uint32_t step, int init_anc, hipStream_t s);
@@ -334,6 +350,8 @@ int simulate_prepare(int model_id, std::string& err);
 hipError_t launch_simulate(int model_id, int nx, int ny, const ModelD* models, int F, const SimArgs& a, hipStream_t s);
 // banks of Kalman filters (k_kalman.hip; kernels/kalman.hpp): one chunk of steps, nx in 1..8, ny in 1..4
 hipError_t launch_kalman(int nx, int ny, const KalmanArgs& a, hipStream_t s);
+// the backward (RTS smoother) pass of those banks over one chunk, nx in 1..8 (ny, nu at run time)
+hipError_t launch_kalman_smooth(int nx, const KalmanSmoothArgs& a, hipStream_t s);
 // kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
 bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
 const char* jit_prelude();

@@ -13,6 +13,7 @@ struct llpf_kalman_bank : BankStream {
     int F = 0, nx = 0, ny = 0, nu = 0;
     int np = 0, npar = 0, nstate = 0;
     DevBuf<double> d_par, d_state;
+    DevBuf<double> d_post;            // [T][nx + np][F] the posterior of every step of the last smooth (grow-only: kept between calls)
     std::vector<double> h_init;       // [nstate][F] what reset loads: mean(d0), packed cov(d0), 0
 };
 
@@ -133,13 +134,31 @@ static int kalman_set_state(llpf_kalman_bank& b, const double* x, const double* 
     return LLPF_OK;
 }
 
-static int kalman_run(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
-                      const llpf_kalman_outputs* out) {
+// the checks of a run's arguments that need no device (llpf_kalman_bank_run and _smooth)
+static int kalman_check_run(const llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter,
+                            const llpf_kalman_outputs* out) {
     if (T < 1) return fail(LLPF_ERR_ARG, "kalman: T must be >= 1");
     if (!Y) return fail(LLPF_ERR_ARG, "kalman: Y is null");
     if (b.nu > 0 && !U) return fail(LLPF_ERR_ARG, "kalman: U is null");
     if (per_filter & ~3) return fail(LLPF_ERR_ARG, "kalman: per_filter has bits other than 0 and 1");
     if (out && out->struct_size < sizeof(llpf_kalman_outputs)) return fail(LLPF_ERR_ARG, "kalman: llpf_kalman_outputs.struct_size too small (ABI)");
+    return LLPF_OK;
+}
+
+static int kalman_forward(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                          const llpf_kalman_outputs* out, double* post);
+
+static int kalman_run(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                      const llpf_kalman_outputs* out) {
+    CHK(kalman_check_run(b, U, Y, T, per_filter, out));
+    test_throw("kalman_run");
+    return kalman_forward(b, U, Y, T, per_filter, ll_total, out, nullptr);
+}
+
+// the forward pass of a run (arguments checked); post: null, or the device array [T][nx + np][F] that receives the posterior of every
+// step (k_kalman<..., true>).  Everything is allocated before the first launch.
+static int kalman_forward(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                          const llpf_kalman_outputs* out, double* post) {
     const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu;
     const bool upf = nu > 0 && (per_filter & 1), ypf = (per_filter & 2) != 0;
     // the outputs of one step, in staging order: ll, x, xt, R, Rt, e
@@ -156,7 +175,6 @@ static int kalman_run(llpf_kalman_bank& b, const double* U, const double* Y, int
         __builtin_mul_overflow(in_step, (uint64_t)T, &in_total) || __builtin_mul_overflow(in_total, (uint64_t)sizeof(double), &in_total) ||
         in_total > (uint64_t)PTRDIFF_MAX)
         return fail(LLPF_ERR_ARG, "kalman: the size of the outputs or of the inputs overflows");
-    test_throw("kalman_run");
     HIPC(hipSetDevice(b.device));
     const size_t step_bytes = (size_t)(step_d + in_step) * sizeof(double);
     // (shared inputs and no per-step outputs: nothing per step scales with F, the chunk is KF_CHUNK_STEPS)
@@ -239,6 +257,7 @@ static int kalman_run(llpf_kalman_bank& b, const double* U, const double* Y, int
         a.u_per = upf ? 1 : 0; a.y_per = ypf ? 1 : 0;
         a.first = c == 0 ? 1 : 0;
         a.par_tstride = 0;
+        a.post = post ? post + (size_t)t0 * (nx + b.np) * F : nullptr;
         HIPC(launch_kalman(nx, ny, a, b.stream));
         if (chunk_out) {
             HIPC(hipEventRecord(pipe.ev_k[s], b.stream));
@@ -251,6 +270,107 @@ static int kalman_run(llpf_kalman_bank& b, const double* U, const double* Y, int
     if (chunk_out) CHK(drain(nchunk - 1));
     if (ll_total)     // the running sum: row nx + np of the state
         HIPC(hipMemcpyAsync(ll_total, b.d_state.p + (size_t)(nx + b.np) * F, sizeof(double) * F, hipMemcpyDeviceToHost, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+// smooth(kf, u, y): the forward pass of a run (the same chunks, outputs and state as kalman_run) that also stores the packed posterior
+// of every step on the device (d_post: (nx + np) * 8 bytes per filter-step), then the backward pass k_kalman_smooth over the chunks in
+// reverse through the same staging pipeline.  Everything is allocated before the first launch, so a call that cannot get its memory
+// leaves the state as it was.  The state after the call is the one kalman_run leaves (the prior of step T and the running ll).
+static int kalman_smooth(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                         const llpf_kalman_outputs* fwd, const llpf_kalman_smooth_outputs* out) {
+    CHK(kalman_check_run(b, U, Y, T, per_filter, fwd));
+    if (out && out->struct_size < sizeof(llpf_kalman_smooth_outputs))
+        return fail(LLPF_ERR_ARG, "kalman: llpf_kalman_smooth_outputs.struct_size too small (ABI)");
+    const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu, ns = nx + b.np;
+    const bool upf = nu > 0 && (per_filter & 1);
+    double* dst[2] = {out ? out->xT : nullptr, out ? out->RT : nullptr};
+    const uint64_t width[2] = {(uint64_t)nx, (uint64_t)nx * nx};
+    const uint64_t w = (dst[0] ? width[0] : 0) + (dst[1] ? width[1] : 0);
+    uint64_t post_d = 0, post_b = 0, step_d = 0, total = 0, in_step = upf ? (uint64_t)F * nu : 0;
+    if (__builtin_mul_overflow((uint64_t)ns * F, (uint64_t)T, &post_d) || __builtin_mul_overflow(post_d, (uint64_t)sizeof(double), &post_b) ||
+        post_b > (uint64_t)PTRDIFF_MAX || __builtin_mul_overflow((uint64_t)F, w, &step_d) || __builtin_mul_overflow(step_d, (uint64_t)T, &total) ||
+        __builtin_mul_overflow(total, (uint64_t)sizeof(double), &total) || total > (uint64_t)PTRDIFF_MAX)
+        return fail(LLPF_ERR_ARG, "kalman: the size of the stored posterior or of the smoothed outputs overflows");
+    test_throw("kalman_smooth");
+    if (!w) return kalman_forward(b, U, Y, T, per_filter, ll_total, fwd, nullptr);     // nothing smoothed is asked for: a run
+    HIPC(hipSetDevice(b.device));
+    const size_t step_bytes = (size_t)(step_d + in_step) * sizeof(double);
+    const int64_t Tc = std::min<int64_t>(T, std::min<int64_t>(KF_CHUNK_STEPS, std::max<int64_t>(1, (int64_t)(KF_CHUNK_BYTES / step_bytes))));
+    const int64_t nchunk = (T + Tc - 1) / Tc;
+    const int nbuf = nchunk > 1 ? 2 : 1;
+    const size_t chunk_out = (size_t)step_d * Tc;
+    const size_t chunk_u = nu > 0 ? (upf ? (size_t)F * Tc * nu : (size_t)Tc * nu) : 0;
+    CHK(b.d_post.ensure((size_t)post_d));
+    DevBuf<double> d_out[2], d_u[2], d_carry;
+    std::vector<double> upack[2];
+    SimPipe pipe;
+    pipe.compute = b.stream;
+    HIPC(hipStreamCreateWithFlags(&pipe.copy, hipStreamNonBlocking));
+    CHK(d_carry.ensure((size_t)ns * F));
+    for (int i = 0; i < nbuf; ++i) {
+        CHK(d_out[i].ensure(chunk_out));
+        HIPC(hipHostMalloc(reinterpret_cast<void**>(&pipe.pinned[i]), chunk_out * sizeof(double), hipHostMallocDefault));
+        if (chunk_u) CHK(d_u[i].ensure(chunk_u));
+        if (upf) upack[i].resize(chunk_u);
+        HIPC(hipEventCreateWithFlags(&pipe.ev_k[i], hipEventDisableTiming));
+        HIPC(hipEventCreateWithFlags(&pipe.ev_c[i], hipEventDisableTiming));
+        HIPC(hipEventCreateWithFlags(&pipe.ev_u[i], hipEventDisableTiming));
+    }
+    // the forward pass allocates its own staging before its first launch: no launch has run when it returns an allocation failure
+    CHK(kalman_forward(b, U, Y, T, per_filter, ll_total, fwd, b.d_post.p));
+    // backward launch i runs chunk nchunk - 1 - i into staging i % 2
+    auto drain = [&](int64_t i) -> int {
+        const int s = (int)(i & 1);
+        const int64_t c = nchunk - 1 - i, t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
+        HIPC(hipEventSynchronize(pipe.ev_c[s]));
+        const double* src = reinterpret_cast<const double*>(pipe.pinned[s]);
+        for (int k = 0; k < 2; ++k) {
+            if (!dst[k]) continue;
+            const size_t n = (size_t)tc * F * width[k];
+            memcpy(dst[k] + (size_t)t0 * F * width[k], src, n * sizeof(double));
+            src += n;
+        }
+        return LLPF_OK;
+    };
+    for (int64_t i = 0; i < nchunk; ++i) {
+        const int s = (int)(i & 1);
+        const int64_t c = nchunk - 1 - i, t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
+        if (i >= 2) HIPC(hipStreamWaitEvent(b.stream, pipe.ev_c[s], 0));       // staging s has been copied out (launch i - 2)
+        if (i >= 2 && upf) HIPC(hipEventSynchronize(pipe.ev_u[s]));           // the copy of launch i - 2 has read the pack
+        if (nu > 0) {
+            if (upf) {
+                for (int64_t k = 0; k < tc; ++k)
+                    for (int f = 0; f < F; ++f)
+                        memcpy(upack[s].data() + ((size_t)k * F + f) * nu, U + ((size_t)f * T + t0 + k) * nu, sizeof(double) * nu);
+                HIPC(hipMemcpyAsync(d_u[s], upack[s].data(), sizeof(double) * tc * F * nu, hipMemcpyHostToDevice, b.stream));
+            } else {
+                HIPC(hipMemcpyAsync(d_u[s], U + (size_t)t0 * nu, sizeof(double) * tc * nu, hipMemcpyHostToDevice, b.stream));
+            }
+        }
+        HIPC(hipEventRecord(pipe.ev_u[s], b.stream));
+        KalmanSmoothArgs a{};
+        a.par = b.d_par;
+        a.post = b.d_post.p + (size_t)t0 * ns * F;
+        a.carry = d_carry;
+        a.u = nu > 0 ? d_u[s].p : nullptr;
+        double* o = d_out[s].p;
+        a.xT = dst[0] ? o : nullptr;
+        if (dst[0]) o += (size_t)tc * F * width[0];
+        a.RT = dst[1] ? o : nullptr;
+        a.F = F; a.Tc = (int32_t)tc; a.ny = ny; a.nu = nu;
+        a.u_per = upf ? 1 : 0;
+        a.init = i == 0 ? 1 : 0;
+        a.par_tstride = 0;
+        HIPC(launch_kalman_smooth(nx, a, b.stream));
+        HIPC(hipEventRecord(pipe.ev_k[s], b.stream));
+        HIPC(hipStreamWaitEvent(pipe.copy, pipe.ev_k[s], 0));
+        HIPC(hipMemcpyAsync(pipe.pinned[s], d_out[s], (size_t)step_d * tc * sizeof(double), hipMemcpyDeviceToHost, pipe.copy));
+        HIPC(hipEventRecord(pipe.ev_c[s], pipe.copy));
+        if (i >= 1) CHK(drain(i - 1));
+    }
+    CHK(drain(nchunk - 1));
     HIPC(hipStreamSynchronize(b.stream));
     return LLPF_OK;
 }

@@ -209,6 +209,124 @@ LLPF_HD void llpf_kf_predict(const int nx, const int ny, const int nu, const dou
 /* One step t of forward_trajectory (reference src/filtering.jl:343-365): x, R on entry are the prior x[t], R[t]; correct! gives ll[t],
  * e[t] and the posterior xt[t], Rt[t]; predict! gives the prior of t + 1.  update! is this step.  A run's ll_total starts at 0.0 and
  * adds ll[t] in step order (ll_total = ll_total + ll[t]), a missing row adding 0. */
+
+/* One backward step of the Rauch-Tung-Striebel smoother, smooth(sol, kf, u, y) (reference src/smoothing.jl:10-102).  For t = T-1 down
+ * to 1 (1-based), from xT[T] = xt[T], RT[T] = Rt[T]:
+ *     C = Rt[t] A' / R[t+1];  xT[t] = xt[t] + C (xT[t+1] - x[t+1]);  RT[t] = Rt[t] + symmetrize(C (RT[t+1] - R[t+1]) C')
+ * On entry xt, Rt are the posterior of step t (packed), u = u[t], and xT, RT the smoothed estimate of step t + 1 (packed); on return
+ * xT, RT hold that of step t.  xt, Rt must not alias xT, RT.
+ * The form computed here:
+ *   - the prior x[t+1], R[t+1] is not stored by the forward pass: it is llpf_kf_predict applied to (xt, Rt, u) — the same function of
+ *     the same numbers, so the bits the forward pass produced;
+ *   - R[t+1] = L L', factored exactly as correct! factors S;
+ *   - G = A Rt (the rows predict! forms), then J' = L^-T (L^-1 G) = R[t+1]^-1 A Rt: J is the reference's C, renamed (C is the
+ *     measurement matrix here).  The forward substitution runs over increasing rows, the back substitution over decreasing rows with its
+ *     sum over increasing index; both multiply by 1 / L_ii;
+ *   - xT = xt + J d with d = xT[t+1] - x[t+1];
+ *   - with D = RT[t+1] - R[t+1] (packed), J D is formed one row at a time and RT = Rt + (J D) J' only in its lower triangle:
+ *     symmetrize() is the identity, as in the forward pass.
+ * A filter whose R[t+1] is not positive definite (a pivot not > 0, or NaN) gets NaN xT, RT at step t and so at every earlier step;
+ * nothing else is touched. */
+LLPF_HD void llpf_kf_smooth(const int nx, const int ny, const int nu, const double* P, const int64_t ps, const double* u, const double* xt,
+                            const double* Rt, double* xT, double* RT) {
+    /* the prior of step t + 1, then d = xT[t+1] - x[t+1], D = RT[t+1] - R[t+1] */
+    double xp[LLPF_KF_MAXX], L[LLPF_KF_NP(LLPF_KF_MAXX)], inv[LLPF_KF_MAXX];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) xp[r] = xt[r];
+    LLPF_KF_UNROLL
+    for (int i = 0; i < LLPF_KF_NP(nx); ++i) L[i] = Rt[i];
+    llpf_kf_predict(nx, ny, nu, P, ps, u, xp, L);
+    double d[LLPF_KF_MAXX], Dl[LLPF_KF_NP(LLPF_KF_MAXX)];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) d[r] = xT[r] - xp[r];
+    LLPF_KF_UNROLL
+    for (int i = 0; i < LLPF_KF_NP(nx); ++i) Dl[i] = RT[i] - L[i];
+    /* L L' = R[t+1], in place */
+    int ok = 1;
+    LLPF_KF_UNROLL
+    for (int i = 0; i < nx; ++i) {
+        LLPF_KF_UNROLL
+        for (int j = 0; j <= i; ++j) {
+            double acc = L[llpf_kf_idx(i, j)];
+            LLPF_KF_UNROLL
+            for (int k = 0; k < j; ++k) acc = llpf_fma(-L[llpf_kf_idx(i, k)], L[llpf_kf_idx(j, k)], acc);
+            if (i == j) {
+                ok = ok & (acc > 0.0);
+                const double piv = llpf_sqrt(acc);
+                L[llpf_kf_idx(i, i)] = piv;
+                inv[i] = 1.0 / piv;
+            } else {
+                L[llpf_kf_idx(i, j)] = acc * inv[j];
+            }
+        }
+    }
+    /* Jt = G = A Rt; Jt = L^-1 Jt; Jt = L^-T Jt.  Jt[i][c] = J'(i, c) = J(c, i) */
+    double Jt[LLPF_KF_MAXX * LLPF_KF_MAXX];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = LLPF_KF_P(r * nx) * Rt[llpf_kf_idx(0, c)];
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(r * nx + q), Rt[llpf_kf_idx(q, c)], acc);
+            Jt[r * LLPF_KF_MAXX + c] = acc;
+        }
+    }
+    LLPF_KF_UNROLL
+    for (int i = 0; i < nx; ++i) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = Jt[i * LLPF_KF_MAXX + c];
+            LLPF_KF_UNROLL
+            for (int q = 0; q < i; ++q) acc = llpf_fma(-L[llpf_kf_idx(i, q)], Jt[q * LLPF_KF_MAXX + c], acc);
+            Jt[i * LLPF_KF_MAXX + c] = acc * inv[i];
+        }
+    }
+    LLPF_KF_UNROLL
+    for (int n = 0; n < nx; ++n) {          /* row i = nx - 1 - n; q = i + 1 + p runs over i + 1 .. nx - 1 (this loop shape unrolls on the device) */
+        const int i = nx - 1 - n;
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = Jt[i * LLPF_KF_MAXX + c];
+            LLPF_KF_UNROLL
+            for (int p = 0; p < n; ++p) acc = llpf_fma(-L[llpf_kf_idx(i + 1 + p, i)], Jt[(i + 1 + p) * LLPF_KF_MAXX + c], acc);
+            Jt[i * LLPF_KF_MAXX + c] = acc * inv[i];
+        }
+    }
+    /* xT = xt + J d */
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        double acc = Jt[r] * d[0];
+        LLPF_KF_UNROLL
+        for (int q = 1; q < nx; ++q) acc = llpf_fma(Jt[q * LLPF_KF_MAXX + r], d[q], acc);
+        xT[r] = xt[r] + acc;
+    }
+    /* RT = Rt + (J D) J'  (lower triangle; row r of J D formed once) */
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        double m[LLPF_KF_MAXX];
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = Jt[r] * Dl[llpf_kf_idx(0, c)];
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(Jt[q * LLPF_KF_MAXX + r], Dl[llpf_kf_idx(q, c)], acc);
+            m[c] = acc;
+        }
+        LLPF_KF_UNROLL
+        for (int c = 0; c <= r; ++c) {
+            double acc = m[0] * Jt[c];
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(m[q], Jt[q * LLPF_KF_MAXX + c], acc);
+            RT[llpf_kf_idx(r, c)] = Rt[llpf_kf_idx(r, c)] + acc;
+        }
+    }
+    if (!ok) {                              /* R[t+1] not positive definite: this filter is NaN from here back */
+        LLPF_KF_UNROLL
+        for (int r = 0; r < nx; ++r) xT[r] = llpf_kf_nan();
+        LLPF_KF_UNROLL
+        for (int i = 0; i < LLPF_KF_NP(nx); ++i) RT[i] = llpf_kf_nan();
+    }
+}
 #undef LLPF_KF_P
 
 #endif /* LLPF_KALMAN_H */

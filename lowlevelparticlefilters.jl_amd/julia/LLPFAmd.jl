@@ -30,7 +30,7 @@ import LowLevelParticleFilters: AbstractParticleFilter, ParticleFilteringSolutio
     particles, weights, expweights, state, num_particles, index, particletype, parameters,
     effective_particles, shouldresample, weighted_mean, weighted_cov, weighted_quantile,
     dynamics, measurement, measurement_likelihood, dynamics_density, measurement_density, initial_density,
-    resample_threshold, resampling_strategy, KalmanFilteringSolution, covariance
+    resample_threshold, resampling_strategy, KalmanFilteringSolution, KalmanSmoothingSolution, covariance
 
 export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter, GPURBPF, GPUFilterBank, GPUMultiBank,
        LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMeasurement, GaussianLikelihood,
@@ -948,6 +948,12 @@ struct CKalmanOutputs                 # llpf_kalman_outputs
     Rt::Ptr{Float64}
     e::Ptr{Float64}
 end
+struct CKalmanSmoothOutputs           # llpf_kalman_smooth_outputs
+    struct_size::UInt32
+    pad::UInt32
+    xT::Ptr{Float64}
+    RT::Ptr{Float64}
+end
 mutable struct GPUKalmanFilterBank
     h::Ptr{Cvoid}
     F::Int
@@ -1000,6 +1006,35 @@ function kalman_run(b::GPUKalmanFilterBank, u, y; outputs = false)
     end
     ll, o
 end
+# the forward pass of kalman_run and the RTS smoother's backward pass (llpf_kalman_bank_smooth): ll_total, the forward outputs (or
+# nothing) and the smoothed xT (nx x F x T), RT (nx x nx x F x T)
+function kalman_smooth(b::GPUKalmanFilterBank, u, y; outputs = false)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    s = (xT = zeros(b.nx, b.F, T), RT = zeros(b.nx, b.nx, b.F, T))
+    GC.@preserve U Y ll o s begin
+        fwd = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        out = Ref(CKalmanSmoothOutputs(UInt32(sizeof(CKalmanSmoothOutputs)), 0, pointer(s.xT), pointer(s.RT)))
+        check(ccall((:llpf_kalman_bank_smooth, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{CKalmanOutputs}, Ptr{CKalmanSmoothOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), pointer(ll), fwd === nothing ? C_NULL : fwd, out))
+    end
+    ll, o, s
+end
+"smooth(bank, u, y): every filter's smoothed estimate (reset! first): ll (F), xT (nx x F x T), RT (nx x nx x F x T)"
+function smooth(b::GPUKalmanFilterBank, u, y)
+    reset!(b)
+    ll, _, s = kalman_smooth(b, u, y)
+    ll, s.xT, s.RT
+end
 "loglik(bank, u, y): every filter's loglik(kf, u, y) (reset! first, then T update! steps)"
 loglik(b::GPUKalmanFilterBank, u, y) = (reset!(b); kalman_run(b, u, y)[1])
 "x (nx x F), R (nx x nx x F) of every filter"
@@ -1021,7 +1056,8 @@ end
     GPUKalmanFilter(A, B, C, D, R1, R2, d0; Ts = 1.0, device = 0)
 
 The reference's `KalmanFilter` with constant matrices, run on the device (a bank of one filter, llpf_kalman_bank_*):
-`forward_trajectory` returns the reference's `KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `state`, `covariance`.
+`forward_trajectory` returns the reference's `KalmanFilteringSolution`, `smooth` its `KalmanSmoothingSolution`; `loglik`, `reset!`,
+`update!`, `state`, `covariance`.
 """
 mutable struct GPUKalmanFilter
     bank::GPUKalmanFilterBank
@@ -1044,6 +1080,20 @@ function forward_trajectory(kf::GPUKalmanFilter, u, y, p = NullParameters())
     T = length(y)
     KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
                             [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+end
+"""
+    smooth(kf::GPUKalmanFilter, u, y, p = NullParameters())
+
+reset!, forward_trajectory and the Rauch-Tung-Striebel smoother on the device: the reference's `KalmanSmoothingSolution`, built as
+`KalmanSmoothingSolution(sol, xT, RT)` from the forward `KalmanFilteringSolution`.
+"""
+function LowLevelParticleFilters.smooth(kf::GPUKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o, s = kalman_smooth(kf.bank, u, y; outputs = true)
+    T = length(y)
+    sol = KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                                  [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+    KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
 end
 
 end # module
