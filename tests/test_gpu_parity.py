@@ -12,9 +12,12 @@ import llpf_amd
 from llpf_amd import _capi, _structs as S
 import models as M
 import oracle_binding as ob
-from gpu_common import TOL_LL_STEP, TOL_LL_SUM, TOL_WE_REL, cfg_of as _cfg, compare_state as _compare_state
+from gpu_common import (TOL_LL_STEP, TOL_LL_SUM, TOL_WE_REL, assert_state_equal, assert_steps_equal, cfg_of as _cfg,
+                        compare_state as _compare_state)
 
 pytestmark = pytest.mark.gpu
+
+INDEP_WE_BOUND = 4.0      # exp-weights against np.longdouble, in units of u scale_i (see the threshold-0.1 test below)
 
 
 def test_device_math_bit_identical_to_host():
@@ -1063,85 +1066,205 @@ def test_repeated_runs_replay_a_captured_graph(thr):
 
 
 # ---- parity evidence at the BASELINE sizes themselves (oracle with OpenMP over the per-particle loops) -----------------
-def test_c2_full_size_leading_steps_bit_identical_to_the_device_order_oracle():
-    """BASELINE config C2 (N = 1e6, resampling at every step): per-step log-likelihoods of the first 20 timesteps, the particles,
-    the log-weights and the ancestors after them — bit for bit the device-order oracle's"""
-    model = M.lg_test_model()
-    _, U, Y = M.simulate_lg(model, 20, seed=1)
-    cfg = _cfg(model, 1000000, thr=1.0, seed=1000)
+# Every full-length case is built as bench.py builds the run it times (bench.build_workload, seed 1000, t_index0 1.0), so the suite
+# holds that very run to the device-order oracle, every step.  The oracle runs on 16 threads: its bits do not depend on them
+# (tests/test_oracle_threads.py).
+def _bench_case(name, N, T, thr=None):
+    import bench
+    model, U, Y, kind, thr0, _ = bench.build_workload(name, N, T)
+    return S.make_config(model, N, kind, S.RESAMPLE_SYSTEMATIC, thr0 if thr is None else thr, 1000, 0), U, Y
+
+
+def _oracle_run(cfg, U, Y, aux=False):
     ob.set_threads(16)
     try:
         o = ob.OracleFilter(cfg, ob.ORDER_DEVICE)
         o.reset()
-        ro = o.run(U, Y, 1.0, ll_steps=True)
+        ro = o.run_aux(U, Y, 1, ll_steps=True) if aux else o.run(U, Y, 1.0, ll_steps=True)
     finally:
         ob.set_threads(1)
+    return o, ro
+
+
+def _engine_run(g, U, Y, aux=False, **kw):
+    return g.run_aux(U, Y, 1, ll_steps=True, **kw) if aux else g.run(U, Y, 1.0, ll_steps=True, **kw)
+
+
+def _compare_full_run(g, rg, o, ro, rb=False):
+    """every step's log-likelihood, the resample count, the final particles, log-weights, exp-weights and ancestors (and, for the RB
+    kinds, every particle's Kalman mean and covariance) bit for bit; a mismatch names its first timestep"""
+    assert_steps_equal(rg["ll_steps"], ro["ll_steps"], resamples=(g.resample_count(), o.resample_count()))
+    assert g.resample_count() == o.resample_count()
+    _compare_state(g, o)
+    if rb:
+        xg, Rg = g.rb_linear_state()
+        xo, Ro = o.rb_linear_state()
+        assert_state_equal(xg, xo, "Kalman means")
+        assert_state_equal(Rg, Ro, "Kalman covariances")
+
+
+def _replays_repeat_the_first_run(g, U, Y, o, ro):
+    """seed(1000) and two reset()s bring the handle back to where its first run started (the constructor draws with reset index 0,
+    the first reset() with 1); the second run of the shape captures the run loop into a hipGraph, the third replays it.  Both must
+    give the first run's bits, which are the oracle's."""
+    for p in (2, 3):
+        g.seed(1000); g.reset(); g.reset()
+        rp = _engine_run(g, U, Y)
+        assert_steps_equal(rp["ll_steps"], ro["ll_steps"], "ll_steps of run %d" % p, resamples=(g.resample_count(), o.resample_count()))
+        _compare_state(g, o)
+
+
+def _c2_full_length(thr):
+    cfg, U, Y = _bench_case("lg", 1000000, 1000, thr)
+    o, ro = _oracle_run(cfg, U, Y)
     g = _capi.FilterHandle(cfg)
     g.reset()
-    rg = g.run(U, Y, 1.0, ll_steps=True)
-    assert np.array_equal(rg["ll_steps"].view(np.uint64), ro["ll_steps"].view(np.uint64))
-    assert g.resample_count() == o.resample_count() == 20
-    _compare_state(g, o)
+    rg = _engine_run(g, U, Y)
+    _compare_full_run(g, rg, o, ro)
+    return g, U, Y, o, ro
+
+
+def test_c2_full_length_bit_identical_to_the_device_order_oracle():
+    """bench.py's headline workload, C2 `lg`: the 2-D linear-Gaussian ParticleFilter, N = 1e6, T = 1000, systematic resampling at
+    every step (threshold 1.0).  Compared with the device-order oracle bit for bit: all 1000 per-step log-likelihoods, the resample
+    count, the final particles, log-weights, exp-weights and ancestors."""
+    g, _, _, _, _ = _c2_full_length(1.0)
+    assert g.resample_count() == 1000
+
+
+def test_c2_threshold_0_1_full_length_and_graph_replays_bit_identical_to_the_device_order_oracle():
+    """C2 `lg` at `bench.py --threshold 0.1` (the reference's default: resampling and non-resampling steps mixed), N = 1e6,
+    T = 1000.  Compared with the device-order oracle bit for bit: all 1000 per-step log-likelihoods, the resample count, the final
+    particles, log-weights, exp-weights and ancestors; then the second and third run of the handle (hipGraph capture, then replay)
+    are held to the same bits."""
+    g, U, Y, o, ro = _c2_full_length(0.1)
+    assert 0 < g.resample_count() < 1000
+    _replays_repeat_the_first_run(g, U, Y, o, ro)
 
 
 def test_c2_full_size_ancestor_mismatches_against_the_reference_order():
     """the count SURVEY 8(d) asks for: the engine's exact fixed-point bins against the reference's serial fp64 cumulative sum at
     N = 1e6, 50 teacher-forced resampling steps.  A threshold within ~1e-13 of a bin edge may fall on the other side: at most a
-    handful of the 5e7 ancestor decisions differ, and every output whose ancestor agrees has bit-identical particles."""
+    handful of the 5e7 ancestor decisions differ, and every output whose ancestor agrees has bit-identical particles.  Every
+    correct! is also held to an np.longdouble evaluation of the same step (gpu_common.independent_correct)."""
     from gpu_common import teacher_forced_ancestor_mismatches
     model = M.lg_test_model()
     _, U, Y = M.simulate_lg(model, 50, seed=1)
-    r = teacher_forced_ancestor_mismatches(_cfg(model, 1000000, thr=1.0, seed=1000), U, Y, 50)
+    r = teacher_forced_ancestor_mismatches(_cfg(model, 1000000, thr=1.0, seed=1000), U, Y, 50, threads=16, independent=True)
     print("teacher-forced ancestor mismatches at N = 1e6:", r)
     assert r["resampling_steps"] == 50
     assert r["mismatches_total"] <= 50 and r["mismatches_per_step_max"] <= 8, r
     assert r["particles_equal_on_matching_ancestors"]
     # the stated fp64 tolerance at the BASELINE size: every correct! from the reference order's own state
     assert r["correct_steps"] == 50 and r["ll_abs_err_max"] <= 1e-10 and r["expweights_rel_err_max"] <= 1e-12, r
+    assert r["indep_ll_abs_err_max"] <= 1e-12 and r["indep_expweights_bound_ratio_max"] <= INDEP_WE_BOUND, r
+
+
+def test_c2_full_size_correct_on_non_uniform_weights_against_independent_arithmetic():
+    """correct! at N = 1e6 on the non-uniform weights of threshold 0.1 (bench.py --threshold 0.1: C2 `lg`, seed 1000), 100
+    teacher-forced steps: lazy normalisation, the analytic-bound fast form and the ESS from fix96 sums, against (a) the reference
+    order (libm exp, pairwise sums, serial cumsum: |dll| <= 1e-10, exp-weights rel <= 1e-12) and (b) an np.longdouble evaluation of
+    the same step from the same fp64 particles and log-weights (gpu_common.independent_correct), which shares no arithmetic with the
+    engine: |dll| <= 1e-12, and every exp-weight within INDEP_WE_BOUND u scale_i of the long-double value (u = 2^-53).
+
+    The bound: log we_i = w_i + logpdf_i - ll is formed in fp64 from terms of size |w_i|, |logpdf_i|, |ll|, |log we_i|, each carrying
+    one or two roundings, and logpdf_i carries the cancellation in v = y - C x_i, worth |v_k| / Sigma_kk times v_k's rounding
+    (|y_k| + (|C| |x_i|)_k + |mu_k|) u; exp, the product by 1 / S and the rounding of the exact fix96 sum S add ~3 u.  scale_i (see
+    independent_correct) sums those sizes, so the relative error of we_i is c u scale_i with c of a few; INDEP_WE_BOUND = 4 holds
+    the count of roundings to that."""
+    from gpu_common import teacher_forced_ancestor_mismatches
+    cfg, U, Y = _bench_case("lg", 1000000, 100, 0.1)
+    r = teacher_forced_ancestor_mismatches(cfg, U, Y, 100, threads=16, independent=True)
+    print("teacher-forced correct! at threshold 0.1, N = 1e6:", r)
+    assert r["correct_steps"] == 100 and 0 < r["resampling_steps"] < 100, r
+    assert r["ll_abs_err_max"] <= 1e-10 and r["expweights_rel_err_max"] <= 1e-12, r
+    assert r["indep_ll_abs_err_max"] <= 1e-12 and r["indep_expweights_bound_ratio_max"] <= INDEP_WE_BOUND, r
+    assert r["mismatches_total"] <= 50 and r["particles_equal_on_matching_ancestors"], r
 
 
 def test_c4_share_bank_against_the_oracle():
-    """three filters of one GPU's share of BASELINE config C4 (128 filters x N = 1e5, noise-level sweep) against the device-order
-    ORACLE (not against single HIP filters): per-step log-likelihoods bit-identical"""
-    F, N, T = 128, 100000, 40
+    """bench.py's C4 workload, one GPU's share: 128 linear-Gaussian filters x N = 1e5, noise levels 10 ** linspace(-2, 0, 128),
+    data simulate_lg(lg_test_model(0.1), 1000, seed=1), T = 1000, threshold 0.1, seed 5 (filter k keys its streams with 5 + k), run
+    through a BankHandle (test_one_shard_is_the_plain_bank ties it to bench.py's MBankHandle).  The split schedule inside a bank over
+    a long run: per-step log-likelihoods bit-identical to the device-order ORACLE (not to single HIP filters), all 1000 steps of
+    filters 0, 63, 64 and 127 and the first 100 steps of all 128."""
+    F, N, T, T_all = 128, 100000, 1000, 100
     svec = 10.0 ** np.linspace(-2, 0, F)
     models = [M.lg_test_model(s) for s in svec]
-    _, U, Y = M.simulate_lg(M.lg_test_model(0.1), T)
-    bank = _capi.BankHandle(_cfg(models[0], N, thr=0.1, seed=900), models)
+    _, U, Y = M.simulate_lg(M.lg_test_model(0.1), T, seed=1)
+    bank = _capi.BankHandle(_cfg(models[0], N, thr=0.1, seed=5), models)
     bank.reset()
     rb = bank.run(U, Y, 1.0, ll_steps=True)
-    ob.set_threads(16)
-    try:
-        for k in (0, 61, 127):
-            o = ob.OracleFilter(_cfg(models[k], N, thr=0.1, seed=900 + k), ob.ORDER_DEVICE)
-            o.reset()
-            ro = o.run(U, Y, 1.0, ll_steps=True)
-            assert np.array_equal(ro["ll_steps"].view(np.uint64), rb["ll_steps"][:, k].copy().view(np.uint64)), k
-    finally:
-        ob.set_threads(1)
+    assert np.all(np.isfinite(rb["ll_steps"]))
+    for k in range(F):
+        full = k in (0, 63, 64, 127)
+        n = T if full else T_all
+        o, ro = _oracle_run(_cfg(models[k], N, thr=0.1, seed=5 + k), U[:n], Y[:n])
+        assert_steps_equal(rb["ll_steps"][:n, k], ro["ll_steps"], "ll_steps of filter %d" % k)
 
 
 def test_c3_full_size_full_length():
-    """BASELINE config C3 as specified: quad-tank AdvancedParticleFilter, N = 1e6, T = 2000 (through the t > 500 switch), threshold
-    0.5.  The first 8 timesteps are the device-order oracle's bit for bit; the whole run is finite, resamples at every step and
+    """bench.py's C3 workload as specified: quad-tank AdvancedParticleFilter (RK4 x 2), N = 1e6, T = 2000 (through the t > 500
+    switch), threshold 0.5, seed 1000, t_index0 1.0.  All 2000 per-step log-likelihoods, the resample count, the final particles,
+    log-weights, exp-weights and ancestors are the device-order oracle's bit for bit; the run is finite, resamples at every step and
     tracks the measured levels."""
-    model = M.quadtank_model()
-    U, Y = M.quadtank_data(2000)
-    cfg = _cfg(model, 1000000, thr=0.5, kind=S.ADVANCED_PARTICLE_FILTER, seed=5)
+    cfg, U, Y = _bench_case("quadtank", 1000000, 2000)
     g = _capi.FilterHandle(cfg)
     g.reset()
-    r = g.run(U, Y, 0.0, ll_steps=True, xmean=True)
+    r = _engine_run(g, U, Y, xmean=True)
     assert np.all(np.isfinite(r["ll_steps"])) and np.all(np.isfinite(r["xmean"]))
     assert g.resample_count() == 2000 and g.index() == 2001
     assert np.max(np.abs(r["xmean"][50:, :2] - Y[50:])) < 0.1
-    ob.set_threads(16)
-    try:
-        o = ob.OracleFilter(cfg, ob.ORDER_DEVICE)
-        o.reset()
-        ro = o.run(U[:8], Y[:8], 0.0, ll_steps=True)
-    finally:
-        ob.set_threads(1)
-    assert np.array_equal(r["ll_steps"][:8].view(np.uint64), ro["ll_steps"].view(np.uint64))
+    o, ro = _oracle_run(cfg, U, Y)
+    _compare_full_run(g, r, o, ro)
+
+
+def test_c5_rbpf_full_full_length():
+    """bench.py's C5 workload: the RBPF with per-particle 8x8 covariance (quad-tank levels + 8 linear states, state-dependent
+    coupling), N = 2e5, T = 1000, threshold 0.1, seed 1000.  All per-step log-likelihoods, the resample count, the final particles
+    ([xn; xl]), log-weights, exp-weights, ancestors and every particle's Kalman mean and covariance, bit for bit the device-order
+    oracle's."""
+    cfg, U, Y = _bench_case("rbpf_full", 200000, 1000)
+    o, ro = _oracle_run(cfg, U, Y)
+    g = _capi.FilterHandle(cfg)
+    g.reset()
+    rg = _engine_run(g, U, Y)
+    _compare_full_run(g, rg, o, ro, rb=True)
+    assert g.resample_count() > 0
+
+
+@pytest.mark.parametrize("thr", [1.0, 0.1])
+def test_c2_beyond_the_infinity_cache_full_length(thr):
+    """bench.py's C2 system at N = 1.6e7 (its `other_configs` run: a 1 GB working set, beyond the 256 MB Infinity Cache), T = 100,
+    seed 1000: threshold 1.0 takes the fused kernel's nontemporal 16-byte loop; threshold 0.1 the split schedule with lazy quanta at
+    its natural size, with blocks that are not all co-resident.  All 100 per-step log-likelihoods, the resample count and the final
+    particles, log-weights, exp-weights and ancestors are the device-order oracle's bit for bit.  At threshold 0.1 the second and
+    third run of the handle (hipGraph capture, then replay) are held to the same bits."""
+    cfg, U, Y = _bench_case("lg", 16000000, 100, thr)
+    o, ro = _oracle_run(cfg, U, Y)
+    g = _capi.FilterHandle(cfg)
+    g.reset()
+    rg = _engine_run(g, U, Y)
+    _compare_full_run(g, rg, o, ro)
+    if thr == 0.1:
+        assert 0 < g.resample_count() < 100
+        _replays_repeat_the_first_run(g, U, Y, o, ro)
+
+
+@pytest.mark.parametrize("name", ["aux", "rbpf"])
+def test_aux_and_rbpf_full_length(name):
+    """bench.py's `aux` workload (the AuxiliaryParticleFilter's loglik loop on the C2 system, run_aux mode 1) and its `rbpf` workload
+    (the RBPF of the reference's test/test_rbpf.jl system, constant coupling, threshold 0.1), N = 1e6, T = 1000, seed 1000.  All
+    per-step log-likelihoods, the resample count, the final particles, log-weights, exp-weights and ancestors bit for bit the
+    device-order oracle's."""
+    aux = name == "aux"
+    cfg, U, Y = _bench_case(name, 1000000, 1000)
+    o, ro = _oracle_run(cfg, U, Y, aux)
+    g = _capi.FilterHandle(cfg)
+    g.reset()
+    rg = _engine_run(g, U, Y, aux)
+    _compare_full_run(g, rg, o, ro)
+    assert g.resample_count() > 0
 
 
 def test_weighted_cov_on_the_device():
