@@ -91,6 +91,7 @@ static void test_throw(const char* site) {
 #include "host/smooth.hpp"
 #include "host/access.hpp"
 #include "host/mbank.hpp"
+#include "host/pipe.hpp"
 #include "host/simulate.hpp"
 #include "host/kalman.hpp"
 

@@ -2,12 +2,10 @@
 // shared/llpf_kalman.h).  Part of capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
 // Device layout: the constants par [npar][F] and the state [nx + np + 1][F] (x, packed R, the running ll_total of a run), SoA so that
-// lane f of a wave reads column f.  A run drives T in chunks as host/simulate.hpp does: chunk c runs into device staging buffer c % 2, a
-// second stream copies it to pinned buffer c % 2 while chunk c + 1 runs, and the host moves it to the caller's arrays while chunk c + 2
-// runs.  The state carries from chunk to chunk (and from run to run) in the device buffer, so the prefix of a long run is a short run and
-// run(a) followed by run(b) is run(a + b), bit for bit.  A run that asks for ll_total only stages nothing per step.
-constexpr size_t KF_CHUNK_BYTES = (size_t)64 << 20;
-constexpr int64_t KF_CHUNK_STEPS = 256;
+// lane f of a wave reads column f.  A run drives T through the chunked staging pipeline of host/pipe.hpp, counting a step's outputs and
+// per-filter inputs; outputs are time-major [T][F][width], per-filter inputs reach the device time-major as well.  The state carries from
+// chunk to chunk (and from run to run) in the device buffer, so the prefix of a long run is a short run and run(a) followed by run(b) is
+// run(a + b), bit for bit.  A run that asks for ll_total only stages nothing per step.
 
 struct llpf_kalman_bank : BankStream {
     int F = 0, nx = 0, ny = 0, nu = 0;
@@ -166,108 +164,37 @@ static int kalman_forward(llpf_kalman_bank& b, const double* U, const double* Y,
                       out ? out->Rt : nullptr, out ? out->e : nullptr};
     const uint64_t width[6] = {1, (uint64_t)nx, (uint64_t)nx, (uint64_t)nx * nx, (uint64_t)nx * nx, (uint64_t)ny};
     uint64_t w = 0;
-    for (int k = 0; k < 6; ++k) if (dst[k]) w += width[k];
+    std::vector<ChunkOut> outs;
+    for (int k = 0; k < 6; ++k) {
+        if (dst[k]) w += width[k];
+        outs.push_back({dst[k], 1, (size_t)F * width[k]});
+    }
     const uint64_t in_w = (upf ? (uint64_t)nu : 0) + (ypf ? (uint64_t)ny : 0);
-    uint64_t step_d = 0, total = 0, in_step = 0, in_total = 0;      // per-step outputs / per-filter inputs of all filters, in doubles
-    if (__builtin_mul_overflow((uint64_t)F, w, &step_d) || __builtin_mul_overflow(step_d, (uint64_t)T, &total) ||
-        __builtin_mul_overflow(total, (uint64_t)sizeof(double), &total) || total > (uint64_t)PTRDIFF_MAX ||
-        __builtin_mul_overflow((uint64_t)F, in_w, &in_step) ||
-        __builtin_mul_overflow(in_step, (uint64_t)T, &in_total) || __builtin_mul_overflow(in_total, (uint64_t)sizeof(double), &in_total) ||
-        in_total > (uint64_t)PTRDIFF_MAX)
+    uint64_t total = 0, in_total = 0;      // the per-step outputs / per-filter inputs of all filters and steps, in doubles
+    if (!doubles_fit({(uint64_t)F, w, (uint64_t)T}, total) || !doubles_fit({(uint64_t)F, in_w, (uint64_t)T}, in_total))
         return fail(LLPF_ERR_ARG, "kalman: the size of the outputs or of the inputs overflows");
     HIPC(hipSetDevice(b.device));
-    const size_t step_bytes = (size_t)(step_d + in_step) * sizeof(double);
-    // (shared inputs and no per-step outputs: nothing per step scales with F, the chunk is KF_CHUNK_STEPS)
-    const int64_t Tc = std::min<int64_t>(T, std::min<int64_t>(KF_CHUNK_STEPS, step_bytes ? std::max<int64_t>(1, (int64_t)(KF_CHUNK_BYTES / step_bytes))
-                                                                                         : KF_CHUNK_STEPS));
-    const int64_t nchunk = (T + Tc - 1) / Tc;
-    const int nbuf = nchunk > 1 ? 2 : 1;
-    const size_t chunk_out = (size_t)step_d * Tc;
-    const size_t chunk_u = nu > 0 ? (upf ? (size_t)F * Tc * nu : (size_t)Tc * nu) : 0;
-    const size_t chunk_y = ypf ? (size_t)F * Tc * ny : (size_t)Tc * ny;
-    // device buffers first: destroyed after the pipe has waited for the streams
-    DevBuf<double> d_out[2], d_u[2], d_y[2];
-    std::vector<double> upack[2], ypack[2];     // per-filter inputs of a chunk, repacked time-major [Tc][F][n] for one copy
-    SimPipe pipe;
-    pipe.compute = b.stream;
-    HIPC(hipStreamCreateWithFlags(&pipe.copy, hipStreamNonBlocking));
-    for (int i = 0; i < nbuf; ++i) {
-        if (chunk_out) {
-            CHK(d_out[i].ensure(chunk_out));
-            HIPC(hipHostMalloc(reinterpret_cast<void**>(&pipe.pinned[i]), chunk_out * sizeof(double), hipHostMallocDefault));
-        }
-        if (chunk_u) CHK(d_u[i].ensure(chunk_u));
-        CHK(d_y[i].ensure(chunk_y));
-        if (upf) upack[i].resize(chunk_u);
-        if (ypf) ypack[i].resize(chunk_y);
-        HIPC(hipEventCreateWithFlags(&pipe.ev_k[i], hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&pipe.ev_c[i], hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&pipe.ev_u[i], hipEventDisableTiming));
-    }
-    // chunk c's outputs from pinned buffer c % 2 into the caller's time-major arrays: one contiguous range per output
-    auto drain = [&](int64_t c) -> int {
-        const int s = (int)(c & 1);
-        const int64_t t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
-        HIPC(hipEventSynchronize(pipe.ev_c[s]));
-        const double* src = reinterpret_cast<const double*>(pipe.pinned[s]);
-        for (int k = 0; k < 6; ++k) {
-            if (!dst[k]) continue;
-            const size_t n = (size_t)tc * F * width[k];
-            memcpy(dst[k] + (size_t)t0 * F * width[k], src, n * sizeof(double));
-            src += n;
-        }
-        return LLPF_OK;
-    };
-    // per-filter rows [F][T][n] of steps [t0, t0 + tc) -> [tc][F][n]
-    auto repack = [&](const double* A, int n, int64_t t0, int64_t tc, double* p) {
-        for (int64_t k = 0; k < tc; ++k)
-            for (int f = 0; f < F; ++f) memcpy(p + ((size_t)k * F + f) * n, A + ((size_t)f * T + t0 + k) * n, sizeof(double) * n);
-    };
-    for (int64_t c = 0; c < nchunk; ++c) {
-        const int s = (int)(c & 1);
-        const int64_t t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
-        if (c >= 2 && chunk_out) HIPC(hipStreamWaitEvent(b.stream, pipe.ev_c[s], 0));     // staging s has been copied out (chunk c - 2)
-        if (c >= 2 && (upf || ypf)) HIPC(hipEventSynchronize(pipe.ev_u[s]));              // the copies of chunk c - 2 have read the packs
-        if (nu > 0) {
-            if (upf) {
-                repack(U, nu, t0, tc, upack[s].data());
-                HIPC(hipMemcpyAsync(d_u[s], upack[s].data(), sizeof(double) * tc * F * nu, hipMemcpyHostToDevice, b.stream));
-            } else {
-                HIPC(hipMemcpyAsync(d_u[s], U + (size_t)t0 * nu, sizeof(double) * tc * nu, hipMemcpyHostToDevice, b.stream));
-            }
-        }
-        if (ypf) {
-            repack(Y, ny, t0, tc, ypack[s].data());
-            HIPC(hipMemcpyAsync(d_y[s], ypack[s].data(), sizeof(double) * tc * F * ny, hipMemcpyHostToDevice, b.stream));
-        } else {
-            HIPC(hipMemcpyAsync(d_y[s], Y + (size_t)t0 * ny, sizeof(double) * tc * ny, hipMemcpyHostToDevice, b.stream));
-        }
-        HIPC(hipEventRecord(pipe.ev_u[s], b.stream));
+    ChunkPipe pipe(b.stream);
+    // (shared inputs and no per-step outputs: nothing per step scales with F, the chunk is CHUNK_STEPS)
+    CHK(pipe.open(T, (size_t)F * (w + in_w) * sizeof(double), outs,
+                  {{nu > 0 ? U : nullptr, upf ? (size_t)F : 0, (size_t)nu, true}, {Y, ypf ? (size_t)F : 0, (size_t)ny, true}}));
+    for (int64_t c = 0; c < pipe.nchunk; ++c) {
+        CHK(pipe.begin(c, c));
         KalmanArgs a{};
         a.par = b.d_par; a.state = b.d_state;
-        a.u = nu > 0 ? d_u[s].p : nullptr;
-        a.y = d_y[s].p;
-        double* o = d_out[s].p;
+        a.u = pipe.in(0);
+        a.y = pipe.in(1);
         double** slot[6] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.e};
-        for (int k = 0; k < 6; ++k) {
-            *slot[k] = dst[k] ? o : nullptr;
-            if (dst[k]) o += (size_t)tc * F * width[k];
-        }
-        a.F = F; a.Tc = (int32_t)tc; a.nu = nu;
+        for (int k = 0; k < 6; ++k) *slot[k] = pipe.out(k);
+        a.F = F; a.Tc = (int32_t)pipe.tc; a.nu = nu;
         a.u_per = upf ? 1 : 0; a.y_per = ypf ? 1 : 0;
         a.first = c == 0 ? 1 : 0;
         a.par_tstride = 0;
-        a.post = post ? post + (size_t)t0 * (nx + b.np) * F : nullptr;
+        a.post = post ? post + (size_t)pipe.t0 * (nx + b.np) * F : nullptr;
         HIPC(launch_kalman(nx, ny, a, b.stream));
-        if (chunk_out) {
-            HIPC(hipEventRecord(pipe.ev_k[s], b.stream));
-            HIPC(hipStreamWaitEvent(pipe.copy, pipe.ev_k[s], 0));
-            HIPC(hipMemcpyAsync(pipe.pinned[s], d_out[s], (size_t)step_d * tc * sizeof(double), hipMemcpyDeviceToHost, pipe.copy));
-            HIPC(hipEventRecord(pipe.ev_c[s], pipe.copy));
-            if (c >= 1) CHK(drain(c - 1));
-        }
+        CHK(pipe.end());
     }
-    if (chunk_out) CHK(drain(nchunk - 1));
+    CHK(pipe.finish());
     if (ll_total)     // the running sum: row nx + np of the state
         HIPC(hipMemcpyAsync(ll_total, b.d_state.p + (size_t)(nx + b.np) * F, sizeof(double) * F, hipMemcpyDeviceToHost, b.stream));
     HIPC(hipStreamSynchronize(b.stream));
@@ -276,8 +203,9 @@ static int kalman_forward(llpf_kalman_bank& b, const double* U, const double* Y,
 
 // smooth(kf, u, y): the forward pass of a run (the same chunks, outputs and state as kalman_run) that also stores the packed posterior
 // of every step on the device (d_post: (nx + np) * 8 bytes per filter-step), then the backward pass k_kalman_smooth over the chunks in
-// reverse through the same staging pipeline.  Everything is allocated before the first launch, so a call that cannot get its memory
-// leaves the state as it was.  The state after the call is the one kalman_run leaves (the prior of step T and the running ll).
+// reverse through a staging pipeline of its own (host/pipe.hpp).  Everything is allocated before the first launch, so a call that cannot
+// get its memory leaves the state as it was.  The state after the call is the one kalman_run leaves (the prior of step T and the running
+// ll).
 static int kalman_smooth(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
                          const llpf_kalman_outputs* fwd, const llpf_kalman_smooth_outputs* out) {
     CHK(kalman_check_run(b, U, Y, T, per_filter, fwd));
@@ -288,89 +216,37 @@ static int kalman_smooth(llpf_kalman_bank& b, const double* U, const double* Y, 
     double* dst[2] = {out ? out->xT : nullptr, out ? out->RT : nullptr};
     const uint64_t width[2] = {(uint64_t)nx, (uint64_t)nx * nx};
     const uint64_t w = (dst[0] ? width[0] : 0) + (dst[1] ? width[1] : 0);
-    uint64_t post_d = 0, post_b = 0, step_d = 0, total = 0, in_step = upf ? (uint64_t)F * nu : 0;
-    if (__builtin_mul_overflow((uint64_t)ns * F, (uint64_t)T, &post_d) || __builtin_mul_overflow(post_d, (uint64_t)sizeof(double), &post_b) ||
-        post_b > (uint64_t)PTRDIFF_MAX || __builtin_mul_overflow((uint64_t)F, w, &step_d) || __builtin_mul_overflow(step_d, (uint64_t)T, &total) ||
-        __builtin_mul_overflow(total, (uint64_t)sizeof(double), &total) || total > (uint64_t)PTRDIFF_MAX)
+    uint64_t post_d = 0, total = 0;
+    if (!doubles_fit({(uint64_t)ns, (uint64_t)F, (uint64_t)T}, post_d) || !doubles_fit({(uint64_t)F, w, (uint64_t)T}, total))
         return fail(LLPF_ERR_ARG, "kalman: the size of the stored posterior or of the smoothed outputs overflows");
     test_throw("kalman_smooth");
     if (!w) return kalman_forward(b, U, Y, T, per_filter, ll_total, fwd, nullptr);     // nothing smoothed is asked for: a run
     HIPC(hipSetDevice(b.device));
-    const size_t step_bytes = (size_t)(step_d + in_step) * sizeof(double);
-    const int64_t Tc = std::min<int64_t>(T, std::min<int64_t>(KF_CHUNK_STEPS, std::max<int64_t>(1, (int64_t)(KF_CHUNK_BYTES / step_bytes))));
-    const int64_t nchunk = (T + Tc - 1) / Tc;
-    const int nbuf = nchunk > 1 ? 2 : 1;
-    const size_t chunk_out = (size_t)step_d * Tc;
-    const size_t chunk_u = nu > 0 ? (upf ? (size_t)F * Tc * nu : (size_t)Tc * nu) : 0;
     CHK(b.d_post.ensure((size_t)post_d));
-    DevBuf<double> d_out[2], d_u[2], d_carry;
-    std::vector<double> upack[2];
-    SimPipe pipe;
-    pipe.compute = b.stream;
-    HIPC(hipStreamCreateWithFlags(&pipe.copy, hipStreamNonBlocking));
-    CHK(d_carry.ensure((size_t)ns * F));
-    for (int i = 0; i < nbuf; ++i) {
-        CHK(d_out[i].ensure(chunk_out));
-        HIPC(hipHostMalloc(reinterpret_cast<void**>(&pipe.pinned[i]), chunk_out * sizeof(double), hipHostMallocDefault));
-        if (chunk_u) CHK(d_u[i].ensure(chunk_u));
-        if (upf) upack[i].resize(chunk_u);
-        HIPC(hipEventCreateWithFlags(&pipe.ev_k[i], hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&pipe.ev_c[i], hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&pipe.ev_u[i], hipEventDisableTiming));
-    }
+    ChunkPipe pipe(b.stream);
+    double* d_carry = nullptr;
+    CHK(pipe.device((size_t)ns * F, d_carry));
+    CHK(pipe.open(T, (size_t)F * (w + (upf ? nu : 0)) * sizeof(double), {{dst[0], 1, (size_t)F * width[0]}, {dst[1], 1, (size_t)F * width[1]}},
+                  {{nu > 0 ? U : nullptr, upf ? (size_t)F : 0, (size_t)nu, true}}));
     // the forward pass allocates its own staging before its first launch: no launch has run when it returns an allocation failure
     CHK(kalman_forward(b, U, Y, T, per_filter, ll_total, fwd, b.d_post.p));
-    // backward launch i runs chunk nchunk - 1 - i into staging i % 2
-    auto drain = [&](int64_t i) -> int {
-        const int s = (int)(i & 1);
-        const int64_t c = nchunk - 1 - i, t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
-        HIPC(hipEventSynchronize(pipe.ev_c[s]));
-        const double* src = reinterpret_cast<const double*>(pipe.pinned[s]);
-        for (int k = 0; k < 2; ++k) {
-            if (!dst[k]) continue;
-            const size_t n = (size_t)tc * F * width[k];
-            memcpy(dst[k] + (size_t)t0 * F * width[k], src, n * sizeof(double));
-            src += n;
-        }
-        return LLPF_OK;
-    };
-    for (int64_t i = 0; i < nchunk; ++i) {
-        const int s = (int)(i & 1);
-        const int64_t c = nchunk - 1 - i, t0 = c * Tc, tc = std::min<int64_t>(Tc, T - t0);
-        if (i >= 2) HIPC(hipStreamWaitEvent(b.stream, pipe.ev_c[s], 0));       // staging s has been copied out (launch i - 2)
-        if (i >= 2 && upf) HIPC(hipEventSynchronize(pipe.ev_u[s]));           // the copy of launch i - 2 has read the pack
-        if (nu > 0) {
-            if (upf) {
-                for (int64_t k = 0; k < tc; ++k)
-                    for (int f = 0; f < F; ++f)
-                        memcpy(upack[s].data() + ((size_t)k * F + f) * nu, U + ((size_t)f * T + t0 + k) * nu, sizeof(double) * nu);
-                HIPC(hipMemcpyAsync(d_u[s], upack[s].data(), sizeof(double) * tc * F * nu, hipMemcpyHostToDevice, b.stream));
-            } else {
-                HIPC(hipMemcpyAsync(d_u[s], U + (size_t)t0 * nu, sizeof(double) * tc * nu, hipMemcpyHostToDevice, b.stream));
-            }
-        }
-        HIPC(hipEventRecord(pipe.ev_u[s], b.stream));
+    for (int64_t i = 0; i < pipe.nchunk; ++i) {      // backward: launch i runs chunk nchunk - 1 - i
+        CHK(pipe.begin(i, pipe.nchunk - 1 - i));
         KalmanSmoothArgs a{};
         a.par = b.d_par;
-        a.post = b.d_post.p + (size_t)t0 * ns * F;
+        a.post = b.d_post.p + (size_t)pipe.t0 * ns * F;
         a.carry = d_carry;
-        a.u = nu > 0 ? d_u[s].p : nullptr;
-        double* o = d_out[s].p;
-        a.xT = dst[0] ? o : nullptr;
-        if (dst[0]) o += (size_t)tc * F * width[0];
-        a.RT = dst[1] ? o : nullptr;
-        a.F = F; a.Tc = (int32_t)tc; a.ny = ny; a.nu = nu;
+        a.u = pipe.in(0);
+        a.xT = pipe.out(0);
+        a.RT = pipe.out(1);
+        a.F = F; a.Tc = (int32_t)pipe.tc; a.ny = ny; a.nu = nu;
         a.u_per = upf ? 1 : 0;
         a.init = i == 0 ? 1 : 0;
         a.par_tstride = 0;
         HIPC(launch_kalman_smooth(nx, a, b.stream));
-        HIPC(hipEventRecord(pipe.ev_k[s], b.stream));
-        HIPC(hipStreamWaitEvent(pipe.copy, pipe.ev_k[s], 0));
-        HIPC(hipMemcpyAsync(pipe.pinned[s], d_out[s], (size_t)step_d * tc * sizeof(double), hipMemcpyDeviceToHost, pipe.copy));
-        HIPC(hipEventRecord(pipe.ev_c[s], pipe.copy));
-        if (i >= 1) CHK(drain(i - 1));
+        CHK(pipe.end());
     }
-    CHK(drain(nchunk - 1));
+    CHK(pipe.finish());
     HIPC(hipStreamSynchronize(b.stream));
     return LLPF_OK;
 }

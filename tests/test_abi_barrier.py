@@ -68,6 +68,19 @@ def test_device_resources_are_owned():
                 assert re.search(r"std::unique_ptr<\w+> \w+\(new \(std::nothrow\)|\w+\.reset\(new \(std::nothrow\)", line), (name, line)
     a, b = _struct_span(bank, "Bank")
     assert not re.search(r"\bcap(_\w+|[A-Z]\w*)\b", bank[a:b])
+    # ... and so are the copy stream, the events and the pinned memory of the chunked staging pipeline (host/pipe.hpp: ChunkPipe): outside
+    # it nothing creates them; the only other streams are the banks' own (BankStream::stream, destroyed by BankStream)
+    pipe = srcs["host/pipe.hpp"]
+    a, b = _struct_span(pipe, "ChunkPipe")
+    assert all(word in pipe[a:b] for word in ("hipHostMalloc(", "hipHostFree(", "hipStreamCreateWithFlags(", "hipEventCreateWithFlags("))
+    srcs["host/pipe.hpp"] = pipe[:a] + pipe[b:]
+    for name, src in srcs.items():
+        for word in ("hipHostMalloc(", "hipHostFree(", "hipEventCreateWithFlags(", "SimPipe"):
+            assert word not in src, (name, word)
+        for line in src.splitlines():
+            if "hipStreamCreateWithFlags(" in line:
+                assert name in ("host/bank.hpp", "host/kalman.hpp") and "(&b.stream, hipStreamNonBlocking)" in line, (name, line)
+    assert sum(src.count("hipStreamCreateWithFlags(") for src in srcs.values()) == 2
 
 
 class _Inject:

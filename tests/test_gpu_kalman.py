@@ -94,6 +94,9 @@ def test_chunks_and_continuation(host):
     h, _ = kc.host_run(host, systems, U, Y, 700)
     _same(long, h, OUTS + ("ll",), "T = 700")
     b.reset()
+    bare = b.run(U, Y)                                 # shared inputs and no per-step output over three chunks: nothing is staged out
+    assert kc.bits_equal(bare["ll"], h["ll"]) and kc.bits_equal(bare["ll"], long["ll"])
+    b.reset()
     whole = b.run(U[:50], Y[:50], outputs=OUTS)
     b.reset()
     first = b.run(U[:25], Y[:25], outputs=OUTS)
@@ -111,6 +114,24 @@ def test_chunks_and_continuation(host):
     b.run(U[25:50], Y[25:50])
     ref = b.run(U[:10], Y[:10], outputs=("ll_steps",))
     assert kc.bits_equal(llonly["ll"], ref["ll"]) and kc.bits_equal(x2, b.get_state()[0])
+
+
+def test_chunks_limited_by_bytes_with_a_ragged_tail(host):
+    # (nx, ny, nu) = (4, 2, 2), F = 4000, per-filter U and Y, every output: 43 + 4 doubles per filter-step, 1.5 MB per step, so the
+    # 64 MiB staging limit gives chunks of 44 steps: 200 steps are chunks of 44, 44, 44, 44 and 24
+    rng = np.random.default_rng(8)
+    F, T = 4000, 200
+    systems = [kc.random_system(rng, 4, 2, 2, k % 3) for k in range(F)]
+    U = rng.standard_normal((F, T, 2))
+    Y = 2.0 * rng.standard_normal((F, T, 2))
+    Y[::9, 43, 0] = Y[::9, 44, 0] = Y[::11, 199, 0] = np.nan
+    g = _bank(systems).run(U, Y, True, True, outputs=OUTS)
+    pick = [0, 1, 63, 64, 65, 1999, 2000, 3998, 3999] + list(range(9, 4000, 99))
+    h, _ = kc.host_run(host, [systems[k] for k in pick], U[pick], Y[pick], T, per_filter=3)
+    for key in OUTS:
+        assert kc.bits_equal(g[key][:, pick], h[key]), key
+    assert kc.bits_equal(g["ll"][pick], h["ll"])
+    assert np.all(np.isfinite(g["ll"])) and np.all(np.isfinite(g["R"][-1]))
 
 
 def test_missing_rows_and_a_filter_that_loses_definiteness(host):

@@ -183,6 +183,32 @@ def test_chunks_a_long_run_has_the_short_run_as_prefix():
     assert np.all(np.isfinite(XL)) and np.std(XL[-1]) > 0
     _, Yonly = h.simulate(Mtr, TL, U, u_per_trajectory=True, seed=21, step0=1, flags=flags, states=False)
     assert np.array_equal(BITS(Yonly), BITS(YL))               # Y alone: the same numbers
+    Xonly, _ = h.simulate(Mtr, TL, U, u_per_trajectory=True, seed=21, step0=1, flags=flags, measurements=False)
+    assert np.array_equal(BITS(Xonly), BITS(XL))               # and X alone
+
+
+@pytest.mark.parametrize("per_trajectory", [False, True], ids=["shared_u", "per_trajectory_u"])
+def test_chunks_limited_by_bytes_with_a_ragged_tail(per_trajectory):
+    # M = 2^15, LG 2 x 2 with X and Y: 1 MiB per step, so the 64 MiB staging limit gives chunks of 64 steps: 200 steps are
+    # chunks of 64, 64, 64 and 8 (both staging slots are used twice, the last chunk is short), 130 end inside the third
+    model = M.lg_c1_model()
+    Mtr, TL, TS = 1 << 15, 200, 130
+    U = np.random.default_rng(6).standard_normal((Mtr, TL, model.nu) if per_trajectory else (TL, model.nu))
+    h = _handle(model, 256, 9)
+    sim = lambda m, T, u, **kw: h.simulate(m, T, np.ascontiguousarray(u), u_per_trajectory=per_trajectory, seed=33, step0=2,
+                                           flags=ALL | _capi.SIM_SAMPLE_INITIAL, **kw)
+    XL, YL = sim(Mtr, TL, U)
+    XS, YS = sim(Mtr, TS, U[..., :TS, :])
+    assert np.array_equal(BITS(XL[:TS]), BITS(XS)) and np.array_equal(BITS(YL[:TS]), BITS(YS))
+    # trajectory m depends on m and the seed only: the first 64 of 2^15 are the 64 of a small run (one chunk of 200 steps)
+    X64, Y64 = sim(64, TL, U[:64] if per_trajectory else U)
+    assert np.array_equal(BITS(XL[:, :64]), BITS(X64)) and np.array_equal(BITS(YL[:, :64]), BITS(Y64))
+    assert np.all(np.isfinite(XL)) and np.std(XL[-1]) > 0 and np.std(YL[-1]) > 0
+    # one output alone (0.5 MiB per step: chunks of 128 and 72) sits at offset 0 of the staging
+    _, Yonly = sim(Mtr, TL, U, states=False)
+    assert np.array_equal(BITS(Yonly), BITS(YL))
+    Xonly, _ = sim(Mtr, TL, U, measurements=False)
+    assert np.array_equal(BITS(Xonly), BITS(XL))
 
 
 def test_the_handle_is_untouched():
