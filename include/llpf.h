@@ -414,6 +414,42 @@ int  llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double*
 int  llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R);
 int  llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R);
 
+/* ---- banks of unscented Kalman filters (the reference's UnscentedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise) -----
+ * n_filters independent unscented Kalman filters, one GPU thread each, in the operation order of csrc/shared/llpf_ukf.h (that header is
+ * the definition: a host build of it around the same model functions gives the same bits):
+ *   x' = f(x, u, p, tau) + w, w ~ N(0, R1);  y = g(x, u, p, tau) + e, e ~ N(0, R2);  x_0 ~ d0;  2 nx + 1 sigma points, drawn from the prior
+ *   for correct! and again from the posterior for predict!.
+ * The descriptors are the llpf_model a bank of particle filters is built from: LLPF_MODEL_LINEAR_GAUSSIAN, LLPF_MODEL_QUADTANK_RK4 or a
+ * model of llpf_model_compile; R1 = cov(dynamics_density), R2 = cov(measurement_density), d0 = initial_density, every covariance kind.
+ * nx <= 8, ny <= 4, nu <= 8, the same model id and dimensions for every filter.  LLPF_ERR_ARG: other dimensions, the Rao-Blackwellized
+ * model ids, a compiled model with a `loglik`, `noise` or `initial` member of its own, a noise density with a non-zero mean, a covariance
+ * that is not positive definite, weights that are not finite or gamma, wi <= 0.
+ * The weights are four numbers for the whole bank: the spread gamma of the points X_0 = m, X_i = m + gamma C[:, i], X_{L+i} = m - gamma
+ * C[:, i] (R = C C'), the mean weights wm0, wi, ..., wi and the covariance weights wc0, wi, ..., wi; every named parameter set is a
+ * host-side formula of these.  A filter whose R or S = cov(Y) + R2 loses definiteness is NaN from that step on; the run returns LLPF_OK
+ * and the other filters are unaffected.  Steps, missing rows, outputs and the carried state are those of llpf_kalman_bank_run; step t
+ * evaluates the model at tau = (t_index0 + t) * Ts as llpf_run does. */
+typedef struct llpf_ukf_bank llpf_ukf_bank;
+typedef struct llpf_ukf_weights {
+    uint32_t struct_size;                /* sizeof(llpf_ukf_weights): guards growth */
+    uint32_t pad;
+    double gamma, wm0, wc0, wi;
+} llpf_ukf_weights;
+int  llpf_ukf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, const llpf_ukf_weights* w, llpf_ukf_bank** out);
+int  llpf_ukf_bank_destroy(llpf_ukf_bank* b);
+/* reset!: x = mean(d0), R = cov(d0) */
+int  llpf_ukf_bank_reset(llpf_ukf_bank* b);
+/* new parameters for every filter (same model id and dimensions, nothing reallocated; the state is left as it is, the next reset uses the
+ * new d0) / new weights for the bank */
+int  llpf_ukf_bank_set_models(llpf_ukf_bank* b, const llpf_model* models);
+int  llpf_ukf_bank_set_weights(llpf_ukf_bank* b, const llpf_ukf_weights* w);
+/* T steps of every filter; U, Y, per_filter, ll_total and out as llpf_kalman_bank_run takes them */
+int  llpf_ukf_bank_run(llpf_ukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                       double* ll_total, const llpf_kalman_outputs* out);
+/* state, covariance of every filter: x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
+int  llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R);
+int  llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R);
+
 /* ---- sweeps sharded over the GPUs of one node (multi-GPU banks) ------------------------------
  * The same sweep as llpf_bank_*, with filter k on shard k mod n_shards (one shard = one GPU, one stream): the reference's
  * one-filter-per-thread layout (src/smoothing.jl:335-347, test/runtests.jl:412-417) with GPUs for threads.  Filters never

@@ -47,6 +47,14 @@ SYMBOLS = {
     "llpf_kalman_bank_smooth": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.KalmanOutputs), C.POINTER(S.KalmanSmoothOutputs)],
     "llpf_kalman_bank_get_state": [_vp, _dp, _dp],
     "llpf_kalman_bank_set_state": [_vp, _dp, _dp],
+    "llpf_ukf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.POINTER(S.UkfWeights), C.POINTER(_vp)],
+    "llpf_ukf_bank_destroy": [_vp],
+    "llpf_ukf_bank_reset": [_vp],
+    "llpf_ukf_bank_set_models": [_vp, C.POINTER(S.Model)],
+    "llpf_ukf_bank_set_weights": [_vp, C.POINTER(S.UkfWeights)],
+    "llpf_ukf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_ukf_bank_get_state": [_vp, _dp, _dp],
+    "llpf_ukf_bank_set_state": [_vp, _dp, _dp],
     "llpf_num_particles": [_vp, _ip],
     "llpf_index": [_vp, _ip],
     "llpf_get_particles": [_vp, _dp],
@@ -558,6 +566,66 @@ class KalmanBankHandle:
         x = f64(x).reshape(self.F, self.nx)
         R = f64(R).reshape(self.F, self.nx, self.nx)
         check(self.L.llpf_kalman_bank_set_state(self.h, dptr(x), dptr(R)))
+
+
+def ukf_weights(w):
+    """(gamma, wm0, wc0, wi) as an llpf_ukf_weights"""
+    gamma, wm0, wc0, wi = (float(v) for v in w)
+    return S.UkfWeights(C.sizeof(S.UkfWeights), 0, gamma, wm0, wc0, wi)
+
+
+class UkfBankHandle(KalmanBankHandle):
+    """RAII wrapper of an `llpf_ukf_bank*` (independent unscented Kalman filters on one device); `weights` = (gamma, wm0, wc0, wi)."""
+
+    def __init__(self, device, models, weights):
+        self.L = lib()
+        self.h = _vp()
+        self.F = len(models)
+        m0 = models[0]
+        self.nx, self.nu, self.ny = m0.nx, m0.nu, m0.ny
+        arr = (S.Model * self.F)(*models)
+        w = ukf_weights(weights)
+        check(self.L.llpf_ukf_bank_create(int(device), arr, self.F, C.byref(w), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.llpf_ukf_bank_destroy(self.h)
+            self.h = None
+
+    def reset(self):
+        check(self.L.llpf_ukf_bank_reset(self.h))
+
+    def set_models(self, models):
+        arr = (S.Model * self.F)(*models)
+        check(self.L.llpf_ukf_bank_set_models(self.h, arr))
+
+    def set_weights(self, weights):
+        w = ukf_weights(weights)
+        check(self.L.llpf_ukf_bank_set_weights(self.h, C.byref(w)))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
+        """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""
+        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
+        res, out = self._forward_outputs(T, outputs)
+        ll = np.empty(self.F)
+        check(self.L.llpf_ukf_bank_run(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), float(t_index0),
+                                       dptr(ll), None if out is None else C.byref(out)))
+        res["ll"] = ll
+        return res
+
+    def smooth(self, *args, **kw):
+        raise NotImplementedError("there is no unscented smoother")
+
+    def get_state(self):
+        x = np.empty((self.F, self.nx))
+        R = np.empty((self.F, self.nx, self.nx))
+        check(self.L.llpf_ukf_bank_get_state(self.h, dptr(x), dptr(R)))
+        return x, R
+
+    def set_state(self, x, R):
+        x = f64(x).reshape(self.F, self.nx)
+        R = f64(R).reshape(self.F, self.nx, self.nx)
+        check(self.L.llpf_ukf_bank_set_state(self.h, dptr(x), dptr(R)))
 
 
 class BankHandle:

@@ -64,6 +64,11 @@ class KalmanSmoothOutputs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_uint32), ("xT", C.POINTER(C.c_double)), ("RT", C.POINTER(C.c_double))]
 
 
+class UkfWeights(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_uint32), ("gamma", C.c_double), ("wm0", C.c_double), ("wc0", C.c_double),
+                ("wi", C.c_double)]
+
+
 class MBankInfo(C.Structure):
     _fields_ = [("n_filters", C.c_int32), ("n_shards", C.c_int32), ("n_local_shards", C.c_int32),
                 ("first_local_shard", C.c_int32), ("n_local_filters", C.c_int32), ("collective", C.c_int32),

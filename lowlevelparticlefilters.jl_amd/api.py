@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -444,7 +444,7 @@ class KalmanSmoothingSolution(KalmanFilteringSolution):
 
 
 def covariance(kf):
-    """covariance(kf) — the covariance R of the current estimate of a KalmanFilter"""
+    """covariance(kf) — the covariance R of the current estimate of a KalmanFilter or an UnscentedKalmanFilter"""
     return kf.R
 
 
@@ -518,6 +518,191 @@ class KalmanFilterBank:
         u, up, y, yp = self._io(u, y)
         self._h.reset()
         return self._h.smooth(u, y, up, yp, outputs=outputs, forward=forward)
+
+
+class MerweParams:
+    """MerweParams(alpha, beta, kappa) — the scaled unscented transform of Van der Merwe.  With L = nx:
+    lambda = alpha^2 (L + kappa) - L,  gamma = sqrt(L + lambda),  wm0 = lambda / (L + lambda),  wc0 = wm0 + 1 - alpha^2 + beta,
+    wi = 1 / (2 (L + lambda)).  Defaults (1e-3, 2, 0): unverified against the reference (no source here)."""
+
+    def __init__(self, alpha=1e-3, beta=2.0, kappa=0.0):
+        self.alpha, self.beta, self.kappa = float(alpha), float(beta), float(kappa)
+
+    def weights(self, L):
+        a2 = self.alpha * self.alpha
+        lam = a2 * (L + self.kappa) - L
+        wm0 = lam / (L + lam)
+        return float(np.sqrt(L + lam)), wm0, wm0 + 1.0 - a2 + self.beta, 1.0 / (2.0 * (L + lam))
+
+
+class WikiParams:
+    """WikiParams(alpha, beta, kappa) — the parametrisation of the Wikipedia article on the Kalman filter.  With L = nx:
+    gamma = alpha sqrt(kappa),  wm0 = (alpha^2 kappa - L) / (alpha^2 kappa),  wc0 = wm0 + 1 - alpha^2 + beta,  wi = 1 / (2 alpha^2 kappa).
+    Defaults (1, 0, 1): unverified against the reference (no source here)."""
+
+    def __init__(self, alpha=1.0, beta=0.0, kappa=1.0):
+        self.alpha, self.beta, self.kappa = float(alpha), float(beta), float(kappa)
+
+    def weights(self, L):
+        a2k = self.alpha * self.alpha * self.kappa
+        wm0 = (a2k - L) / a2k
+        return float(self.alpha * np.sqrt(self.kappa)), wm0, wm0 + 1.0 - self.alpha * self.alpha + self.beta, 1.0 / (2.0 * a2k)
+
+
+class TrivialParams:
+    """TrivialParams() — every one of the 2 L + 1 points carries the same weight: wm0 = wc0 = wi = 1 / (2 L + 1), gamma = sqrt(L + 1/2)
+    (so that wi gamma^2 = 1/2: mean and covariance of a linear map are exact).  The default of UnscentedKalmanFilter.  Name and default
+    follow the reference's documentation; the formula is unverified against the reference (no source here)."""
+
+    def weights(self, L):
+        w = 1.0 / (2.0 * L + 1.0)
+        return float(np.sqrt(L + 0.5)), w, w, w
+
+
+def _ukf_weights(weight_params, L):
+    """(gamma, wm0, wc0, wi) from a preset (an object with weights(L)), a raw 4-tuple, or None (TrivialParams)"""
+    if weight_params is None:
+        weight_params = TrivialParams()
+    if hasattr(weight_params, "weights"):
+        return tuple(float(v) for v in weight_params.weights(int(L)))
+    w = tuple(float(v) for v in weight_params)
+    if len(w) != 4:
+        raise ValueError("weight_params: a preset (MerweParams, WikiParams, TrivialParams) or the four numbers (gamma, wm0, wc0, wi)")
+    return w
+
+
+class UnscentedKalmanFilter:
+    """UnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts, nu, ny, p, weight_params, device) — the reference's unscented Kalman
+    filter with additive noise: x' = f(x, u, p, t) + w, w ~ N(0, R1);  y = g(x, u, p, t) + e, e ~ N(0, R2);  x_0 ~ d0 (csrc/shared/llpf_ukf.h
+    is the definition).  `dynamics` / `measurement` are what a ParticleFilter takes: LinearDynamics + LinearMeasurement, QuadTankDynamics +
+    QuadTankMeasurement, UserDynamics + UserMeasurement, or a pair of plain callables (traced: tracing.py; pass nu=, and ny= unless R2 is
+    a matrix).  R1, R2: matrices (a 1-D array: the diagonal; a float: sigma^2 I); d0: MvNormal.  weight_params: MerweParams, WikiParams,
+    TrivialParams (the default) or the four numbers (gamma, wm0, wc0, wi).  Runs on the device as a bank of one filter (llpf_ukf_bank_*),
+    created on first use.  nx <= 8, ny <= 4, nu <= 8."""
+
+    def __init__(self, dynamics, measurement, R1, R2, d0, *, Ts=1.0, nu=-1, ny=-1, p=None, weight_params=None, device=0):
+        nx = len(d0)
+        if ny < 0 and np.ndim(R2) >= 1:
+            ny = np.asarray(R2).shape[0]
+        if _is_plain_callable(dynamics):
+            if ny < 0:
+                raise ValueError("pass ny= with callable dynamics and a scalar R2")
+            dynamics, measurement, _ = _trace_callables(dynamics, measurement, None, nx, nu, ny, p)
+        if isinstance(dynamics, UserDynamics):
+            ny = dynamics.ny
+        elif isinstance(measurement, LinearMeasurement):
+            ny = measurement.C.shape[0]
+        elif isinstance(measurement, QuadTankMeasurement):
+            ny = 2
+        cov = lambda c, n: MvNormal(np.zeros(n), c if np.ndim(c) < 2 else np.atleast_2d(np.asarray(c, float)))
+        self.dynamics, self.measurement, self.R1, self.R2, self.d0 = dynamics, measurement, R1, R2, d0
+        self.dynamics_density, self.measurement_density, self.initial_density = cov(R1, nx), cov(R2, ny), d0
+        self.p, self.Ts, self.device = p, float(Ts), int(device)
+        self._model = _build_model(dynamics, measurement, self.dynamics_density, self.measurement_density, d0, Ts)
+        self.nx, self.nu, self.ny = self._model.nx, self._model.nu, self._model.ny
+        self.weight_params = weight_params
+        self.weights = _ukf_weights(weight_params, self.nx)
+        self._handle = None
+        self._index = 0
+
+    @property
+    def _h(self):
+        if self._handle is None:
+            self._handle = _capi.UkfBankHandle(self.device, [self._model], self.weights)
+        return self._handle
+
+    @property
+    def x(self):
+        """state(ukf): the current estimate"""
+        return self._h.get_state()[0][0]
+
+    @property
+    def R(self):
+        """covariance(ukf)"""
+        return self._h.get_state()[1][0]
+
+    def reset(self):
+        self._h.reset()
+        self._index = 1         # index(pf) after reset!, as the particle filters count it
+
+    def _run(self, u, y, outputs=(), t_index0=0.0):
+        y = np.asarray(y, dtype=np.float64)
+        y = y.reshape(y.shape[0], -1) if y.ndim else y.reshape(1, 1)
+        u = None if self.nu == 0 else np.asarray(u, dtype=np.float64).reshape(y.shape[0], -1)
+        r = self._h.run(u, y, outputs=outputs, t_index0=t_index0)
+        self._index += y.shape[0]
+        return r
+
+    def _step(self, u, y, t, outputs):
+        """one step at time t (default index * Ts): y None is a missing measurement"""
+        t0 = float(self._index) if t is None else float(t) / self.Ts
+        yr = np.full((1, self.ny), np.nan) if y is None else np.atleast_1d(np.asarray(y, float))[None]
+        ur = np.zeros((1, max(self.nu, 1))) if u is None else np.atleast_1d(np.asarray(u, float))[None]
+        return self._run(ur, yr, outputs, t0)
+
+    def __call__(self, u, y, p=None, t=None):
+        return update(self, u, y, p, t)
+
+
+class UnscentedKalmanFilterBank:
+    """n independent unscented Kalman filters of the same model family and dimensions on one device, one GPU thread each
+    (llpf_ukf_bank_*): the deterministic log-likelihood of every parameter set of a nonlinear sweep.  `filters_spec` is a list of
+    UnscentedKalmanFilter or of (dynamics, measurement, R1, R2, d0) tuples; `weight_params` as UnscentedKalmanFilter takes them, one set
+    for the bank."""
+
+    def __init__(self, filters_spec, device=0, weight_params=None, Ts=1.0):
+        models = self._models(filters_spec, Ts)
+        self._init(models, device, weight_params)
+
+    def _init(self, models, device, weight_params):
+        self.device = int(device)
+        self.weights = _ukf_weights(weight_params, models[0].nx)
+        self._h = _capi.UkfBankHandle(self.device, models, self.weights)
+        self.n_filters = len(models)
+        self.Ts = float(models[0].Ts)
+
+    @staticmethod
+    def _models(filters_spec, Ts):
+        return [(f if isinstance(f, UnscentedKalmanFilter) else UnscentedKalmanFilter(*f, Ts=Ts))._model for f in filters_spec]
+
+    @classmethod
+    def from_filter_bank(cls, bank, device=None, weight_params=None):
+        """the unscented twin of a FilterBank: the same descriptors (any model that is not Rao-Blackwellized and keeps the Gaussian
+        densities), loglik and forward at the times FilterBank.loglik and FilterBank.forward use"""
+        self = cls.__new__(cls)
+        self._init(list(bank._models), bank._h.cfg.device if device is None else device, weight_params)
+        return self
+
+    def set_parameters(self, filters_spec):
+        """new parameters for every filter (same model and dimensions, nothing reallocated: llpf_ukf_bank_set_models)"""
+        self._h.set_models(self._models(filters_spec, self.Ts))
+
+    def set_weights(self, weight_params):
+        self.weights = _ukf_weights(weight_params, self._h.nx)
+        self._h.set_weights(self.weights)
+
+    def reset(self):
+        self._h.reset()
+
+    def state(self):
+        """(x [F, nx], R [F, nx, nx]) of every filter"""
+        return self._h.get_state()
+
+    _io = KalmanFilterBank._io
+
+    def loglik(self, u, y):
+        """[loglik(ukf_k, u, y) for k]: reset, then T update! steps, the first at t = 1 * Ts as FilterBank.loglik.  u [T, nu] / y [T, ny]
+        shared, or [F, T, n] per filter (by ndim)."""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.run(u, y, up, yp, t_index0=1.0)["ll"]
+
+    def forward(self, u, y, outputs=_capi.KALMAN_OUTPUTS):
+        """forward_trajectory of every filter (the first step at t = 0): {"ll": [F], "ll_steps": [T, F], "x", "xt": [T, F, nx], "R", "Rt":
+        [T, F, nx, nx], "e": [T, F, ny]} for the names in `outputs`"""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.run(u, y, up, yp, outputs=outputs, t_index0=0.0)
 
 
 class RBMeasurementModel:
@@ -654,6 +839,8 @@ class ParticleFilteringSolution:
 # ---------------------------------------------------------------------------------------------------
 def reset(pf):
     """reset!(pf) — reference src/filtering.jl:4-14 (src/kalman.jl:159-164 for a KalmanFilter)."""
+    if isinstance(pf, UnscentedKalmanFilter):
+        return pf.reset()
     pf._h.reset()
 
 
@@ -672,6 +859,9 @@ def _pt(args, kw, skip):
 def predict(pf, u, *args, **kw):
     """predict!(pf, u, p, t = index(pf)*Ts) — reference src/filtering.jl:140-153;
     predict!(pf::AuxiliaryParticleFilter, u, y1, p, t) — :195-217 (y1 = the NEXT measurement)."""
+    if isinstance(pf, UnscentedKalmanFilter):      # a step whose measurement is missing: correct! is skipped, predict! runs
+        pf._step(u, None, _pt(args, kw, 0)[1], ())
+        return
     if isinstance(pf, AuxiliaryParticleFilter):
         y1 = args[0] if args else kw.get("y1")
         pf._h.aux_predict(u, y1, _t(pf, _pt(args, kw, 1)[1]))
@@ -682,6 +872,13 @@ def predict(pf, u, *args, **kw):
 def correct(pf, u, y, p=None, t=None):
     """ll, 0 = correct!(pf, u, y, p, t) — reference src/filtering.jl:164-168.  y=None means missing.
     For an AuxiliaryParticleFilter (:170-174) only logsumexp! runs: the measurement update was done in predict!."""
+    if isinstance(pf, UnscentedKalmanFilter):
+        # the posterior of a one-step run put back as the state: the same numbers (the packed lower triangle of Rt is what the step holds)
+        i = pf._index
+        r = pf._step(u, y, t, ("xt", "Rt", "e"))
+        pf._h.set_state(r["xt"][0], r["Rt"][0])
+        pf._index = i
+        return float(r["ll"][0]), r["e"][0, 0]
     if isinstance(pf, AuxiliaryParticleFilter):
         return pf._h.aux_correct(), 0
     return pf._h.correct(u, y, _t(pf, t)), 0
@@ -693,6 +890,9 @@ def update(pf, u, y, *args, **kw):
     ll, e = update!(kf::KalmanFilter, u, y): correct! then predict!, continuing the filter's state."""
     if isinstance(pf, KalmanFilter):
         r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], ("e",))
+        return float(r["ll"][0]), r["e"][0, 0]
+    if isinstance(pf, UnscentedKalmanFilter):
+        r = pf._step(u, y, _pt(args, kw, 0)[1], ("e",))
         return float(r["ll"][0]), r["e"][0, 0]
     if isinstance(pf, AuxiliaryParticleFilter):
         y1 = args[0] if args else kw.get("y1")
@@ -711,6 +911,10 @@ def forward_trajectory(pf, u, y, p=None, quantiles=None):
         reset(pf)
         r = pf._run(u, y, _capi.KALMAN_OUTPUTS)
         return KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
+    if isinstance(pf, UnscentedKalmanFilter):
+        reset(pf)
+        r = pf._run(u, y, _capi.KALMAN_OUTPUTS, 0.0)
+        return KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
     reset(pf)
     if isinstance(pf, AuxiliaryParticleFilter):
         if quantiles is not None:
@@ -728,6 +932,8 @@ def loglik(pf, u, y, p=None):
     reset(pf)
     if isinstance(pf, KalmanFilter):
         return float(pf._run(u, y)["ll"][0])
+    if isinstance(pf, UnscentedKalmanFilter):      # the first step at t = 1 * Ts, as the particle filters' loglik
+        return float(pf._run(u, y, (), 1.0)["ll"][0])
     if isinstance(pf, AuxiliaryParticleFilter):
         return pf._h.run_aux(u, y, mode=1)["ll"]
     return pf._h.run(u, y, t_index0=1.0)["ll"]
@@ -1007,7 +1213,7 @@ def expweights(pf):
 
 
 def state(pf):
-    if isinstance(pf, KalmanFilter):
+    if isinstance(pf, (KalmanFilter, UnscentedKalmanFilter)):
         return pf.x
     return pf.state
 

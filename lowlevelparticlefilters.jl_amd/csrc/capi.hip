@@ -16,6 +16,7 @@
 #include "engine.hpp"
 #include "shared/llpf_rbkf.h"
 #include "shared/llpf_kalman.h"
+#include "shared/llpf_ukf.h"
 
 using namespace llpf;
 
@@ -94,6 +95,7 @@ static void test_throw(const char* site) {
 #include "host/pipe.hpp"
 #include "host/simulate.hpp"
 #include "host/kalman.hpp"
+#include "host/ukf.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -234,6 +236,28 @@ int llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double* 
 } LLPF_GUARD(llpf_kalman_bank_smooth)
 int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kalman_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
 int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kalman_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
+
+// ---- banks of unscented Kalman filters (host/ukf.hpp) ----
+int llpf_ukf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, const llpf_ukf_weights* w, llpf_ukf_bank** out) LLPF_TRY {
+    if (!out) return fail(LLPF_ERR_ARG, "null out pointer");
+    *out = nullptr;
+    std::unique_ptr<llpf_ukf_bank> b(new (std::nothrow) llpf_ukf_bank());
+    if (!b) return fail(LLPF_ERR_ALLOC, "out of host memory");
+    CHK(ukf_create(device, models, n_filters, w, *b));
+    *out = b.release();
+    return LLPF_OK;
+} LLPF_GUARD(llpf_ukf_bank_create)
+int llpf_ukf_bank_destroy(llpf_ukf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_ukf_bank_destroy)
+int llpf_ukf_bank_reset(llpf_ukf_bank* b) LLPF_TRY { NEEDF(b); return ukf_reset(*b); } LLPF_GUARD(llpf_ukf_bank_reset)
+int llpf_ukf_bank_set_models(llpf_ukf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return ukf_set_models(*b, models); } LLPF_GUARD(llpf_ukf_bank_set_models)
+int llpf_ukf_bank_set_weights(llpf_ukf_bank* b, const llpf_ukf_weights* w) LLPF_TRY { NEEDF(b); return ukf_set_weights(*b, w); } LLPF_GUARD(llpf_ukf_bank_set_weights)
+int llpf_ukf_bank_run(llpf_ukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                      const llpf_kalman_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return ukf_run(*b, U, Y, T, per_filter, t_index0, ll_total, out);
+} LLPF_GUARD(llpf_ukf_bank_run)
+int llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return ukf_get_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_get_state)
+int llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return ukf_set_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_set_state)
 
 int llpf_rb_get_covariance(llpf_filter* f, double* R) LLPF_TRY {
     NEEDF(f);

@@ -260,6 +260,7 @@ struct ResArgs {
 
 // ---- end of the part the run-time compiled user-model kernels see (tools/gen_jit_prelude.py cuts here) ----
 #include "kernels/sim_args.hpp"
+#include "kernels/ukf_args.hpp"
 // arguments of k_kalman (kernels/kalman.hpp): one launch is one chunk of steps [t0, t0 + Tc) of F Kalman filters, one thread per filter.
 // Device arrays are SoA / time-major: a wave's 64 lanes read and write whole lines.
 struct KalmanArgs {
@@ -352,6 +353,10 @@ hipError_t launch_simulate(int model_id, int nx, int ny, const ModelD* models, i
 hipError_t launch_kalman(int nx, int ny, const KalmanArgs& a, hipStream_t s);
 // the backward (RTS smoother) pass of those banks over one chunk, nx in 1..8 (ny, nu at run time)
 hipError_t launch_kalman_smooth(int nx, const KalmanSmoothArgs& a, hipStream_t s);
+// banks of unscented Kalman filters (k_ukf.hip; kernels/ukf.hpp): ukf_prepare compiles the k_ukf of a run-time compiled model (a user model,
+// the linear-Gaussian model above 4 states) on its first use (0, or -1 with `err` set); launch_ukf runs one chunk of steps
+int ukf_prepare(int model_id, int nx, int ny, std::string& err);
+hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const UkfArgs& a, hipStream_t s);
 // kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
 bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
 const char* jit_prelude();

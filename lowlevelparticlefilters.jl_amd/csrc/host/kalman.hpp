@@ -61,6 +61,14 @@ static int kalman_pack(const llpf_model* models, const double* D, int32_t F, int
     return LLPF_OK;
 }
 
+// the device and the stream of a bank of one-thread-per-filter filters (this file's, and host/ukf.hpp's)
+static int kf_open_stream(BankStream& b, int device) {
+    b.device = device;
+    HIPC(hipSetDevice(device));
+    HIPC(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    return LLPF_OK;
+}
+
 static int kalman_create(int32_t device, const llpf_model* models, const double* D, int32_t F, llpf_kalman_bank& b) {
     std::vector<double> par;
     CHK(kalman_pack(models, D, F, b.nx, b.ny, b.nu, par, b.h_init));
@@ -73,9 +81,7 @@ static int kalman_create(int32_t device, const llpf_model* models, const double*
     b.np = LLPF_KF_NP(b.nx);
     b.npar = LLPF_KF_NPAR(b.nx, b.ny, b.nu);
     b.nstate = b.nx + b.np + 1;
-    b.device = device;
-    HIPC(hipSetDevice(device));
-    HIPC(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    CHK(kf_open_stream(b, device));
     CHK(b.d_par.ensure(par.size()));
     CHK(b.d_state.ensure(b.h_init.size()));
     HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));

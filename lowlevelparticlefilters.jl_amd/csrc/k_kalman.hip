@@ -9,6 +9,7 @@ namespace llpf {
 
 #define DEV __device__ __forceinline__
 
+#include "kernels/kf_store.hpp"
 #include "kernels/kalman.hpp"
 
 template <int NX, int NY>

@@ -1,0 +1,161 @@
+// k_ukf.hip — k_ukf (kernels/ukf.hpp): banks of unscented Kalman filters (llpf_ukf_bank_run).
+// One of the engine's device translation units: LinGauss<NX, NY> for NX, NY in 1..4 and QuadTank<4, 2> are instantiated here and nowhere
+// else.  A run-time compiled model (a user snippet, a traced callable, the linear-Gaussian model above 4 states) gets its k_ukf from a
+// hiprtc program of its own, compiled on the first bank of that model and cached per model — the program of llpf_model_compile is left
+// as it is.
+#include <hip/hiprtc.h>
+
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "engine.hpp"
+#include "shared/llpf_ukf.h"
+#include "jit_ukf.inc"
+
+namespace llpf {
+
+#define DEV __device__ __forceinline__
+
+#include "kernels/reduce.hpp"
+#include "kernels/models.hpp"
+#include "kernels/kf_store.hpp"
+#include "kernels/ukf.hpp"
+
+template <class Model, int NX, int NY>
+static hipError_t launch_ukf_t(const ModelD* models, const UkfArgs& a, hipStream_t s) {
+    const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
+    hipLaunchKernelGGL((k_ukf<Model, NX, NY>), g, dim3(KF_BLOCK), 0, s, models, a);
+    return hipGetLastError();
+}
+template <int NX>
+static hipError_t launch_ukf_lg(int ny, const ModelD* models, const UkfArgs& a, hipStream_t s) {
+    switch (ny) {
+        case 1: return launch_ukf_t<LinGauss<NX, 1>, NX, 1>(models, a, s);
+        case 2: return launch_ukf_t<LinGauss<NX, 2>, NX, 2>(models, a, s);
+        case 3: return launch_ukf_t<LinGauss<NX, 3>, NX, 3>(models, a, s);
+        case 4: return launch_ukf_t<LinGauss<NX, 4>, NX, 4>(models, a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- run-time compiled models ----
+struct JitUkf {
+    std::vector<char> code;
+    std::string name;                          // lowered name of k_ukf<UserModel, nx, ny>
+    struct PerDevice { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; };
+    std::vector<PerDevice> dev;                // indexed by device ordinal, loaded on first use
+};
+static std::mutex g_ukf_mutex;
+static std::map<std::string, std::unique_ptr<JitUkf>> g_ukf;      // by ukf_key
+
+static bool ukf_builtin(int model_id, int nx, int ny) {
+    return (model_id == LLPF_MODEL_LINEAR_GAUSSIAN && nx <= 4 && ny <= 4) || model_id == LLPF_MODEL_QUADTANK_RK4;
+}
+// the model's snippet: a user model's own source, or LinGauss<nx, ny> above the precompiled dimensions
+static bool ukf_snippet(int model_id, int nx, int ny, std::string& snippet) {
+    if (model_id == LLPF_MODEL_LINEAR_GAUSSIAN) {
+        snippet = "struct UserModel : LinGauss<" + std::to_string(nx) + ", " + std::to_string(ny) + "> {};\n";
+        return true;
+    }
+    int sx = 0, sy = 0;
+    return jit_model_source(model_id, snippet, sx, sy) && sx == nx && sy == ny;
+}
+static std::string ukf_key(int model_id, int nx, int ny) {
+    return std::to_string(model_id) + ":" + std::to_string(nx) + ":" + std::to_string(ny);
+}
+
+int ukf_prepare(int model_id, int nx, int ny, std::string& err) {
+    if (ukf_builtin(model_id, nx, ny)) return 0;
+    const std::string key = ukf_key(model_id, nx, ny);
+    {
+        std::lock_guard<std::mutex> lk(g_ukf_mutex);
+        if (g_ukf.count(key)) return 0;
+    }
+    std::string snippet;
+    if (!ukf_snippet(model_id, nx, ny, snippet)) { err = "unknown model id " + std::to_string(model_id) + " at these dimensions"; return -1; }
+    std::string src(jit_prelude());
+    src += "\n";
+    src += LLPF_JIT_UKF_SHARED;
+    src += "\nnamespace llpf {\n";
+    src += snippet;
+    src += "\n";
+    src += LLPF_JIT_UKF;
+    src += "\n}  // namespace llpf\n";
+    hiprtcProgram prog = nullptr;
+    if (hiprtcCreateProgram(&prog, src.c_str(), "llpf_user_ukf.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) { err = "hiprtcCreateProgram failed"; return -1; }
+    const std::string expr = "llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ">";
+    hiprtcAddNameExpression(prog, expr.c_str());
+    int devid = 0;
+    hipDeviceProp_t prop;
+    std::string arch = "gfx950";
+    if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.gcnArchName[0]) arch = prop.gcnArchName;
+    const std::string archopt = "--offload-arch=" + arch;
+    // the options of this unit (Makefile): -ffp-contract=off, the same bits
+    const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-value"};
+    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
+    if (rc != HIPRTC_SUCCESS) {
+        size_t n = 0;
+        hiprtcGetProgramLogSize(prog, &n);
+        std::string log(n, '\0');
+        if (n) hiprtcGetProgramLog(prog, &log[0]);
+        err = std::string("hiprtc (k_ukf): ") + hiprtcGetErrorString(rc) + "\n" + log;
+        hiprtcDestroyProgram(&prog);
+        return -1;
+    }
+    std::unique_ptr<JitUkf> ju(new JitUkf());
+    size_t sz = 0;
+    hiprtcGetCodeSize(prog, &sz);
+    ju->code.resize(sz);
+    hiprtcGetCode(prog, ju->code.data());
+    const char* low = nullptr;
+    if (hiprtcGetLoweredName(prog, expr.c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + expr; hiprtcDestroyProgram(&prog); return -1; }
+    ju->name = low;
+    hiprtcDestroyProgram(&prog);
+    std::lock_guard<std::mutex> lk(g_ukf_mutex);
+    if (!g_ukf.count(key)) g_ukf[key] = std::move(ju);      // another thread may have compiled it meanwhile: the first one stays
+    return 0;
+}
+
+// this device's handle of the compiled kernel (loaded on first use)
+static hipError_t ukf_function(int model_id, int nx, int ny, hipFunction_t* fn) {
+    int devid = 0;
+    hipError_t e = hipGetDevice(&devid);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(g_ukf_mutex);
+    auto it = g_ukf.find(ukf_key(model_id, nx, ny));
+    if (it == g_ukf.end()) return hipErrorInvalidValue;      // ukf_prepare compiles it first
+    JitUkf& ju = *it->second;
+    if ((int)ju.dev.size() <= devid) ju.dev.resize((size_t)devid + 1);
+    JitUkf::PerDevice& pd = ju.dev[(size_t)devid];
+    if (!pd.mod && (e = hipModuleLoadData(&pd.mod, ju.code.data())) != hipSuccess) return e;
+    if (!pd.fn && (e = hipModuleGetFunction(&pd.fn, pd.mod, ju.name.c_str())) != hipSuccess) return e;
+    *fn = pd.fn;
+    return hipSuccess;
+}
+
+hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const UkfArgs& a, hipStream_t s) {
+    if (!ukf_builtin(model_id, nx, ny)) {
+        hipFunction_t fn = nullptr;
+        const hipError_t e = ukf_function(model_id, nx, ny, &fn);
+        if (e != hipSuccess) return e;
+        UkfArgs aa = a;
+        void* args[] = {&models, &aa};
+        return hipModuleLaunchKernel(fn, (unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1, KF_BLOCK, 1, 1, 0, s, args, nullptr);
+    }
+    if (model_id == LLPF_MODEL_QUADTANK_RK4) {
+        if (nx != 4 || ny != 2) return hipErrorInvalidValue;
+        return launch_ukf_t<QuadTank<4, 2>, 4, 2>(models, a, s);
+    }
+    switch (nx) {
+        case 1: return launch_ukf_lg<1>(ny, models, a, s);
+        case 2: return launch_ukf_lg<2>(ny, models, a, s);
+        case 3: return launch_ukf_lg<3>(ny, models, a, s);
+        case 4: return launch_ukf_lg<4>(ny, models, a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace llpf

@@ -7,38 +7,10 @@
 // lines); shared U / Y rows are one address for every lane, per-filter rows come time-major [Tc][F][n].  Outputs are time-major
 // [Tc][F][...], a lane's n doubles consecutive.
 // ------------------------------------------------------------------------------------------------
-constexpr int KF_BLOCK = 64;
+// (KF_BLOCK, kf_store, kf_store_dense: kernels/kf_store.hpp, shared with k_ukf)
 #ifndef KF_RELOAD
 #define KF_RELOAD(nx, ny) ((nx) >= 5)
-#endif        // one wave per workgroup: a bank of 10^3 filters still spreads over 16 CUs
-
-typedef double llpf_kf_d2 __attribute__((ext_vector_type(2)));
-template <int N>
-DEV void kf_store(double* p, const double* v) {
-    if constexpr (N % 2 == 0) {       // 16-byte stores: p is 16-byte aligned (N even, the buffer 256-byte aligned)
-#pragma unroll
-        for (int d = 0; d < N; d += 2) {
-            llpf_kf_d2 w;
-            w.x = v[d];
-            w.y = v[d + 1];
-            *reinterpret_cast<llpf_kf_d2*>(p + d) = w;
-        }
-    } else {
-#pragma unroll
-        for (int d = 0; d < N; ++d) p[d] = v[d];
-    }
-}
-// the dense nx x nx form of the packed R, row by row
-template <int NX>
-DEV void kf_store_dense(double* p, const double* R) {
-    double row[NX];
-#pragma unroll
-    for (int r = 0; r < NX; ++r) {
-#pragma unroll
-        for (int c = 0; c < NX; ++c) row[c] = R[llpf_kf_idx(r, c)];
-        kf_store<NX>(p + r * NX, row);
-    }
-}
+#endif
 
 // POST: also store the posterior of every step for the backward pass (KalmanArgs::post; a run without it compiles to the kernel it was)
 template <int NX, int NY, bool POST>

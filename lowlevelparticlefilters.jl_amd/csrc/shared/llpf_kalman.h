@@ -55,52 +55,12 @@
 LLPF_HD int llpf_kf_idx(int r, int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
 LLPF_HD double llpf_kf_nan(void) { return llpf_u2d(0x7ff8000000000000ULL); }
 
-/* correct!(kf, u, y): the innovation e (ny), x and R updated in place; returns logpdf(N(0, S), e).
- * A row whose first element is NaN is missing: x and R stay, e is NaN, the result is 0. */
-LLPF_HD double llpf_kf_correct(const int nx, const int ny, const int nu, const double* P, const int64_t ps, const double* u,
-                               const double* y, double* x, double* R, double* e) {
-    if (!(y[0] == y[0])) {
-        LLPF_KF_UNROLL
-        for (int r = 0; r < ny; ++r) e[r] = llpf_kf_nan();
-        return 0.0;
-    }
-    const int oC = LLPF_KF_OFF_C(nx), oR2 = LLPF_KF_OFF_R2(nx, ny), oD = LLPF_KF_OFF_D(nx, ny, nu);
-    /* e = y - (C x + D u) */
-    LLPF_KF_UNROLL
-    for (int r = 0; r < ny; ++r) {
-        double acc = LLPF_KF_P(oC + r * nx) * x[0];
-        LLPF_KF_UNROLL
-        for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(oC + r * nx + q), x[q], acc);
-        for (int c = 0; c < nu; ++c) acc = llpf_fma(LLPF_KF_P(oD + r * nu + c), u[c], acc);
-        e[r] = y[r] - acc;
-    }
-    /* CR = C R  (ny x nx) */
-    double CR[LLPF_KF_MAXY * LLPF_KF_MAXX];
-    LLPF_KF_UNROLL
-    for (int r = 0; r < ny; ++r) {
-        LLPF_KF_UNROLL
-        for (int c = 0; c < nx; ++c) {
-            double acc = LLPF_KF_P(oC + r * nx) * R[llpf_kf_idx(0, c)];
-            LLPF_KF_UNROLL
-            for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(oC + r * nx + q), R[llpf_kf_idx(q, c)], acc);
-            CR[r * LLPF_KF_MAXX + c] = acc;
-        }
-    }
-    /* S = (C R) C' + R2, lower triangle, factored in place: L L' = S */
-    double L[LLPF_KF_NP(LLPF_KF_MAXY)], inv[LLPF_KF_MAXY];
-    LLPF_KF_UNROLL
-    for (int r = 0; r < ny; ++r) {
-        LLPF_KF_UNROLL
-        for (int c = 0; c <= r; ++c) {
-            double acc = CR[r * LLPF_KF_MAXX] * LLPF_KF_P(oC + c * nx);
-            LLPF_KF_UNROLL
-            for (int q = 1; q < nx; ++q) acc = llpf_fma(CR[r * LLPF_KF_MAXX + q], LLPF_KF_P(oC + c * nx + q), acc);
-            L[llpf_kf_idx(r, c)] = acc + LLPF_KF_P(oR2 + llpf_kf_idx(r, c));
-        }
-    }
+/* L L' = S in place: S is the packed lower triangle (n x n) on entry, its lower Cholesky factor on return; inv[i] = 1 / L_ii.
+ * Returns 1 when every pivot is > 0 (a NaN pivot fails the test), else 0 — the factor is then not usable. */
+LLPF_HD int llpf_kf_chol(const int n, double* L, double* inv) {
     int ok = 1;
     LLPF_KF_UNROLL
-    for (int i = 0; i < ny; ++i) {
+    for (int i = 0; i < n; ++i) {
         LLPF_KF_UNROLL
         for (int j = 0; j <= i; ++j) {
             double acc = L[llpf_kf_idx(i, j)];
@@ -116,6 +76,16 @@ LLPF_HD double llpf_kf_correct(const int nx, const int ny, const int nu, const d
             }
         }
     }
+    return ok;
+}
+
+/* The measurement update from the innovation covariance S (packed lower triangle in L, factored here), the cross term CR (ny x nx, row
+ * stride LLPF_KF_MAXX: C R of the Kalman filter, Cxy' of the unscented one) and the innovation e:
+ *     W = L^-1 CR,  z = L^-1 e,  x += W' z,  R -= W' W (lower triangle),  returns -(ny/2) log(2 pi) - log(L11 ... Lnn) - z'z / 2.
+ * ok: 0 when something before this call already made the filter invalid.  Not positive definite (or !ok): NaN ll, x, R. */
+LLPF_HD double llpf_kf_gain_update(const int nx, const int ny, int ok, double* L, const double* CR, const double* e, double* x, double* R) {
+    double inv[LLPF_KF_MAXY];
+    ok = ok & llpf_kf_chol(ny, L, inv);
     /* W = L^-1 (C R)  (ny x nx),  z = L^-1 e */
     double W[LLPF_KF_MAXY * LLPF_KF_MAXX], z[LLPF_KF_MAXY];
     LLPF_KF_UNROLL
@@ -167,6 +137,52 @@ LLPF_HD double llpf_kf_correct(const int nx, const int ny, const int nu, const d
         for (int i = 0; i < LLPF_KF_NP(nx); ++i) R[i] = llpf_kf_nan();
     }
     return ll;
+}
+
+/* correct!(kf, u, y): the innovation e (ny), x and R updated in place; returns logpdf(N(0, S), e).
+ * A row whose first element is NaN is missing: x and R stay, e is NaN, the result is 0. */
+LLPF_HD double llpf_kf_correct(const int nx, const int ny, const int nu, const double* P, const int64_t ps, const double* u,
+                               const double* y, double* x, double* R, double* e) {
+    if (!(y[0] == y[0])) {
+        LLPF_KF_UNROLL
+        for (int r = 0; r < ny; ++r) e[r] = llpf_kf_nan();
+        return 0.0;
+    }
+    const int oC = LLPF_KF_OFF_C(nx), oR2 = LLPF_KF_OFF_R2(nx, ny), oD = LLPF_KF_OFF_D(nx, ny, nu);
+    /* e = y - (C x + D u) */
+    LLPF_KF_UNROLL
+    for (int r = 0; r < ny; ++r) {
+        double acc = LLPF_KF_P(oC + r * nx) * x[0];
+        LLPF_KF_UNROLL
+        for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(oC + r * nx + q), x[q], acc);
+        for (int c = 0; c < nu; ++c) acc = llpf_fma(LLPF_KF_P(oD + r * nu + c), u[c], acc);
+        e[r] = y[r] - acc;
+    }
+    /* CR = C R  (ny x nx) */
+    double CR[LLPF_KF_MAXY * LLPF_KF_MAXX];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < ny; ++r) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = LLPF_KF_P(oC + r * nx) * R[llpf_kf_idx(0, c)];
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(oC + r * nx + q), R[llpf_kf_idx(q, c)], acc);
+            CR[r * LLPF_KF_MAXX + c] = acc;
+        }
+    }
+    /* S = (C R) C' + R2, lower triangle, factored in place: L L' = S */
+    double L[LLPF_KF_NP(LLPF_KF_MAXY)];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < ny; ++r) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c <= r; ++c) {
+            double acc = CR[r * LLPF_KF_MAXX] * LLPF_KF_P(oC + c * nx);
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(CR[r * LLPF_KF_MAXX + q], LLPF_KF_P(oC + c * nx + q), acc);
+            L[llpf_kf_idx(r, c)] = acc + LLPF_KF_P(oR2 + llpf_kf_idx(r, c));
+        }
+    }
+    return llpf_kf_gain_update(nx, ny, 1, L, CR, e, x, R);
 }
 
 /* predict!(kf, u): x = A x + B u, R = A R A' + R1 (lower triangle; A R formed one row at a time) */
@@ -242,24 +258,7 @@ LLPF_HD void llpf_kf_smooth(const int nx, const int ny, const int nu, const doub
     LLPF_KF_UNROLL
     for (int i = 0; i < LLPF_KF_NP(nx); ++i) Dl[i] = RT[i] - L[i];
     /* L L' = R[t+1], in place */
-    int ok = 1;
-    LLPF_KF_UNROLL
-    for (int i = 0; i < nx; ++i) {
-        LLPF_KF_UNROLL
-        for (int j = 0; j <= i; ++j) {
-            double acc = L[llpf_kf_idx(i, j)];
-            LLPF_KF_UNROLL
-            for (int k = 0; k < j; ++k) acc = llpf_fma(-L[llpf_kf_idx(i, k)], L[llpf_kf_idx(j, k)], acc);
-            if (i == j) {
-                ok = ok & (acc > 0.0);
-                const double piv = llpf_sqrt(acc);
-                L[llpf_kf_idx(i, i)] = piv;
-                inv[i] = 1.0 / piv;
-            } else {
-                L[llpf_kf_idx(i, j)] = acc * inv[j];
-            }
-        }
-    }
+    const int ok = llpf_kf_chol(nx, L, inv);
     /* Jt = G = A Rt; Jt = L^-1 Jt; Jt = L^-T Jt.  Jt[i][c] = J'(i, c) = J(c, i) */
     double Jt[LLPF_KF_MAXX * LLPF_KF_MAXX];
     LLPF_KF_UNROLL

@@ -36,7 +36,8 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMeasurement, GaussianLikelihood,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
-       GPUKalmanFilter, GPUKalmanFilterBank
+       GPUKalmanFilter, GPUKalmanFilterBank, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
+       ukf_weights, set_weights!
 
 const LIB = get(ENV, "LLPF_HIP_LIB", joinpath(@__DIR__, "..", "libllpf_hip.so"))
 const MAXD = 16          # LLPF_MAX_DIM: states / outputs
@@ -1094,6 +1095,168 @@ function LowLevelParticleFilters.smooth(kf::GPUKalmanFilter, u, y, p = NullParam
     sol = KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
                                   [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
     KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
+end
+
+# ---- banks of unscented Kalman filters (the reference's UnscentedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise): llpf_ukf_bank_* ----
+struct CUkfWeights                    # llpf_ukf_weights
+    struct_size::UInt32
+    pad::UInt32
+    gamma::Float64
+    wm0::Float64
+    wc0::Float64
+    wi::Float64
+end
+"MerweParams(alpha, beta, kappa): lambda = alpha^2 (L + kappa) - L, gamma = sqrt(L + lambda), wm0 = lambda / (L + lambda), wc0 = wm0 + 1 - alpha^2 + beta, wi = 1 / (2 (L + lambda))"
+struct MerweParams
+    alpha::Float64
+    beta::Float64
+    kappa::Float64
+end
+MerweParams(; alpha = 1e-3, beta = 2.0, kappa = 0.0) = MerweParams(alpha, beta, kappa)
+"WikiParams(alpha, beta, kappa): gamma = alpha sqrt(kappa), wm0 = (alpha^2 kappa - L) / (alpha^2 kappa), wc0 = wm0 + 1 - alpha^2 + beta, wi = 1 / (2 alpha^2 kappa)"
+struct WikiParams
+    alpha::Float64
+    beta::Float64
+    kappa::Float64
+end
+WikiParams(; alpha = 1.0, beta = 0.0, kappa = 1.0) = WikiParams(alpha, beta, kappa)
+"TrivialParams(): every point the same weight 1 / (2 L + 1), gamma = sqrt(L + 1/2)"
+struct TrivialParams end
+# (gamma, wm0, wc0, wi) of a parameter set for L states; a raw 4-tuple passes through
+function ukf_weights(p::MerweParams, L)
+    lam = p.alpha^2 * (L + p.kappa) - L
+    wm0 = lam / (L + lam)
+    (sqrt(L + lam), wm0, wm0 + 1 - p.alpha^2 + p.beta, 1 / (2 * (L + lam)))
+end
+function ukf_weights(p::WikiParams, L)
+    a2k = p.alpha^2 * p.kappa
+    wm0 = (a2k - L) / a2k
+    (p.alpha * sqrt(p.kappa), wm0, wm0 + 1 - p.alpha^2 + p.beta, 1 / (2 * a2k))
+end
+ukf_weights(::TrivialParams, L) = (sqrt(L + 0.5), 1 / (2L + 1), 1 / (2L + 1), 1 / (2L + 1))
+ukf_weights(w::NTuple{4, <:Real}, L) = Float64.(w)
+cukfweights(w) = CUkfWeights(UInt32(sizeof(CUkfWeights)), 0, w[1], w[2], w[3], w[4])
+
+mutable struct GPUUnscentedKalmanFilterBank
+    h::Ptr{Cvoid}
+    F::Int
+    nx::Int
+    nu::Int
+    ny::Int
+    Ts::Float64
+end
+ukf_model(f, Ts) = cmodel(f[1], f[2], GaussianSpec(zeros(length(f[5])), f[3]), GaussianSpec(zeros(size(f[4], 1)), f[4]), f[5], Float64(Ts))
+"""
+    GPUUnscentedKalmanFilterBank(filters; Ts = 1.0, device = 0, weight_params = TrivialParams())
+
+Independent unscented Kalman filters (additive noise) on the device, one GPU thread each; `filters` is a vector of
+(dynamics, measurement, R1, R2, d0) tuples with the model descriptors a `GPUParticleFilter` takes (LinearDynamics + LinearMeasurement,
+QuadTankDynamics + QuadTankMeasurement, UserDynamics + UserMeasurement), R1 and R2 covariance matrices, d0 a GaussianSpec; nx <= 8,
+ny <= 4, nu <= 8.  `weight_params`: MerweParams, WikiParams, TrivialParams or the four numbers (gamma, wm0, wc0, wi).
+`loglik(bank, u, y)` is the vector of every filter's log-likelihood.
+"""
+function GPUUnscentedKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0, weight_params = TrivialParams())
+    cms = [ukf_model(f, Ts) for f in filters]
+    w = Ref(cukfweights(ukf_weights(weight_params, cms[1].nx)))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_ukf_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Int32, Ptr{CUkfWeights}, Ref{Ptr{Cvoid}}), device, cms, length(cms), w, h))
+    b = GPUUnscentedKalmanFilterBank(h[], length(cms), cms[1].nx, cms[1].nu, cms[1].ny, Float64(Ts))
+    finalizer(x -> ccall((:llpf_ukf_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    b
+end
+function set_parameters!(b::GPUUnscentedKalmanFilterBank, filters::Vector)
+    cms = [ukf_model(f, b.Ts) for f in filters]
+    length(cms) == b.F || throw(ArgumentError("set_parameters!: $(length(cms)) filters for a bank of $(b.F)"))
+    check(ccall((:llpf_ukf_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}), b.h, cms))
+    b
+end
+function set_weights!(b::GPUUnscentedKalmanFilterBank, weight_params)
+    w = Ref(cukfweights(ukf_weights(weight_params, b.nx)))
+    check(ccall((:llpf_ukf_bank_set_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{CUkfWeights}), b.h, w))
+    b
+end
+reset!(b::GPUUnscentedKalmanFilterBank) = check(ccall((:llpf_ukf_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+# u, y: vectors of T vectors shared by every filter (a missing y is `missing` / a NaN first element); step t runs at time (t_index0 + t - 1) Ts
+function ukf_run(b::GPUUnscentedKalmanFilterBank, u, y; outputs = false, t_index0 = 0.0)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        check(ccall((:llpf_ukf_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Ptr{CKalmanOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), Float64(t_index0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+"loglik(bank, u, y): every filter's loglik(ukf, u, y) (reset! first, then T update! steps, the first at t = 1 Ts as the particle filters' loglik)"
+loglik(b::GPUUnscentedKalmanFilterBank, u, y) = (reset!(b); ukf_run(b, u, y; t_index0 = 1.0)[1])
+"x (nx x F), R (nx x nx x F) of every filter"
+function state(b::GPUUnscentedKalmanFilterBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_ukf_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, x, R))
+    x, R
+end
+covariance(b::GPUUnscentedKalmanFilterBank) = state(b)[2]
+"set the estimate of every filter: x (nx x F), R (nx x nx x F; its lower triangle is read)"
+function set_state!(b::GPUUnscentedKalmanFilterBank, x, R)
+    xm = Matrix{Float64}(reshape(x, b.nx, b.F)); Rm = Array{Float64}(reshape(R, b.nx, b.nx, b.F))
+    Rr = permutedims(Rm, (2, 1, 3))                  # column-major nx x nx = the row-major [nx][nx] of its transpose
+    check(ccall((:llpf_ukf_bank_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, xm, Rr))
+    b
+end
+
+"""
+    GPUUnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0, weight_params = TrivialParams())
+
+The reference's `UnscentedKalmanFilter` with additive noise, run on the device (a bank of one filter, llpf_ukf_bank_*):
+`forward_trajectory` returns the reference's `KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `correct!`, `predict!`, `state`,
+`covariance`.  Unverified against the reference (its source was not available when this was written): the default weight parameters and
+whether its predict! draws the sigma points again from the posterior, as this one does.
+"""
+mutable struct GPUUnscentedKalmanFilter
+    bank::GPUUnscentedKalmanFilterBank
+    Ts::Float64
+    index::Int
+end
+GPUUnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0, weight_params = TrivialParams()) =
+    GPUUnscentedKalmanFilter(GPUUnscentedKalmanFilterBank([(dynamics, measurement, R1, R2, d0)]; Ts = Ts, device = device, weight_params = weight_params),
+                             Float64(Ts), 0)
+reset!(kf::GPUUnscentedKalmanFilter) = (reset!(kf.bank); kf.index = 1; nothing)
+loglik(kf::GPUUnscentedKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
+"update!(ukf, u, y): correct! then predict! at time t; returns (ll, e)"
+function update!(kf::GPUUnscentedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = ukf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    kf.index += 1
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"correct!(ukf, u, y): the posterior of a one-step run put back as the state (exact: the step holds the lower triangle of Rt); returns (ll, e)"
+function correct!(kf::GPUUnscentedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = ukf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    set_state!(kf.bank, o.xt[:, :, 1], o.Rt[:, :, :, 1])
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"predict!(ukf, u): a step whose measurement is missing (correct! is skipped)"
+function predict!(kf::GPUUnscentedKalmanFilter, u, p = NullParameters(), t = kf.index * kf.Ts)
+    ukf_run(kf.bank, [u], [missing]; t_index0 = t / kf.Ts)
+    kf.index += 1
+    nothing
+end
+state(kf::GPUUnscentedKalmanFilter) = state(kf.bank)[1][:, 1]
+covariance(kf::GPUUnscentedKalmanFilter) = state(kf.bank)[2][:, :, 1]
+function forward_trajectory(kf::GPUUnscentedKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o = ukf_run(kf.bank, u, y; outputs = true)
+    T = length(y)
+    kf.index = T
+    KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                            [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
 end
 
 end # module
