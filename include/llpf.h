@@ -446,6 +446,15 @@ int  llpf_ukf_bank_set_weights(llpf_ukf_bank* b, const llpf_ukf_weights* w);
 /* T steps of every filter; U, Y, per_filter, ll_total and out as llpf_kalman_bank_run takes them */
 int  llpf_ukf_bank_run(llpf_ukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
                        double* ll_total, const llpf_kalman_outputs* out);
+/* smooth(ukf, u, y): the unscented Rauch-Tung-Striebel smoother (Sarkka 2008, additive noise) of every filter, in the operation order of
+ * llpf_ukf_smooth_finish (csrc/shared/llpf_ukf.h).  The forward pass is llpf_ukf_bank_run on the same arguments (the same ll_total, the
+ * same optional forward outputs, the same state afterwards); the posterior of every step is kept on the device, (nx + np) * 8 bytes per
+ * filter-step, in a buffer the bank keeps for its next call.  The backward pass maps the sigma points of every posterior through the
+ * dynamics once more and gives xT[t], RT[t] as llpf_kalman_bank_smooth does; xT[T] = xt[T].  A filter whose posterior or predicted
+ * covariance is not positive definite at a step is NaN at that step and every earlier one.  A run-time compiled model's backward kernel
+ * is compiled on the first smooth of that model.  LLPF_ERR_ALLOC when the memory cannot be had: the state is then untouched. */
+int  llpf_ukf_bank_smooth(llpf_ukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                          double* ll_total, const llpf_kalman_outputs* forward /* or NULL */, const llpf_kalman_smooth_outputs* out);
 /* state, covariance of every filter: x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
 int  llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R);
 int  llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R);

@@ -53,6 +53,7 @@ SYMBOLS = {
     "llpf_ukf_bank_set_models": [_vp, C.POINTER(S.Model)],
     "llpf_ukf_bank_set_weights": [_vp, C.POINTER(S.UkfWeights)],
     "llpf_ukf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_ukf_bank_smooth": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs), C.POINTER(S.KalmanSmoothOutputs)],
     "llpf_ukf_bank_get_state": [_vp, _dp, _dp],
     "llpf_ukf_bank_set_state": [_vp, _dp, _dp],
     "llpf_num_particles": [_vp, _ip],
@@ -613,8 +614,24 @@ class UkfBankHandle(KalmanBankHandle):
         res["ll"] = ll
         return res
 
-    def smooth(self, *args, **kw):
-        raise NotImplementedError("there is no unscented smoother")
+    def smooth(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=KALMAN_SMOOTH_OUTPUTS, forward=(), t_index0=0.0):
+        """the forward pass of run() and the unscented RTS smoother's backward pass (llpf_ukf_bank_smooth), step t at time
+        (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.smooth"""
+        F, nx = self.F, self.nx
+        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
+        res, fwd = self._forward_outputs(T, forward)
+        shapes = {"xT": (T, F, nx), "RT": (T, F, nx, nx)}
+        sm = {k: np.empty(shapes[k]) for k in outputs}
+        out = S.KalmanSmoothOutputs()
+        out.struct_size = C.sizeof(S.KalmanSmoothOutputs)
+        for k, a in sm.items():
+            setattr(out, k, dptr(a))
+        ll = np.empty(F)
+        check(self.L.llpf_ukf_bank_smooth(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), float(t_index0),
+                                          dptr(ll), None if fwd is None else C.byref(fwd), C.byref(out)))
+        res.update(sm)
+        res["ll"] = ll
+        return res
 
     def get_state(self):
         x = np.empty((self.F, self.nx))

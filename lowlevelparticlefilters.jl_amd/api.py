@@ -704,6 +704,13 @@ class UnscentedKalmanFilterBank:
         self._h.reset()
         return self._h.run(u, y, up, yp, outputs=outputs, t_index0=0.0)
 
+    def smooth(self, u, y, outputs=_capi.KALMAN_SMOOTH_OUTPUTS, forward=()):
+        """smooth(ukf_k, u, y) of every filter (reset, the forward pass of forward(), the unscented RTS smoother on the device): what
+        KalmanFilterBank.smooth returns"""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.smooth(u, y, up, yp, outputs=outputs, forward=forward, t_index0=0.0)
+
 
 class RBMeasurementModel:
     """RBMeasurementModel(measurement, R2, ny) — reference src/rbpf.jl:36-60; `measurement` is a LinearMeasurement
@@ -1144,7 +1151,9 @@ def smooth(pf, *args):
     """xb, ll = smooth(pf, M, u, y, p) / smooth(pf, xf, wf, wef, ll, M, u, y, p) — forward filtering, backward
     simulation (reference src/smoothing.jl:103-143).  xb is [T, M, nx].
     sol = smooth(kf::KalmanFilter, u, y, p) — reset!, forward_trajectory and the Rauch-Tung-Striebel smoother (src/smoothing.jl:10-102),
-    on the device: a KalmanSmoothingSolution."""
+    on the device: a KalmanSmoothingSolution.
+    sol = smooth(ukf::UnscentedKalmanFilter, u, y, p) — reset!, forward_trajectory and the unscented Rauch-Tung-Striebel smoother
+    (csrc/shared/llpf_ukf.h: llpf_ukf_smooth_finish), on the device: a KalmanSmoothingSolution."""
     if isinstance(pf, KalmanFilter):
         u, y = args[:2]
         reset(pf)
@@ -1152,6 +1161,16 @@ def smooth(pf, *args):
         yy = yy.reshape(yy.shape[0], -1) if yy.ndim else yy.reshape(1, 1)
         uu = None if pf._h.nu == 0 else np.asarray(u, dtype=np.float64).reshape(yy.shape[0], -1)
         r = pf._h.smooth(uu, yy, forward=_capi.KALMAN_OUTPUTS)
+        sol = KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
+        return KalmanSmoothingSolution(sol, r["xT"][:, 0], r["RT"][:, 0])
+    if isinstance(pf, UnscentedKalmanFilter):      # the first step at t = 0, as forward_trajectory counts time
+        u, y = args[:2]
+        reset(pf)
+        yy = np.asarray(y, dtype=np.float64)
+        yy = yy.reshape(yy.shape[0], -1) if yy.ndim else yy.reshape(1, 1)
+        uu = None if pf.nu == 0 else np.asarray(u, dtype=np.float64).reshape(yy.shape[0], -1)
+        r = pf._h.smooth(uu, yy, forward=_capi.KALMAN_OUTPUTS, t_index0=0.0)
+        pf._index += yy.shape[0]
         sol = KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
         return KalmanSmoothingSolution(sol, r["xT"][:, 0], r["RT"][:, 0])
     if len(args) >= 7:

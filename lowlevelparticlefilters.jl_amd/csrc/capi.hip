@@ -256,6 +256,11 @@ int llpf_ukf_bank_run(llpf_ukf_bank* b, const double* U, const double* Y, int64_
     NEEDF(b);
     return ukf_run(*b, U, Y, T, per_filter, t_index0, ll_total, out);
 } LLPF_GUARD(llpf_ukf_bank_run)
+int llpf_ukf_bank_smooth(llpf_ukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                         const llpf_kalman_outputs* forward, const llpf_kalman_smooth_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return ukf_smooth(*b, U, Y, T, per_filter, t_index0, ll_total, forward, out);
+} LLPF_GUARD(llpf_ukf_bank_smooth)
 int llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return ukf_get_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_get_state)
 int llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return ukf_set_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_set_state)
 

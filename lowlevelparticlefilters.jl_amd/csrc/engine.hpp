@@ -357,6 +357,11 @@ hipError_t launch_kalman_smooth(int nx, const KalmanSmoothArgs& a, hipStream_t s
 // the linear-Gaussian model above 4 states) on its first use (0, or -1 with `err` set); launch_ukf runs one chunk of steps
 int ukf_prepare(int model_id, int nx, int ny, std::string& err);
 hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const UkfArgs& a, hipStream_t s);
+// the backward (unscented RTS smoother) pass of those banks over one chunk: ukf_smooth_prepare compiles the k_ukf_smooth of a run-time
+// compiled model, and the k_ukf<..., true> that launch_ukf runs when UkfArgs::post is set, on the first smooth of that model, into a
+// cache entry of its own
+int ukf_smooth_prepare(int model_id, int nx, int ny, std::string& err);
+hipError_t launch_ukf_smooth(int model_id, int nx, int ny, const ModelD* models, const UkfSmoothArgs& a, hipStream_t s);
 // kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
 bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
 const char* jit_prelude();

@@ -6,6 +6,7 @@
 // the state [nx + np + 1][F] (x, packed R, the running ll_total of a run), SoA as the Kalman bank's.  A run drives T through the chunked
 // staging pipeline of host/pipe.hpp exactly as kalman_forward does; the state carries from chunk to chunk (and from run to run) in the
 // device buffer, so run(a) followed by run(b) is run(a + b), bit for bit.  A run that asks for ll_total only stages nothing per step.
+// A smooth (ukf_smooth) is that run with the posterior of every step kept on the device, and k_ukf_smooth over the chunks in reverse.
 
 struct llpf_ukf_bank : BankStream {
     int F = 0, nx = 0, ny = 0, nu = 0;
@@ -15,6 +16,7 @@ struct llpf_ukf_bank : BankStream {
     llpf_ukf_weights w{};
     DevBuf<ModelD> d_models;
     DevBuf<double> d_par, d_state, d_zero;
+    DevBuf<double> d_post;            // [T][nx + np][F] the posterior of every step of the last smooth (grow-only: kept between calls)
     std::vector<double> h_init;       // [nstate][F] what reset loads: mean(d0), packed cov(d0), 0
 };
 
@@ -178,16 +180,33 @@ static int ukf_set_state(llpf_ukf_bank& b, const double* x, const double* R) {
     return LLPF_OK;
 }
 
-// T steps of every filter from the current state.  Everything is allocated before the first launch.
-static int ukf_run(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
-                   const llpf_kalman_outputs* out) {
+// the checks of a run's arguments that need no device (llpf_ukf_bank_run and _smooth)
+static int ukf_check_run(const llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                         const llpf_kalman_outputs* out) {
     if (T < 1) return fail(LLPF_ERR_ARG, "ukf: T must be >= 1");
     if (!Y) return fail(LLPF_ERR_ARG, "ukf: Y is null");
     if (b.nu > 0 && !U) return fail(LLPF_ERR_ARG, "ukf: U is null");
     if (per_filter & ~3) return fail(LLPF_ERR_ARG, "ukf: per_filter has bits other than 0 and 1");
     if (out && out->struct_size < sizeof(llpf_kalman_outputs)) return fail(LLPF_ERR_ARG, "ukf: llpf_kalman_outputs.struct_size too small (ABI)");
     if (!std::isfinite(t_index0)) return fail(LLPF_ERR_ARG, "ukf: t_index0 must be finite");
+    return LLPF_OK;
+}
+
+static int ukf_forward(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                       const llpf_kalman_outputs* out, double* post);
+
+// T steps of every filter from the current state
+static int ukf_run(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                   const llpf_kalman_outputs* out) {
+    CHK(ukf_check_run(b, U, Y, T, per_filter, t_index0, out));
     test_throw("ukf_run");
+    return ukf_forward(b, U, Y, T, per_filter, t_index0, ll_total, out, nullptr);
+}
+
+// the forward pass of a run (arguments checked); post: null, or the device array [T][nx + np][F] that receives the posterior of every
+// step (k_ukf<..., true>).  Everything is allocated before the first launch.
+static int ukf_forward(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                       const llpf_kalman_outputs* out, double* post) {
     const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu;
     const bool upf = nu > 0 && (per_filter & 1), ypf = (per_filter & 2) != 0;
     // the outputs of one step, in staging order: ll, x, xt, R, Rt, e
@@ -221,12 +240,69 @@ static int ukf_run(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T
         a.first = c == 0 ? 1 : 0;
         a.t_index0 = t_index0; a.Ts = b.Ts;
         a.gamma = b.w.gamma; a.wm0 = b.w.wm0; a.wc0 = b.w.wc0; a.wi = b.w.wi;
+        a.post = post ? post + (size_t)pipe.t0 * (nx + b.np) * F : nullptr;
         HIPC(launch_ukf(b.model_id, nx, ny, b.d_models, a, b.stream));
         CHK(pipe.end());
     }
     CHK(pipe.finish());
     if (ll_total)     // the running sum: row nx + np of the state
         HIPC(hipMemcpyAsync(ll_total, b.d_state.p + (size_t)(nx + b.np) * F, sizeof(double) * F, hipMemcpyDeviceToHost, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+// smooth(ukf, u, y): the forward pass of a run (the same chunks, outputs and state as ukf_run) that also stores the packed posterior of
+// every step on the device (d_post: (nx + np) * 8 bytes per filter-step), then the backward pass k_ukf_smooth over the chunks in reverse
+// through a staging pipeline of its own (host/pipe.hpp) — kalman_smooth, with the model's dynamics in the place of A.  A run-time
+// compiled model's k_ukf_smooth is compiled first; everything is allocated before the first launch, so a call that cannot get its memory
+// leaves the state as it was.  The state after the call is the one ukf_run leaves (the prior of step T and the running ll).
+static int ukf_smooth(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                      const llpf_kalman_outputs* fwd, const llpf_kalman_smooth_outputs* out) {
+    CHK(ukf_check_run(b, U, Y, T, per_filter, t_index0, fwd));
+    if (out && out->struct_size < sizeof(llpf_kalman_smooth_outputs))
+        return fail(LLPF_ERR_ARG, "ukf: llpf_kalman_smooth_outputs.struct_size too small (ABI)");
+    const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu, ns = nx + b.np;
+    const bool upf = nu > 0 && (per_filter & 1);
+    double* dst[2] = {out ? out->xT : nullptr, out ? out->RT : nullptr};
+    const uint64_t width[2] = {(uint64_t)nx, (uint64_t)nx * nx};
+    const uint64_t w = (dst[0] ? width[0] : 0) + (dst[1] ? width[1] : 0);
+    uint64_t post_d = 0, total = 0;
+    if (!doubles_fit({(uint64_t)ns, (uint64_t)F, (uint64_t)T}, post_d) || !doubles_fit({(uint64_t)F, w, (uint64_t)T}, total))
+        return fail(LLPF_ERR_ARG, "ukf: the size of the stored posterior or of the smoothed outputs overflows");
+    test_throw("ukf_smooth");
+    if (!w) return ukf_forward(b, U, Y, T, per_filter, t_index0, ll_total, fwd, nullptr);     // nothing smoothed is asked for: a run
+    HIPC(hipSetDevice(b.device));
+    {
+        std::string err;      // a run-time compiled model's k_ukf_smooth and k_ukf<..., true>, on the first smooth of that model
+        if (ukf_smooth_prepare(b.model_id, nx, ny, err) != 0) return fail(LLPF_ERR_HIP, "ukf: " + err);
+    }
+    CHK(b.d_post.ensure((size_t)post_d));
+    ChunkPipe pipe(b.stream);
+    double* d_carry = nullptr;
+    CHK(pipe.device((size_t)ns * F, d_carry));
+    CHK(pipe.open(T, (size_t)F * (w + (upf ? nu : 0)) * sizeof(double), {{dst[0], 1, (size_t)F * width[0]}, {dst[1], 1, (size_t)F * width[1]}},
+                  {{nu > 0 ? U : nullptr, upf ? (size_t)F : 0, (size_t)nu, true}}));
+    // the forward pass allocates its own staging before its first launch: no launch has run when it returns an allocation failure
+    CHK(ukf_forward(b, U, Y, T, per_filter, t_index0, ll_total, fwd, b.d_post.p));
+    for (int64_t i = 0; i < pipe.nchunk; ++i) {      // backward: launch i runs chunk nchunk - 1 - i
+        CHK(pipe.begin(i, pipe.nchunk - 1 - i));
+        UkfSmoothArgs a{};
+        a.par = b.d_par;
+        a.post = b.d_post.p + (size_t)pipe.t0 * ns * F;
+        a.carry = d_carry;
+        a.u = pipe.in(0);
+        a.zero_u = b.d_zero;
+        a.xT = pipe.out(0);
+        a.RT = pipe.out(1);
+        a.F = F; a.t0 = pipe.t0; a.Tc = (int32_t)pipe.tc; a.nu = nu;
+        a.u_per = upf ? 1 : 0;
+        a.init = i == 0 ? 1 : 0;
+        a.t_index0 = t_index0; a.Ts = b.Ts;
+        a.gamma = b.w.gamma; a.wm0 = b.w.wm0; a.wc0 = b.w.wc0; a.wi = b.w.wi;
+        HIPC(launch_ukf_smooth(b.model_id, nx, ny, b.d_models, a, b.stream));
+        CHK(pipe.end());
+    }
+    CHK(pipe.finish());
     HIPC(hipStreamSynchronize(b.stream));
     return LLPF_OK;
 }

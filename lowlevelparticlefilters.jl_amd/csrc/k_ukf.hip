@@ -1,8 +1,10 @@
-// k_ukf.hip — k_ukf (kernels/ukf.hpp): banks of unscented Kalman filters (llpf_ukf_bank_run).
+// k_ukf.hip — k_ukf, k_ukf_smooth (kernels/ukf.hpp): banks of unscented Kalman filters (llpf_ukf_bank_run, llpf_ukf_bank_smooth).
 // One of the engine's device translation units: LinGauss<NX, NY> for NX, NY in 1..4 and QuadTank<4, 2> are instantiated here and nowhere
-// else.  A run-time compiled model (a user snippet, a traced callable, the linear-Gaussian model above 4 states) gets its k_ukf from a
-// hiprtc program of its own, compiled on the first bank of that model and cached per model — the program of llpf_model_compile is left
-// as it is.
+// else, for both kernels.  A run-time compiled model (a user snippet, a traced callable, the linear-Gaussian model above 4 states) gets
+// its k_ukf from a hiprtc program of its own, compiled on the first bank of that model and cached per model — the program of
+// llpf_model_compile is left as it is — and its k_ukf_smooth, with the posterior-storing k_ukf<..., true> of the smoother's forward pass,
+// from another one, compiled on the first smooth of that model and cached in an entry of its own: a bank that never smooths compiles what
+// it always did.
 #include <hip/hiprtc.h>
 
 #include <map>
@@ -27,7 +29,16 @@ namespace llpf {
 template <class Model, int NX, int NY>
 static hipError_t launch_ukf_t(const ModelD* models, const UkfArgs& a, hipStream_t s) {
     const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
-    hipLaunchKernelGGL((k_ukf<Model, NX, NY>), g, dim3(KF_BLOCK), 0, s, models, a);
+    if (a.post)
+        hipLaunchKernelGGL((k_ukf<Model, NX, NY, true>), g, dim3(KF_BLOCK), 0, s, models, a);
+    else
+        hipLaunchKernelGGL((k_ukf<Model, NX, NY, false>), g, dim3(KF_BLOCK), 0, s, models, a);
+    return hipGetLastError();
+}
+template <class Model, int NX>
+static hipError_t launch_ukf_smooth_t(const ModelD* models, const UkfSmoothArgs& a, hipStream_t s) {
+    const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
+    hipLaunchKernelGGL((k_ukf_smooth<Model, NX>), g, dim3(KF_BLOCK), 0, s, models, a);
     return hipGetLastError();
 }
 template <int NX>
@@ -40,16 +51,27 @@ static hipError_t launch_ukf_lg(int ny, const ModelD* models, const UkfArgs& a, 
         default: return hipErrorInvalidValue;
     }
 }
+template <int NX>
+static hipError_t launch_ukf_smooth_lg(int ny, const ModelD* models, const UkfSmoothArgs& a, hipStream_t s) {
+    switch (ny) {
+        case 1: return launch_ukf_smooth_t<LinGauss<NX, 1>, NX>(models, a, s);
+        case 2: return launch_ukf_smooth_t<LinGauss<NX, 2>, NX>(models, a, s);
+        case 3: return launch_ukf_smooth_t<LinGauss<NX, 3>, NX>(models, a, s);
+        case 4: return launch_ukf_smooth_t<LinGauss<NX, 4>, NX>(models, a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
 
 // ---- run-time compiled models ----
 struct JitUkf {
     std::vector<char> code;
-    std::string name;                          // lowered name of k_ukf<UserModel, nx, ny>
-    struct PerDevice { hipModule_t mod = nullptr; hipFunction_t fn = nullptr; };
+    std::string name;                          // lowered name of k_ukf<UserModel, nx, ny> / k_ukf_smooth<UserModel, nx>
+    std::string name_post;                     // the smoother's entry: lowered name of k_ukf<UserModel, nx, ny, true>, its forward pass
+    struct PerDevice { hipModule_t mod = nullptr; hipFunction_t fn = nullptr, fn_post = nullptr; };
     std::vector<PerDevice> dev;                // indexed by device ordinal, loaded on first use
 };
 static std::mutex g_ukf_mutex;
-static std::map<std::string, std::unique_ptr<JitUkf>> g_ukf;      // by ukf_key
+static std::map<std::string, std::unique_ptr<JitUkf>> g_ukf;      // by ukf_key: the forward and the backward kernel are entries of their own
 
 static bool ukf_builtin(int model_id, int nx, int ny) {
     return (model_id == LLPF_MODEL_LINEAR_GAUSSIAN && nx <= 4 && ny <= 4) || model_id == LLPF_MODEL_QUADTANK_RK4;
@@ -63,13 +85,15 @@ static bool ukf_snippet(int model_id, int nx, int ny, std::string& snippet) {
     int sx = 0, sy = 0;
     return jit_model_source(model_id, snippet, sx, sy) && sx == nx && sy == ny;
 }
-static std::string ukf_key(int model_id, int nx, int ny) {
-    return std::to_string(model_id) + ":" + std::to_string(nx) + ":" + std::to_string(ny);
+static std::string ukf_key(int model_id, int nx, int ny, bool smooth) {
+    return std::to_string(model_id) + ":" + std::to_string(nx) + ":" + std::to_string(ny) + (smooth ? ":smooth" : "");
 }
 
-int ukf_prepare(int model_id, int nx, int ny, std::string& err) {
+// compiles k_ukf (smooth = false), or k_ukf_smooth and the posterior-storing k_ukf<..., true> (smooth = true), of a run-time compiled
+// model unless its entry exists
+static int ukf_compile(int model_id, int nx, int ny, bool smooth, std::string& err) {
     if (ukf_builtin(model_id, nx, ny)) return 0;
-    const std::string key = ukf_key(model_id, nx, ny);
+    const std::string key = ukf_key(model_id, nx, ny, smooth);
     {
         std::lock_guard<std::mutex> lk(g_ukf_mutex);
         if (g_ukf.count(key)) return 0;
@@ -86,8 +110,11 @@ int ukf_prepare(int model_id, int nx, int ny, std::string& err) {
     src += "\n}  // namespace llpf\n";
     hiprtcProgram prog = nullptr;
     if (hiprtcCreateProgram(&prog, src.c_str(), "llpf_user_ukf.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) { err = "hiprtcCreateProgram failed"; return -1; }
-    const std::string expr = "llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ">";
+    const std::string expr = smooth ? "llpf::k_ukf_smooth<llpf::UserModel, " + std::to_string(nx) + ">"
+                                    : "llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ">";
+    const std::string expr_post = "llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ", true>";
     hiprtcAddNameExpression(prog, expr.c_str());
+    if (smooth) hiprtcAddNameExpression(prog, expr_post.c_str());
     int devid = 0;
     hipDeviceProp_t prop;
     std::string arch = "gfx950";
@@ -101,7 +128,7 @@ int ukf_prepare(int model_id, int nx, int ny, std::string& err) {
         hiprtcGetProgramLogSize(prog, &n);
         std::string log(n, '\0');
         if (n) hiprtcGetProgramLog(prog, &log[0]);
-        err = std::string("hiprtc (k_ukf): ") + hiprtcGetErrorString(rc) + "\n" + log;
+        err = std::string(smooth ? "hiprtc (k_ukf_smooth): " : "hiprtc (k_ukf): ") + hiprtcGetErrorString(rc) + "\n" + log;
         hiprtcDestroyProgram(&prog);
         return -1;
     }
@@ -113,33 +140,41 @@ int ukf_prepare(int model_id, int nx, int ny, std::string& err) {
     const char* low = nullptr;
     if (hiprtcGetLoweredName(prog, expr.c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + expr; hiprtcDestroyProgram(&prog); return -1; }
     ju->name = low;
+    if (smooth) {
+        if (hiprtcGetLoweredName(prog, expr_post.c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + expr_post; hiprtcDestroyProgram(&prog); return -1; }
+        ju->name_post = low;
+    }
     hiprtcDestroyProgram(&prog);
     std::lock_guard<std::mutex> lk(g_ukf_mutex);
     if (!g_ukf.count(key)) g_ukf[key] = std::move(ju);      // another thread may have compiled it meanwhile: the first one stays
     return 0;
 }
 
-// this device's handle of the compiled kernel (loaded on first use)
-static hipError_t ukf_function(int model_id, int nx, int ny, hipFunction_t* fn) {
+int ukf_prepare(int model_id, int nx, int ny, std::string& err) { return ukf_compile(model_id, nx, ny, false, err); }
+int ukf_smooth_prepare(int model_id, int nx, int ny, std::string& err) { return ukf_compile(model_id, nx, ny, true, err); }
+
+// this device's handle of the compiled kernel (loaded on first use); post: the smoother's forward kernel k_ukf<..., true>
+static hipError_t ukf_function(int model_id, int nx, int ny, bool smooth, bool post, hipFunction_t* fn) {
     int devid = 0;
     hipError_t e = hipGetDevice(&devid);
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lk(g_ukf_mutex);
-    auto it = g_ukf.find(ukf_key(model_id, nx, ny));
-    if (it == g_ukf.end()) return hipErrorInvalidValue;      // ukf_prepare compiles it first
+    auto it = g_ukf.find(ukf_key(model_id, nx, ny, smooth));
+    if (it == g_ukf.end()) return hipErrorInvalidValue;      // ukf_prepare / ukf_smooth_prepare compiles it first
     JitUkf& ju = *it->second;
     if ((int)ju.dev.size() <= devid) ju.dev.resize((size_t)devid + 1);
     JitUkf::PerDevice& pd = ju.dev[(size_t)devid];
     if (!pd.mod && (e = hipModuleLoadData(&pd.mod, ju.code.data())) != hipSuccess) return e;
     if (!pd.fn && (e = hipModuleGetFunction(&pd.fn, pd.mod, ju.name.c_str())) != hipSuccess) return e;
-    *fn = pd.fn;
+    if (post && !pd.fn_post && (e = hipModuleGetFunction(&pd.fn_post, pd.mod, ju.name_post.c_str())) != hipSuccess) return e;
+    *fn = post ? pd.fn_post : pd.fn;
     return hipSuccess;
 }
 
 hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const UkfArgs& a, hipStream_t s) {
     if (!ukf_builtin(model_id, nx, ny)) {
         hipFunction_t fn = nullptr;
-        const hipError_t e = ukf_function(model_id, nx, ny, &fn);
+        const hipError_t e = a.post ? ukf_function(model_id, nx, ny, true, true, &fn) : ukf_function(model_id, nx, ny, false, false, &fn);
         if (e != hipSuccess) return e;
         UkfArgs aa = a;
         void* args[] = {&models, &aa};
@@ -154,6 +189,28 @@ hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const 
         case 2: return launch_ukf_lg<2>(ny, models, a, s);
         case 3: return launch_ukf_lg<3>(ny, models, a, s);
         case 4: return launch_ukf_lg<4>(ny, models, a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_ukf_smooth(int model_id, int nx, int ny, const ModelD* models, const UkfSmoothArgs& a, hipStream_t s) {
+    if (!ukf_builtin(model_id, nx, ny)) {
+        hipFunction_t fn = nullptr;
+        const hipError_t e = ukf_function(model_id, nx, ny, true, false, &fn);
+        if (e != hipSuccess) return e;
+        UkfSmoothArgs aa = a;
+        void* args[] = {&models, &aa};
+        return hipModuleLaunchKernel(fn, (unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1, KF_BLOCK, 1, 1, 0, s, args, nullptr);
+    }
+    if (model_id == LLPF_MODEL_QUADTANK_RK4) {
+        if (nx != 4 || ny != 2) return hipErrorInvalidValue;
+        return launch_ukf_smooth_t<QuadTank<4, 2>, 4>(models, a, s);
+    }
+    switch (nx) {
+        case 1: return launch_ukf_smooth_lg<1>(ny, models, a, s);
+        case 2: return launch_ukf_smooth_lg<2>(ny, models, a, s);
+        case 3: return launch_ukf_smooth_lg<3>(ny, models, a, s);
+        case 4: return launch_ukf_smooth_lg<4>(ny, models, a, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -226,51 +226,21 @@ LLPF_HD void llpf_kf_predict(const int nx, const int ny, const int nu, const dou
  * e[t] and the posterior xt[t], Rt[t]; predict! gives the prior of t + 1.  update! is this step.  A run's ll_total starts at 0.0 and
  * adds ll[t] in step order (ll_total = ll_total + ll[t]), a missing row adding 0. */
 
-/* One backward step of the Rauch-Tung-Striebel smoother, smooth(sol, kf, u, y) (reference src/smoothing.jl:10-102).  For t = T-1 down
- * to 1 (1-based), from xT[T] = xt[T], RT[T] = Rt[T]:
- *     C = Rt[t] A' / R[t+1];  xT[t] = xt[t] + C (xT[t+1] - x[t+1]);  RT[t] = Rt[t] + symmetrize(C (RT[t+1] - R[t+1]) C')
- * On entry xt, Rt are the posterior of step t (packed), u = u[t], and xT, RT the smoothed estimate of step t + 1 (packed); on return
- * xT, RT hold that of step t.  xt, Rt must not alias xT, RT.
- * The form computed here:
- *   - the prior x[t+1], R[t+1] is not stored by the forward pass: it is llpf_kf_predict applied to (xt, Rt, u) — the same function of
- *     the same numbers, so the bits the forward pass produced;
- *   - R[t+1] = L L', factored exactly as correct! factors S;
- *   - G = A Rt (the rows predict! forms), then J' = L^-T (L^-1 G) = R[t+1]^-1 A Rt: J is the reference's C, renamed (C is the
- *     measurement matrix here).  The forward substitution runs over increasing rows, the back substitution over decreasing rows with its
- *     sum over increasing index; both multiply by 1 / L_ii;
- *   - xT = xt + J d with d = xT[t+1] - x[t+1];
- *   - with D = RT[t+1] - R[t+1] (packed), J D is formed one row at a time and RT = Rt + (J D) J' only in its lower triangle:
- *     symmetrize() is the identity, as in the forward pass.
- * A filter whose R[t+1] is not positive definite (a pivot not > 0, or NaN) gets NaN xT, RT at step t and so at every earlier step;
- * nothing else is touched. */
-LLPF_HD void llpf_kf_smooth(const int nx, const int ny, const int nu, const double* P, const int64_t ps, const double* u, const double* xt,
-                            const double* Rt, double* xT, double* RT) {
-    /* the prior of step t + 1, then d = xT[t+1] - x[t+1], D = RT[t+1] - R[t+1] */
-    double xp[LLPF_KF_MAXX], L[LLPF_KF_NP(LLPF_KF_MAXX)], inv[LLPF_KF_MAXX];
-    LLPF_KF_UNROLL
-    for (int r = 0; r < nx; ++r) xp[r] = xt[r];
-    LLPF_KF_UNROLL
-    for (int i = 0; i < LLPF_KF_NP(nx); ++i) L[i] = Rt[i];
-    llpf_kf_predict(nx, ny, nu, P, ps, u, xp, L);
-    double d[LLPF_KF_MAXX], Dl[LLPF_KF_NP(LLPF_KF_MAXX)];
+/* The second half of a backward step, shared by this smoother and the unscented one (llpf_ukf.h: llpf_ukf_smooth_finish), from the prior
+ * of step t + 1 (xp, and the packed R[t+1] in L, factored here) and the cross term G = Cov(x[t+1], x[t] | y[1..t]) (nx x nx, row stride
+ * LLPF_KF_MAXX, in Jt: A Rt of the Kalman filter, sum wc_i dX'_i dX_i' of the unscented one):
+ *     d = xT - xp,  D = RT - R[t+1],  L L' = R[t+1],  J' = L^-T (L^-1 G),  xT = xt + J d,  RT = Rt + (J D) J' (lower triangle).
+ * ok: 0 when something before this call already made the filter invalid.  Not positive definite (or !ok): NaN xT, RT. */
+LLPF_HD void llpf_kf_smooth_finish(const int nx, int ok, const double* xp, double* L, double* Jt, const double* xt, const double* Rt,
+                                   double* xT, double* RT) {
+    double d[LLPF_KF_MAXX], Dl[LLPF_KF_NP(LLPF_KF_MAXX)], inv[LLPF_KF_MAXX];
     LLPF_KF_UNROLL
     for (int r = 0; r < nx; ++r) d[r] = xT[r] - xp[r];
     LLPF_KF_UNROLL
     for (int i = 0; i < LLPF_KF_NP(nx); ++i) Dl[i] = RT[i] - L[i];
     /* L L' = R[t+1], in place */
-    const int ok = llpf_kf_chol(nx, L, inv);
-    /* Jt = G = A Rt; Jt = L^-1 Jt; Jt = L^-T Jt.  Jt[i][c] = J'(i, c) = J(c, i) */
-    double Jt[LLPF_KF_MAXX * LLPF_KF_MAXX];
-    LLPF_KF_UNROLL
-    for (int r = 0; r < nx; ++r) {
-        LLPF_KF_UNROLL
-        for (int c = 0; c < nx; ++c) {
-            double acc = LLPF_KF_P(r * nx) * Rt[llpf_kf_idx(0, c)];
-            LLPF_KF_UNROLL
-            for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(r * nx + q), Rt[llpf_kf_idx(q, c)], acc);
-            Jt[r * LLPF_KF_MAXX + c] = acc;
-        }
-    }
+    ok = ok & llpf_kf_chol(nx, L, inv);
+    /* Jt = L^-1 Jt; Jt = L^-T Jt.  Jt[i][c] = J'(i, c) = J(c, i) */
     LLPF_KF_UNROLL
     for (int i = 0; i < nx; ++i) {
         LLPF_KF_UNROLL
@@ -325,6 +295,47 @@ LLPF_HD void llpf_kf_smooth(const int nx, const int ny, const int nu, const doub
         LLPF_KF_UNROLL
         for (int i = 0; i < LLPF_KF_NP(nx); ++i) RT[i] = llpf_kf_nan();
     }
+}
+
+/* One backward step of the Rauch-Tung-Striebel smoother, smooth(sol, kf, u, y) (reference src/smoothing.jl:10-102).  For t = T-1 down
+ * to 1 (1-based), from xT[T] = xt[T], RT[T] = Rt[T]:
+ *     C = Rt[t] A' / R[t+1];  xT[t] = xt[t] + C (xT[t+1] - x[t+1]);  RT[t] = Rt[t] + symmetrize(C (RT[t+1] - R[t+1]) C')
+ * On entry xt, Rt are the posterior of step t (packed), u = u[t], and xT, RT the smoothed estimate of step t + 1 (packed); on return
+ * xT, RT hold that of step t.  xt, Rt must not alias xT, RT.
+ * The form computed here:
+ *   - the prior x[t+1], R[t+1] is not stored by the forward pass: it is llpf_kf_predict applied to (xt, Rt, u) — the same function of
+ *     the same numbers, so the bits the forward pass produced;
+ *   - R[t+1] = L L', factored exactly as correct! factors S;
+ *   - G = A Rt (the rows predict! forms), then J' = L^-T (L^-1 G) = R[t+1]^-1 A Rt: J is the reference's C, renamed (C is the
+ *     measurement matrix here).  The forward substitution runs over increasing rows, the back substitution over decreasing rows with its
+ *     sum over increasing index; both multiply by 1 / L_ii;
+ *   - xT = xt + J d with d = xT[t+1] - x[t+1];
+ *   - with D = RT[t+1] - R[t+1] (packed), J D is formed one row at a time and RT = Rt + (J D) J' only in its lower triangle:
+ *     symmetrize() is the identity, as in the forward pass.
+ * A filter whose R[t+1] is not positive definite (a pivot not > 0, or NaN) gets NaN xT, RT at step t and so at every earlier step;
+ * nothing else is touched. */
+LLPF_HD void llpf_kf_smooth(const int nx, const int ny, const int nu, const double* P, const int64_t ps, const double* u, const double* xt,
+                            const double* Rt, double* xT, double* RT) {
+    /* the prior of step t + 1 */
+    double xp[LLPF_KF_MAXX], L[LLPF_KF_NP(LLPF_KF_MAXX)];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) xp[r] = xt[r];
+    LLPF_KF_UNROLL
+    for (int i = 0; i < LLPF_KF_NP(nx); ++i) L[i] = Rt[i];
+    llpf_kf_predict(nx, ny, nu, P, ps, u, xp, L);
+    /* Jt = G = A Rt */
+    double Jt[LLPF_KF_MAXX * LLPF_KF_MAXX];
+    LLPF_KF_UNROLL
+    for (int r = 0; r < nx; ++r) {
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) {
+            double acc = LLPF_KF_P(r * nx) * Rt[llpf_kf_idx(0, c)];
+            LLPF_KF_UNROLL
+            for (int q = 1; q < nx; ++q) acc = llpf_fma(LLPF_KF_P(r * nx + q), Rt[llpf_kf_idx(q, c)], acc);
+            Jt[r * LLPF_KF_MAXX + c] = acc;
+        }
+    }
+    llpf_kf_smooth_finish(nx, 1, xp, L, Jt, xt, Rt, xT, RT);
 }
 #undef LLPF_KF_P
 

@@ -3,8 +3,8 @@
  * share.  This header IS the device-order definition: the GPU reproduces a host build of it (-ffp-contract=off) bit for bit.
  *
  * Plain C for host and device, with the conventions of llpf_kalman.h, whose pieces it uses (llpf_kf_idx, LLPF_KF_NP, llpf_kf_chol,
- * llpf_kf_gain_update): packed lower triangles, every accumulation over its summation index in increasing order with explicit
- * llpf_fma, sqrt and log those of llpf_detmath.h, triangular solves multiply by 1 / L_ii.
+ * llpf_kf_gain_update, llpf_kf_smooth_finish): packed lower triangles, every accumulation over its summation index in increasing order
+ * with explicit llpf_fma, sqrt and log those of llpf_detmath.h, triangular solves multiply by 1 / L_ii.
  *
  * Model: x' = f(x, u, p, tau) + w, w ~ N(0, R1);  y = g(x, u, p, tau) + e, e ~ N(0, R2).  With L = nx and N = 2 L + 1 points:
  *   points of (m, R):  R = C C' (lower Cholesky factor),  X_0 = m,  X_i = m + gamma C[:, i],  X_{L+i} = m - gamma C[:, i],  i = 1..L
@@ -21,7 +21,7 @@
  * measurement, on the host a shim with function pointers:
  *     ok = llpf_ukf_factor(nx, R, Cf)                                    the factor of R
  *     for i in 0 .. 2 nx:  llpf_ukf_point(nx, gamma, x, Cf, i, X);  Z[i][:] = g(X)  (or f(X))
- *     ll = llpf_ukf_correct_finish(...)   /   llpf_ukf_predict_finish(...)
+ *     ll = llpf_ukf_correct_finish(...)   /   llpf_ukf_predict_finish(...)   /   llpf_ukf_smooth_finish(...)  (f, backward pass)
  * The mapped points are the only per-point storage: Z[(i * dim + d) * zs] (dim = ny or nx; zs = 1 for a local array, the number of
  * lanes for a [point][d][lane] array in LDS).  A sigma point itself is a function of (x, Cf, i) and is formed again where the cross
  * covariance needs it — the same operations on the same numbers, so the same bits — never a second evaluation of f or g.
@@ -129,6 +129,45 @@ LLPF_HD void llpf_ukf_predict_finish(const int nx, const double wm0, const doubl
         LLPF_KF_UNROLL
         for (int i = 0; i < LLPF_KF_NP(nx); ++i) R[i] = llpf_kf_nan();
     }
+}
+
+/* One backward step of the unscented Rauch-Tung-Striebel smoother (Sarkka 2008, additive noise), after the caller has put
+ * X'_i = f(X_i) of the points of the posterior (xt, Cf) of step t into Z (dim = nx).  ok: what llpf_ukf_factor(nx, Rt, Cf) returned.
+ * On entry xT, RT are the smoothed estimate of step t + 1 (packed), on return that of step t; xt, Rt must not alias them.  From
+ * xT[T] = xt[T], RT[T] = Rt[T], for t = T-1 down to 1 (1-based):
+ *     x- = sum wm_i X'_i;  R- = sum wc_i dX'_i dX'_i' + R1;  G = sum wc_i dX'_i (X_i - xt)';
+ *     J' = R-^-1 G;  xT[t] = xt[t] + J (xT[t+1] - x-);  RT[t] = Rt[t] + J (RT[t+1] - R-) J'
+ * The form computed here:
+ *   - x-, R- are llpf_ukf_center and llpf_ukf_cov on the mapped points exactly as llpf_ukf_predict_finish applies them — the same
+ *     functions of the same numbers, so the bits of the forward pass's prior x[t+1], R[t+1], which is not stored;
+ *   - G (nx x nx, G[r][c] = Cov(x'_r, x_c)) is accumulated as llpf_ukf_correct_finish accumulates Cxy': point i is formed again from
+ *     (xt, Cf, i), f is not evaluated a second time;
+ *   - the rest is llpf_kf_smooth_finish (llpf_kalman.h) with G in the place of A Rt: the Cholesky of R-, the two triangular solves,
+ *     xT and the (J D) J' update in the lower triangle.
+ * A filter whose Rt (!ok) or R- is not positive definite gets NaN xT, RT at step t and so at every earlier step; nothing else is
+ * touched.  A missing row needs nothing: its posterior is its prior. */
+LLPF_HD void llpf_ukf_smooth_finish(const int nx, const double gamma, const double wm0, const double wc0, const double wi, const double* P,
+                                    const int64_t ps, const int ok, const double* Cf, double* Z, const int64_t zs, const double* xt,
+                                    const double* Rt, double* xT, double* RT) {
+    const int dim = nx;
+    double xp[LLPF_KF_MAXX], L[LLPF_KF_NP(LLPF_KF_MAXX)], Jt[LLPF_KF_MAXX * LLPF_KF_MAXX];
+    llpf_ukf_center(nx, nx, wm0, wi, Z, zs, xp);
+    llpf_ukf_cov(nx, nx, wc0, wi, Z, zs, P, ps, LLPF_UKF_OFF_R1, L);
+    /* Jt = G = sum wc_i (X'_i - x-)(X_i - xt)' */
+    LLPF_KF_UNROLL
+    for (int i = 0; i < LLPF_UKF_NPTS(nx); ++i) {
+        double X[LLPF_KF_MAXX];
+        llpf_ukf_point(nx, gamma, xt, Cf, i, X);
+        LLPF_KF_UNROLL
+        for (int c = 0; c < nx; ++c) X[c] = X[c] - xt[c];
+        LLPF_KF_UNROLL
+        for (int r = 0; r < nx; ++r) {
+            const double t = (i == 0 ? wc0 : wi) * LLPF_UKF_Z(i, r);
+            LLPF_KF_UNROLL
+            for (int c = 0; c < nx; ++c) Jt[r * LLPF_KF_MAXX + c] = i == 0 ? t * X[c] : llpf_fma(t, X[c], Jt[r * LLPF_KF_MAXX + c]);
+        }
+    }
+    llpf_kf_smooth_finish(nx, ok, xp, L, Jt, xt, Rt, xT, RT);
 }
 
 /* One step t of forward_trajectory: x, R on entry are the prior; correct! (skipped at a missing row) gives ll[t], e[t] and the posterior

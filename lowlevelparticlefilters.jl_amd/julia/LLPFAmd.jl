@@ -1195,6 +1195,36 @@ function ukf_run(b::GPUUnscentedKalmanFilterBank, u, y; outputs = false, t_index
     end
     ll, o
 end
+# the forward pass of ukf_run and the unscented RTS smoother's backward pass (llpf_ukf_bank_smooth): ll_total, the forward outputs (or
+# nothing) and the smoothed xT (nx x F x T), RT (nx x nx x F x T)
+function ukf_smooth(b::GPUUnscentedKalmanFilterBank, u, y; outputs = false, t_index0 = 0.0)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    s = (xT = zeros(b.nx, b.F, T), RT = zeros(b.nx, b.nx, b.F, T))
+    GC.@preserve U Y ll o s begin
+        fwd = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        out = Ref(CKalmanSmoothOutputs(UInt32(sizeof(CKalmanSmoothOutputs)), 0, pointer(s.xT), pointer(s.RT)))
+        check(ccall((:llpf_ukf_bank_smooth, LIB), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Ptr{CKalmanOutputs}, Ptr{CKalmanSmoothOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), Float64(t_index0), pointer(ll),
+                    fwd === nothing ? C_NULL : fwd, out))
+    end
+    ll, o, s
+end
+"smooth(bank, u, y): every filter's smoothed estimate (reset! first, the first step at t = 0): ll (F), xT (nx x F x T), RT (nx x nx x F x T)"
+function smooth(b::GPUUnscentedKalmanFilterBank, u, y)
+    reset!(b)
+    ll, _, s = ukf_smooth(b, u, y)
+    ll, s.xT, s.RT
+end
 "loglik(bank, u, y): every filter's loglik(ukf, u, y) (reset! first, then T update! steps, the first at t = 1 Ts as the particle filters' loglik)"
 loglik(b::GPUUnscentedKalmanFilterBank, u, y) = (reset!(b); ukf_run(b, u, y; t_index0 = 1.0)[1])
 "x (nx x F), R (nx x nx x F) of every filter"
@@ -1216,8 +1246,8 @@ end
     GPUUnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0, weight_params = TrivialParams())
 
 The reference's `UnscentedKalmanFilter` with additive noise, run on the device (a bank of one filter, llpf_ukf_bank_*):
-`forward_trajectory` returns the reference's `KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `correct!`, `predict!`, `state`,
-`covariance`.  Unverified against the reference (its source was not available when this was written): the default weight parameters and
+`forward_trajectory` returns the reference's `KalmanFilteringSolution`, `smooth` its `KalmanSmoothingSolution`; `loglik`, `reset!`,
+`update!`, `correct!`, `predict!`, `state`, `covariance`.  Unverified against the reference (its source was not available when this was written): the default weight parameters and
 whether its predict! draws the sigma points again from the posterior, as this one does.
 """
 mutable struct GPUUnscentedKalmanFilter
@@ -1257,6 +1287,22 @@ function forward_trajectory(kf::GPUUnscentedKalmanFilter, u, y, p = NullParamete
     kf.index = T
     KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
                             [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+end
+"""
+    smooth(ukf::GPUUnscentedKalmanFilter, u, y, p = NullParameters())
+
+reset!, forward_trajectory and the unscented Rauch-Tung-Striebel smoother (additive noise) on the device: the reference's
+`KalmanSmoothingSolution`, built as `KalmanSmoothingSolution(sol, xT, RT)` from the forward `KalmanFilteringSolution`.  Unverified against
+the reference's smoother, as the filter is.
+"""
+function LowLevelParticleFilters.smooth(ukf::GPUUnscentedKalmanFilter, u, y, p = NullParameters())
+    reset!(ukf.bank)
+    ll, o, s = ukf_smooth(ukf.bank, u, y; outputs = true)
+    T = length(y)
+    ukf.index = T
+    sol = KalmanFilteringSolution(ukf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                                  [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+    KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
 end
 
 end # module
