@@ -546,6 +546,10 @@ int  llpf_last_run_ms(llpf_filter* f, double* ms);
  * the survivor fraction the choice for the NEXT run is made by (distinct ancestors per predict! / N, a step that did not resample
  * counting as 1; -1 when the model cannot take the source-side form).  Results do not depend on the form: the choice is a schedule. */
 int  llpf_last_run_stats(llpf_filter* f, int64_t* fused_launches, int64_t* source_side_timesteps, double* survivor_fraction);
+/* two more facts about the last llpf_run: whether its fused launches left the weights they formed unstored (a merged-schedule run of
+ * filters of several tiles at resample_threshold 1: every step resamples and nobody reads them; LLPF_SKIP_W=0 pins the storing form), and
+ * how many failed bound tests its host loop redid in the exact-max form.  Results do not depend on either. */
+int  llpf_last_run_form(llpf_filter* f, int32_t* weights_not_stored, int64_t* exact_redos);
 int  llpf_bank_last_run_ms(llpf_bank* b, double* ms);
 
 /* ---- misc -------------------------------------------------------------------------------- */

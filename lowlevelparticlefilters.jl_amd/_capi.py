@@ -107,6 +107,7 @@ SYMBOLS = {
     "llpf_bank_resample_count": [_vp, _ip],
     "llpf_last_run_ms": [_vp, _dp],
     "llpf_last_run_stats": [_vp, _ip, _ip, _dp],
+    "llpf_last_run_form": [_vp, C.POINTER(C.c_int32), _ip],
     "llpf_bank_last_run_ms": [_vp, _dp],
     "llpf_last_error": [],
     "llpf_version": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
@@ -455,6 +456,11 @@ class FilterHandle:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
         check(self.L.llpf_last_run_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return {"fused_launches": a.value, "source_side_timesteps": b.value, "survivor_fraction": c.value}
+
+    def last_run_form(self):
+        a, b = C.c_int32(0), C.c_int64(0)
+        check(self.L.llpf_last_run_form(self.h, C.byref(a), C.byref(b)))
+        return {"weights_not_stored": bool(a.value), "exact_redos": b.value}
 
     def set_profiling(self, on):
         check(self.L.llpf_set_profiling(self.h, 1 if on else 0))

@@ -440,6 +440,12 @@ int llpf_last_run_stats(llpf_filter* f, int64_t* fused_launches, int64_t* source
     if (survivor_fraction) *survivor_fraction = f->bank.last_run_surv;
     return LLPF_OK;
 } LLPF_GUARD(llpf_last_run_stats)
+int llpf_last_run_form(llpf_filter* f, int32_t* weights_not_stored, int64_t* exact_redos) LLPF_TRY {
+    NEEDF(f);
+    if (weights_not_stored) *weights_not_stored = f->bank.last_run_skip_w ? 1 : 0;
+    if (exact_redos) *exact_redos = f->bank.last_run_redos;
+    return LLPF_OK;
+} LLPF_GUARD(llpf_last_run_form)
 int llpf_last_run_ms(llpf_filter* f, double* ms) LLPF_TRY { NEEDF(f); if (ms) *ms = f->bank.last_run_ms; return LLPF_OK; } LLPF_GUARD(llpf_last_run_ms)
 
 static int set_prof(Bank& b, int on) {

@@ -153,6 +153,14 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
         b.d_w_spare = b.d_w_alloc;
         HIPC(hipMemcpyAsync(b.d_w_spare, b.d_w, bytes, hipMemcpyDeviceToDevice, b.stream));
     }
+    // Merged fused run at threshold 1: every step resamples, so the weights a launch forms are never read again — the next step's prior is
+    // log(1/N), its head consumes their integer sums and quanta, and the run ends uniform (k_post_predict) — and the fused launches do not
+    // store them (k_resprop<..., SKIPW>: 8 of the 44 bytes an output writes).  Their one reader is the exact redo of a failed bound test, in
+    // front of which the weights of the flagged filters are formed again (reweight_flagged, below).  Not for one-tile filters (their kernel
+    // redoes a failed test in place, from the stored weights) nor for the Rao-Blackwellized model (its weighting also updates the linear
+    // substate).  LLPF_SKIP_W=0: the storing form.
+    const char* skw_env = getenv("LLPF_SKIP_W");
+    const bool skip_w_run = !unfused && acc_in_weighting && !rbm && b.cfg.resample_threshold == 1.0 && b.P2 > 1 && !(skw_env && atoi(skw_env) == 0);
     double* const wbuf0 = b.d_w;
     double* const wbuf1 = lazy_run ? b.d_w_spare : b.d_w;
     // however the run ends (a failed status or a throw included), the verbs after it weight in place, on the buffer it began in
@@ -240,6 +248,7 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
             HIPC(launch_norm(d, ra.parity, want_xm, ne2, rel_step(b), 0, lazy_q ? 3 : 1, k, b.stream));
         }
         ra.lazy_q = lazy_q ? 1 : 0;
+        ra.skip_w = (skip_w_run && fast) ? 1 : 0;      // (the exact redo of a failed step keeps the storing form)
         ra.nt_id = nt_env ? (atoi(nt_env) != 0 ? 1 : 0) : (((int64_t)b.F * b.Ns >= ((int64_t)7 << 20)) ? 1 : 0);      // nontemporal accesses on the steps that do not resample: working sets well beyond the Infinity Cache (LLPF_NT_ID=0|1 pins it)
         if (!fast) {
             ProfScope ps(b, LLPF_PROF_NORMALISE);
@@ -314,7 +323,23 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
         HIPC(launch_step(d, MODE_WEIGHT, a, b.stream));
         return LLPF_OK;
     };
+    // A run whose fused launches store no weights, in front of the exact redo of step kf (>= 1; the weights in front of step 0 are the
+    // first weighting's, which stores): the weights of the flagged filters again, by the weighting launch, from the states step kf - 1 left
+    // in memory, the measurement of step kf and the prior log(1/N) of a step that resampled — the expression the fused kernel evaluated, on
+    // the same doubles.  The launch republishes the slot's bound, uniform and flags with the values they already have.
+    auto reweight_flagged = [&](int64_t kf) -> int {
+        at_step(kf - 1);
+        StepArgs st = step_args(kf - 1);                 // the weighting half of the launch that formed them
+        st.accumulate = 0; st.want_xmean = 0; st.only_fallback = 1; st.k = kf;
+        at_step(kf);
+        BankDev d = b.dev();
+        ProfScope ps(b, LLPF_PROF_PROPAGATE);
+        HIPC(launch_fb_clear(d, 0, 2, b.stream));        // prior of the flagged filters: uniform, log(1/N)
+        HIPC(launch_step(d, MODE_WEIGHT, st, b.stream));
+        return LLPF_OK;
+    };
     b.last_run_launches = 0; b.last_run_fx_steps = source_fx ? T : 0; b.last_run_surv = -1.0;
+    b.last_run_skip_w = skip_w_run; b.last_run_redos = 0;
     // the asynchronous loop as a captured graph, replayed when nothing a launch argument depends on has changed
     static const char* graph_env = getenv("LLPF_GRAPH");
     const bool use_graph = !hist && !b.profiling && !dbg_env && !(graph_env && atoi(graph_env) == 0);
@@ -322,7 +347,7 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     if (use_graph) {
         Bank::RunGraph key{};
         key.T = T; key.t_index0 = t_index0; key.par0 = par0; key.cur0 = cur0; key.qcur0 = qcur0;
-        key.flags = (merged ? 1 : 0) | (unfused ? 2 : 0) | (want_xm ? 4 : 0) | (ll_steps ? 8 : 0) | (xm_launch ? 16 : 0) | (multi ? 32 : 0) | (source_fx ? 64 : 0) | (xcov ? 128 : 0) | (xquant ? 256 : 0) | ((abl_env ? atoi(abl_env) : 0) << 9) | (lazy_run ? (1 << 30) : 0) | ((nt_env && atoi(nt_env) != 0) ? (1 << 29) : 0) | ((nt_env && atoi(nt_env) == 0) ? (1 << 28) : 0);      // (no_bound is a property of the model id, which a handle keeps)
+        key.flags = (merged ? 1 : 0) | (unfused ? 2 : 0) | (want_xm ? 4 : 0) | (ll_steps ? 8 : 0) | (xm_launch ? 16 : 0) | (multi ? 32 : 0) | (source_fx ? 64 : 0) | (xcov ? 128 : 0) | (xquant ? 256 : 0) | (((abl_env ? atoi(abl_env) : 0) & 0xff) << 9) | (skip_w_run ? (1 << 27) : 0) | (lazy_run ? (1 << 30) : 0) | ((nt_env && atoi(nt_env) != 0) ? (1 << 29) : 0) | ((nt_env && atoi(nt_env) == 0) ? (1 << 28) : 0);      // (no_bound is a property of the model id, which a handle keeps)
         key.np_parity = (int)(np0 & 1u);
         key.dU = b.d_U; key.dY = b.d_Y; key.dll = ll_steps ? b.d_ll_steps : nullptr; key.dxm = xmean ? b.d_xmean : nullptr; key.dxc = xcov ? b.d_xcov : nullptr; key.drb = b.d_rbseq;
         key.dw = wbuf0; key.dws = wbuf1;
@@ -367,6 +392,7 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
             int64_t kf;
             CHK(poll_fallback(b, fl, kf));
             if (!fl.empty()) {
+                b.last_run_redos += 1;
                 CHK(clear_slot_sums(b, ra.parity, fl));
                 HIPC(launch_norm(d, ra.parity, want_xm, 1, rel_step(b), 1, 0, k, b.stream));
                 ra.fast_head = 0; ra.only_fallback = 1;
@@ -424,6 +450,8 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
             CHK(poll_fallback(b, fl, kf));
             if (fl.empty()) { k0 = k1; batch = std::min(T, batch * 2); continue; }
             // step kf of the flagged filters: exact-max normalisation of the same weights, then the step again
+            b.last_run_redos += 1;
+            if (skip_w_run && kf > 0) CHK(reweight_flagged(kf));
             CHK(clear_slot_sums(b, head_slot(kf), fl));
             CHK(launch_timestep(kf, false, 1));
             CHK(clear_fallback(b, fl));

@@ -265,6 +265,7 @@ __global__ void k_post_predict(BankDev b) {
 
 // host side of a failed bound test, for the filters whose `fallback` flag is set: mode 0 zeroes the exp-sum words of
 // accumulator slot `slot` (the exact-form k_norm accumulates them afresh), mode 1 clears the flags and the run's stop word
+// (mode 2: below)
 __global__ void k_fb_clear(BankDev b, int slot, int mode) {
     const int f = blockIdx.x;
     FilterScal* sc = b.scal + f;
@@ -274,6 +275,10 @@ __global__ void k_fb_clear(BankDev b, int slot, int mode) {
         const int words[7] = {ACC_S(slot), ACC_S(slot) + 1, ACC_S(slot) + 2, ACC_E2(slot), ACC_E2(slot) + 1, ACC_E2(slot) + 2, ACC_BAD(slot)};
         for (int i = threadIdx.x; i < 7 * NSHARD * ACC_STRIDE; i += blockDim.x)
             acc[(size_t)words[i / (NSHARD * ACC_STRIDE)] * NSHARD * ACC_STRIDE + (i % (NSHARD * ACC_STRIDE))] = 0;
+    } else if (mode == 2) {
+        // a run whose fused launches store no weights (ResArgs::skip_w): the step in front of the failed head resampled, so the prior of the
+        // weights the host is about to form again (k_step<MODE_WEIGHT>) is log(1/N); the redo's head clears `uniform` again
+        if (threadIdx.x == 0) { sc->uniform = 1; sc->wconst = b.log1N; }
     } else if (threadIdx.x == 0) {
         sc->fallback = 0;
     }

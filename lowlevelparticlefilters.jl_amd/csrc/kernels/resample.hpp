@@ -141,7 +141,9 @@ DEV double head_log(const ResHead& h) { return h.fast ? llpf_log(h.stot) : llpf_
 struct NoOverlap { DEV void operator()() const {} };
 // `overlap`: work of the caller that needs nothing from memory the head waits for (particle-independent model terms: their
 // own scalar loads); it runs after the head's vector loads are issued and before the first of them is consumed
-template <int SRC, bool COH = false, class Overlap = NoOverlap>
+// `NO_TOT0`: a fast head whose quanta sum to zero asks for the exact redo as well (k_resprop<..., SKIPW>: such a head would otherwise
+// not resample and read weights that the launch in front of it did not store)
+template <int SRC, bool COH = false, class Overlap = NoOverlap, bool NO_TOT0 = false>
 DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResShared& sh,
                      bool defer_skip = false, uint32_t stop_flag = 0, int fb_flag = 0, Overlap&& overlap = NoOverlap()) {
     FilterScal* sc = b.scal + f;
@@ -243,7 +245,7 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
         const bool bad = sh.accw[7] != 0;
         if (h.fast) {
             h.a = off_pre;                                        // published by the weighting kernel that filled this slot
-            if (bad || s128.hi < ((uint64_t)1 << 22)) {           // sum exp(w - bound) < 2^-10, or NaN weights
+            if (bad || s128.hi < ((uint64_t)1 << 22) || (NO_TOT0 && h.tot == 0)) {           // sum exp(w - bound) < 2^-10, or NaN weights
                 h.status = RES_STATUS_FALLBACK;
                 h.stot = 0.0;
             } else {

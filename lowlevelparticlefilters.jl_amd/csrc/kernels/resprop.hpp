@@ -47,7 +47,8 @@ template <class T> DEV void st_off(T* base, uint32_t byte_off, T v) {
 #endif
 #define LLPF_STCOH ((LLPF_WT && !LLPF_RB_PLAIN_ST) ? STP : COH)
 #define LLPF_STCOH0 ((LLPF_WT && !LLPF_RB_PLAIN_ST) ? LLPF_RESPROP_ST : 0)
-template <class Model, int NX, int NY, bool WEIGHT, bool COH = false, bool LTAB = false>
+// STW = false: the weights formed here are not stored (k_resprop<..., SKIPW>: nobody reads them)
+template <class Model, int NX, int NY, bool WEIGHT, bool COH = false, bool LTAB = false, bool STW = true>
 struct PropCtx {
     const BankDev& b;
     const Model& model;
@@ -138,7 +139,10 @@ struct PropCtx {
             }
             if (o >= (uint32_t)b.N) wv = -LLPF_INF;
             bad = bad || (wv != wv);
-            if constexpr (STP >= 0) Mem<LLPF_STCOH>::st_off(wn, oo, wv);
+#ifdef LLPF_DEVTOOLS
+            if (!(ablate & 8))
+#endif
+            if constexpr (STP >= 0 && STW) Mem<LLPF_STCOH>::st_off(wn, oo, wv);
         }
         return wv;
     }
@@ -173,7 +177,11 @@ static_assert(TILE == 1024, "TileSum assumes 1024-particle tiles");
 #define LLPF_HOT_ARGS(b, a) (b).acc, (b).tileq, (b).scal, (b).bank_flag, (b).quanta, (b).F, (b).P2, (a).parity
 
 // ONE: the filter is a single tile (launched only when P2 == 1): a failed bound test is redone inside this kernel
-template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false>
+// SKIPW: a run at resample_threshold 1 (host/run.hpp: every step resamples, so the prior of every weight is log(1/N) and the next head
+// consumes only the integer sums and the quanta): the weights formed here are not stored — 8 of the 44 bytes an output writes, one of its
+// five stores.  The only reader of those weights, the exact redo of a failed bound test, has the host form them again first, from the
+// states in memory.  A head that would not resample (no quanta at all) asks for that redo instead of reading the weights.
+template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, bool SKIPW = false>
 // amdgpu_waves_per_eu(4): the ~3.8 blocks per CU of a 10^6-particle filter must be resident together (<= 128 VGPRs); the
 // larger state dimensions would spill under that cap and keep the compiler's choice; the Rao-Blackwellized propagate uses
 // 130-156 VGPRs and is pinned to three waves per SIMD (<= 168): twice in this round an unrelated change pushed it past 170 and
@@ -248,7 +256,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
             else if (t < LLPF_RNG_SC_ENTRIES + LLPF_RNG_LG_ENTRIES) { rt0 = LLPF_LOG_INVC[t - LLPF_RNG_SC_ENTRIES]; rt1 = LLPF_LOG_LNC[t - LLPF_RNG_SC_ENTRIES]; }
         }
     };
-    const ResHead h = res_head<SRC_FILTER, false>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
+    static_assert(!SKIPW || (WEIGHT && ACC && !AUX && !ONE && !Model::RB), "the form without the weight store: merged schedule, several tiles");
+    const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
     if (h.status) return;
     // Values of FilterScal fetched above with the head's loads but wanted only from here on.  FilterScal is written by this
     // kernel, so they are vector loads made uniform with v_readfirstlane — which the compiler otherwise places right behind the
@@ -264,7 +273,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
         else if (t < LLPF_RNG_SC_ENTRIES + LLPF_RNG_LG_ENTRIES) { sh_rng_lg[2 * (t - LLPF_RNG_SC_ENTRIES)] = rt0; sh_rng_lg[2 * (t - LLPF_RNG_SC_ENTRIES) + 1] = rt1; }
     }
     LLPF_STAMP(1);
-    PropCtx<Model, NX, NY, WEIGHT, false, !RBFAT> pc{b, model, md, st, y, b.xcur + (size_t)f * NX * Ns, b.xnext + (size_t)f * NX * Ns,
+    PropCtx<Model, NX, NY, WEIGHT, false, !RBFAT, !SKIPW> pc{b, model, md, st, y, b.xcur + (size_t)f * NX * Ns, b.xnext + (size_t)f * NX * Ns,
                                       b.w + (size_t)f * Ns, b.w_next + (size_t)f * Ns, key0, key1, sb + st.step, a.ablate, 0.0, b.quanta_next + (size_t)f * Ns,
                                       RBFAT ? nullptr : sh_rng_lg, RBFAT ? nullptr : sh_rng_sc};
     int32_t* anc = b.anc + (size_t)f * Ns;
