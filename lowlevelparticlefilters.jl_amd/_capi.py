@@ -476,22 +476,25 @@ KALMAN_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
 KALMAN_SMOOTH_OUTPUTS = ("xT", "RT")
 
 
-class KalmanBankHandle:
-    """RAII wrapper of an `llpf_kalman_bank*` (independent Kalman filters with constant matrices on one device)."""
+class _KfBankHandle:
+    """What the handles of the one-thread-per-filter Kalman banks share.  `_SYM`: the prefix of the bank's symbols; `times`: the arguments
+    the bank's run and smooth take between per_filter and ll_total (none, or t_index0)."""
+    _SYM = None
 
-    def __init__(self, device, models, D=None):
+    def _open(self, models):
         self.L = lib()
         self.h = _vp()
         self.F = len(models)
         m0 = models[0]
         self.nx, self.nu, self.ny = m0.nx, m0.nu, m0.ny
-        arr = (S.Model * self.F)(*models)
-        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
-        check(self.L.llpf_kalman_bank_create(int(device), arr, dptr(D), self.F, C.byref(self.h)))
+        return (S.Model * self.F)(*models)
+
+    def _call(self, verb, *args):
+        check(getattr(self.L, "%s_%s" % (self._SYM, verb))(self.h, *args))
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.llpf_kalman_bank_destroy(self.h)
+            getattr(self.L, self._SYM + "_destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -501,24 +504,7 @@ class KalmanBankHandle:
             pass
 
     def reset(self):
-        check(self.L.llpf_kalman_bank_reset(self.h))
-
-    def set_models(self, models, D=None):
-        arr = (S.Model * self.F)(*models)
-        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
-        check(self.L.llpf_kalman_bank_set_models(self.h, arr, dptr(D)))
-
-    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
-        """T steps of every filter: U [T, nu] or [F, T, nu] (u_per_filter), Y [T, ny] or [F, T, ny] (y_per_filter).  Returns
-        {"ll": [F], name: array} for every name of `outputs` (KALMAN_OUTPUTS), time-major: ll_steps [T, F], x / xt [T, F, nx],
-        R / Rt [T, F, nx, nx], e [T, F, ny]."""
-        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
-        res, out = self._forward_outputs(T, outputs)
-        ll = np.empty(self.F)
-        check(self.L.llpf_kalman_bank_run(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
-                                          None if out is None else C.byref(out)))
-        res["ll"] = ll
-        return res
+        self._call("reset")
 
     def _inputs(self, U, Y, u_per_filter, y_per_filter):
         F, nu, ny = self.F, self.nu, self.ny
@@ -543,10 +529,16 @@ class KalmanBankHandle:
                 setattr(out, k, dptr(a))
         return res, out
 
-    def smooth(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=KALMAN_SMOOTH_OUTPUTS, forward=()):
-        """the forward pass of run() and the RTS smoother's backward pass (llpf_kalman_bank_smooth).  Returns {"ll": [F]} with xT [T, F, nx]
-        and RT [T, F, nx, nx] for the names in `outputs` (KALMAN_SMOOTH_OUTPUTS) and the forward outputs named in `forward`
-        (KALMAN_OUTPUTS); the state afterwards is the one run() leaves."""
+    def _run(self, U, Y, u_per_filter, y_per_filter, outputs, *times):
+        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
+        res, out = self._forward_outputs(T, outputs)
+        ll = np.empty(self.F)
+        self._call("run", dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), *times, dptr(ll),
+                   None if out is None else C.byref(out))
+        res["ll"] = ll
+        return res
+
+    def _smooth(self, U, Y, u_per_filter, y_per_filter, outputs, forward, *times):
         F, nx = self.F, self.nx
         U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
         res, fwd = self._forward_outputs(T, forward)
@@ -557,8 +549,8 @@ class KalmanBankHandle:
         for k, a in sm.items():
             setattr(out, k, dptr(a))
         ll = np.empty(F)
-        check(self.L.llpf_kalman_bank_smooth(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
-                                             None if fwd is None else C.byref(fwd), C.byref(out)))
+        self._call("smooth", dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), *times, dptr(ll),
+                   None if fwd is None else C.byref(fwd), C.byref(out))
         res.update(sm)
         res["ll"] = ll
         return res
@@ -566,13 +558,40 @@ class KalmanBankHandle:
     def get_state(self):
         x = np.empty((self.F, self.nx))
         R = np.empty((self.F, self.nx, self.nx))
-        check(self.L.llpf_kalman_bank_get_state(self.h, dptr(x), dptr(R)))
+        self._call("get_state", dptr(x), dptr(R))
         return x, R
 
     def set_state(self, x, R):
         x = f64(x).reshape(self.F, self.nx)
         R = f64(R).reshape(self.F, self.nx, self.nx)
-        check(self.L.llpf_kalman_bank_set_state(self.h, dptr(x), dptr(R)))
+        self._call("set_state", dptr(x), dptr(R))
+
+
+class KalmanBankHandle(_KfBankHandle):
+    """RAII wrapper of an `llpf_kalman_bank*` (independent Kalman filters with constant matrices on one device)."""
+    _SYM = "llpf_kalman_bank"
+
+    def __init__(self, device, models, D=None):
+        arr = self._open(models)
+        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
+        check(self.L.llpf_kalman_bank_create(int(device), arr, dptr(D), self.F, C.byref(self.h)))
+
+    def set_models(self, models, D=None):
+        arr = (S.Model * self.F)(*models)
+        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
+        self._call("set_models", arr, dptr(D))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
+        """T steps of every filter: U [T, nu] or [F, T, nu] (u_per_filter), Y [T, ny] or [F, T, ny] (y_per_filter).  Returns
+        {"ll": [F], name: array} for every name of `outputs` (KALMAN_OUTPUTS), time-major: ll_steps [T, F], x / xt [T, F, nx],
+        R / Rt [T, F, nx, nx], e [T, F, ny]."""
+        return self._run(U, Y, u_per_filter, y_per_filter, outputs)
+
+    def smooth(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=KALMAN_SMOOTH_OUTPUTS, forward=()):
+        """the forward pass of run() and the RTS smoother's backward pass (llpf_kalman_bank_smooth).  Returns {"ll": [F]} with xT [T, F, nx]
+        and RT [T, F, nx, nx] for the names in `outputs` (KALMAN_SMOOTH_OUTPUTS) and the forward outputs named in `forward`
+        (KALMAN_OUTPUTS); the state afterwards is the one run() leaves."""
+        return self._smooth(U, Y, u_per_filter, y_per_filter, outputs, forward)
 
 
 def ukf_weights(w):
@@ -581,74 +600,30 @@ def ukf_weights(w):
     return S.UkfWeights(C.sizeof(S.UkfWeights), 0, gamma, wm0, wc0, wi)
 
 
-class UkfBankHandle(KalmanBankHandle):
+class UkfBankHandle(_KfBankHandle):
     """RAII wrapper of an `llpf_ukf_bank*` (independent unscented Kalman filters on one device); `weights` = (gamma, wm0, wc0, wi)."""
+    _SYM = "llpf_ukf_bank"
 
     def __init__(self, device, models, weights):
-        self.L = lib()
-        self.h = _vp()
-        self.F = len(models)
-        m0 = models[0]
-        self.nx, self.nu, self.ny = m0.nx, m0.nu, m0.ny
-        arr = (S.Model * self.F)(*models)
+        arr = self._open(models)
         w = ukf_weights(weights)
         check(self.L.llpf_ukf_bank_create(int(device), arr, self.F, C.byref(w), C.byref(self.h)))
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.llpf_ukf_bank_destroy(self.h)
-            self.h = None
-
-    def reset(self):
-        check(self.L.llpf_ukf_bank_reset(self.h))
-
     def set_models(self, models):
-        arr = (S.Model * self.F)(*models)
-        check(self.L.llpf_ukf_bank_set_models(self.h, arr))
+        self._call("set_models", (S.Model * self.F)(*models))
 
     def set_weights(self, weights):
         w = ukf_weights(weights)
-        check(self.L.llpf_ukf_bank_set_weights(self.h, C.byref(w)))
+        self._call("set_weights", C.byref(w))
 
     def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
         """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""
-        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
-        res, out = self._forward_outputs(T, outputs)
-        ll = np.empty(self.F)
-        check(self.L.llpf_ukf_bank_run(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), float(t_index0),
-                                       dptr(ll), None if out is None else C.byref(out)))
-        res["ll"] = ll
-        return res
+        return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
 
     def smooth(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=KALMAN_SMOOTH_OUTPUTS, forward=(), t_index0=0.0):
         """the forward pass of run() and the unscented RTS smoother's backward pass (llpf_ukf_bank_smooth), step t at time
         (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.smooth"""
-        F, nx = self.F, self.nx
-        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
-        res, fwd = self._forward_outputs(T, forward)
-        shapes = {"xT": (T, F, nx), "RT": (T, F, nx, nx)}
-        sm = {k: np.empty(shapes[k]) for k in outputs}
-        out = S.KalmanSmoothOutputs()
-        out.struct_size = C.sizeof(S.KalmanSmoothOutputs)
-        for k, a in sm.items():
-            setattr(out, k, dptr(a))
-        ll = np.empty(F)
-        check(self.L.llpf_ukf_bank_smooth(self.h, dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), float(t_index0),
-                                          dptr(ll), None if fwd is None else C.byref(fwd), C.byref(out)))
-        res.update(sm)
-        res["ll"] = ll
-        return res
-
-    def get_state(self):
-        x = np.empty((self.F, self.nx))
-        R = np.empty((self.F, self.nx, self.nx))
-        check(self.L.llpf_ukf_bank_get_state(self.h, dptr(x), dptr(R)))
-        return x, R
-
-    def set_state(self, x, R):
-        x = f64(x).reshape(self.F, self.nx)
-        R = f64(R).reshape(self.F, self.nx, self.nx)
-        check(self.L.llpf_ukf_bank_set_state(self.h, dptr(x), dptr(R)))
+        return self._smooth(U, Y, u_per_filter, y_per_filter, outputs, forward, float(t_index0))
 
 
 class BankHandle:

@@ -448,7 +448,50 @@ def covariance(kf):
     return kf.R
 
 
-class KalmanFilterBank:
+class _KfBank:
+    """What KalmanFilterBank and UnscentedKalmanFilterBank share: a bank handle `_h` of one GPU thread per filter.  `_AT_LOGLIK` and
+    `_AT_FORWARD` are the keyword arguments the handle's run / smooth take for the time of the first step."""
+    _AT_LOGLIK = _AT_FORWARD = {}
+
+    def reset(self):
+        self._h.reset()
+
+    def state(self):
+        """(x [F, nx], R [F, nx, nx]) of every filter"""
+        return self._h.get_state()
+
+    def _io(self, u, y):
+        y = np.asarray(y, dtype=np.float64)
+        y_per = y.ndim == 3
+        if self._h.nu == 0 or u is None:
+            return None, False, y, y_per
+        u = np.asarray(u, dtype=np.float64)
+        return u, u.ndim == 3, y, y_per
+
+    def loglik(self, u, y):
+        """[loglik(f_k, u, y) for k]: reset, then T update! steps (those of an unscented bank the first at t = 1 * Ts as FilterBank.loglik).
+        u [T, nu] / y [T, ny] shared, or [F, T, n] per filter (by ndim)."""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.run(u, y, up, yp, **self._AT_LOGLIK)["ll"]
+
+    def forward(self, u, y, outputs=_capi.KALMAN_OUTPUTS):
+        """forward_trajectory of every filter (the first step at t = 0): {"ll": [F], "ll_steps": [T, F], "x", "xt": [T, F, nx], "R", "Rt":
+        [T, F, nx, nx], "e": [T, F, ny]} for the names in `outputs`"""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.run(u, y, up, yp, outputs=outputs, **self._AT_FORWARD)
+
+    def smooth(self, u, y, outputs=_capi.KALMAN_SMOOTH_OUTPUTS, forward=()):
+        """smooth(f_k, u, y) of every filter (reset, the forward pass of forward(), the RTS smoother — an unscented bank's the unscented one —
+        on the device): {"ll": [F], "xT": [T, F, nx], "RT": [T, F, nx, nx]} for the names in `outputs`, plus the forward outputs named in
+        `forward` (as forward())"""
+        u, up, y, yp = self._io(u, y)
+        self._h.reset()
+        return self._h.smooth(u, y, up, yp, outputs=outputs, forward=forward, **self._AT_FORWARD)
+
+
+class KalmanFilterBank(_KfBank):
     """n independent Kalman filters with constant matrices of the same dimensions on one device, one GPU thread each
     (llpf_kalman_bank_*): the exact log-likelihood of every parameter set of a linear-Gaussian sweep.  `filters_spec` is a list of
     KalmanFilter or of (A, B, C, D, R1, R2, d0) tuples."""
@@ -483,41 +526,6 @@ class KalmanFilterBank:
         """new matrices for every filter (same dimensions, nothing reallocated: llpf_kalman_bank_set_models)"""
         models, Ds = self._models(filters_spec)
         self._h.set_models(models, Ds)
-
-    def reset(self):
-        self._h.reset()
-
-    def state(self):
-        """(x [F, nx], R [F, nx, nx]) of every filter"""
-        return self._h.get_state()
-
-    def _io(self, u, y):
-        y = np.asarray(y, dtype=np.float64)
-        y_per = y.ndim == 3
-        if self._h.nu == 0 or u is None:
-            return None, False, y, y_per
-        u = np.asarray(u, dtype=np.float64)
-        return u, u.ndim == 3, y, y_per
-
-    def loglik(self, u, y):
-        """[loglik(kf_k, u, y) for k]: reset, then T update! steps.  u [T, nu] / y [T, ny] shared, or [F, T, n] per filter (by ndim)."""
-        u, up, y, yp = self._io(u, y)
-        self._h.reset()
-        return self._h.run(u, y, up, yp)["ll"]
-
-    def forward(self, u, y, outputs=_capi.KALMAN_OUTPUTS):
-        """forward_trajectory of every filter: {"ll": [F], "ll_steps": [T, F], "x", "xt": [T, F, nx], "R", "Rt": [T, F, nx, nx],
-        "e": [T, F, ny]} for the names in `outputs`"""
-        u, up, y, yp = self._io(u, y)
-        self._h.reset()
-        return self._h.run(u, y, up, yp, outputs=outputs)
-
-    def smooth(self, u, y, outputs=_capi.KALMAN_SMOOTH_OUTPUTS, forward=()):
-        """smooth(kf_k, u, y) of every filter (reset, the forward pass, the RTS smoother on the device): {"ll": [F], "xT": [T, F, nx],
-        "RT": [T, F, nx, nx]} for the names in `outputs`, plus the forward outputs named in `forward` (as forward())"""
-        u, up, y, yp = self._io(u, y)
-        self._h.reset()
-        return self._h.smooth(u, y, up, yp, outputs=outputs, forward=forward)
 
 
 class MerweParams:
@@ -644,11 +652,12 @@ class UnscentedKalmanFilter:
         return update(self, u, y, p, t)
 
 
-class UnscentedKalmanFilterBank:
+class UnscentedKalmanFilterBank(_KfBank):
     """n independent unscented Kalman filters of the same model family and dimensions on one device, one GPU thread each
     (llpf_ukf_bank_*): the deterministic log-likelihood of every parameter set of a nonlinear sweep.  `filters_spec` is a list of
     UnscentedKalmanFilter or of (dynamics, measurement, R1, R2, d0) tuples; `weight_params` as UnscentedKalmanFilter takes them, one set
     for the bank."""
+    _AT_LOGLIK, _AT_FORWARD = {"t_index0": 1.0}, {"t_index0": 0.0}
 
     def __init__(self, filters_spec, device=0, weight_params=None, Ts=1.0):
         models = self._models(filters_spec, Ts)
@@ -680,36 +689,6 @@ class UnscentedKalmanFilterBank:
     def set_weights(self, weight_params):
         self.weights = _ukf_weights(weight_params, self._h.nx)
         self._h.set_weights(self.weights)
-
-    def reset(self):
-        self._h.reset()
-
-    def state(self):
-        """(x [F, nx], R [F, nx, nx]) of every filter"""
-        return self._h.get_state()
-
-    _io = KalmanFilterBank._io
-
-    def loglik(self, u, y):
-        """[loglik(ukf_k, u, y) for k]: reset, then T update! steps, the first at t = 1 * Ts as FilterBank.loglik.  u [T, nu] / y [T, ny]
-        shared, or [F, T, n] per filter (by ndim)."""
-        u, up, y, yp = self._io(u, y)
-        self._h.reset()
-        return self._h.run(u, y, up, yp, t_index0=1.0)["ll"]
-
-    def forward(self, u, y, outputs=_capi.KALMAN_OUTPUTS):
-        """forward_trajectory of every filter (the first step at t = 0): {"ll": [F], "ll_steps": [T, F], "x", "xt": [T, F, nx], "R", "Rt":
-        [T, F, nx, nx], "e": [T, F, ny]} for the names in `outputs`"""
-        u, up, y, yp = self._io(u, y)
-        self._h.reset()
-        return self._h.run(u, y, up, yp, outputs=outputs, t_index0=0.0)
-
-    def smooth(self, u, y, outputs=_capi.KALMAN_SMOOTH_OUTPUTS, forward=()):
-        """smooth(ukf_k, u, y) of every filter (reset, the forward pass of forward(), the unscented RTS smoother on the device): what
-        KalmanFilterBank.smooth returns"""
-        u, up, y, yp = self._io(u, y)
-        self._h.reset()
-        return self._h.smooth(u, y, up, yp, outputs=outputs, forward=forward, t_index0=0.0)
 
 
 class RBMeasurementModel:

@@ -94,6 +94,7 @@ static void test_throw(const char* site) {
 #include "host/mbank.hpp"
 #include "host/pipe.hpp"
 #include "host/simulate.hpp"
+#include "host/kfbank.hpp"
 #include "host/kalman.hpp"
 #include "host/ukf.hpp"
 
@@ -208,7 +209,7 @@ int llpf_bank_simulate(llpf_bank* b, int64_t M, int64_t T, const double* U, int3
     return bank_simulate(b->bank, M, T, U, u_per_trajectory, t_index0, seed, step0, flags, X, Y);
 } LLPF_GUARD(llpf_bank_simulate)
 
-// ---- banks of Kalman filters (host/kalman.hpp) ----
+// ---- banks of Kalman filters (host/kfbank.hpp, host/kalman.hpp) ----
 int llpf_kalman_bank_create(int32_t device, const llpf_model* models, const double* D, int32_t n_filters, llpf_kalman_bank** out) LLPF_TRY {
     if (!out) return fail(LLPF_ERR_ARG, "null out pointer");
     *out = nullptr;
@@ -219,7 +220,7 @@ int llpf_kalman_bank_create(int32_t device, const llpf_model* models, const doub
     return LLPF_OK;
 } LLPF_GUARD(llpf_kalman_bank_create)
 int llpf_kalman_bank_destroy(llpf_kalman_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_kalman_bank_destroy)
-int llpf_kalman_bank_reset(llpf_kalman_bank* b) LLPF_TRY { NEEDF(b); return kalman_reset(*b); } LLPF_GUARD(llpf_kalman_bank_reset)
+int llpf_kalman_bank_reset(llpf_kalman_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_kalman_bank_reset)
 int llpf_kalman_bank_set_models(llpf_kalman_bank* b, const llpf_model* models, const double* D) LLPF_TRY {
     NEEDF(b);
     return kalman_set_models(*b, models, D);
@@ -234,10 +235,10 @@ int llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double* 
     NEEDF(b);
     return kalman_smooth(*b, U, Y, T, per_filter, ll_total, forward, out);
 } LLPF_GUARD(llpf_kalman_bank_smooth)
-int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kalman_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
-int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kalman_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
+int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
+int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
 
-// ---- banks of unscented Kalman filters (host/ukf.hpp) ----
+// ---- banks of unscented Kalman filters (host/kfbank.hpp, host/ukf.hpp) ----
 int llpf_ukf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, const llpf_ukf_weights* w, llpf_ukf_bank** out) LLPF_TRY {
     if (!out) return fail(LLPF_ERR_ARG, "null out pointer");
     *out = nullptr;
@@ -248,7 +249,7 @@ int llpf_ukf_bank_create(int32_t device, const llpf_model* models, int32_t n_fil
     return LLPF_OK;
 } LLPF_GUARD(llpf_ukf_bank_create)
 int llpf_ukf_bank_destroy(llpf_ukf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_ukf_bank_destroy)
-int llpf_ukf_bank_reset(llpf_ukf_bank* b) LLPF_TRY { NEEDF(b); return ukf_reset(*b); } LLPF_GUARD(llpf_ukf_bank_reset)
+int llpf_ukf_bank_reset(llpf_ukf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_ukf_bank_reset)
 int llpf_ukf_bank_set_models(llpf_ukf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return ukf_set_models(*b, models); } LLPF_GUARD(llpf_ukf_bank_set_models)
 int llpf_ukf_bank_set_weights(llpf_ukf_bank* b, const llpf_ukf_weights* w) LLPF_TRY { NEEDF(b); return ukf_set_weights(*b, w); } LLPF_GUARD(llpf_ukf_bank_set_weights)
 int llpf_ukf_bank_run(llpf_ukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
@@ -261,8 +262,8 @@ int llpf_ukf_bank_smooth(llpf_ukf_bank* b, const double* U, const double* Y, int
     NEEDF(b);
     return ukf_smooth(*b, U, Y, T, per_filter, t_index0, ll_total, forward, out);
 } LLPF_GUARD(llpf_ukf_bank_smooth)
-int llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return ukf_get_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_get_state)
-int llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return ukf_set_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_set_state)
+int llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_get_state)
+int llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_set_state)
 
 int llpf_rb_get_covariance(llpf_filter* f, double* R) LLPF_TRY {
     NEEDF(f);

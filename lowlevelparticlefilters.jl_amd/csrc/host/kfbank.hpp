@@ -1,0 +1,229 @@
+// host/kfbank.hpp — what the banks of one-thread-per-filter Kalman filters share (host/kalman.hpp, host/ukf.hpp): the bank, its state, the
+// checks of a run's arguments and the drivers of the forward and the backward pass.  Part of capi.hip (one translation unit).
+// ------------------------------------------------------------------------------------------------
+// Device layout: the constants par [npar][F] (each bank's own rows) and the state [nx + np + 1][F] (x, packed R, the running ll_total of a
+// run), SoA so that lane f of a wave reads column f.  A run drives T through the chunked staging pipeline of host/pipe.hpp, counting a
+// step's outputs and per-filter inputs; outputs are time-major [T][F][width], per-filter inputs reach the device time-major as well.  The
+// state carries from chunk to chunk (and from run to run) in the device buffer, so the prefix of a long run is a short run and run(a)
+// followed by run(b) is run(a + b), bit for bit.  A run that asks for ll_total only stages nothing per step.
+// Nothing here knows which bank it serves: a bank gives its name (the prefix of its messages), its fault-injection sites and, per chunk,
+// a launcher that fills its kernel's own argument struct from a KfChunk / KfSmoothChunk.
+
+struct KfBank : BankStream {
+    const char* who;                  // "kalman" / "ukf": the prefix of every message
+    int F = 0, nx = 0, ny = 0, nu = 0;
+    int np = 0, npar = 0, nstate = 0;
+    DevBuf<double> d_par, d_state;
+    DevBuf<double> d_post;            // [T][nx + np][F] the posterior of every step of the last smooth (grow-only: kept between calls)
+    std::vector<double> h_init;       // [nstate][F] what reset loads: mean(d0), packed cov(d0), 0
+    explicit KfBank(const char* who_) : who(who_) {}
+};
+
+static int kf_fail(const char* who, const char* msg) { return fail(LLPF_ERR_ARG, std::string(who) + ": " + msg); }
+
+// the part of a pack that every filter of either bank needs: the checks of the three densities (`at`: the filter's message prefix), R1
+// and R2 as packed lower triangles into the rows of par from off_r1 / off_r2, mean(d0) and the packed cov(d0) into init
+static int kf_pack_filter(const llpf_model& m, const std::string& at, int f, int F, int nx, int ny, int off_r1, int off_r2,
+                          std::vector<double>& par, std::vector<double>& init) {
+    const llpf_gaussian* g[3] = {&m.dynamics_density, &m.measurement_density, &m.initial_density};
+    const int dims[3] = {nx, ny, nx};
+    for (int k = 0; k < 3; ++k) {
+        if (g[k]->dim != dims[k]) return fail(LLPF_ERR_ARG, at + "a density's dimension does not match the model");
+        if (g[k]->kind != LLPF_COV_SCAL && g[k]->kind != LLPF_COV_DIAG && g[k]->kind != LLPF_COV_FULL)
+            return fail(LLPF_ERR_ARG, at + "unknown covariance kind");
+    }
+    for (int k = 0; k < 2; ++k)
+        for (int i = 0; i < dims[k]; ++i)
+            if (g[k]->mu[i] != 0.0) return fail(LLPF_ERR_ARG, at + "the noise densities must have zero mean");
+    double S[MAXD * MAXD];
+    double* const row[3] = {par.data() + (size_t)off_r1 * F, par.data() + (size_t)off_r2 * F, init.data() + (size_t)nx * F};
+    for (int k = 0; k < 3; ++k) {
+        gauss_cov_dense(g[k], S);
+        for (int r = 0; r < dims[k]; ++r) for (int c = 0; c <= r; ++c) row[k][(size_t)llpf_kf_idx(r, c) * F + f] = S[r * dims[k] + c];
+    }
+    for (int i = 0; i < nx; ++i) init[(size_t)i * F + f] = m.initial_density.mu[i];
+    return LLPF_OK;
+}
+
+// the device, the dimensions (b.nx, ny, nu are the pack's) and the stream of a new bank; `site`: the bank's create site of test_throw
+static int kf_open(KfBank& b, int32_t device, int32_t F, int npar, const char* site) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(LLPF_ERR_NO_DEVICE, "no HIP device visible; this engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(LLPF_ERR_ARG, "device ordinal out of range");
+    test_throw(site);
+    b.F = F;
+    b.np = LLPF_KF_NP(b.nx);
+    b.npar = npar;
+    b.nstate = b.nx + b.np + 1;
+    b.device = device;
+    HIPC(hipSetDevice(device));
+    HIPC(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    return LLPF_OK;
+}
+
+static int kf_reset(KfBank& b) {
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+// x [F][nx], R [F][nx][nx] (either may be NULL) of the current state
+static int kf_get_state(KfBank& b, double* x, double* R) {
+    std::vector<double> h((size_t)b.nstate * b.F);
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(h.data(), b.d_state, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    const size_t F = (size_t)b.F;
+    for (size_t f = 0; f < F; ++f) {
+        if (x) for (int i = 0; i < b.nx; ++i) x[f * b.nx + i] = h[i * F + f];
+        if (R) for (int r = 0; r < b.nx; ++r) for (int c = 0; c < b.nx; ++c) R[(f * b.nx + r) * b.nx + c] = h[(b.nx + llpf_kf_idx(r, c)) * F + f];
+    }
+    return LLPF_OK;
+}
+
+// the lower triangle of R is taken (R is a covariance: the upper one is not read)
+static int kf_set_state(KfBank& b, const double* x, const double* R) {
+    if (!x || !R) return kf_fail(b.who, "x and R must both be given");
+    std::vector<double> h((size_t)b.nstate * b.F, 0.0);
+    const size_t F = (size_t)b.F;
+    for (size_t f = 0; f < F; ++f) {
+        for (int i = 0; i < b.nx; ++i) h[i * F + f] = x[f * b.nx + i];
+        for (int r = 0; r < b.nx; ++r) for (int c = 0; c <= r; ++c) h[(b.nx + llpf_kf_idx(r, c)) * F + f] = R[(f * b.nx + r) * b.nx + c];
+    }
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(b.d_state, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+// the checks of a run's arguments that need no device (run and smooth of either bank)
+static int kf_check_run(const KfBank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, const llpf_kalman_outputs* out) {
+    if (T < 1) return kf_fail(b.who, "T must be >= 1");
+    if (!Y) return kf_fail(b.who, "Y is null");
+    if (b.nu > 0 && !U) return kf_fail(b.who, "U is null");
+    if (per_filter & ~3) return kf_fail(b.who, "per_filter has bits other than 0 and 1");
+    if (out && out->struct_size < sizeof(llpf_kalman_outputs)) return kf_fail(b.who, "llpf_kalman_outputs.struct_size too small (ABI)");
+    return LLPF_OK;
+}
+
+// one chunk of the forward pass, as its launcher gets it: steps [t0, t0 + tc) of the run
+struct KfChunk {
+    const double *u, *y;      // the chunk's inputs on the device (u null: the model has none)
+    double* out[6];           // ... and where its outputs are staged, each null when not asked for: ll, x, xt, R, Rt, e
+    int64_t t0;
+    int32_t tc;
+    int32_t first;            // 1: the first chunk of the run
+    int32_t upf, ypf;         // 1: u / y is per filter
+    double* post;             // null, or where the posterior of the chunk's steps goes: [tc][nx + np][F]
+};
+
+// the forward pass of a run (arguments checked); post: null, or the device array [T][nx + np][F] that receives the posterior of every
+// step.  launch(const KfChunk&) fills the bank's kernel arguments and launches on b.stream (a status).  Everything is allocated before
+// the first launch.
+template <class Launch>
+static int kf_forward(KfBank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                      const llpf_kalman_outputs* out, double* post, Launch&& launch) {
+    const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu;
+    const bool upf = nu > 0 && (per_filter & 1), ypf = (per_filter & 2) != 0;
+    // the outputs of one step, in staging order: ll, x, xt, R, Rt, e
+    double* dst[6] = {out ? out->ll_steps : nullptr, out ? out->x : nullptr, out ? out->xt : nullptr, out ? out->R : nullptr,
+                      out ? out->Rt : nullptr, out ? out->e : nullptr};
+    const uint64_t width[6] = {1, (uint64_t)nx, (uint64_t)nx, (uint64_t)nx * nx, (uint64_t)nx * nx, (uint64_t)ny};
+    uint64_t w = 0;
+    std::vector<ChunkOut> outs;
+    for (int k = 0; k < 6; ++k) {
+        if (dst[k]) w += width[k];
+        outs.push_back({dst[k], 1, (size_t)F * width[k]});
+    }
+    const uint64_t in_w = (upf ? (uint64_t)nu : 0) + (ypf ? (uint64_t)ny : 0);
+    uint64_t total = 0, in_total = 0;      // the per-step outputs / per-filter inputs of all filters and steps, in doubles
+    if (!doubles_fit({(uint64_t)F, w, (uint64_t)T}, total) || !doubles_fit({(uint64_t)F, in_w, (uint64_t)T}, in_total))
+        return kf_fail(b.who, "the size of the outputs or of the inputs overflows");
+    HIPC(hipSetDevice(b.device));
+    ChunkPipe pipe(b.stream);
+    // (shared inputs and no per-step outputs: nothing per step scales with F, the chunk is CHUNK_STEPS)
+    CHK(pipe.open(T, (size_t)F * (w + in_w) * sizeof(double), outs,
+                  {{nu > 0 ? U : nullptr, upf ? (size_t)F : 0, (size_t)nu, true}, {Y, ypf ? (size_t)F : 0, (size_t)ny, true}}));
+    for (int64_t c = 0; c < pipe.nchunk; ++c) {
+        CHK(pipe.begin(c, c));
+        KfChunk ch{};
+        ch.u = pipe.in(0);
+        ch.y = pipe.in(1);
+        for (int k = 0; k < 6; ++k) ch.out[k] = pipe.out(k);
+        ch.t0 = pipe.t0; ch.tc = (int32_t)pipe.tc;
+        ch.first = c == 0 ? 1 : 0;
+        ch.upf = upf ? 1 : 0; ch.ypf = ypf ? 1 : 0;
+        ch.post = post ? post + (size_t)pipe.t0 * (nx + b.np) * F : nullptr;
+        CHK(launch(ch));
+        CHK(pipe.end());
+    }
+    CHK(pipe.finish());
+    if (ll_total)     // the running sum: row nx + np of the state
+        HIPC(hipMemcpyAsync(ll_total, b.d_state.p + (size_t)(nx + b.np) * F, sizeof(double) * F, hipMemcpyDeviceToHost, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+// one chunk of the backward pass, as its launcher gets it: steps [t0, t0 + tc), run from the last down
+struct KfSmoothChunk {
+    const double* post;       // [tc][nx + np][F] the posterior of the chunk's steps
+    double* carry;            // [nx + np][F] xT, packed RT between the chunks
+    const double* u;          // the chunk's inputs on the device (null: the model has none)
+    double *xT, *RT;          // where its outputs are staged, each null when not asked for
+    int64_t t0;
+    int32_t tc;
+    int32_t upf;              // 1: u is per filter
+    int32_t init;             // 1: the chunk holds the run's last step
+};
+
+// smooth(f, u, y) of every filter (the run's arguments checked): the forward pass of a run (the same chunks, outputs and state) that also
+// stores the packed posterior of every step on the device (d_post: (nx + np) * 8 bytes per filter-step), then the backward pass over the
+// chunks in reverse through a staging pipeline of its own (host/pipe.hpp).  `site`: the bank's smooth site of test_throw; prepare():
+// what the bank's kernels need before their first launch (a status); forward(post): the bank's kf_forward; launch(const KfSmoothChunk&):
+// as kf_forward's.  Everything is allocated before the first launch, so a call that cannot get its memory leaves the state as it was.
+// The state after the call is the one a run leaves (the prior of step T and the running ll).
+template <class Prepare, class Forward, class Launch>
+static int kf_smooth(KfBank& b, const double* U, int64_t T, int32_t per_filter, const llpf_kalman_smooth_outputs* out, const char* site,
+                     Prepare&& prepare, Forward&& forward, Launch&& launch) {
+    if (out && out->struct_size < sizeof(llpf_kalman_smooth_outputs))
+        return kf_fail(b.who, "llpf_kalman_smooth_outputs.struct_size too small (ABI)");
+    const int F = b.F, nx = b.nx, nu = b.nu, ns = nx + b.np;
+    const bool upf = nu > 0 && (per_filter & 1);
+    double* dst[2] = {out ? out->xT : nullptr, out ? out->RT : nullptr};
+    const uint64_t width[2] = {(uint64_t)nx, (uint64_t)nx * nx};
+    const uint64_t w = (dst[0] ? width[0] : 0) + (dst[1] ? width[1] : 0);
+    uint64_t post_d = 0, total = 0;
+    if (!doubles_fit({(uint64_t)ns, (uint64_t)F, (uint64_t)T}, post_d) || !doubles_fit({(uint64_t)F, w, (uint64_t)T}, total))
+        return kf_fail(b.who, "the size of the stored posterior or of the smoothed outputs overflows");
+    test_throw(site);
+    if (!w) return forward(nullptr);     // nothing smoothed is asked for: a run
+    HIPC(hipSetDevice(b.device));
+    CHK(prepare());
+    CHK(b.d_post.ensure((size_t)post_d));
+    ChunkPipe pipe(b.stream);
+    double* d_carry = nullptr;
+    CHK(pipe.device((size_t)ns * F, d_carry));
+    CHK(pipe.open(T, (size_t)F * (w + (upf ? nu : 0)) * sizeof(double), {{dst[0], 1, (size_t)F * width[0]}, {dst[1], 1, (size_t)F * width[1]}},
+                  {{nu > 0 ? U : nullptr, upf ? (size_t)F : 0, (size_t)nu, true}}));
+    // the forward pass allocates its own staging before its first launch: no launch has run when it returns an allocation failure
+    CHK(forward(b.d_post.p));
+    for (int64_t i = 0; i < pipe.nchunk; ++i) {      // backward: launch i runs chunk nchunk - 1 - i
+        CHK(pipe.begin(i, pipe.nchunk - 1 - i));
+        KfSmoothChunk ch{};
+        ch.post = b.d_post.p + (size_t)pipe.t0 * ns * F;
+        ch.carry = d_carry;
+        ch.u = pipe.in(0);
+        ch.xT = pipe.out(0);
+        ch.RT = pipe.out(1);
+        ch.t0 = pipe.t0; ch.tc = (int32_t)pipe.tc;
+        ch.upf = upf ? 1 : 0;
+        ch.init = i == 0 ? 1 : 0;
+        CHK(launch(ch));
+        CHK(pipe.end());
+    }
+    CHK(pipe.finish());
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}

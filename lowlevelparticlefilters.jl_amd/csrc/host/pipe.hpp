@@ -1,5 +1,6 @@
-// host/pipe.hpp — the chunked staging pipeline of the batch verbs (simulate, Kalman run, Kalman smooth).  Part of capi.hip (one
-// translation unit).
+// host/pipe.hpp — the chunked staging pipeline of the batch verbs.  Part of capi.hip (one translation unit).  Its callers: bank_simulate
+// (host/simulate.hpp: llpf_simulate, llpf_bank_simulate), and kf_forward and kf_smooth (host/kfbank.hpp: the run and the smooth of the
+// Kalman banks, host/kalman.hpp, and of the unscented banks, host/ukf.hpp).
 // ------------------------------------------------------------------------------------------------
 // The T steps of a call are driven in chunks so that device and pinned memory stay bounded whatever T is: a chunk is
 // Tc = min(T, 256, max(1, 64 MiB / bytes the caller counts per step)) steps.  Launch i runs its chunk into device staging buffer i % 2; a

@@ -1,4 +1,6 @@
 """Shared helpers of the GPU parity tests."""
+import os
+
 import numpy as np
 
 from llpf_amd import _structs as S
@@ -10,6 +12,19 @@ TOL_WE_REL = 1e-12       # max relative error of exp-weights vs reference order
 
 def cfg_of(model, N, strategy=S.RESAMPLE_SYSTEMATIC, thr=0.1, seed=7, kind=S.PARTICLE_FILTER):
     return S.make_config(model, N, kind, strategy, thr, seed, 0)
+
+
+class _Inject:
+    """with _Inject("<kind>:<site>"): the library's fault injection (LLPF_TEST_THROW) for the calls inside"""
+
+    def __init__(self, spec):
+        self.spec = spec
+
+    def __enter__(self):
+        os.environ["LLPF_TEST_THROW"] = self.spec      # os.environ assigns through putenv: the library's getenv sees it
+
+    def __exit__(self, *a):
+        del os.environ["LLPF_TEST_THROW"]
 
 
 def _bits(a):

@@ -157,3 +157,23 @@ def bits_equal(a, b):
     a[np.isnan(a)] = np.nan
     b[np.isnan(b)] = np.nan
     return np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+# ------------------------------------------------------------------------------------------------
+# helpers of the GPU tests of the Kalman and the unscented banks
+# ------------------------------------------------------------------------------------------------
+OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+
+
+def _data(rng, T, nu, ny, missing=()):
+    """shared inputs U [T, nu] and measurements Y [T, ny], the first output missing (NaN) at the steps `missing`"""
+    U = rng.standard_normal((T, nu))
+    Y = 2.0 * rng.standard_normal((T, ny))
+    for t in missing:
+        Y[t, 0] = np.nan
+    return U, Y
+
+
+def _same(g, h, keys=OUTS + ("ll",), what=""):
+    for k in keys:
+        assert bits_equal(g[k], h[k]), (what, k)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from llpf_amd import _capi, _structs as S
+from gpu_common import _Inject
 import models as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,19 +80,8 @@ def test_device_resources_are_owned():
             assert word not in src, (name, word)
         for line in src.splitlines():
             if "hipStreamCreateWithFlags(" in line:
-                assert name in ("host/bank.hpp", "host/kalman.hpp") and "(&b.stream, hipStreamNonBlocking)" in line, (name, line)
+                assert name in ("host/bank.hpp", "host/kfbank.hpp") and "(&b.stream, hipStreamNonBlocking)" in line, (name, line)
     assert sum(src.count("hipStreamCreateWithFlags(") for src in srcs.values()) == 2
-
-
-class _Inject:
-    def __init__(self, spec):
-        self.spec = spec
-
-    def __enter__(self):
-        os.environ["LLPF_TEST_THROW"] = self.spec      # os.environ assigns through putenv: the library's getenv sees it
-
-    def __exit__(self, *a):
-        del os.environ["LLPF_TEST_THROW"]
 
 
 @pytest.mark.parametrize("kind,code,needle", [("alloc", _capi.ERR_ALLOC, b"out of host memory"),

@@ -1,14 +1,18 @@
 """Banks of Kalman filters on the device (llpf_kalman_bank_*; kernels/kalman.hpp, host/kalman.hpp): the GPU reproduces the host build
 of csrc/shared/llpf_kalman.h bit for bit, whatever the shape, the bank, the chunking of T or the split of a run; and the Python API
 (KalmanFilter, KalmanFilterBank) computes the reference's Kalman filter."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import llpf_amd
-from llpf_amd import _capi
+from llpf_amd import _capi, _structs as S
 import kalman_common as kc
+from kalman_common import _data, _same
 import models as M
 import oracle_binding as ob
+import ukf_common as uc
 
 pytestmark = pytest.mark.gpu
 OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
@@ -21,19 +25,6 @@ def host(tmp_path_factory):
 
 def _bank(systems):
     return _capi.KalmanBankHandle(0, [m for m, _ in systems], np.stack([D for _, D in systems]))
-
-
-def _data(rng, T, nu, ny, missing=()):
-    U = rng.standard_normal((T, nu))
-    Y = 2.0 * rng.standard_normal((T, ny))
-    for t in missing:
-        Y[t, 0] = np.nan
-    return U, Y
-
-
-def _same(g, h, keys=OUTS, what=""):
-    for k in keys:
-        assert kc.bits_equal(g[k], h[k]), (what, k)
 
 
 @pytest.mark.parametrize("nx", range(1, 9))
@@ -153,6 +144,52 @@ def test_missing_rows_and_a_filter_that_loses_definiteness(host):
         assert kc.bits_equal(bad[k][:, keep], ok[k][:, keep]), k
     h, _ = kc.host_run(host, systems, None, Y, 40, state=(x, R))
     _same(bad, h, OUTS + ("ll",), "NaN filter")
+
+
+@pytest.mark.parametrize("verb", ["run", "smooth"])
+@pytest.mark.parametrize("kind", ["kalman", "ukf"])
+def test_bad_run_arguments_on_a_live_handle_are_refused_and_leave_it_as_it_was(kind, verb):
+    """llpf_{kalman,ukf}_bank_{run,smooth} on a bank that has run (linear-Gaussian, F = 65: one full workgroup of 64 and a ragged one;
+    nx = 2, ny = 1, nu = 1, T = 3): T = 0, Y null, U null with nu > 0, per_filter = 4, a forward struct_size one byte short and, for the
+    unscented bank, t_index0 = inf and nan are each LLPF_ERR_ARG under the bank's own prefix; the state keeps its bits, and the run that
+    follows is the run of a bank that never saw them."""
+    F, T = 65, 3
+    rng = np.random.default_rng(11)
+    systems = [kc.random_system(rng, 2, 1, 1, k % 3, D=kind == "kalman") for k in range(F)]
+    U, Y = _data(rng, T, 1, 1)
+
+    def bank():
+        return _bank(systems) if kind == "kalman" else _capi.UkfBankHandle(0, [m for m, _ in systems], uc.merwe(2, 1.0, 0.0, 1.0))
+
+    fresh = bank()
+    fresh.run(U, Y)
+    ref = fresh.run(U, Y, outputs=OUTS)
+    b = bank()
+    b.run(U, Y)
+    x0, R0 = b.get_state()
+    L = _capi.lib()
+    fn = getattr(L, "llpf_%s_bank_%s" % (kind, verb))
+    ll, xT = np.empty(F), np.empty((T, F, 2))
+    sm = S.KalmanSmoothOutputs()
+    sm.struct_size = C.sizeof(S.KalmanSmoothOutputs)
+    sm.xT = _capi.dptr(xT)
+    short = S.KalmanOutputs()
+    short.struct_size = C.sizeof(S.KalmanOutputs) - 1
+
+    def call(U=U, Y=Y, T=T, per_filter=0, t_index0=0.0, fwd=None):
+        times = (t_index0,) if kind == "ukf" else ()
+        tail = (None if fwd is None else C.byref(fwd),) + ((C.byref(sm),) if verb == "smooth" else ())
+        return fn(b.h, _capi.dptr(U), _capi.dptr(Y), T, per_filter, *times, _capi.dptr(ll), *tail)
+
+    cases = [dict(T=0), dict(Y=None), dict(U=None), dict(per_filter=4), dict(fwd=short)]
+    if kind == "ukf":
+        cases += [dict(t_index0=np.inf), dict(t_index0=np.nan)]
+    for case in cases:
+        assert call(**case) == _capi.ERR_ARG, case
+        assert L.llpf_last_error().startswith(kind.encode() + b": "), (case, L.llpf_last_error())
+        x, R = b.get_state()
+        assert kc.bits_equal(x, x0) and kc.bits_equal(R, R0), case
+    _same(b.run(U, Y, outputs=OUTS), ref, what="after the refused calls")
 
 
 def test_python_api():

@@ -3,14 +3,15 @@ host/kalman.hpp): the GPU reproduces the host build of csrc/shared/llpf_kalman.h
 whatever the shape, the bank or the chunking; the handle's state after a smooth is the state after a run; and the Python API
 (smooth(kf, u, y), KalmanFilterBank.smooth) computes the reference's smoother."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import llpf_amd
 from llpf_amd import _capi, _structs as S
+from gpu_common import _Inject
 import kalman_common as kc
+from kalman_common import _data, _same
 import kalman_smooth_common as ks
 import models as M
 
@@ -31,19 +32,6 @@ def hsmooth(tmp_path_factory):
 
 def _bank(systems):
     return _capi.KalmanBankHandle(0, [m for m, _ in systems], np.stack([D for _, D in systems]))
-
-
-def _data(rng, T, nu, ny, missing=()):
-    U = rng.standard_normal((T, nu))
-    Y = 2.0 * rng.standard_normal((T, ny))
-    for t in missing:
-        Y[t, 0] = np.nan
-    return U, Y
-
-
-def _same(g, h, keys, what=""):
-    for k in keys:
-        assert kc.bits_equal(g[k], h[k]), (what, k)
 
 
 @pytest.mark.parametrize("nx", range(1, 9))
@@ -222,17 +210,6 @@ def test_from_filter_bank_smooths_like_each_filter():
         kf = llpf_amd.KalmanFilter(mt["A"], mt["B"], mt["C"], 0.0, mt["R1"], mt["R2"], llpf_amd.MvNormal(mt["x0"], mt["P0"]), Ts=model.Ts)
         s = llpf_amd.smooth(kf, U, Y)
         assert kc.bits_equal(r["xT"][:, j], s.xT) and kc.bits_equal(r["RT"][:, j], s.RT) and r["ll"][j] == s.ll, j
-
-
-class _Inject:
-    def __init__(self, spec):
-        self.spec = spec
-
-    def __enter__(self):
-        os.environ["LLPF_TEST_THROW"] = self.spec
-
-    def __exit__(self, *a):
-        del os.environ["LLPF_TEST_THROW"]
 
 
 def test_a_throw_and_a_refused_allocation_leave_a_usable_handle():

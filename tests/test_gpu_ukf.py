@@ -8,6 +8,7 @@ import pytest
 import llpf_amd
 from llpf_amd import _capi, _structs as S
 import kalman_common as kc
+from kalman_common import _data, _same
 import models as M
 import ukf_common as uc
 import user_models as UM
@@ -24,19 +25,6 @@ def host(tmp_path_factory):
 
 def _bank(models, w):
     return _capi.UkfBankHandle(0, list(models), w)
-
-
-def _data(rng, T, nu, ny, missing=()):
-    U = rng.standard_normal((T, nu))
-    Y = 2.0 * rng.standard_normal((T, ny))
-    for t in missing:
-        Y[t, 0] = np.nan
-    return U, Y
-
-
-def _same(g, h, keys=OUTS + ("ll",), what=""):
-    for k in keys:
-        assert kc.bits_equal(g[k], h[k]), (what, k)
 
 
 def _with_id(m, model_id):

@@ -4,19 +4,20 @@ functions) bit for bit in every output — smoothed and forward, precompiled and
 of T or the split of a run — the state after a smooth is the state after a run, and the Python API is the smoother the CPU tests pin
 down."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import llpf_amd
 from llpf_amd import _capi, _structs as S
+from gpu_common import _Inject
 import kalman_common as kc
 import models as M
 import ukf_common as uc
 import ukf_smooth_common as us
 import user_models as UM
-from test_gpu_ukf import OUTS, W1, _bank, _data, _lg_models, _quadtank_models, _quadtank_specs, _same, _with_id
+from kalman_common import _data, _same
+from test_gpu_ukf import OUTS, W1, _bank, _lg_models, _quadtank_models, _quadtank_specs, _with_id
 
 pytestmark = pytest.mark.gpu
 SOUTS = ("xT", "RT")
@@ -253,17 +254,6 @@ def test_a_filters_bits_do_not_depend_on_the_bank_and_nan_stays_home(host, hsmoo
         assert kc.bits_equal(bad[k][:, keep], ok[k][:, keep]), k
     hb, _ = _host(host, hsmooth, models, W1, U, Y, 40, per_filter=3, state=(x, R))
     _same(bad, hb, ALL, what="NaN filter")
-
-
-class _Inject:
-    def __init__(self, spec):
-        self.spec = spec
-
-    def __enter__(self):
-        os.environ["LLPF_TEST_THROW"] = self.spec
-
-    def __exit__(self, *a):
-        del os.environ["LLPF_TEST_THROW"]
 
 
 def test_a_throw_and_a_refused_allocation_leave_a_usable_handle():

@@ -260,8 +260,10 @@ def test_the_symbol_is_declared_exported_bound_and_guarded():
     ma, mi = C.c_int32(), C.c_int32()
     L.llpf_version(C.byref(ma), C.byref(mi))
     assert (ma.value, mi.value) == (0, 7)
-    # the fault-injection site of the call
-    assert 'test_throw("ukf_smooth")' in open(os.path.join(ROOT, "lowlevelparticlefilters.jl_amd", "csrc", "host", "ukf.hpp")).read()
+    # the fault-injection site of the call: ukf_smooth names it, kf_smooth (host/kfbank.hpp) reads it
+    host = os.path.join(ROOT, "lowlevelparticlefilters.jl_amd", "csrc", "host")
+    assert 'out, "ukf_smooth",' in open(os.path.join(host, "ukf.hpp")).read()
+    assert "test_throw(site);\n    if (!w) return forward(nullptr);" in open(os.path.join(host, "kfbank.hpp")).read()
 
 
 def test_julia_ccall_has_the_prototypes_arity():
