@@ -286,7 +286,8 @@ int  llpf_model_compile(const char* device_src, int32_t nx, int32_t ny, int32_t*
  *       one draw of the initial density: x_i = rand(rng, initial_density) of reset! / the constructor (src/filtering.jl:4-14, src/PFtypes.jl:66).
  * llpf_model_traits reports which optional members a compiled model has (bit set of LLPF_TRAIT_*), so that a binding can refuse a
  * UserLikelihood paired with a snippet without `loglik`, or a Gaussian likelihood paired with a snippet that defines one. */
-enum { LLPF_TRAIT_LOGLIK = 1, LLPF_TRAIT_LOGLIK_BOUND = 2, LLPF_TRAIT_NOISE = 4, LLPF_TRAIT_INITIAL = 8 };
+enum { LLPF_TRAIT_LOGLIK = 1, LLPF_TRAIT_LOGLIK_BOUND = 2, LLPF_TRAIT_NOISE = 4, LLPF_TRAIT_INITIAL = 8,
+       LLPF_TRAIT_DYNAMICS_JAC = 16, LLPF_TRAIT_MEASUREMENT_JAC = 32 };
 int  llpf_model_traits(int32_t model_id, int32_t* traits);
 
 /* ---- accessors (reference src/PFtypes.jl:296-334) --------------------------------------- */
@@ -458,6 +459,32 @@ int  llpf_ukf_bank_smooth(llpf_ukf_bank* b, const double* U, const double* Y, in
 /* state, covariance of every filter: x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
 int  llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R);
 int  llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R);
+
+/* ---- banks of extended Kalman filters (the reference's ExtendedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise) -------
+ * n_filters independent first-order extended Kalman filters, one GPU thread each, in the operation order of csrc/shared/llpf_ekf.h (that
+ * header is the definition: a host build of it around the same model functions gives the same bits):
+ *   x' = f(x, u, p, tau) + w, w ~ N(0, R1);  y = g(x, u, p, tau) + e, e ~ N(0, R2);  x_0 ~ d0;  correct! linearises g at the prior mean,
+ *   predict! linearises f at the posterior mean — one evaluation of the model and its Jacobian per stage.
+ * The descriptors, the dimensions and the refusals are those of llpf_ukf_bank_create.  The model supplies its Jacobians through the two
+ * optional members dynamics_jac(x, fx, J) and measurement_jac(x, gx, J) (J[r * nx + c] = d out_r / d x_c, the value from the same
+ * evaluation): the built-in models have them; a model of llpf_model_compile without either (llpf_model_traits:
+ * LLPF_TRAIT_DYNAMICS_JAC, LLPF_TRAIT_MEASUREMENT_JAC) is refused with LLPF_ERR_ARG.  A filter whose S = C R C' + R2 loses definiteness
+ * is NaN from that step on; the run returns LLPF_OK and the other filters are unaffected.  Steps, missing rows, outputs and the carried
+ * state are those of llpf_kalman_bank_run; step t evaluates the model at tau = (t_index0 + t) * Ts as llpf_run does. */
+typedef struct llpf_ekf_bank llpf_ekf_bank;
+int  llpf_ekf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, llpf_ekf_bank** out);
+int  llpf_ekf_bank_destroy(llpf_ekf_bank* b);
+/* reset!: x = mean(d0), R = cov(d0) */
+int  llpf_ekf_bank_reset(llpf_ekf_bank* b);
+/* new parameters for every filter (same model id and dimensions, nothing reallocated; the state is left as it is, the next reset uses the
+ * new d0) */
+int  llpf_ekf_bank_set_models(llpf_ekf_bank* b, const llpf_model* models);
+/* T steps of every filter; U, Y, per_filter, ll_total and out as llpf_kalman_bank_run takes them */
+int  llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                       double* ll_total, const llpf_kalman_outputs* out);
+/* state, covariance of every filter: x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
+int  llpf_ekf_bank_get_state(llpf_ekf_bank* b, double* x, double* R);
+int  llpf_ekf_bank_set_state(llpf_ekf_bank* b, const double* x, const double* R);
 
 /* ---- sweeps sharded over the GPUs of one node (multi-GPU banks) ------------------------------
  * The same sweep as llpf_bank_*, with filter k on shard k mod n_shards (one shard = one GPU, one stream): the reference's

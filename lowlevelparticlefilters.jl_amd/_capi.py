@@ -56,6 +56,13 @@ SYMBOLS = {
     "llpf_ukf_bank_smooth": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs), C.POINTER(S.KalmanSmoothOutputs)],
     "llpf_ukf_bank_get_state": [_vp, _dp, _dp],
     "llpf_ukf_bank_set_state": [_vp, _dp, _dp],
+    "llpf_ekf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.POINTER(_vp)],
+    "llpf_ekf_bank_destroy": [_vp],
+    "llpf_ekf_bank_reset": [_vp],
+    "llpf_ekf_bank_set_models": [_vp, C.POINTER(S.Model)],
+    "llpf_ekf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_ekf_bank_get_state": [_vp, _dp, _dp],
+    "llpf_ekf_bank_set_state": [_vp, _dp, _dp],
     "llpf_num_particles": [_vp, _ip],
     "llpf_index": [_vp, _ip],
     "llpf_get_particles": [_vp, _dp],
@@ -626,6 +633,22 @@ class UkfBankHandle(_KfBankHandle):
         return self._smooth(U, Y, u_per_filter, y_per_filter, outputs, forward, float(t_index0))
 
 
+class EkfBankHandle(_KfBankHandle):
+    """RAII wrapper of an `llpf_ekf_bank*` (independent extended Kalman filters on one device)."""
+    _SYM = "llpf_ekf_bank"
+
+    def __init__(self, device, models):
+        arr = self._open(models)
+        check(self.L.llpf_ekf_bank_create(int(device), arr, self.F, C.byref(self.h)))
+
+    def set_models(self, models):
+        self._call("set_models", (S.Model * self.F)(*models))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
+        """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""
+        return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
+
+
 class BankHandle:
     """RAII wrapper of an `llpf_bank*` (many independent filters on one device)."""
 
@@ -863,10 +886,11 @@ def model_compile(device_src, nx, ny):
 
 
 TRAIT_LOGLIK, TRAIT_LOGLIK_BOUND, TRAIT_NOISE, TRAIT_INITIAL = 1, 2, 4, 8
+TRAIT_DYNAMICS_JAC, TRAIT_MEASUREMENT_JAC = 16, 32
 
 
 def model_traits(model_id):
-    """llpf_model_traits: which optional members (loglik, loglik_bound, noise, initial) a compiled model has, as TRAIT_* bits"""
+    """llpf_model_traits: which optional members (loglik, loglik_bound, noise, initial, dynamics_jac, measurement_jac) a compiled model has, as TRAIT_* bits"""
     t = C.c_int32(0)
     check(lib().llpf_model_traits(int(model_id), C.byref(t)))
     return t.value

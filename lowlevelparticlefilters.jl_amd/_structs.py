@@ -9,6 +9,7 @@ MAX_INPUTS = 8       # inputs (LLPF_MAX_INPUTS)
 
 COV_SCAL, COV_DIAG, COV_FULL = 0, 1, 2
 MODEL_LINEAR_GAUSSIAN, MODEL_QUADTANK_RK4, MODEL_RB_LINEAR, MODEL_RB_BILINEAR = 0, 1, 2, 3
+MODEL_USER_BASE = 1000      # ids of llpf_model_compile start here
 RESAMPLE_SYSTEMATIC, RESAMPLE_STRATIFIED, RESAMPLE_RESIDUAL = 0, 1, 2
 PARTICLE_FILTER, ADVANCED_PARTICLE_FILTER = 0, 1
 

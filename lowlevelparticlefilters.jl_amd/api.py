@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -219,7 +219,7 @@ def _is_plain_callable(f):
     return callable(f) and not isinstance(f, _DESCRIPTORS)
 
 
-def _trace_callables(dyn, meas, mlik, nx, nu, ny, p, likelihood_bound=None):
+def _trace_callables(dyn, meas, mlik, nx, nu, ny, p, likelihood_bound=None, jacobians=False):
     """The reference's constructors take closures (src/PFtypes.jl:59-63, 189-193).  Plain Python callables with the reference's signatures
     — dynamics(x, u, p, t), measurement(x, u, p, t), measurement_likelihood(x, u, y, p, t) — are traced once (tracing.py) and emitted
     as the device snippet; returns the (UserDynamics, UserMeasurement, UserLikelihood | None) descriptors that stand for them."""
@@ -229,7 +229,7 @@ def _trace_callables(dyn, meas, mlik, nx, nu, ny, p, likelihood_bound=None):
     if nu < 0:
         raise ValueError("pass nu= (the number of inputs) with callable dynamics: it cannot be read off a closure")
     d = tracing.traced_dynamics(dyn, nx, nu, p=p, measurement=meas, ny=ny, measurement_likelihood=mlik if _is_plain_callable(mlik) else None,
-                                loglik_bound=likelihood_bound)
+                                loglik_bound=likelihood_bound, jacobians=jacobians)
     return d, d.measurement_model, d.likelihood_model
 
 
@@ -444,12 +444,12 @@ class KalmanSmoothingSolution(KalmanFilteringSolution):
 
 
 def covariance(kf):
-    """covariance(kf) — the covariance R of the current estimate of a KalmanFilter or an UnscentedKalmanFilter"""
+    """covariance(kf) — the covariance R of the current estimate of a KalmanFilter, an UnscentedKalmanFilter or an ExtendedKalmanFilter"""
     return kf.R
 
 
 class _KfBank:
-    """What KalmanFilterBank and UnscentedKalmanFilterBank share: a bank handle `_h` of one GPU thread per filter.  `_AT_LOGLIK` and
+    """What KalmanFilterBank, UnscentedKalmanFilterBank and ExtendedKalmanFilterBank share: a bank handle `_h` of one GPU thread per filter.  `_AT_LOGLIK` and
     `_AT_FORWARD` are the keyword arguments the handle's run / smooth take for the time of the first step."""
     _AT_LOGLIK = _AT_FORWARD = {}
 
@@ -579,23 +579,19 @@ def _ukf_weights(weight_params, L):
     return w
 
 
-class UnscentedKalmanFilter:
-    """UnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts, nu, ny, p, weight_params, device) — the reference's unscented Kalman
-    filter with additive noise: x' = f(x, u, p, t) + w, w ~ N(0, R1);  y = g(x, u, p, t) + e, e ~ N(0, R2);  x_0 ~ d0 (csrc/shared/llpf_ukf.h
-    is the definition).  `dynamics` / `measurement` are what a ParticleFilter takes: LinearDynamics + LinearMeasurement, QuadTankDynamics +
-    QuadTankMeasurement, UserDynamics + UserMeasurement, or a pair of plain callables (traced: tracing.py; pass nu=, and ny= unless R2 is
-    a matrix).  R1, R2: matrices (a 1-D array: the diagonal; a float: sigma^2 I); d0: MvNormal.  weight_params: MerweParams, WikiParams,
-    TrivialParams (the default) or the four numbers (gamma, wm0, wc0, wi).  Runs on the device as a bank of one filter (llpf_ukf_bank_*),
-    created on first use.  nx <= 8, ny <= 4, nu <= 8."""
+class _NonlinearKalmanFilter:
+    """What UnscentedKalmanFilter and ExtendedKalmanFilter share: the model descriptor of (dynamics, measurement, R1, R2, d0) and a bank of
+    one filter on the device, created on first use by `_open()`.  `_JACOBIANS`: plain callables are traced with their Jacobians."""
+    _JACOBIANS = False
 
-    def __init__(self, dynamics, measurement, R1, R2, d0, *, Ts=1.0, nu=-1, ny=-1, p=None, weight_params=None, device=0):
+    def _setup(self, dynamics, measurement, R1, R2, d0, Ts, nu, ny, p, device):
         nx = len(d0)
         if ny < 0 and np.ndim(R2) >= 1:
             ny = np.asarray(R2).shape[0]
         if _is_plain_callable(dynamics):
             if ny < 0:
                 raise ValueError("pass ny= with callable dynamics and a scalar R2")
-            dynamics, measurement, _ = _trace_callables(dynamics, measurement, None, nx, nu, ny, p)
+            dynamics, measurement, _ = _trace_callables(dynamics, measurement, None, nx, nu, ny, p, jacobians=self._JACOBIANS)
         if isinstance(dynamics, UserDynamics):
             ny = dynamics.ny
         elif isinstance(measurement, LinearMeasurement):
@@ -608,25 +604,23 @@ class UnscentedKalmanFilter:
         self.p, self.Ts, self.device = p, float(Ts), int(device)
         self._model = _build_model(dynamics, measurement, self.dynamics_density, self.measurement_density, d0, Ts)
         self.nx, self.nu, self.ny = self._model.nx, self._model.nu, self._model.ny
-        self.weight_params = weight_params
-        self.weights = _ukf_weights(weight_params, self.nx)
         self._handle = None
         self._index = 0
 
     @property
     def _h(self):
         if self._handle is None:
-            self._handle = _capi.UkfBankHandle(self.device, [self._model], self.weights)
+            self._handle = self._open()
         return self._handle
 
     @property
     def x(self):
-        """state(ukf): the current estimate"""
+        """state(kf): the current estimate"""
         return self._h.get_state()[0][0]
 
     @property
     def R(self):
-        """covariance(ukf)"""
+        """covariance(kf)"""
         return self._h.get_state()[1][0]
 
     def reset(self):
@@ -650,6 +644,53 @@ class UnscentedKalmanFilter:
 
     def __call__(self, u, y, p=None, t=None):
         return update(self, u, y, p, t)
+
+
+class UnscentedKalmanFilter(_NonlinearKalmanFilter):
+    """UnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts, nu, ny, p, weight_params, device) — the reference's unscented Kalman
+    filter with additive noise: x' = f(x, u, p, t) + w, w ~ N(0, R1);  y = g(x, u, p, t) + e, e ~ N(0, R2);  x_0 ~ d0 (csrc/shared/llpf_ukf.h
+    is the definition).  `dynamics` / `measurement` are what a ParticleFilter takes: LinearDynamics + LinearMeasurement, QuadTankDynamics +
+    QuadTankMeasurement, UserDynamics + UserMeasurement, or a pair of plain callables (traced: tracing.py; pass nu=, and ny= unless R2 is
+    a matrix).  R1, R2: matrices (a 1-D array: the diagonal; a float: sigma^2 I); d0: MvNormal.  weight_params: MerweParams, WikiParams,
+    TrivialParams (the default) or the four numbers (gamma, wm0, wc0, wi).  Runs on the device as a bank of one filter (llpf_ukf_bank_*),
+    created on first use.  nx <= 8, ny <= 4, nu <= 8."""
+
+    def __init__(self, dynamics, measurement, R1, R2, d0, *, Ts=1.0, nu=-1, ny=-1, p=None, weight_params=None, device=0):
+        self._setup(dynamics, measurement, R1, R2, d0, Ts, nu, ny, p, device)
+        self.weight_params = weight_params
+        self.weights = _ukf_weights(weight_params, self.nx)
+
+    def _open(self):
+        return _capi.UkfBankHandle(self.device, [self._model], self.weights)
+
+
+class ExtendedKalmanFilter(_NonlinearKalmanFilter):
+    """ExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts, nu, ny, p, device) — the first-order extended Kalman filter with
+    additive noise: x' = f(x, u, p, t) + w, w ~ N(0, R1);  y = g(x, u, p, t) + e, e ~ N(0, R2);  x_0 ~ d0; correct! linearises g at the
+    prior mean, predict! linearises f at the posterior mean (csrc/shared/llpf_ekf.h is the definition).  The arguments are
+    UnscentedKalmanFilter's.  The Jacobians come from the model: the built-in descriptors have them, a pair of plain callables is traced
+    and differentiated in forward mode (tracing.py, jacobians=True), and a UserDynamics snippet must define the members
+    `dynamics_jac(x, fx, J)` and `measurement_jac(x, gx, J)` itself.  Runs on the device as a bank of one filter (llpf_ekf_bank_*), created
+    on first use.  nx <= 8, ny <= 4, nu <= 8."""
+    _JACOBIANS = True
+
+    def __init__(self, dynamics, measurement, R1, R2, d0, *, Ts=1.0, nu=-1, ny=-1, p=None, device=0):
+        self._setup(dynamics, measurement, R1, R2, d0, Ts, nu, ny, p, device)
+        _need_jacobians(self._model)
+
+    def _open(self):
+        return _capi.EkfBankHandle(self.device, [self._model])
+
+
+def _need_jacobians(model):
+    """a compiled model under an extended Kalman filter must define both Jacobian members"""
+    if model.model_id < S.MODEL_USER_BASE:
+        return
+    traits = _capi.model_traits(model.model_id)
+    missing = [name for name, bit in (("dynamics_jac", _capi.TRAIT_DYNAMICS_JAC), ("measurement_jac", _capi.TRAIT_MEASUREMENT_JAC)) if not traits & bit]
+    if missing:
+        raise TypeError("an ExtendedKalmanFilter needs the model's Jacobians: the snippet defines no `%s` member "
+                        "(DEV void dynamics_jac(const double* x, double* fx, double* J) const, measurement_jac likewise)" % "`, `".join(missing))
 
 
 class UnscentedKalmanFilterBank(_KfBank):
@@ -689,6 +730,43 @@ class UnscentedKalmanFilterBank(_KfBank):
     def set_weights(self, weight_params):
         self.weights = _ukf_weights(weight_params, self._h.nx)
         self._h.set_weights(self.weights)
+
+
+class ExtendedKalmanFilterBank(_KfBank):
+    """n independent extended Kalman filters of the same model family and dimensions on one device, one GPU thread each
+    (llpf_ekf_bank_*): the deterministic log-likelihood of every parameter set of a nonlinear sweep at one evaluation of the model and
+    its Jacobian per stage.  `filters_spec` is a list of ExtendedKalmanFilter or of (dynamics, measurement, R1, R2, d0) tuples."""
+    _AT_LOGLIK, _AT_FORWARD = {"t_index0": 1.0}, {"t_index0": 0.0}
+
+    def __init__(self, filters_spec, device=0, Ts=1.0):
+        self._init(self._models(filters_spec, Ts), device)
+
+    def _init(self, models, device):
+        self.device = int(device)
+        for m in models:
+            _need_jacobians(m)
+        self._h = _capi.EkfBankHandle(self.device, models)
+        self.n_filters = len(models)
+        self.Ts = float(models[0].Ts)
+
+    @staticmethod
+    def _models(filters_spec, Ts):
+        return [(f if isinstance(f, ExtendedKalmanFilter) else ExtendedKalmanFilter(*f, Ts=Ts))._model for f in filters_spec]
+
+    @classmethod
+    def from_filter_bank(cls, bank, device=None):
+        """the extended twin of a FilterBank: the same descriptors (any model that is not Rao-Blackwellized, keeps the Gaussian densities
+        and has its Jacobians), loglik and forward at the times FilterBank.loglik and FilterBank.forward use"""
+        self = cls.__new__(cls)
+        self._init(list(bank._models), bank._h.cfg.device if device is None else device)
+        return self
+
+    def set_parameters(self, filters_spec):
+        """new parameters for every filter (same model and dimensions, nothing reallocated: llpf_ekf_bank_set_models)"""
+        self._h.set_models(self._models(filters_spec, self.Ts))
+
+    def smooth(self, u, y, outputs=None, forward=()):
+        raise TypeError("the extended Kalman filter has no smoother yet: use UnscentedKalmanFilterBank.smooth")
 
 
 class RBMeasurementModel:
@@ -825,7 +903,7 @@ class ParticleFilteringSolution:
 # ---------------------------------------------------------------------------------------------------
 def reset(pf):
     """reset!(pf) — reference src/filtering.jl:4-14 (src/kalman.jl:159-164 for a KalmanFilter)."""
-    if isinstance(pf, UnscentedKalmanFilter):
+    if isinstance(pf, _NonlinearKalmanFilter):
         return pf.reset()
     pf._h.reset()
 
@@ -845,7 +923,7 @@ def _pt(args, kw, skip):
 def predict(pf, u, *args, **kw):
     """predict!(pf, u, p, t = index(pf)*Ts) — reference src/filtering.jl:140-153;
     predict!(pf::AuxiliaryParticleFilter, u, y1, p, t) — :195-217 (y1 = the NEXT measurement)."""
-    if isinstance(pf, UnscentedKalmanFilter):      # a step whose measurement is missing: correct! is skipped, predict! runs
+    if isinstance(pf, _NonlinearKalmanFilter):      # a step whose measurement is missing: correct! is skipped, predict! runs
         pf._step(u, None, _pt(args, kw, 0)[1], ())
         return
     if isinstance(pf, AuxiliaryParticleFilter):
@@ -858,7 +936,7 @@ def predict(pf, u, *args, **kw):
 def correct(pf, u, y, p=None, t=None):
     """ll, 0 = correct!(pf, u, y, p, t) — reference src/filtering.jl:164-168.  y=None means missing.
     For an AuxiliaryParticleFilter (:170-174) only logsumexp! runs: the measurement update was done in predict!."""
-    if isinstance(pf, UnscentedKalmanFilter):
+    if isinstance(pf, _NonlinearKalmanFilter):
         # the posterior of a one-step run put back as the state: the same numbers (the packed lower triangle of Rt is what the step holds)
         i = pf._index
         r = pf._step(u, y, t, ("xt", "Rt", "e"))
@@ -877,7 +955,7 @@ def update(pf, u, y, *args, **kw):
     if isinstance(pf, KalmanFilter):
         r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], ("e",))
         return float(r["ll"][0]), r["e"][0, 0]
-    if isinstance(pf, UnscentedKalmanFilter):
+    if isinstance(pf, _NonlinearKalmanFilter):
         r = pf._step(u, y, _pt(args, kw, 0)[1], ("e",))
         return float(r["ll"][0]), r["e"][0, 0]
     if isinstance(pf, AuxiliaryParticleFilter):
@@ -897,7 +975,7 @@ def forward_trajectory(pf, u, y, p=None, quantiles=None):
         reset(pf)
         r = pf._run(u, y, _capi.KALMAN_OUTPUTS)
         return KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
-    if isinstance(pf, UnscentedKalmanFilter):
+    if isinstance(pf, _NonlinearKalmanFilter):
         reset(pf)
         r = pf._run(u, y, _capi.KALMAN_OUTPUTS, 0.0)
         return KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
@@ -918,7 +996,7 @@ def loglik(pf, u, y, p=None):
     reset(pf)
     if isinstance(pf, KalmanFilter):
         return float(pf._run(u, y)["ll"][0])
-    if isinstance(pf, UnscentedKalmanFilter):      # the first step at t = 1 * Ts, as the particle filters' loglik
+    if isinstance(pf, _NonlinearKalmanFilter):      # the first step at t = 1 * Ts, as the particle filters' loglik
         return float(pf._run(u, y, (), 1.0)["ll"][0])
     if isinstance(pf, AuxiliaryParticleFilter):
         return pf._h.run_aux(u, y, mode=1)["ll"]
@@ -1152,6 +1230,8 @@ def smooth(pf, *args):
         pf._index += yy.shape[0]
         sol = KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
         return KalmanSmoothingSolution(sol, r["xT"][:, 0], r["RT"][:, 0])
+    if isinstance(pf, ExtendedKalmanFilter):
+        raise TypeError("the extended Kalman filter has no smoother yet: smooth an UnscentedKalmanFilter of the same model")
     if len(args) >= 7:
         xf, wf, wef, ll, M, u, y = args[:7]
     else:
@@ -1211,7 +1291,7 @@ def expweights(pf):
 
 
 def state(pf):
-    if isinstance(pf, (KalmanFilter, UnscentedKalmanFilter)):
+    if isinstance(pf, (KalmanFilter, _NonlinearKalmanFilter)):
         return pf.x
     return pf.state
 

@@ -17,6 +17,7 @@
 #include "shared/llpf_rbkf.h"
 #include "shared/llpf_kalman.h"
 #include "shared/llpf_ukf.h"
+#include "shared/llpf_ekf.h"
 
 using namespace llpf;
 
@@ -97,6 +98,7 @@ static void test_throw(const char* site) {
 #include "host/kfbank.hpp"
 #include "host/kalman.hpp"
 #include "host/ukf.hpp"
+#include "host/ekf.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -264,6 +266,27 @@ int llpf_ukf_bank_smooth(llpf_ukf_bank* b, const double* U, const double* Y, int
 } LLPF_GUARD(llpf_ukf_bank_smooth)
 int llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_get_state)
 int llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_ukf_bank_set_state)
+
+// ---- banks of extended Kalman filters (host/kfbank.hpp, host/ekf.hpp) ----
+int llpf_ekf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, llpf_ekf_bank** out) LLPF_TRY {
+    if (!out) return fail(LLPF_ERR_ARG, "out is null");
+    *out = nullptr;
+    std::unique_ptr<llpf_ekf_bank> b(new (std::nothrow) llpf_ekf_bank());
+    if (!b) return fail(LLPF_ERR_ALLOC, "out of host memory");
+    CHK(ekf_create(device, models, n_filters, *b));
+    *out = b.release();
+    return LLPF_OK;
+} LLPF_GUARD(llpf_ekf_bank_create)
+int llpf_ekf_bank_destroy(llpf_ekf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_ekf_bank_destroy)
+int llpf_ekf_bank_reset(llpf_ekf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_ekf_bank_reset)
+int llpf_ekf_bank_set_models(llpf_ekf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return ekf_set_models(*b, models); } LLPF_GUARD(llpf_ekf_bank_set_models)
+int llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                      const llpf_kalman_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return ekf_run(*b, U, Y, T, per_filter, t_index0, ll_total, out);
+} LLPF_GUARD(llpf_ekf_bank_run)
+int llpf_ekf_bank_get_state(llpf_ekf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_get_state)
+int llpf_ekf_bank_set_state(llpf_ekf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_set_state)
 
 int llpf_rb_get_covariance(llpf_filter* f, double* R) LLPF_TRY {
     NEEDF(f);

@@ -31,6 +31,7 @@
 #include "shared/llpf_fixed.h"
 #include "shared/llpf_philox.h"
 #include "shared/llpf_rbfull.h"
+#include "shared/llpf_quadtank_jac.h"
 
 namespace llpf {
 
@@ -264,6 +265,7 @@ struct ResArgs {
 // ---- end of the part the run-time compiled user-model kernels see (tools/gen_jit_prelude.py cuts here) ----
 #include "kernels/sim_args.hpp"
 #include "kernels/ukf_args.hpp"
+#include "kernels/ekf_args.hpp"
 // arguments of k_kalman (kernels/kalman.hpp): one launch is one chunk of steps [t0, t0 + Tc) of F Kalman filters, one thread per filter.
 // Device arrays are SoA / time-major: a wave's 64 lanes read and write whole lines.
 struct KalmanArgs {
@@ -365,6 +367,11 @@ hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const 
 // cache entry of its own
 int ukf_smooth_prepare(int model_id, int nx, int ny, std::string& err);
 hipError_t launch_ukf_smooth(int model_id, int nx, int ny, const ModelD* models, const UkfSmoothArgs& a, hipStream_t s);
+// banks of extended Kalman filters (k_ekf.hip; kernels/ekf.hpp): ekf_prepare compiles the k_ekf of a run-time compiled model (a user model
+// with dynamics_jac and measurement_jac, the linear-Gaussian model above 4 states) on its first use (0, or -1 with `err` set); launch_ekf
+// runs one chunk of steps
+int ekf_prepare(int model_id, int nx, int ny, std::string& err);
+hipError_t launch_ekf(int model_id, int nx, int ny, const ModelD* models, const EkfArgs& a, hipStream_t s);
 // kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
 bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
 const char* jit_prelude();

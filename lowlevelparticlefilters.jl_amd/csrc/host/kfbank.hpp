@@ -1,4 +1,4 @@
-// host/kfbank.hpp — what the banks of one-thread-per-filter Kalman filters share (host/kalman.hpp, host/ukf.hpp): the bank, its state, the
+// host/kfbank.hpp — what the banks of one-thread-per-filter Kalman filters share (host/kalman.hpp, host/ukf.hpp, host/ekf.hpp): the bank, its state, the
 // checks of a run's arguments and the drivers of the forward and the backward pass.  Part of capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
 // Device layout: the constants par [npar][F] (each bank's own rows) and the state [nx + np + 1][F] (x, packed R, the running ll_total of a
@@ -42,6 +42,56 @@ static int kf_pack_filter(const llpf_model& m, const std::string& at, int f, int
         for (int r = 0; r < dims[k]; ++r) for (int c = 0; c <= r; ++c) row[k][(size_t)llpf_kf_idx(r, c) * F + f] = S[r * dims[k] + c];
     }
     for (int i = 0; i < nx; ++i) init[(size_t)i * F + f] = m.initial_density.mu[i];
+    return LLPF_OK;
+}
+
+// The pack of a bank whose filters are driven by a model's own functions (the unscented and the extended bank): models -> the descriptors
+// ModelD[F], the SoA covariances par [np(nx) + np(ny)][F] (R1 packed, then R2 packed) and the initial state; every check that needs no
+// device.  `who`: the prefix of every message; `filter_name`: what the Rao-Blackwellized ids are said not to have; `need_traits`: the
+// optional members (LLPF_TRAIT_DYNAMICS_JAC, LLPF_TRAIT_MEASUREMENT_JAC) a compiled model must define for this bank
+static int kf_pack_models(const char* who, const char* filter_name, int need_traits, const llpf_model* models, int32_t F, int& model_id, int& nx,
+                          int& ny, int& nu, std::vector<ModelD>& hm, std::vector<double>& par, std::vector<double>& init) {
+    const std::string w = std::string(who) + ": ";
+    if (!models) return fail(LLPF_ERR_ARG, w + "models is null");
+    if (F < 1) return fail(LLPF_ERR_ARG, w + "n_filters must be >= 1");
+    model_id = models[0].model_id; nx = models[0].nx; ny = models[0].ny; nu = models[0].nu;
+    if (model_id == LLPF_MODEL_RB_LINEAR || model_id == LLPF_MODEL_RB_BILINEAR)
+        return fail(LLPF_ERR_ARG, w + "the Rao-Blackwellized models (LLPF_MODEL_RB_LINEAR, LLPF_MODEL_RB_BILINEAR) have no " + filter_name);
+    if (nx < 1 || nx > LLPF_KF_MAXX || ny < 1 || ny > LLPF_KF_MAXY || nu < 0 || nu > LLPF_KF_MAXU)
+        return fail(LLPF_ERR_ARG, w + "nx must be in 1..8, ny in 1..4 and nu in 0..8");
+    if (model_id == LLPF_MODEL_QUADTANK_RK4) {
+        if (nx != 4 || ny != 2 || nu != 2) return fail(LLPF_ERR_ARG, w + "the quad-tank has 4 states, 2 outputs and 2 inputs");
+    } else if (model_id >= LLPF_MODEL_USER_BASE) {
+        std::string src;
+        int sx = 0, sy = 0;
+        if (!jit_model_source(model_id, src, sx, sy)) return fail(LLPF_ERR_ARG, w + "unknown model id " + std::to_string(model_id));
+        if (sx != nx || sy != ny) return fail(LLPF_ERR_ARG, w + "nx, ny differ from the dimensions the model was compiled for");
+        const int traits = jit_model_traits(model_id);
+        if (traits & LLPF_TRAIT_LOGLIK) return fail(LLPF_ERR_ARG, w + "the model has a likelihood of its own (loglik): there is no Gaussian R2");
+        if (traits & LLPF_TRAIT_NOISE) return fail(LLPF_ERR_ARG, w + "the model forms its own noise (noise): only additive noise is supported");
+        if (traits & LLPF_TRAIT_INITIAL) return fail(LLPF_ERR_ARG, w + "the model has an initial density of its own (initial): d0 must be Gaussian");
+        if (need_traits & LLPF_TRAIT_DYNAMICS_JAC & ~traits)
+            return fail(LLPF_ERR_ARG, w + "the model has no dynamics_jac(x, fx, J): add the member to the snippet, or trace the callable with jacobians = true");
+        if (need_traits & LLPF_TRAIT_MEASUREMENT_JAC & ~traits)
+            return fail(LLPF_ERR_ARG, w + "the model has no measurement_jac(x, gx, J): add the member to the snippet, or trace the callable with jacobians = true");
+    } else if (model_id != LLPF_MODEL_LINEAR_GAUSSIAN) {
+        return fail(LLPF_ERR_ARG, w + "unknown model id " + std::to_string(model_id));
+    }
+    const int np = LLPF_KF_NP(nx), npar = np + LLPF_KF_NP(ny), nstate = nx + np + 1;
+    hm.resize((size_t)F);
+    par.assign((size_t)npar * F, 0.0);
+    init.assign((size_t)nstate * F, 0.0);
+    for (int f = 0; f < F; ++f) {
+        const llpf_model& m = models[f];
+        const std::string at = w + "filter " + std::to_string(f) + ": ";
+        if (m.model_id != model_id || m.nx != nx || m.ny != ny || m.nu != nu) return fail(LLPF_ERR_ARG, at + "model id or dimensions differ from filter 0's");
+        CHK(kf_pack_filter(m, at, f, F, nx, ny, 0, np, par, init));
+        const int rc = model_prepare(&m, &hm[(size_t)f]);      // the descriptor the model's own methods read; positive definiteness of R1, R2, cov(d0)
+        if (rc == -1) return fail(LLPF_ERR_ARG, at + "R1 (dynamics_density) is not positive definite");
+        if (rc == -2) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
+        if (rc == -3) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
+        if (rc) return fail(LLPF_ERR_ARG, at + "invalid model descriptor, code " + std::to_string(rc));
+    }
     return LLPF_OK;
 }
 

@@ -24,46 +24,10 @@ static int ukf_check_weights(const llpf_ukf_weights* w) {
     return LLPF_OK;
 }
 
-// models -> the descriptors, the SoA covariances and the initial state; every check that needs no device
+// models -> the descriptors, the SoA covariances and the initial state; every check that needs no device (kf_pack_models)
 static int ukf_pack(const llpf_model* models, int32_t F, int& model_id, int& nx, int& ny, int& nu, std::vector<ModelD>& hm,
                     std::vector<double>& par, std::vector<double>& init) {
-    if (!models) return fail(LLPF_ERR_ARG, "ukf: models is null");
-    if (F < 1) return fail(LLPF_ERR_ARG, "ukf: n_filters must be >= 1");
-    model_id = models[0].model_id; nx = models[0].nx; ny = models[0].ny; nu = models[0].nu;
-    if (model_id == LLPF_MODEL_RB_LINEAR || model_id == LLPF_MODEL_RB_BILINEAR)
-        return fail(LLPF_ERR_ARG, "ukf: the Rao-Blackwellized models (LLPF_MODEL_RB_LINEAR, LLPF_MODEL_RB_BILINEAR) have no unscented filter");
-    if (nx < 1 || nx > LLPF_KF_MAXX || ny < 1 || ny > LLPF_KF_MAXY || nu < 0 || nu > LLPF_KF_MAXU)
-        return fail(LLPF_ERR_ARG, "ukf: nx must be in 1..8, ny in 1..4 and nu in 0..8");
-    if (model_id == LLPF_MODEL_QUADTANK_RK4) {
-        if (nx != 4 || ny != 2 || nu != 2) return fail(LLPF_ERR_ARG, "ukf: the quad-tank has 4 states, 2 outputs and 2 inputs");
-    } else if (model_id >= LLPF_MODEL_USER_BASE) {
-        std::string src;
-        int sx = 0, sy = 0;
-        if (!jit_model_source(model_id, src, sx, sy)) return fail(LLPF_ERR_ARG, "ukf: unknown model id " + std::to_string(model_id));
-        if (sx != nx || sy != ny) return fail(LLPF_ERR_ARG, "ukf: nx, ny differ from the dimensions the model was compiled for");
-        const int traits = jit_model_traits(model_id);
-        if (traits & LLPF_TRAIT_LOGLIK) return fail(LLPF_ERR_ARG, "ukf: the model has a likelihood of its own (loglik): there is no Gaussian R2");
-        if (traits & LLPF_TRAIT_NOISE) return fail(LLPF_ERR_ARG, "ukf: the model forms its own noise (noise): only additive noise is supported");
-        if (traits & LLPF_TRAIT_INITIAL) return fail(LLPF_ERR_ARG, "ukf: the model has an initial density of its own (initial): d0 must be Gaussian");
-    } else if (model_id != LLPF_MODEL_LINEAR_GAUSSIAN) {
-        return fail(LLPF_ERR_ARG, "ukf: unknown model id " + std::to_string(model_id));
-    }
-    const int np = LLPF_KF_NP(nx), npar = LLPF_UKF_NPAR(nx, ny), nstate = nx + np + 1;
-    hm.resize((size_t)F);
-    par.assign((size_t)npar * F, 0.0);
-    init.assign((size_t)nstate * F, 0.0);
-    for (int f = 0; f < F; ++f) {
-        const llpf_model& m = models[f];
-        const std::string at = "ukf: filter " + std::to_string(f) + ": ";
-        if (m.model_id != model_id || m.nx != nx || m.ny != ny || m.nu != nu) return fail(LLPF_ERR_ARG, at + "model id or dimensions differ from filter 0's");
-        CHK(kf_pack_filter(m, at, f, F, nx, ny, LLPF_UKF_OFF_R1, LLPF_UKF_OFF_R2(nx), par, init));
-        const int rc = model_prepare(&m, &hm[(size_t)f]);      // the descriptor the model's own methods read; positive definiteness of R1, R2, cov(d0)
-        if (rc == -1) return fail(LLPF_ERR_ARG, at + "R1 (dynamics_density) is not positive definite");
-        if (rc == -2) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
-        if (rc == -3) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
-        if (rc) return fail(LLPF_ERR_ARG, at + "invalid model descriptor, code " + std::to_string(rc));
-    }
-    return LLPF_OK;
+    return kf_pack_models("ukf", "unscented filter", 0, models, F, model_id, nx, ny, nu, hm, par, init);
 }
 
 static int ukf_create(int32_t device, const llpf_model* models, int32_t F, const llpf_ukf_weights* w, llpf_ukf_bank& b) {

@@ -25,6 +25,7 @@ namespace llpf {
 #include "kernels/models.hpp"
 #include "kernels/kf_store.hpp"
 #include "kernels/ukf.hpp"
+#include "kernels/jit_bank.hpp"
 
 template <class Model, int NX, int NY>
 static hipError_t launch_ukf_t(const ModelD* models, const UkfArgs& a, hipStream_t s) {
@@ -62,28 +63,14 @@ static hipError_t launch_ukf_smooth_lg(int ny, const ModelD* models, const UkfSm
     }
 }
 
-// ---- run-time compiled models ----
-struct JitUkf {
-    std::vector<char> code;
-    std::string name;                          // lowered name of k_ukf<UserModel, nx, ny> / k_ukf_smooth<UserModel, nx>
-    std::string name_post;                     // the smoother's entry: lowered name of k_ukf<UserModel, nx, ny, true>, its forward pass
-    struct PerDevice { hipModule_t mod = nullptr; hipFunction_t fn = nullptr, fn_post = nullptr; };
-    std::vector<PerDevice> dev;                // indexed by device ordinal, loaded on first use
-};
+// ---- run-time compiled models (kernels/jit_bank.hpp) ----
+// by ukf_key: the forward and the backward kernel are entries of their own.  Kernel 0: k_ukf<UserModel, nx, ny> of a forward entry,
+// k_ukf_smooth<UserModel, nx> of a smoother's; kernel 1 of a smoother's entry: k_ukf<UserModel, nx, ny, true>, its forward pass
 static std::mutex g_ukf_mutex;
-static std::map<std::string, std::unique_ptr<JitUkf>> g_ukf;      // by ukf_key: the forward and the backward kernel are entries of their own
+static std::map<std::string, std::unique_ptr<JitBankKernels>> g_ukf;
 
 static bool ukf_builtin(int model_id, int nx, int ny) {
     return (model_id == LLPF_MODEL_LINEAR_GAUSSIAN && nx <= 4 && ny <= 4) || model_id == LLPF_MODEL_QUADTANK_RK4;
-}
-// the model's snippet: a user model's own source, or LinGauss<nx, ny> above the precompiled dimensions
-static bool ukf_snippet(int model_id, int nx, int ny, std::string& snippet) {
-    if (model_id == LLPF_MODEL_LINEAR_GAUSSIAN) {
-        snippet = "struct UserModel : LinGauss<" + std::to_string(nx) + ", " + std::to_string(ny) + "> {};\n";
-        return true;
-    }
-    int sx = 0, sy = 0;
-    return jit_model_source(model_id, snippet, sx, sy) && sx == nx && sy == ny;
 }
 static std::string ukf_key(int model_id, int nx, int ny, bool smooth) {
     return std::to_string(model_id) + ":" + std::to_string(nx) + ":" + std::to_string(ny) + (smooth ? ":smooth" : "");
@@ -99,54 +86,18 @@ static int ukf_compile(int model_id, int nx, int ny, bool smooth, std::string& e
         if (g_ukf.count(key)) return 0;
     }
     std::string snippet;
-    if (!ukf_snippet(model_id, nx, ny, snippet)) { err = "unknown model id " + std::to_string(model_id) + " at these dimensions"; return -1; }
-    std::string src(jit_prelude());
-    src += "\n";
-    src += LLPF_JIT_UKF_SHARED;
-    src += "\nnamespace llpf {\n";
-    src += snippet;
-    src += "\n";
-    src += LLPF_JIT_UKF;
-    src += "\n}  // namespace llpf\n";
-    hiprtcProgram prog = nullptr;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "llpf_user_ukf.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) { err = "hiprtcCreateProgram failed"; return -1; }
-    const std::string expr = smooth ? "llpf::k_ukf_smooth<llpf::UserModel, " + std::to_string(nx) + ">"
-                                    : "llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ">";
-    const std::string expr_post = "llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ", true>";
-    hiprtcAddNameExpression(prog, expr.c_str());
-    if (smooth) hiprtcAddNameExpression(prog, expr_post.c_str());
-    int devid = 0;
-    hipDeviceProp_t prop;
-    std::string arch = "gfx950";
-    if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.gcnArchName[0]) arch = prop.gcnArchName;
-    const std::string archopt = "--offload-arch=" + arch;
-    // the options of this unit (Makefile): -ffp-contract=off, the same bits
-    const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-value"};
-    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
-    if (rc != HIPRTC_SUCCESS) {
-        size_t n = 0;
-        hiprtcGetProgramLogSize(prog, &n);
-        std::string log(n, '\0');
-        if (n) hiprtcGetProgramLog(prog, &log[0]);
-        err = std::string(smooth ? "hiprtc (k_ukf_smooth): " : "hiprtc (k_ukf): ") + hiprtcGetErrorString(rc) + "\n" + log;
-        hiprtcDestroyProgram(&prog);
-        return -1;
-    }
-    std::unique_ptr<JitUkf> ju(new JitUkf());
-    size_t sz = 0;
-    hiprtcGetCodeSize(prog, &sz);
-    ju->code.resize(sz);
-    hiprtcGetCode(prog, ju->code.data());
-    const char* low = nullptr;
-    if (hiprtcGetLoweredName(prog, expr.c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + expr; hiprtcDestroyProgram(&prog); return -1; }
-    ju->name = low;
+    if (!jit_bank_snippet(model_id, nx, ny, snippet)) { err = "unknown model id " + std::to_string(model_id) + " at these dimensions"; return -1; }
+    std::vector<std::string> exprs;
     if (smooth) {
-        if (hiprtcGetLoweredName(prog, expr_post.c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + expr_post; hiprtcDestroyProgram(&prog); return -1; }
-        ju->name_post = low;
+        exprs.push_back("llpf::k_ukf_smooth<llpf::UserModel, " + std::to_string(nx) + ">");
+        exprs.push_back("llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ", true>");
+    } else {
+        exprs.push_back("llpf::k_ukf<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ">");
     }
-    hiprtcDestroyProgram(&prog);
+    std::unique_ptr<JitBankKernels> jk;
+    if (jit_bank_compile(LLPF_JIT_UKF_SHARED, snippet, LLPF_JIT_UKF, "llpf_user_ukf.hip", exprs, smooth ? "k_ukf_smooth" : "k_ukf", jk, err) != 0) return -1;
     std::lock_guard<std::mutex> lk(g_ukf_mutex);
-    if (!g_ukf.count(key)) g_ukf[key] = std::move(ju);      // another thread may have compiled it meanwhile: the first one stays
+    if (!g_ukf.count(key)) g_ukf[key] = std::move(jk);      // another thread may have compiled it meanwhile: the first one stays
     return 0;
 }
 
@@ -155,20 +106,10 @@ int ukf_smooth_prepare(int model_id, int nx, int ny, std::string& err) { return 
 
 // this device's handle of the compiled kernel (loaded on first use); post: the smoother's forward kernel k_ukf<..., true>
 static hipError_t ukf_function(int model_id, int nx, int ny, bool smooth, bool post, hipFunction_t* fn) {
-    int devid = 0;
-    hipError_t e = hipGetDevice(&devid);
-    if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lk(g_ukf_mutex);
     auto it = g_ukf.find(ukf_key(model_id, nx, ny, smooth));
     if (it == g_ukf.end()) return hipErrorInvalidValue;      // ukf_prepare / ukf_smooth_prepare compiles it first
-    JitUkf& ju = *it->second;
-    if ((int)ju.dev.size() <= devid) ju.dev.resize((size_t)devid + 1);
-    JitUkf::PerDevice& pd = ju.dev[(size_t)devid];
-    if (!pd.mod && (e = hipModuleLoadData(&pd.mod, ju.code.data())) != hipSuccess) return e;
-    if (!pd.fn && (e = hipModuleGetFunction(&pd.fn, pd.mod, ju.name.c_str())) != hipSuccess) return e;
-    if (post && !pd.fn_post && (e = hipModuleGetFunction(&pd.fn_post, pd.mod, ju.name_post.c_str())) != hipSuccess) return e;
-    *fn = post ? pd.fn_post : pd.fn;
-    return hipSuccess;
+    return jit_bank_function(*it->second, post ? 1 : 0, fn);
 }
 
 hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const UkfArgs& a, hipStream_t s) {

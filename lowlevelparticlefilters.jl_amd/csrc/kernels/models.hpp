@@ -175,6 +175,17 @@ struct LinGauss {   // f = A x .+ B u ; g = C x   (reference examples/example_li
             out[r] = cx;
         }
     }
+    // value and Jacobian (the Model concept's optional members, below): the Jacobians are the matrices themselves
+    DEV void dynamics_jac(const double* x, double* fx, double* J) const {
+        dynamics(x, fx);
+#pragma unroll
+        for (int i = 0; i < NX * NX; ++i) J[i] = md->A[i];
+    }
+    DEV void measurement_jac(const double* x, double* gx, double* J) const {
+        measurement(x, gx);
+#pragma unroll
+        for (int i = 0; i < NY * NX; ++i) J[i] = md->C[i];
+    }
 };
 
 // Rao-Blackwellized filter with constant matrices (reference src/rbpf.jl:163-283): the particle is [xn; xl], the
@@ -383,6 +394,20 @@ struct QuadTank {   // reference examples/example_quadtank.jl:8-35 with rk4 of s
         out[0] = x[0];
         out[1] = x[1];
     }
+    // value and Jacobian of the RK4 map from one pass through its stages: shared/llpf_quadtank_jac.h, the text a host build runs too
+    DEV void dynamics_jac(const double* x0, double* fx, double* J) const {
+        llpf_qt_coef c;
+        c.c1a = c1a; c.c1a_sw = c1a_sw; c.c1b = c1b; c.c1u = c1u; c.c2a = c2a; c.c2b = c2b; c.c2u = c2u;
+        c.c3a = c3a; c.c3u = c3u; c.c4a = c4a; c.c4u = c4u;
+        c.tg = tg; c.eps = eps; c.tsw = tsw; c.h = Ts; c.h2 = Ts2; c.h6 = Ts6; c.ss = ss;
+        llpf_qt_dynamics_jac(&c, u0, u1, t0, x0, fx, J);
+    }
+    DEV void measurement_jac(const double* x, double* gx, double* J) const {
+        gx[0] = x[0];
+        gx[1] = x[1];
+        J[0] = 1.0; J[1] = 0.0; J[2] = 0.0; J[3] = 0.0;
+        J[4] = 0.0; J[5] = 1.0; J[6] = 0.0; J[7] = 0.0;
+    }
     // The same RK4 with the four states on the four lanes of a quad (lane & 3 = state): every lane runs the chain of ITS state — the same
     // IEEE operations in the same order as dynamics() — and the one cross term of the right-hand side (h1' takes sqrt(h3), h2' takes
     // sqrt(h4)) arrives through a quad permute.  One evaluation is a third of the dependent instructions: for the launches in which a
@@ -443,6 +468,15 @@ template <class M, class = void> struct has_user_noise { static constexpr bool v
 template <class M> struct has_user_noise<M, decltype((void)&M::noise)> { static constexpr bool value = true; };
 template <class M, class = void> struct has_user_initial { static constexpr bool value = false; };
 template <class M> struct has_user_initial<M, decltype((void)&M::initial)> { static constexpr bool value = true; };
+
+// Optional members of a model for the filters that linearise it (banks of extended Kalman filters, kernels/ekf.hpp), after prepare():
+//   DEV void dynamics_jac(const double* x, double* fx, double* J) const      fx[NX] = f(x), J[r * NX + c] = d f_r / d x_c
+//   DEV void measurement_jac(const double* x, double* gx, double* J) const   gx[NY] = g(x), J[r * NX + c] = d g_r / d x_c
+// value and Jacobian from one evaluation; fx / gx must be the bits of dynamics(x, .) / measurement(x, .)
+template <class M, class = void> struct has_dynamics_jac { static constexpr bool value = false; };
+template <class M> struct has_dynamics_jac<M, decltype((void)&M::dynamics_jac)> { static constexpr bool value = true; };
+template <class M, class = void> struct has_measurement_jac { static constexpr bool value = false; };
+template <class M> struct has_measurement_jac<M, decltype((void)&M::measurement_jac)> { static constexpr bool value = true; };
 
 // Is f(x) expensive enough to be computed once per distinct ancestor of a block and handed to the outputs that share it
 // (k_step)?  Yes unless the model says otherwise: run-time compiled user models and the quad-tank's RK4 are; a matrix-vector

@@ -37,7 +37,7 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
        GPUKalmanFilter, GPUKalmanFilterBank, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
-       ukf_weights, set_weights!
+       ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank
 
 const LIB = get(ENV, "LLPF_HIP_LIB", joinpath(@__DIR__, "..", "libllpf_hip.so"))
 const MAXD = 16          # LLPF_MAX_DIM: states / outputs
@@ -299,6 +299,7 @@ struct UserInitial
 end
 UserInitial() = UserInitial(nothing)
 const TRAIT_LOGLIK, TRAIT_LOGLIK_BOUND, TRAIT_NOISE, TRAIT_INITIAL = Int32(1), Int32(2), Int32(4), Int32(8)
+const TRAIT_DYNAMICS_JAC, TRAIT_MEASUREMENT_JAC = Int32(16), Int32(32)      # the members an extended Kalman filter needs
 function cmodel(f::UserDynamics, ::UserMeasurement, df, dg, d0, Ts; user_likelihood::Bool = false)
     id = Ref{Int32}(-1)
     check(ccall((:llpf_model_compile, LIB), Cint, (Cstring, Int32, Int32, Ref{Int32}), f.src, f.nx, f.ny, id))
@@ -1303,6 +1304,133 @@ function LowLevelParticleFilters.smooth(ukf::GPUUnscentedKalmanFilter, u, y, p =
     sol = KalmanFilteringSolution(ukf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
                                   [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
     KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
+end
+
+# ---- banks of extended Kalman filters (the reference's ExtendedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise): llpf_ekf_bank_* ----
+mutable struct GPUExtendedKalmanFilterBank
+    h::Ptr{Cvoid}
+    F::Int
+    nx::Int
+    nu::Int
+    ny::Int
+    Ts::Float64
+end
+# a compiled model under an extended Kalman filter must define both Jacobian members: refused here, by name, before the library is asked
+function need_jacobians(cm::CModel)
+    cm.model_id < 1000 && return nothing
+    traits = Ref{Int32}(0)
+    check(ccall((:llpf_model_traits, LIB), Cint, (Int32, Ref{Int32}), cm.model_id, traits))
+    missing_ = [name for (name, bit) in (("dynamics_jac", TRAIT_DYNAMICS_JAC), ("measurement_jac", TRAIT_MEASUREMENT_JAC)) if traits[] & bit == 0]
+    isempty(missing_) || throw(ArgumentError("an extended Kalman filter needs the model's Jacobians: the snippet defines no `" *
+                                             join(missing_, "`, `") * "` member (trace_dynamics(...; jacobians = true) emits them)"))
+    nothing
+end
+"""
+    GPUExtendedKalmanFilterBank(filters; Ts = 1.0, device = 0)
+
+Independent first-order extended Kalman filters (additive noise) on the device, one GPU thread each; `filters` is a vector of
+(dynamics, measurement, R1, R2, d0) tuples as `GPUUnscentedKalmanFilterBank` takes them.  The model supplies its Jacobians: the built-in
+descriptors have them, `trace_dynamics(...; jacobians = true)` differentiates a closure, and a UserDynamics snippet must define
+`dynamics_jac` and `measurement_jac` itself (the library refuses one that does not).  `loglik(bank, u, y)` is the vector of every
+filter's log-likelihood.
+"""
+function GPUExtendedKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0)
+    cms = [ukf_model(f, Ts) for f in filters]
+    foreach(need_jacobians, cms)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_ekf_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Int32, Ref{Ptr{Cvoid}}), device, cms, length(cms), h))
+    b = GPUExtendedKalmanFilterBank(h[], length(cms), cms[1].nx, cms[1].nu, cms[1].ny, Float64(Ts))
+    finalizer(x -> ccall((:llpf_ekf_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    b
+end
+function set_parameters!(b::GPUExtendedKalmanFilterBank, filters::Vector)
+    cms = [ukf_model(f, b.Ts) for f in filters]
+    foreach(need_jacobians, cms)
+    length(cms) == b.F || throw(ArgumentError("set_parameters!: $(length(cms)) filters for a bank of $(b.F)"))
+    check(ccall((:llpf_ekf_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}), b.h, cms))
+    b
+end
+reset!(b::GPUExtendedKalmanFilterBank) = check(ccall((:llpf_ekf_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+# u, y: vectors of T vectors shared by every filter (a missing y is `missing` / a NaN first element); step t runs at time (t_index0 + t - 1) Ts
+function ekf_run(b::GPUExtendedKalmanFilterBank, u, y; outputs = false, t_index0 = 0.0)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        check(ccall((:llpf_ekf_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Ptr{CKalmanOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), Float64(t_index0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+"loglik(bank, u, y): every filter's loglik(ekf, u, y) (reset! first, then T update! steps, the first at t = 1 Ts as the particle filters' loglik)"
+loglik(b::GPUExtendedKalmanFilterBank, u, y) = (reset!(b); ekf_run(b, u, y; t_index0 = 1.0)[1])
+"x (nx x F), R (nx x nx x F) of every filter"
+function state(b::GPUExtendedKalmanFilterBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_ekf_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, x, R))
+    x, R
+end
+covariance(b::GPUExtendedKalmanFilterBank) = state(b)[2]
+"set the estimate of every filter: x (nx x F), R (nx x nx x F; its lower triangle is read)"
+function set_state!(b::GPUExtendedKalmanFilterBank, x, R)
+    xm = Matrix{Float64}(reshape(x, b.nx, b.F)); Rm = Array{Float64}(reshape(R, b.nx, b.nx, b.F))
+    Rr = permutedims(Rm, (2, 1, 3))                  # column-major nx x nx = the row-major [nx][nx] of its transpose
+    check(ccall((:llpf_ekf_bank_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, xm, Rr))
+    b
+end
+
+"""
+    GPUExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0)
+
+The textbook first-order extended Kalman filter with additive noise — the Jacobian of the measurement at the prior mean, of the dynamics
+at the posterior mean — run on the device (a bank of one filter, llpf_ekf_bank_*): `forward_trajectory` returns the reference's
+`KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `correct!`, `predict!`, `state`, `covariance`.  Unverified against the
+reference's `ExtendedKalmanFilter` (its source was not available when this was written).
+"""
+mutable struct GPUExtendedKalmanFilter
+    bank::GPUExtendedKalmanFilterBank
+    Ts::Float64
+    index::Int
+end
+GPUExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0) =
+    GPUExtendedKalmanFilter(GPUExtendedKalmanFilterBank([(dynamics, measurement, R1, R2, d0)]; Ts = Ts, device = device), Float64(Ts), 0)
+reset!(kf::GPUExtendedKalmanFilter) = (reset!(kf.bank); kf.index = 1; nothing)
+loglik(kf::GPUExtendedKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
+"update!(ekf, u, y): correct! then predict! at time t; returns (ll, e)"
+function update!(kf::GPUExtendedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = ekf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    kf.index += 1
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"correct!(ekf, u, y): the posterior of a one-step run put back as the state (exact: the step holds the lower triangle of Rt); returns (ll, e)"
+function correct!(kf::GPUExtendedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = ekf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    set_state!(kf.bank, o.xt[:, :, 1], o.Rt[:, :, :, 1])
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"predict!(ekf, u): a step whose measurement is missing (correct! is skipped)"
+function predict!(kf::GPUExtendedKalmanFilter, u, p = NullParameters(), t = kf.index * kf.Ts)
+    ekf_run(kf.bank, [u], [missing]; t_index0 = t / kf.Ts)
+    kf.index += 1
+    nothing
+end
+state(kf::GPUExtendedKalmanFilter) = state(kf.bank)[1][:, 1]
+covariance(kf::GPUExtendedKalmanFilter) = state(kf.bank)[2][:, :, 1]
+function forward_trajectory(kf::GPUExtendedKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o = ekf_run(kf.bank, u, y; outputs = true)
+    T = length(y)
+    kf.index = T
+    KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                            [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
 end
 
 end # module

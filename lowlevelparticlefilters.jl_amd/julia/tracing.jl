@@ -131,19 +131,120 @@ function trace_outputs(g::TraceGraph, out, n::Int, what::String)
 end
 trace_inputs(g::TraceGraph, sym::Symbol, n::Int) = Tr[Tr(g, addnode!(g, (sym, k - 1))) for k in 1:n]
 
+# ---- forward-mode differentiation (the twin of tracing.py: jacobian) ----
+const TRACE_ONE, TRACE_TWO, TRACE_ZERO = reinterpret(UInt64, 1.0), reinterpret(UInt64, 2.0), reinterpret(UInt64, 0.0)
+
 """
-    emit_user_model(dynamics, nx, nu, ny; p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing) -> String
+    trace_jacobian(g, outs, nx) -> Matrix{Int}
+
+J[k, c] = the node of d outs[k] / d x_c, or 0 where the derivative is structurally zero.  The derivative nodes are appended to `g` itself
+(after every node of the value, which keep their ids), so common subexpressions are shared and emission stays in creation order.  Rules,
+with da the derivative of the operand a and v the node itself: add da + db; sub da - db; mul da b + a db; div (da - v db) / b; neg -da;
+abs a < 0 ? -da : da; sqrt da / (2 v); exp v da; log da / a; log1p da / (1 + a); sel c ? da : db with the same condition node; the inputs
+u, t, y and constants have none, x_d has the unit one.  A missing operand derivative drops its term (no `0 * ...` is ever formed) and a
+unit factor drops its multiplication."""
+function trace_jacobian(g::TraceGraph, outs::Vector{Int}, nx::Int)
+    one() = addnode!(g, (:const, TRACE_ONE))
+    isone(i) = g.nodes[i] == (:const, TRACE_ONE)
+    mul(a, b) = isone(a) ? b : isone(b) ? a : addnode!(g, (:mul, a, b))
+    add(a, b) = a == 0 ? b : b == 0 ? a : addnode!(g, (:add, a, b))
+    sub(a, b) = b == 0 ? a : a == 0 ? addnode!(g, (:neg, b)) : addnode!(g, (:sub, a, b))
+    need = Set{Int}()
+    stack = copy(outs)
+    while !isempty(stack)
+        i = pop!(stack)
+        i in need && continue
+        push!(need, i)
+        node = g.nodes[i]
+        node[1] in TRACE_INPUT && continue
+        append!(stack, Int[a for a in node[2:end]])
+    end
+    d = Dict{Int,Dict{Int,Int}}()          # node -> (state index -> derivative node), only the entries that are not structurally zero
+    for i in sort!(collect(need))
+        node = g.nodes[i]
+        op = node[1]
+        if op === :x
+            d[i] = Dict(Int(node[2]) => one())
+            continue
+        elseif op in TRACE_INPUT || op in TRACE_BOOL
+            d[i] = Dict{Int,Int}()
+            continue
+        end
+        ops = Int[a for a in node[2:end]]
+        vals = op === :sel ? ops[2:end] : ops
+        cols = sort!(collect(union((keys(d[a]) for a in vals)...)))
+        di = Dict{Int,Int}()
+        for c in cols
+            if op === :sel
+                zero = addnode!(g, (:const, TRACE_ZERO))
+                da = get(d[ops[2]], c, zero); db = get(d[ops[3]], c, zero)
+                di[c] = addnode!(g, (:sel, ops[1], da, db))
+                continue
+            end
+            a = ops[1]
+            b = length(ops) > 1 ? ops[2] : 0
+            da = get(d[a], c, 0)
+            db = b == 0 ? 0 : get(d[b], c, 0)
+            di[c] = if op === :add
+                add(da, db)
+            elseif op === :sub
+                sub(da, db)
+            elseif op === :mul
+                add(da == 0 ? 0 : mul(da, b), db == 0 ? 0 : mul(a, db))
+            elseif op === :div
+                addnode!(g, (:div, sub(da, db == 0 ? 0 : mul(i, db)), b))
+            elseif op === :neg
+                addnode!(g, (:neg, da))
+            elseif op === :abs
+                addnode!(g, (:sel, addnode!(g, (:lt, a, addnode!(g, (:const, TRACE_ZERO)))), addnode!(g, (:neg, da)), da))
+            elseif op === :sqrt
+                addnode!(g, (:div, da, addnode!(g, (:mul, addnode!(g, (:const, TRACE_TWO)), i))))
+            elseif op === :exp
+                mul(i, da)
+            elseif op === :log
+                addnode!(g, (:div, da, a))
+            elseif op === :log1p
+                addnode!(g, (:div, da, addnode!(g, (:add, one(), a))))
+            else
+                error("no derivative rule for the node kind $op")
+            end
+        end
+        d[i] = di
+    end
+    Int[get(d[outs[k]], c - 1, 0) for k in 1:length(outs), c in 1:nx]
+end
+
+"the `member`(x, val, J) body: the value's statements (the very text of the value member), then the derivative nodes, the value outputs, the Jacobian entries that have a node and the literal 0.0 of those that are structurally zero"
+function emit_jac_member(g::TraceGraph, outs::Vector{Int}, nx::Int, member::String, val::String)
+    J = trace_jacobian(g, outs, nx)
+    entries = [((k - 1) * nx + (c - 1), J[k, c]) for k in 1:length(outs) for c in 1:nx]
+    live = [e for e in entries if e[2] != 0]
+    nval = length(outs)
+    stmt = (k, n) -> k < nval ? "$val[$k] = $n;" : "J[$(live[k - nval + 1][1])] = $n;"
+    body = emit_body(g, vcat(outs, Int[e[2] for e in live]), stmt, Set{Symbol}())
+    zeros_ = join(["\n        J[$(e[1])] = 0.0;" for e in entries if e[2] == 0])
+    "    DEV void $member(const double* x, double* $val, double* J) const {\n" * body * zeros_ * "\n    }"
+end
+
+"""
+    emit_user_model(dynamics, nx, nu, ny; p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing, jacobians = false) -> String
 
 The `struct UserModel` device snippet of closures with the reference's signatures (traced once on `Tr` numbers).  The traced
-measurement may depend on the state only and the likelihood not on `u` (the engine's Model concept hands neither to them)."""
-function emit_user_model(dynamics, nx::Int, nu::Int, ny::Int; p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing)
+measurement may depend on the state only and the likelihood not on `u` (the engine's Model concept hands neither to them).
+`jacobians = true` appends the members `dynamics_jac` and `measurement_jac` (forward-mode derivatives of the same traces: what a
+GPUExtendedKalmanFilter needs); without it the text is what it always was."""
+function emit_user_model(dynamics, nx::Int, nu::Int, ny::Int; p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing, jacobians = false)
     used = Set{Symbol}()
     g = TraceGraph()
     x = trace_inputs(g, :x, nx); u = trace_inputs(g, :u, nu); t = Tr(g, addnode!(g, (:t,)))
     od = trace_outputs(g, dynamics(x, u, p, t), nx, "dynamics")
     parts = String["    DEV void dynamics(const double* x, double* out) const {\n" * emit_body(g, od, (k, n) -> "out[$k] = $n;", used) * "\n    }"]
+    jac = String[]
+    jacobians && push!(jac, emit_jac_member(g, od, nx, "dynamics_jac", "fx"))
     if measurement === nothing
         push!(parts, "    DEV void measurement(const double* x, double* out) const { for (int k = 0; k < $ny; ++k) out[k] = x[k]; }")
+        jacobians && push!(jac, "    DEV void measurement_jac(const double* x, double* gx, double* J) const {\n        for (int k = 0; k < $ny; ++k) gx[k] = x[k];\n" *
+                                "        for (int k = 0; k < $(ny * nx); ++k) J[k] = (k / $nx == k % $nx) ? 1.0 : 0.0;\n    }")
     else
         gm = TraceGraph(); um = Set{Symbol}()
         xm = trace_inputs(gm, :x, nx); uu = trace_inputs(gm, :u, nu); tm = Tr(gm, addnode!(gm, (:t,)))
@@ -151,6 +252,7 @@ function emit_user_model(dynamics, nx::Int, nu::Int, ny::Int; p = nothing, measu
         body = emit_body(gm, om, (k, n) -> "out[$k] = $n;", um)
         (:u in um || :t in um) && error("a traced measurement may depend on the state only: put the dependence into measurement_likelihood")
         push!(parts, "    DEV void measurement(const double* x, double* out) const {\n" * body * "\n    }")
+        jacobians && push!(jac, emit_jac_member(gm, om, nx, "measurement_jac", "gx"))
     end
     if measurement_likelihood !== nothing
         gl = TraceGraph(); ul = Set{Symbol}()
@@ -161,19 +263,21 @@ function emit_user_model(dynamics, nx::Int, nu::Int, ny::Int; p = nothing, measu
         push!(parts, "    DEV double loglik(const double* x, const double* y, double t) const {\n" * body * "\n    }")
         loglik_bound === nothing || push!(parts, "    DEV double loglik_bound() const { return llpf_u2d(0x$(string(reinterpret(UInt64, Float64(loglik_bound)), base = 16, pad = 16))ULL); }")
     end
+    append!(parts, jac)
     "struct UserModel {\n    static constexpr bool RB = false;\n    double u_[$(max(nu, 1))];\n    double t_;\n" *
     "    DEV void prepare(const ModelD* m, const double* u, double t) {\n        for (int j = 0; j < $nu; ++j) u_[j] = (u != nullptr) ? u[j] : 0.0;\n        t_ = t;\n    }\n" *
     join(parts, "\n") * "\n};\n"
 end
 
 """
-    trace_dynamics(dynamics, nx, nu; ny, p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing)
+    trace_dynamics(dynamics, nx, nu; ny, p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing, jacobians = false)
         -> (UserDynamics, UserMeasurement, UserLikelihood or nothing)
 
 The descriptors that stand for the closures in `GPUParticleFilter` / `GPUAdvancedParticleFilter` (the closures stay their host
-versions, for `simulate`)."""
-function trace_dynamics(dynamics, nx::Int, nu::Int; ny::Int, p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing)
-    src = emit_user_model(dynamics, nx, nu, ny; p = p, measurement = measurement, measurement_likelihood = measurement_likelihood, loglik_bound = loglik_bound)
+versions, for `simulate`).  `jacobians = true`: the snippet also defines dynamics_jac / measurement_jac (GPUExtendedKalmanFilter)."""
+function trace_dynamics(dynamics, nx::Int, nu::Int; ny::Int, p = nothing, measurement = nothing, measurement_likelihood = nothing, loglik_bound = nothing, jacobians = false)
+    src = emit_user_model(dynamics, nx, nu, ny; p = p, measurement = measurement, measurement_likelihood = measurement_likelihood, loglik_bound = loglik_bound,
+                          jacobians = jacobians)
     dyn = UserDynamics(src, nx, nu, ny; host = (x, u, pp, t) -> dynamics(x, u, p, t))
     meas = UserMeasurement(measurement === nothing ? nothing : (x, u, pp, t) -> measurement(x, u, p, t))
     lik = measurement_likelihood === nothing ? nothing : UserLikelihood((x, u, y, pp, t) -> measurement_likelihood(x, u, y, p, t))

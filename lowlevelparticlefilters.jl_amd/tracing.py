@@ -14,13 +14,19 @@ compiled with -ffp-contract=off), so a traced model written with the built-in mo
 
 What cannot be traced: data-dependent Python control flow (`if x[0] > 0:` — use ifelse), loops whose trip count depends on the state,
 calls into libraries that do not accept these numbers.  Those still go through UserDynamics.  The Julia wrapper's twin is
-`trace_dynamics` in julia/LLPFAmd.jl (a `Tr <: Real` number type with the same node set)."""
+`trace_dynamics` in julia/LLPFAmd.jl (a `Tr <: Real` number type with the same node set).
+
+Jacobians (the extended Kalman filter's `dynamics_jac` / `measurement_jac` members, kernels/models.hpp): `jacobian(graph, outs, nx)`
+differentiates the DAG in forward mode INTO THE SAME graph — common subexpressions are shared with the value, the value's nodes keep their
+ids and their place in the emitted text — and `emit_user_model(..., jacobians=True)` appends the two members.  A structurally zero
+derivative is the absence of a node, never a multiplication by zero.  `evaluate(graph, outs, x, u, t)` runs a DAG on the host."""
 import math
 import struct
 
 import numpy as np
 
-__all__ = ["Tr", "sqrt", "exp", "log", "log1p", "abs_", "maximum", "minimum", "ifelse", "rk4", "trace", "emit_user_model", "traced_dynamics"]
+__all__ = ["Tr", "sqrt", "exp", "log", "log1p", "abs_", "maximum", "minimum", "ifelse", "rk4", "trace", "jacobian", "evaluate", "emit_user_model",
+           "traced_dynamics"]
 
 
 class TraceError(TypeError):
@@ -240,6 +246,182 @@ def trace(fn, nx, nu, p=None, ny=0, with_y=False, n_out=None, what="dynamics"):
     return g, ids
 
 
+def _reachable(g, outs):
+    """the nodes the outputs `outs` depend on (None entries skipped), themselves included"""
+    need = set()
+    stack = [o for o in outs if o is not None]
+    while stack:
+        i = stack.pop()
+        if i in need:
+            continue
+        need.add(i)
+        if g.nodes[i][0] not in _INPUT_OPS and g.nodes[i][0] != "const":
+            stack.extend(g.nodes[i][1:])
+    return need
+
+
+# ---- forward-mode differentiation -------------------------------------------------------------------------------------------------
+_ONE, _TWO, _ZERO = _bits(1.0), _bits(2.0), _bits(0.0)
+
+
+def jacobian(g, outs, nx):
+    """J[k][c] = the node of d outs[k] / d x_c, or None where the derivative is structurally zero.  The derivative nodes are appended to
+    g itself (after every node of the value, which keep their ids).  Rules, with da the derivative of the operand a and v the node itself:
+    add da + db; sub da - db; mul da b + a db; div (da - v db) / b; neg -da; abs a < 0 ? -da : da; sqrt da / (2 v); exp v da; log da / a;
+    log1p da / (1 + a); sel c ? da : db with the same condition node; the inputs u, t, y and constants have none, x_d has the unit one.
+    A missing operand derivative drops its term (no `0 * ...` is formed) and a unit factor drops its multiplication."""
+    one = lambda: g.add("const", _ONE)
+    is_one = lambda i: g.nodes[i] == ("const", _ONE)
+
+    def mul(a, b):
+        return b if is_one(a) else a if is_one(b) else g.add("mul", a, b)
+
+    def div(a, b):
+        return g.add("div", a, b)
+
+    def add(a, b):
+        return b if a is None else a if b is None else g.add("add", a, b)
+
+    def sub(a, b):
+        return a if b is None else g.add("neg", b) if a is None else g.add("sub", a, b)
+
+    need = _reachable(g, outs)
+    d = {}                        # node -> {state index: derivative node}, only the entries that are not structurally zero
+    for i in sorted(need):
+        node = g.nodes[i]
+        op = node[0]
+        if op == "x":
+            d[i] = {node[1]: one()}
+            continue
+        if op in _INPUT_OPS or op == "const" or op in _BOOL:
+            d[i] = {}
+            continue
+        ops = node[1:]
+        cols = sorted(set().union(*[d[a].keys() for a in (ops[1:] if op == "sel" else ops)]))
+        di = {}
+        for c in cols:
+            if op == "sel":
+                da, db = d[ops[1]].get(c), d[ops[2]].get(c)
+                zero = g.add("const", _ZERO)
+                di[c] = g.add("sel", ops[0], zero if da is None else da, zero if db is None else db)
+                continue
+            da = d[ops[0]].get(c)
+            db = d[ops[1]].get(c) if len(ops) > 1 else None
+            a = ops[0]
+            b = ops[1] if len(ops) > 1 else None
+            if op == "add":
+                r = add(da, db)
+            elif op == "sub":
+                r = sub(da, db)
+            elif op == "mul":
+                r = add(None if da is None else mul(da, b), None if db is None else mul(a, db))
+            elif op == "div":
+                r = div(sub(da, None if db is None else mul(i, db)), b)
+            elif op == "neg":
+                r = g.add("neg", da)
+            elif op == "abs":
+                r = g.add("sel", g.add("lt", a, g.add("const", _ZERO)), g.add("neg", da), da)
+            elif op == "sqrt":
+                r = div(da, g.add("mul", g.add("const", _TWO), i))
+            elif op == "exp":
+                r = mul(i, da)
+            elif op == "log":
+                r = div(da, a)
+            elif op == "log1p":
+                r = div(da, g.add("add", one(), a))
+            else:
+                raise TraceError("no derivative rule for the node kind %r" % op)
+            di[c] = r
+        d[i] = di
+    return [[d[o].get(c) for c in range(nx)] for o in outs]
+
+
+def _safe(fn, x, pole):
+    try:
+        return fn(x)
+    except (ValueError, OverflowError, ZeroDivisionError):
+        return pole(x)
+
+
+def _fdiv(a, b):
+    if b != 0.0:
+        return a / b
+    if a != a or a == 0.0:
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def evaluate(g, outs, x, u=(), t=0.0, y=None):
+    """the values of the nodes `outs` of a DAG at (x, u, t, y), in float64 on the host with math's functions (None in outs, a structurally
+    zero derivative, gives 0.0).  `outs` may be nested lists, as jacobian() returns them; the result has the same shape.  Only the nodes
+    the outputs depend on are evaluated, so u, t, y matter only where they are read."""
+    if isinstance(outs, (list, tuple)) and any(isinstance(o, (list, tuple)) for o in outs):
+        flat = [o for row in outs for o in row]
+        vals = evaluate(g, flat, x, u, t, y)
+        it = iter(vals)
+        return [[next(it) for _ in row] for row in outs]
+    v = {}
+    inf = math.inf
+    for i in sorted(_reachable(g, outs)):      # only what the outputs depend on: an input they never read need not be given
+        node = g.nodes[i]
+        op = node[0]
+        a = [v[k] for k in node[1:]] if op not in _INPUT_OPS and op != "const" else None
+        if op == "x":
+            r = float(x[node[1]])
+        elif op == "u":
+            r = float(u[node[1]])
+        elif op == "t":
+            r = float(t)
+        elif op == "y":
+            r = float(y[node[1]])
+        elif op == "const":
+            r = struct.unpack("<d", struct.pack("<Q", node[1]))[0]
+        elif op == "add":
+            r = a[0] + a[1]
+        elif op == "sub":
+            r = a[0] - a[1]
+        elif op == "mul":
+            r = a[0] * a[1]
+        elif op == "div":
+            r = _fdiv(a[0], a[1])
+        elif op == "neg":
+            r = -a[0]
+        elif op == "abs":
+            r = math.fabs(a[0])
+        elif op == "sqrt":
+            r = _safe(math.sqrt, a[0], lambda z: math.nan)
+        elif op == "exp":
+            r = _safe(math.exp, a[0], lambda z: inf)
+        elif op == "log":
+            r = _safe(math.log, a[0], lambda z: -inf if z == 0.0 else math.nan)
+        elif op == "log1p":
+            r = _safe(math.log1p, a[0], lambda z: -inf if z == -1.0 else math.nan)
+        elif op == "lt":
+            r = a[0] < a[1]
+        elif op == "le":
+            r = a[0] <= a[1]
+        elif op == "gt":
+            r = a[0] > a[1]
+        elif op == "ge":
+            r = a[0] >= a[1]
+        elif op == "eq":
+            r = a[0] == a[1]
+        elif op == "ne":
+            r = a[0] != a[1]
+        elif op == "and":
+            r = a[0] and a[1]
+        elif op == "or":
+            r = a[0] or a[1]
+        elif op == "not":
+            r = not a[0]
+        elif op == "sel":
+            r = a[1] if a[0] else a[2]
+        else:
+            raise TraceError("unknown node kind %r" % op)
+        v[i] = r
+    return [0.0 if o is None else v[o] for o in outs]
+
+
 _FMT = {"add": "({0} + {1})", "sub": "({0} - {1})", "mul": "({0} * {1})", "div": "({0} / {1})", "neg": "(-{0})", "abs": "llpf_fabs({0})",
         "sqrt": "llpf_sqrt({0})", "exp": "llpf_exp({0})", "log": "llpf_log({0})", "log1p": "llpf_log1p_nonneg({0})",
         "lt": "({0} < {1})", "le": "({0} <= {1})", "gt": "({0} > {1})", "ge": "({0} >= {1})", "eq": "({0} == {1})", "ne": "({0} != {1})",
@@ -258,17 +440,7 @@ def _const_literal(bits):
 
 def _emit_body(g, outs, out_stmt, uses, indent="        ", tname="t_"):
     """statements computing the nodes reachable from outs (in creation order = the callable's own order), then out_stmt(k, name)"""
-    need = set()
-    stack = list(outs)
-    while stack:
-        i = stack.pop()
-        if i in need:
-            continue
-        need.add(i)
-        op = g.nodes[i][0]
-        if op in _INPUT_OPS or op == "const":
-            continue
-        stack.extend(a for a in g.nodes[i][1:])
+    need = _reachable(g, outs)
     lines = []
     name = {}
     for i in sorted(need):
@@ -293,15 +465,33 @@ def _emit_body(g, outs, out_stmt, uses, indent="        ", tname="t_"):
     return "\n".join(lines)
 
 
-def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_bound=None, p=None):
+def _emit_jac_member(g, outs, nx, member, val, uses):
+    """the `member`(x, val, J) body: the value's statements (the very text of the value member), then the derivative nodes, the value
+    outputs, the Jacobian entries that have a node, and the literal 0.0 of those that are structurally zero"""
+    J = jacobian(g, outs, nx)
+    entries = [(r * nx + c, J[r][c]) for r in range(len(outs)) for c in range(nx)]
+    live = [(k, n) for k, n in entries if n is not None]
+    n_val = len(outs)
+    stmt = lambda k, n: ("%s[%d] = %s;" % (val, k, n)) if k < n_val else ("J[%d] = %s;" % (live[k - n_val][0], n))
+    body = _emit_body(g, list(outs) + [n for _, n in live], stmt, uses)
+    zeros = "".join("\n        J[%d] = 0.0;" % k for k, n in entries if n is None)
+    return "    DEV void %s(const double* x, double* %s, double* J) const {\n%s%s\n    }" % (member, val, body, zeros)
+
+
+def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_bound=None, p=None, jacobians=False):
     """the `struct UserModel` snippet (include/llpf.h: llpf_model_compile) of traced callables.
     dynamics(x, u, p, t) -> nx values; measurement(x, u, p, t) -> ny values (may use neither u nor t: the engine's Model concept hands
     neither to the measurement); loglik(x, u, y, p, t) -> one value (the AdvancedParticleFilter's measurement_likelihood; may use t, not u)
-    with loglik_bound: an upper bound of it (a number), or None (every step then normalises against the true maximum)."""
+    with loglik_bound: an upper bound of it (a number), or None (every step then normalises against the true maximum).
+    jacobians: also emit `dynamics_jac` and `measurement_jac` (forward-mode derivatives of the same traces, jacobian()); without it the
+    text is what it always was."""
     uses = set()
     gd, od = trace(dynamics, nx, nu, p, n_out=nx, what="dynamics")
     body_d = _emit_body(gd, od, lambda k, n: "out[%d] = %s;" % (k, n), uses)
     parts = ["    DEV void dynamics(const double* x, double* out) const {\n%s\n    }" % body_d]
+    jac = []
+    if jacobians:
+        jac.append(_emit_jac_member(gd, od, nx, "dynamics_jac", "fx", set()))
     if measurement is not None:
         um = set()
         gm, om = trace(measurement, nx, nu, p, n_out=ny, what="measurement")
@@ -310,7 +500,12 @@ def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_
             raise TraceError("a traced measurement may depend on the state only (the engine's Model::measurement receives neither u nor t): "
                              "put the dependence into measurement_likelihood")
         parts.append("    DEV void measurement(const double* x, double* out) const {\n%s\n    }" % body_m)
+        if jacobians:
+            jac.append(_emit_jac_member(gm, om, nx, "measurement_jac", "gx", set()))
     else:
+        if jacobians:
+            jac.append("    DEV void measurement_jac(const double* x, double* gx, double* J) const {\n        for (int k = 0; k < %d; ++k) gx[k] = x[k];\n"
+                       "        for (int k = 0; k < %d; ++k) J[k] = (k / %d == k %% %d) ? 1.0 : 0.0;\n    }" % (ny, ny * nx, nx, nx))
         parts.append("    DEV void measurement(const double* x, double* out) const { for (int k = 0; k < %d; ++k) out[k] = x[k]; }" % ny)
     if loglik is not None:
         ul = set()
@@ -321,6 +516,7 @@ def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_
         parts.append("    DEV double loglik(const double* x, const double* y, double t) const {\n%s\n    }" % body_l)
         if loglik_bound is not None:
             parts.append("    DEV double loglik_bound() const { return %s; }" % _const_literal(_bits(loglik_bound)))
+    parts += jac
     src = ("struct UserModel {\n    static constexpr bool RB = false;\n    double u_[%d];\n    double t_;\n"
            "    DEV void prepare(const ModelD* m, const double* u, double t) {\n"
            "        for (int j = 0; j < %d; ++j) u_[j] = (u != nullptr) ? u[j] : 0.0;\n        t_ = t;\n    }\n%s\n};\n"
@@ -328,13 +524,14 @@ def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_
     return src
 
 
-def traced_dynamics(f, nx, nu, p=None, measurement=None, ny=None, measurement_likelihood=None, loglik_bound=None, Ts=1.0):
+def traced_dynamics(f, nx, nu, p=None, measurement=None, ny=None, measurement_likelihood=None, loglik_bound=None, Ts=1.0, jacobians=False):
     """UserDynamics (+ its UserMeasurement / UserLikelihood, as attributes `measurement_model` / `likelihood_model`) from ordinary Python
-    callables with the reference's signatures; the callables themselves remain the host versions (simulate)."""
+    callables with the reference's signatures; the callables themselves remain the host versions (simulate).  jacobians: the snippet also
+    defines dynamics_jac / measurement_jac (what an ExtendedKalmanFilter needs)."""
     from . import api
     if ny is None:
         raise ValueError("ny (the number of outputs) is needed")
-    src = emit_user_model(nx, nu, ny, f, measurement, measurement_likelihood, loglik_bound, p)
+    src = emit_user_model(nx, nu, ny, f, measurement, measurement_likelihood, loglik_bound, p, jacobians=jacobians)
     dyn = api.UserDynamics(src, nx, nu, ny, host=lambda x, u, pp, t: np.asarray(f(list(np.atleast_1d(x)), list(np.atleast_1d(u)) if u is not None else [], p, t), dtype=np.float64))
     dyn.measurement_model = api.UserMeasurement(host=None if measurement is None else
                                                 (lambda x, u, pp, t: np.asarray(measurement(list(np.atleast_1d(x)), [], p, t), dtype=np.float64)))
