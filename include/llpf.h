@@ -479,6 +479,13 @@ int  llpf_ekf_bank_reset(llpf_ekf_bank* b);
 /* new parameters for every filter (same model id and dimensions, nothing reallocated; the state is left as it is, the next reset uses the
  * new d0) */
 int  llpf_ekf_bank_set_models(llpf_ekf_bank* b, const llpf_model* models);
+/* The iterated extended Kalman filter (the reference's IteratedExtendedKalmanFilter): correct! becomes a Gauss-Newton iteration that
+ * moves the linearisation point of g from the prior mean towards the posterior mode — at most maxiters linearisations per step, stopped
+ * once no state moved by more than epsilon between two iterates (csrc/shared/llpf_ekf.h: llpf_iekf_iterate; the full step, no step
+ * length).  The setting holds for every later run until it is set again; set_models, set_state and reset keep it.  After create it is
+ * (1, 0.0), the plain filter.  maxiters must be in 1..100 (LLPF_IEKF_MAXITERS) and epsilon finite and >= 0, else LLPF_ERR_ARG.  ll, e,
+ * xt and Rt of a step are those of the last linearisation.  The first iterated use of a run-time compiled model compiles its kernel. */
+int  llpf_ekf_bank_set_iterations(llpf_ekf_bank* b, int32_t maxiters, double epsilon);
 /* T steps of every filter; U, Y, per_filter, ll_total and out as llpf_kalman_bank_run takes them */
 int  llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
                        double* ll_total, const llpf_kalman_outputs* out);

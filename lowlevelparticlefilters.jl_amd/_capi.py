@@ -60,6 +60,7 @@ SYMBOLS = {
     "llpf_ekf_bank_destroy": [_vp],
     "llpf_ekf_bank_reset": [_vp],
     "llpf_ekf_bank_set_models": [_vp, C.POINTER(S.Model)],
+    "llpf_ekf_bank_set_iterations": [_vp, C.c_int32, C.c_double],
     "llpf_ekf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
     "llpf_ekf_bank_get_state": [_vp, _dp, _dp],
     "llpf_ekf_bank_set_state": [_vp, _dp, _dp],
@@ -643,6 +644,11 @@ class EkfBankHandle(_KfBankHandle):
 
     def set_models(self, models):
         self._call("set_models", (S.Model * self.F)(*models))
+
+    def set_iterations(self, maxiters, epsilon):
+        """the iterated filter for every later run: at most `maxiters` linearisations of a step's measurement, stopped once no state moved
+        by more than `epsilon`; (1, 0.0) is the plain filter (llpf_ekf_bank_set_iterations)"""
+        self._call("set_iterations", int(maxiters), float(epsilon))
 
     def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
         """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""

@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -682,6 +682,23 @@ class ExtendedKalmanFilter(_NonlinearKalmanFilter):
         return _capi.EkfBankHandle(self.device, [self._model])
 
 
+class IteratedExtendedKalmanFilter(ExtendedKalmanFilter):
+    """IteratedExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; maxiters=10, epsilon=1e-8, Ts, nu, ny, p, device) — the iterated
+    extended Kalman filter: ExtendedKalmanFilter whose correct! is a Gauss-Newton iteration that moves the linearisation point of g from
+    the prior mean towards the posterior mode, at most `maxiters` linearisations per step, stopped once no state moved by more than
+    `epsilon` (csrc/shared/llpf_ekf.h: llpf_iekf_iterate is the definition; the full step, no step length).  predict! is the extended
+    filter's, and maxiters=1 is that filter bit for bit.  ll, e, xt and Rt of a step are those of its last linearisation."""
+
+    def __init__(self, dynamics, measurement, R1, R2, d0, *, maxiters=10, epsilon=1e-8, Ts=1.0, nu=-1, ny=-1, p=None, device=0):
+        super().__init__(dynamics, measurement, R1, R2, d0, Ts=Ts, nu=nu, ny=ny, p=p, device=device)
+        self.maxiters, self.epsilon = int(maxiters), float(epsilon)
+
+    def _open(self):
+        h = super()._open()
+        h.set_iterations(self.maxiters, self.epsilon)
+        return h
+
+
 def _need_jacobians(model):
     """a compiled model under an extended Kalman filter must define both Jacobian members"""
     if model.model_id < S.MODEL_USER_BASE:
@@ -767,6 +784,28 @@ class ExtendedKalmanFilterBank(_KfBank):
 
     def smooth(self, u, y, outputs=None, forward=()):
         raise TypeError("the extended Kalman filter has no smoother yet: use UnscentedKalmanFilterBank.smooth")
+
+
+class IteratedExtendedKalmanFilterBank(ExtendedKalmanFilterBank):
+    """n independent iterated extended Kalman filters on one device: ExtendedKalmanFilterBank with IteratedExtendedKalmanFilter's
+    correct!, one (maxiters, epsilon) for the bank.  The lanes of a wave stop after different numbers of linearisations; a step costs
+    what its slowest lane needs."""
+
+    def __init__(self, filters_spec, device=0, Ts=1.0, maxiters=10, epsilon=1e-8):
+        super().__init__(filters_spec, device, Ts)
+        self.set_iterations(maxiters, epsilon)
+
+    @classmethod
+    def from_filter_bank(cls, bank, device=None, maxiters=10, epsilon=1e-8):
+        """the iterated extended twin of a FilterBank (ExtendedKalmanFilterBank.from_filter_bank)"""
+        self = super().from_filter_bank(bank, device)
+        self.set_iterations(maxiters, epsilon)
+        return self
+
+    def set_iterations(self, maxiters, epsilon):
+        """(maxiters, epsilon) of every later run (llpf_ekf_bank_set_iterations); (1, 0.0) is the extended filter"""
+        self._h.set_iterations(maxiters, epsilon)
+        self.maxiters, self.epsilon = int(maxiters), float(epsilon)
 
 
 class RBMeasurementModel:

@@ -280,6 +280,11 @@ int llpf_ekf_bank_create(int32_t device, const llpf_model* models, int32_t n_fil
 int llpf_ekf_bank_destroy(llpf_ekf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_ekf_bank_destroy)
 int llpf_ekf_bank_reset(llpf_ekf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_ekf_bank_reset)
 int llpf_ekf_bank_set_models(llpf_ekf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return ekf_set_models(*b, models); } LLPF_GUARD(llpf_ekf_bank_set_models)
+int llpf_ekf_bank_set_iterations(llpf_ekf_bank* b, int32_t maxiters, double epsilon) LLPF_TRY {
+    CHK(ekf_check_iterations(maxiters, epsilon));
+    if (!b) return fail(LLPF_ERR_ARG, "ekf: null handle");
+    return ekf_set_iterations(*b, maxiters, epsilon);
+} LLPF_GUARD(llpf_ekf_bank_set_iterations)
 int llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
                       const llpf_kalman_outputs* out) LLPF_TRY {
     NEEDF(b);

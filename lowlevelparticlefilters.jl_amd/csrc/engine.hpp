@@ -372,6 +372,10 @@ hipError_t launch_ukf_smooth(int model_id, int nx, int ny, const ModelD* models,
 // runs one chunk of steps
 int ekf_prepare(int model_id, int nx, int ny, std::string& err);
 hipError_t launch_ekf(int model_id, int nx, int ny, const ModelD* models, const EkfArgs& a, hipStream_t s);
+// the iterated extended Kalman filter of those banks (k_ekf<..., IekfArgs>, maxiters >= 2): iekf_prepare compiles that kernel of a
+// run-time compiled model on the first iterated use of the model, into a cache entry of its own; launch_iekf runs one chunk of steps
+int iekf_prepare(int model_id, int nx, int ny, std::string& err);
+hipError_t launch_iekf(int model_id, int nx, int ny, const ModelD* models, const EkfArgs& a, int32_t maxiters, double epsilon, hipStream_t s);
 // kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
 bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
 const char* jit_prelude();

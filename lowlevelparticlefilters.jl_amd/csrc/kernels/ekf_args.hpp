@@ -3,6 +3,7 @@
 // One launch is one chunk of steps [t0, t0 + Tc) of F extended Kalman filters, one thread per filter.  Device arrays are SoA / time-major
 // as k_kalman's: a wave's 64 lanes read and write whole lines.
 struct EkfArgs {
+    static constexpr bool ITERATED = false;
     const double* par;       // [np(nx) + np(ny)][F] R1, R2 as packed lower triangles (shared/llpf_ekf.h: LLPF_EKF_OFF_*)
     double* state;           // [nx + np + 1][F] x, packed R, the run's running ll_total: in at t0, out at t0 + Tc
     const double* u;         // inputs of the chunk: [Tc][nu] shared, or [Tc][F][nu] (u_per = 1); unused when nu = 0
@@ -16,4 +17,10 @@ struct EkfArgs {
     int32_t first;           // 1: the first chunk of a run (ll_total starts at 0)
     int32_t pad;
     double t_index0, Ts;     // tau_t = (t_index0 + t) * Ts, as llpf_run and k_simulate take it
+};
+// ... and of its iterated form, k_ekf<Model, NX, NY, IekfArgs>: the same chunk with the iteration of correct! (shared/llpf_ekf.h)
+struct IekfArgs : EkfArgs {
+    static constexpr bool ITERATED = true;
+    int32_t maxiters, pad2;  // 2..LLPF_IEKF_MAXITERS linearisations of a step's measurement at most
+    double epsilon;          // >= 0: the step is over once no state moved by more than this
 };

@@ -37,7 +37,7 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
        GPUKalmanFilter, GPUKalmanFilterBank, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
-       ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank
+       ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank, set_iterations!
 
 const LIB = get(ENV, "LLPF_HIP_LIB", joinpath(@__DIR__, "..", "libllpf_hip.so"))
 const MAXD = 16          # LLPF_MAX_DIM: states / outputs
@@ -1326,21 +1326,33 @@ function need_jacobians(cm::CModel)
     nothing
 end
 """
-    GPUExtendedKalmanFilterBank(filters; Ts = 1.0, device = 0)
+    GPUExtendedKalmanFilterBank(filters; Ts = 1.0, device = 0, maxiters = 1, epsilon = 0.0)
 
 Independent first-order extended Kalman filters (additive noise) on the device, one GPU thread each; `filters` is a vector of
 (dynamics, measurement, R1, R2, d0) tuples as `GPUUnscentedKalmanFilterBank` takes them.  The model supplies its Jacobians: the built-in
 descriptors have them, `trace_dynamics(...; jacobians = true)` differentiates a closure, and a UserDynamics snippet must define
 `dynamics_jac` and `measurement_jac` itself (the library refuses one that does not).  `loglik(bank, u, y)` is the vector of every
-filter's log-likelihood.
+filter's log-likelihood.  `maxiters > 1` makes every filter the iterated extended Kalman filter (`set_iterations!`).
 """
-function GPUExtendedKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0)
+function GPUExtendedKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0, maxiters = 1, epsilon = 0.0)
     cms = [ukf_model(f, Ts) for f in filters]
     foreach(need_jacobians, cms)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:llpf_ekf_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Int32, Ref{Ptr{Cvoid}}), device, cms, length(cms), h))
     b = GPUExtendedKalmanFilterBank(h[], length(cms), cms[1].nx, cms[1].nu, cms[1].ny, Float64(Ts))
     finalizer(x -> ccall((:llpf_ekf_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    (maxiters, epsilon) == (1, 0.0) || set_iterations!(b, maxiters, epsilon)
+    b
+end
+"""
+    set_iterations!(bank, maxiters, epsilon)
+
+The iterated extended Kalman filter (the reference's `IteratedExtendedKalmanFilter`) for every later run: `correct!` becomes a
+Gauss-Newton iteration that moves the linearisation point of the measurement from the prior mean towards the posterior mode, at most
+`maxiters` (1..100) linearisations per step, stopped once no state moved by more than `epsilon` (>= 0).  `(1, 0.0)` is the plain filter.
+"""
+function set_iterations!(b::GPUExtendedKalmanFilterBank, maxiters, epsilon)
+    check(ccall((:llpf_ekf_bank_set_iterations, LIB), Cint, (Ptr{Cvoid}, Int32, Float64), b.h, Int32(maxiters), Float64(epsilon)))
     b
 end
 function set_parameters!(b::GPUExtendedKalmanFilterBank, filters::Vector)
@@ -1388,20 +1400,24 @@ function set_state!(b::GPUExtendedKalmanFilterBank, x, R)
 end
 
 """
-    GPUExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0)
+    GPUExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0, maxiters = 1, epsilon = 0.0)
 
 The textbook first-order extended Kalman filter with additive noise — the Jacobian of the measurement at the prior mean, of the dynamics
 at the posterior mean — run on the device (a bank of one filter, llpf_ekf_bank_*): `forward_trajectory` returns the reference's
-`KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `correct!`, `predict!`, `state`, `covariance`.  Unverified against the
-reference's `ExtendedKalmanFilter` (its source was not available when this was written).
+`KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `correct!`, `predict!`, `state`, `covariance`.  `maxiters > 1` (the
+reference's `IteratedExtendedKalmanFilter` has `maxiters = 10, epsilon = 1e-8`) iterates `correct!` as `set_iterations!` describes.
+Unverified against the reference's `ExtendedKalmanFilter` and `IteratedExtendedKalmanFilter` (their source was not available when this
+was written).
 """
 mutable struct GPUExtendedKalmanFilter
     bank::GPUExtendedKalmanFilterBank
     Ts::Float64
     index::Int
 end
-GPUExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0) =
-    GPUExtendedKalmanFilter(GPUExtendedKalmanFilterBank([(dynamics, measurement, R1, R2, d0)]; Ts = Ts, device = device), Float64(Ts), 0)
+GPUExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0, maxiters = 1, epsilon = 0.0) =
+    GPUExtendedKalmanFilter(GPUExtendedKalmanFilterBank([(dynamics, measurement, R1, R2, d0)]; Ts = Ts, device = device, maxiters = maxiters,
+                                                        epsilon = epsilon), Float64(Ts), 0)
+set_iterations!(kf::GPUExtendedKalmanFilter, maxiters, epsilon) = (set_iterations!(kf.bank, maxiters, epsilon); kf)
 reset!(kf::GPUExtendedKalmanFilter) = (reset!(kf.bank); kf.index = 1; nothing)
 loglik(kf::GPUExtendedKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
 "update!(ekf, u, y): correct! then predict! at time t; returns (ll, e)"

@@ -4,7 +4,12 @@ only and with every per-step output, against the single-thread host build of the
 unscented bank (llpf_ukf_bank_run, Merwe (1, 0, 1)) timed in the same process on the same inputs.  End-to-end wall time of the call
 around its synchronise (median of --reps after one warm-up, with the spread of the repetitions); the kernels' own times come from a
 `rocprofv3 --kernel-trace --stats` run of this script.  Runs whose outputs would exceed --max-out-gb of host memory are skipped.
-Prints one JSON line per configuration."""
+Prints one JSON line per configuration.
+--iterated: the iterated extended Kalman filter (llpf_ekf_bank_set_iterations, maxiters 10, epsilon 1e-8) beside the plain one instead
+of the unscented bank — the same bank handle, ll_total only, plain then iterated in the same process — on the same models and sizes and
+on a bank of pendulum snippets with per-filter priors (tests/ekf_common.py: PENDULUM_JAC_SRC), the one case whose lanes iterate more
+than twice; its mean linearisations per step come from the host build (tests/iekf_host.c) over --host-filters filters.  In a rocprofv3
+run the plain kernel is k_ekf<..., EkfArgs> and the iterated one k_ekf<..., IekfArgs>."""
 import argparse
 import json
 import os
@@ -20,6 +25,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import llpf_amd  # noqa: E402,F401
 from llpf_amd import _capi, _structs as S  # noqa: E402
 import ekf_common as ec  # noqa: E402
+import iekf_common as ic  # noqa: E402
 import kalman_common as kc  # noqa: E402
 import models as M  # noqa: E402
 import ukf_common as uc  # noqa: E402
@@ -45,6 +51,45 @@ def timed(bank, U, Y, outputs, t_index0, reps):
     return float(np.median(ts[1:])), min(ts[1:]), max(ts[1:])
 
 
+ITERATIONS = (10, 1e-8)
+
+
+def iterated(a):
+    """plain against iterated, ll only: one JSON line per (case, F)"""
+    host = ic.build_host(tempfile.mkdtemp())
+    rng = np.random.default_rng(0)
+    T = a.T
+    for case in a.cases.split(",") + ["pendulum"]:
+        kind = None
+        if case == "quadtank":
+            nx, ny = 4, 2
+            base = hbase = quadtank_models(256)
+            U, Y = M.quadtank_data(T)
+            t_index0 = 1.0
+        elif case == "pendulum":
+            nx, ny = 2, 1
+            hbase, base = ic.pendulum_bank_models(256), ic.pendulum_bank_models(256, _capi.model_compile(ec.PENDULUM_JAC_SRC, 2, 1))
+            U, Y = uc.pendulum_data(T)
+            t_index0, kind = 0.0, ec.KIND_PENDULUM
+        else:
+            nx, ny = (int(v) for v in case.split("x"))
+            base = hbase = [kc.random_system(rng, nx, ny, 1, k % 3, D=False)[0] for k in range(256)]
+            U = rng.standard_normal((T, 1))
+            Y = rng.standard_normal((T, ny))
+            t_index0 = 0.0
+        h, _ = ic.host_run(host, hbase[: a.host_filters], U, Y, T, *ITERATIONS, t_index0=t_index0, kind=kind)
+        for F in (int(v) for v in a.F.split(",")):
+            be = _capi.EkfBankHandle(0, [base[k % len(base)] for k in range(F)])
+            wall, lo, hi = timed(be, U, Y, (), t_index0, a.reps)
+            be.set_iterations(*ITERATIONS)
+            iwall, ilo, ihi = timed(be, U, Y, (), t_index0, a.reps)
+            print(json.dumps(dict(bench="iekf", case=case, nx=nx, ny=ny, F=F, T=T, outputs="ll", maxiters=ITERATIONS[0], epsilon=ITERATIONS[1],
+                                  mean_linearisations=float(h["iters"].mean()), max_linearisations=int(h["iters"].max()),
+                                  wall_s=wall, wall_min_s=lo, wall_max_s=hi, iterated_wall_s=iwall, iterated_wall_min_s=ilo,
+                                  iterated_wall_max_s=ihi, iterated_over_plain=iwall / wall)), flush=True)
+            be.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--F", default="1000,10000,100000")
@@ -53,7 +98,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--max-out-gb", type=float, default=6.0)
     ap.add_argument("--host-filters", type=int, default=100)
+    ap.add_argument("--iterated", action="store_true")
     a = ap.parse_args()
+    if a.iterated:
+        return iterated(a)
     host = ec.build_host(tempfile.mkdtemp())
     rng = np.random.default_rng(0)
     T = a.T
