@@ -575,7 +575,8 @@ int  llpf_resample_count(llpf_filter* f, int64_t* n);
 int  llpf_bank_resample_count(llpf_bank* b, int64_t* n);
 /* elapsed device milliseconds of the last llpf_run / llpf_bank_run (hipEvents on the handle's stream) */
 int  llpf_last_run_ms(llpf_filter* f, double* ms);
-/* how the last llpf_run drove its timesteps: launches of the fused predict! kernel (0: the balanced form ran); timesteps that took the
+/* how the last llpf_run drove its timesteps: launches of the fused predict! kernel (0: the balanced form ran; after llpf_aux_run, the
+ * launches of the auxiliary filter's fused second half, the other two figures being left as they were); timesteps that took the
  * source-side form of the balanced timestep (dynamics once per surviving source, k_resample_fx; 0: dynamics per output particle); and
  * the survivor fraction the choice for the NEXT run is made by (distinct ancestors per predict! / N, a step that did not resample
  * counting as 1; -1 when the model cannot take the source-side form).  Results do not depend on the form: the choice is a schedule. */

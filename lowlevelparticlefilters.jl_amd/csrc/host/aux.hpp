@@ -47,6 +47,7 @@ static int aux_launch_resprop(Bank& b, bool has_y1, double t, bool fast, int onl
     st.only_fallback = only_fb;
     ProfScope ps(b, LLPF_PROF_PROPAGATE);
     HIPC(launch_resprop(d, ra, st, 1, b.stream));
+    b.last_run_launches += 1;
     return LLPF_OK;
 }
 static int aux_ensure_lam(Bank& b) { return b.d_lam.ensure_zeroed((size_t)b.F * b.Ns, b.stream); }
@@ -237,6 +238,7 @@ static int bank_aux_run(Bank& b, const double* U, const double* Y, int64_t T, in
     const int want_xm = xmean ? 1 : 0;
     if (want_xm) CHK(ensure_xmpart(b));
     b.run_resamples = 0;
+    b.last_run_launches = 0;      // counted by aux_launch_resprop; stays 0 where the balanced second half runs (residual resampling)
     {
         std::vector<FilterScal> h;
         CHK(scal_download(b, h));

@@ -157,8 +157,11 @@ struct TileSum {
     DEV void flush(uint64_t* sh_tq, uint64_t* tq_global, int32_t tbase) {
         if (run) {
             const int32_t idx = tcur - tbase;
-            if (idx >= 0 && idx < 8) atomicAdd(reinterpret_cast<unsigned long long*>(sh_tq + idx), (unsigned long long)run);
-            else atomicAdd(reinterpret_cast<unsigned long long*>(tq_global + tcur), (unsigned long long)run);
+            // two atomics the compiler cannot merge into ONE on a generic pointer (different scopes): behind a flat atomic it can no longer
+            // tell LDS from memory traffic, and every wait of the output loop after it — all of them, round the back edge — becomes a full
+            // drain of both counters (the gather's consumption: vmcnt(0) where nothing but the gather's own second half need be waited for)
+            if (idx >= 0 && idx < 8) __hip_atomic_fetch_add(sh_tq + idx, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else __hip_atomic_fetch_add(tq_global + tcur, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         run = 0;
     }
@@ -343,6 +346,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     if (a.dbg && threadIdx.x == 0 && f == 0) a.dbg[(size_t)tile * 8 + 5] = (uint64_t)(last - first);
 #endif
     const uint32_t tile0 = (uint32_t)tile * TILE, ulast = (uint32_t)last, ucend = (uint32_t)c_end;
+    // end of the outputs that have an owner in this tile; [umain, ulast) is the last tile's [c_end, M) of a resampling step, else empty
+    // PEEL: the merged-schedule kernels.  The run-time-split Rao-Blackwellized kernels keep the test inside their one loop (a second copy
+    // of their body costs them 16 bytes of stack), and so do the split-schedule forms: their loops do not wait for their gathers, and with
+    // the second loop they measured 1.1 % (C4 share) and 1.5 % (N = 1.6e7, threshold 1) slower (EXPERIMENTS: the output loop's rounds)
+    constexpr bool PEEL = WEIGHT && ACC && !RBFAT;
+    const uint32_t umain = (res && PEEL) ? (ucend < ulast ? ucend : ulast) : ulast;
     __builtin_amdgcn_s_setprio(0);
     // tile-local source of output o (< c_end): the owner table, the descent beyond it
     auto owner_of = [&](uint32_t o) -> uint32_t {
@@ -358,13 +367,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     // the block-uniform resample flag where that measured faster (split-schedule and Rao-Blackwellized kernels: each version
     // keeps only its own uniform values live; the merged single-filter kernel is 0.3 us faster with ONE loop and the flag
     // tested inside).
-#define LLPF_OUTPUT_LOOP(RESX, NTLX) \
+    // The rounds of [c_end, M) are a loop of their own behind the others (STALE = 1; 0: the rounds with an owner; 2: either, tested per
+    // round): their source is a LOAD (the previous ancestor), the loop's only other vector load, and with it in the common round the
+    // compiler's wait-count pass drained the vector-memory counter four times at the top of EVERY round — stores count in vmcnt on
+    // gfx950, so each round's owner lookup and gather waited for the previous round's write-through stores to be acknowledged
+    // (profiles/loop_chain_isa.txt).  A thread still visits its outputs in increasing order (TileSum sees the same sequence), and the
+    // body is the same text.
+#define LLPF_OUTPUT_ROUNDS(RESX, NTLX, STALE, OEND) \
 _Pragma("unroll 1") \
-    for (uint32_t o = (uint32_t)first + threadIdx.x; o < ulast; o += BLOCK) { \
+    for (; o < (OEND); o += BLOCK) { \
         uint32_t src = o; \
         double wprev = b.log1N; \
         if (RESX) { \
-            if (o < ucend) src = tile0 + owner_of(o); \
+            if ((STALE) == 0 || ((STALE) == 2 && o < ucend)) src = tile0 + owner_of(o); \
             else src = anc_ident_prev ? o : (uint32_t)ld_off(anc, o << 2); \
             Mem<LLPF_STCOH0>::st_off(anc, o << 2, (int32_t)src); \
             if (AUX) wprev = ld_off(lamp, o << 3) - lN; \
@@ -376,17 +391,26 @@ _Pragma("unroll 1") \
         double xs[NX]; \
         const double wv = pc.template one<LLPF_RESPROP_ST, NTLX>(src, o, wprev, bad, xs); \
         bmax = llpf_fmax(bmax, wv); \
+        LLPF_OUTPUT_ACC(o, wv, xs) \
+    }
+#define LLPF_OUTPUT_ACC(o, wv, xs) \
         if (WEIGHT && ACC) { \
             double e; \
             const uint64_t q = wacc.add(wv, pc.off, st.K, st.need_e2 != 0, &e); \
-            Mem<LLPF_STCOH0>::st_off(pc.qnext, o << 3, q); \
+            Mem<LLPF_STCOH0>::st_off(pc.qnext, (o) << 3, q); \
             ts.add(o, q, sh_tq, tq_next, tbase); \
             if (st.want_xmean) { \
 _Pragma("unroll") \
                 for (int d = 0; d < NX; ++d) xm[d] = xm[d] + xs[d] * e; \
             } \
-        } \
-    }
+        }
+#define LLPF_OUTPUT_STALE \
+    if (umain < ulast) { LLPF_OUTPUT_ROUNDS(true, false, 1, ulast) }
+#define LLPF_OUTPUT_LOOP(RESX, NTLX) { \
+    uint32_t o = (uint32_t)first + threadIdx.x; \
+    LLPF_OUTPUT_ROUNDS(RESX, NTLX, PEEL ? 0 : 2, umain) \
+    if (PEEL && (RESX)) { LLPF_OUTPUT_STALE } \
+}
     // The same loop with the sources of LLPF_RESPROP_PF consecutive rounds requested together, for the split-schedule form — the kernel of
     // filters and banks beyond 3 M particles, whose states come from HBM instead of the Infinity Cache.  Worth 2 % at depth 2 and
     // nothing beyond (depth 4 is slower): the loop of such a launch does not wait for its gathers — what moved it was the store policy
@@ -475,6 +499,9 @@ _Pragma("unroll") \
     else if (res) { LLPF_OUTPUT_LOOP(true, false) }
     else { LLPF_OUTPUT_LOOP(false, (LLPF_RESPROP_LD_ID != 0)) }
 #undef LLPF_OUTPUT_LOOP
+#undef LLPF_OUTPUT_ROUNDS
+#undef LLPF_OUTPUT_STALE
+#undef LLPF_OUTPUT_ACC
 #undef LLPF_OUTPUT_LOOP_PF
 #undef LLPF_OUTPUT_LOOP_ID2
     if (WEIGHT && ACC) ts.flush(sh_tq, tq_next, tbase);

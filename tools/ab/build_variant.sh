@@ -11,6 +11,6 @@ cd $C
 if [ $UNIT = k_rbfull ] || [ $UNIT = k_step ]; then FLAGS="$FLAGS -mllvm -disable-machine-licm"; fi
 /opt/rocm/bin/hipcc $FLAGS "$@" -c $UNIT.hip -o /tmp/${UNIT}_$NAME.o
 OBJS=""
-for u in kernels k_step k_resprop k_resprop_split k_rbfull k_quantile k_simulate k_kalman k_ukf capi; do if [ $u = $UNIT ]; then OBJS="$OBJS /tmp/${UNIT}_$NAME.o"; else OBJS="$OBJS $u.o"; fi; done
+for u in kernels k_step k_resprop k_resprop_split k_rbfull k_quantile k_simulate k_kalman k_ukf k_ekf capi; do if [ $u = $UNIT ]; then OBJS="$OBJS /tmp/${UNIT}_$NAME.o"; else OBJS="$OBJS $u.o"; fi; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/lib_$NAME.so $OBJS -lhiprtc
 echo built $ROOT/lib_$NAME.so
