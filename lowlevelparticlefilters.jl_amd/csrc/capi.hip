@@ -252,7 +252,7 @@ int llpf_ukf_bank_create(int32_t device, const llpf_model* models, int32_t n_fil
 } LLPF_GUARD(llpf_ukf_bank_create)
 int llpf_ukf_bank_destroy(llpf_ukf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_ukf_bank_destroy)
 int llpf_ukf_bank_reset(llpf_ukf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_ukf_bank_reset)
-int llpf_ukf_bank_set_models(llpf_ukf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return ukf_set_models(*b, models); } LLPF_GUARD(llpf_ukf_bank_set_models)
+int llpf_ukf_bank_set_models(llpf_ukf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return kf_model_set_models(*b, models); } LLPF_GUARD(llpf_ukf_bank_set_models)
 int llpf_ukf_bank_set_weights(llpf_ukf_bank* b, const llpf_ukf_weights* w) LLPF_TRY { NEEDF(b); return ukf_set_weights(*b, w); } LLPF_GUARD(llpf_ukf_bank_set_weights)
 int llpf_ukf_bank_run(llpf_ukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
                       const llpf_kalman_outputs* out) LLPF_TRY {
@@ -273,13 +273,13 @@ int llpf_ekf_bank_create(int32_t device, const llpf_model* models, int32_t n_fil
     *out = nullptr;
     std::unique_ptr<llpf_ekf_bank> b(new (std::nothrow) llpf_ekf_bank());
     if (!b) return fail(LLPF_ERR_ALLOC, "out of host memory");
-    CHK(ekf_create(device, models, n_filters, *b));
+    CHK(kf_model_create(*b, device, models, n_filters, "ekf_create", ekf_prepare));
     *out = b.release();
     return LLPF_OK;
 } LLPF_GUARD(llpf_ekf_bank_create)
 int llpf_ekf_bank_destroy(llpf_ekf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_ekf_bank_destroy)
 int llpf_ekf_bank_reset(llpf_ekf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_ekf_bank_reset)
-int llpf_ekf_bank_set_models(llpf_ekf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return ekf_set_models(*b, models); } LLPF_GUARD(llpf_ekf_bank_set_models)
+int llpf_ekf_bank_set_models(llpf_ekf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return kf_model_set_models(*b, models); } LLPF_GUARD(llpf_ekf_bank_set_models)
 int llpf_ekf_bank_set_iterations(llpf_ekf_bank* b, int32_t maxiters, double epsilon) LLPF_TRY {
     CHK(ekf_check_iterations(maxiters, epsilon));
     if (!b) return fail(LLPF_ERR_ARG, "ekf: null handle");

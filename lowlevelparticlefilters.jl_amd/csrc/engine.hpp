@@ -263,6 +263,57 @@ struct ResArgs {
 };
 
 // ---- end of the part the run-time compiled user-model kernels see (tools/gen_jit_prelude.py cuts here) ----
+}  // namespace llpf
+
+#include <map>
+#include <memory>
+#include <mutex>
+#include <type_traits>
+#include <vector>
+
+namespace llpf {
+
+// One run-time compiled (hiprtc) program, whatever it holds: a user model's step kernels, a k_rbfull shape, a model's k_simulate, k_ukf
+// or k_ekf.  Both functions are defined in kernels/jit.hpp (k_step.hip) and take no lock: whoever owns the program holds its own.
+struct JitProgram {
+    std::vector<char> code;
+    std::vector<std::string> names;            // lowered kernel names, in the order of the name expressions given to the compile
+    struct PerDevice { hipModule_t mod = nullptr; std::vector<hipFunction_t> fn; };
+    std::vector<PerDevice> dev;                // indexed by device ordinal, loaded on first use
+};
+// compiles `src` (named `file` in the log) for the current device's arch (gfx950 when none is visible) with the engine's own options
+// and `extra_opts`, and resolves the kernel name expressions `exprs`.  0, or -1 with `err` set; `what` is the prefix of a compile error
+int jit_program_compile(const std::string& src, const char* file, const std::vector<std::string>& exprs, const std::vector<const char*>& extra_opts,
+                        const char* what, std::unique_ptr<JitProgram>& out, std::string& err);
+// the current device's handle of kernel `which` of the program (module and function loaded on first use)
+hipError_t jit_program_function(JitProgram& prog, int which, hipFunction_t* fn);
+
+// Programs by key, compiled on first use.  The compile runs outside the lock, so two threads may compile the same key side by side:
+// the first registration stays.
+struct JitCache {
+    std::mutex mutex;
+    std::map<std::string, std::unique_ptr<JitProgram>> progs;
+    // build(): the compiled program, or null (with the caller's error text set).  0, or -1
+    template <class Build>
+    int prepare(const std::string& key, Build&& build) {
+        {
+            std::lock_guard<std::mutex> lk(mutex);
+            if (progs.count(key)) return 0;
+        }
+        std::unique_ptr<JitProgram> p = build();
+        if (!p) return -1;
+        std::lock_guard<std::mutex> lk(mutex);
+        if (!progs.count(key)) progs[key] = std::move(p);
+        return 0;
+    }
+    hipError_t function(const std::string& key, int which, hipFunction_t* fn) {
+        std::lock_guard<std::mutex> lk(mutex);
+        auto it = progs.find(key);
+        if (it == progs.end()) return hipErrorInvalidValue;      // prepare() compiles it first
+        return jit_program_function(*it->second, which, fn);
+    }
+};
+
 #include "kernels/sim_args.hpp"
 #include "kernels/ukf_args.hpp"
 #include "kernels/ekf_args.hpp"

@@ -1,5 +1,6 @@
 // host/kfbank.hpp — what the banks of one-thread-per-filter Kalman filters share (host/kalman.hpp, host/ukf.hpp, host/ekf.hpp): the bank, its state, the
-// checks of a run's arguments and the drivers of the forward and the backward pass.  Part of capi.hip (one translation unit).
+// checks of a run's arguments and the drivers of the forward and the backward pass; for the two model-driven banks also their models
+// (KfModelBank).  Part of capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
 // Device layout: the constants par [npar][F] (each bank's own rows) and the state [nx + np + 1][F] (x, packed R, the running ll_total of a
 // run), SoA so that lane f of a wave reads column f.  A run drives T through the chunked staging pipeline of host/pipe.hpp, counting a
@@ -112,6 +113,59 @@ static int kf_open(KfBank& b, int32_t device, int32_t F, int npar, const char* s
     return LLPF_OK;
 }
 
+// ---- the banks whose filters are driven by a model's own functions (host/ukf.hpp, host/ekf.hpp) ----
+// Next to the bank: the model descriptors ModelD[F] as a bank of particle filters keeps them (the model's own parameters) and a zero
+// input; par is [np(nx) + np(ny)][F] (R1, R2 packed, from the llpf_model covariances as given — GaussD keeps a factor, not the covariance)
+struct KfModelBank : KfBank {
+    const char* filter_name;          // kf_pack_models: what the Rao-Blackwellized ids are said not to have
+    int need_traits;                  // ... and the optional members a compiled model must define for this bank
+    int model_id = 0;
+    double Ts = 1.0;
+    DevBuf<ModelD> d_models;
+    DevBuf<double> d_zero;
+    KfModelBank(const char* who_, const char* filter_name_, int need_traits_) : KfBank(who_), filter_name(filter_name_), need_traits(need_traits_) {}
+};
+
+// `site`: the bank's create site of test_throw; prepare(model_id, nx, ny, err): the bank's kernel of a run-time compiled model, on the
+// first bank of that model
+static int kf_model_create(KfModelBank& b, int32_t device, const llpf_model* models, int32_t F, const char* site,
+                           int (*prepare)(int, int, int, std::string&)) {
+    std::vector<ModelD> hm;
+    std::vector<double> par;
+    CHK(kf_pack_models(b.who, b.filter_name, b.need_traits, models, F, b.model_id, b.nx, b.ny, b.nu, hm, par, b.h_init));
+    CHK(kf_open(b, device, F, LLPF_KF_NP(b.nx) + LLPF_KF_NP(b.ny), site));
+    b.Ts = models[0].Ts;
+    {
+        std::string err;
+        if (prepare(b.model_id, b.nx, b.ny, err) != 0) return fail(LLPF_ERR_HIP, std::string(b.who) + ": " + err);
+    }
+    CHK(b.d_models.ensure(hm.size()));
+    CHK(b.d_par.ensure(par.size()));
+    CHK(b.d_state.ensure(b.h_init.size()));
+    CHK(b.d_zero.ensure(MAXU));
+    HIPC(hipMemsetAsync(b.d_zero, 0, sizeof(double) * MAXU, b.stream));
+    HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
+static int kf_model_set_models(KfModelBank& b, const llpf_model* models) {
+    std::vector<ModelD> hm;
+    std::vector<double> par, init;
+    int id = 0, nx = 0, ny = 0, nu = 0;
+    CHK(kf_pack_models(b.who, b.filter_name, b.need_traits, models, b.F, id, nx, ny, nu, hm, par, init));
+    if (id != b.model_id || nx != b.nx || ny != b.ny || nu != b.nu) return kf_fail(b.who, "set_models must keep the model id and the dimensions of the bank");
+    HIPC(hipSetDevice(b.device));
+    HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    b.h_init.swap(init);
+    b.Ts = models[0].Ts;
+    return LLPF_OK;
+}
+
 static int kf_reset(KfBank& b) {
     HIPC(hipSetDevice(b.device));
     HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
@@ -168,6 +222,22 @@ struct KfChunk {
     int32_t upf, ypf;         // 1: u / y is per filter
     double* post;             // null, or where the posterior of the chunk's steps goes: [tc][nx + np][F]
 };
+
+// the arguments of one chunk that the kernels of the model-driven banks have in common (UkfArgs, EkfArgs)
+template <class Args>
+static Args kf_model_args(const KfModelBank& b, const KfChunk& c, double t_index0) {
+    Args a{};
+    a.par = b.d_par; a.state = b.d_state; a.zero_u = b.d_zero;
+    a.u = c.u;
+    a.y = c.y;
+    double** slot[6] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.e};
+    for (int k = 0; k < 6; ++k) *slot[k] = c.out[k];
+    a.F = b.F; a.t0 = c.t0; a.Tc = c.tc; a.nu = b.nu;
+    a.u_per = c.upf; a.y_per = c.ypf;
+    a.first = c.first;
+    a.t_index0 = t_index0; a.Ts = b.Ts;
+    return a;
+}
 
 // the forward pass of a run (arguments checked); post: null, or the device array [T][nx + np][F] that receives the posterior of every
 // step.  launch(const KfChunk&) fills the bank's kernel arguments and launches on b.stream (a status).  Everything is allocated before

@@ -1,17 +1,12 @@
 // host/ukf.hpp — banks of unscented Kalman filters (llpf_ukf_bank_*; kernel: kernels/ukf.hpp, step: shared/llpf_ukf.h).  Part of
 // capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
-// The bank, its state and the drivers of a run and a smooth are host/kfbank.hpp's.  Here are the model descriptors ModelD[F] as a bank of
-// particle filters keeps them (the model's own parameters), the covariances par [np(nx) + np(ny)][F] (R1, R2 packed, from the llpf_model
-// covariances as given — GaussD keeps a factor, not the covariance), the weights, and the launchers of k_ukf and k_ukf_smooth.
+// The bank, its models, its state and the drivers of a run and a smooth are host/kfbank.hpp's (KfModelBank).  Here are the weights and
+// the launchers of k_ukf and k_ukf_smooth.
 
-struct llpf_ukf_bank : KfBank {
-    int model_id = 0;
-    double Ts = 1.0;
+struct llpf_ukf_bank : KfModelBank {
     llpf_ukf_weights w{};
-    DevBuf<ModelD> d_models;
-    DevBuf<double> d_zero;
-    llpf_ukf_bank() : KfBank("ukf") {}
+    llpf_ukf_bank() : KfModelBank("ukf", "unscented filter", 0) {}
 };
 
 // every check of the weights that needs no device
@@ -24,49 +19,10 @@ static int ukf_check_weights(const llpf_ukf_weights* w) {
     return LLPF_OK;
 }
 
-// models -> the descriptors, the SoA covariances and the initial state; every check that needs no device (kf_pack_models)
-static int ukf_pack(const llpf_model* models, int32_t F, int& model_id, int& nx, int& ny, int& nu, std::vector<ModelD>& hm,
-                    std::vector<double>& par, std::vector<double>& init) {
-    return kf_pack_models("ukf", "unscented filter", 0, models, F, model_id, nx, ny, nu, hm, par, init);
-}
-
 static int ukf_create(int32_t device, const llpf_model* models, int32_t F, const llpf_ukf_weights* w, llpf_ukf_bank& b) {
-    std::vector<ModelD> hm;
-    std::vector<double> par;
     CHK(ukf_check_weights(w));
-    CHK(ukf_pack(models, F, b.model_id, b.nx, b.ny, b.nu, hm, par, b.h_init));
-    CHK(kf_open(b, device, F, LLPF_UKF_NPAR(b.nx, b.ny), "ukf_create"));
-    b.Ts = models[0].Ts;
     b.w = *w;
-    {
-        std::string err;      // a run-time compiled model's k_ukf, on the first bank of that model
-        if (ukf_prepare(b.model_id, b.nx, b.ny, err) != 0) return fail(LLPF_ERR_HIP, "ukf: " + err);
-    }
-    CHK(b.d_models.ensure(hm.size()));
-    CHK(b.d_par.ensure(par.size()));
-    CHK(b.d_state.ensure(b.h_init.size()));
-    CHK(b.d_zero.ensure(MAXU));
-    HIPC(hipMemsetAsync(b.d_zero, 0, sizeof(double) * MAXU, b.stream));
-    HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipStreamSynchronize(b.stream));
-    return LLPF_OK;
-}
-
-static int ukf_set_models(llpf_ukf_bank& b, const llpf_model* models) {
-    std::vector<ModelD> hm;
-    std::vector<double> par, init;
-    int id = 0, nx = 0, ny = 0, nu = 0;
-    CHK(ukf_pack(models, b.F, id, nx, ny, nu, hm, par, init));
-    if (id != b.model_id || nx != b.nx || ny != b.ny || nu != b.nu) return fail(LLPF_ERR_ARG, "ukf: set_models must keep the model id and the dimensions of the bank");
-    HIPC(hipSetDevice(b.device));
-    HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipStreamSynchronize(b.stream));
-    b.h_init.swap(init);
-    b.Ts = models[0].Ts;
-    return LLPF_OK;
+    return kf_model_create(b, device, models, F, "ukf_create", ukf_prepare);
 }
 
 static int ukf_set_weights(llpf_ukf_bank& b, const llpf_ukf_weights* w) {
@@ -86,21 +42,11 @@ static int ukf_check_run(const llpf_ukf_bank& b, const double* U, const double* 
 // the forward pass of a run (arguments checked): kf_forward with k_ukf, or k_ukf<..., true> where post is given
 static int ukf_forward(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
                        const llpf_kalman_outputs* out, double* post) {
-    const int nx = b.nx, ny = b.ny;
     return kf_forward(b, U, Y, T, per_filter, ll_total, out, post, [&](const KfChunk& c) -> int {
-        UkfArgs a{};
-        a.par = b.d_par; a.state = b.d_state; a.zero_u = b.d_zero;
-        a.u = c.u;
-        a.y = c.y;
-        double** slot[6] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.e};
-        for (int k = 0; k < 6; ++k) *slot[k] = c.out[k];
-        a.F = b.F; a.t0 = c.t0; a.Tc = c.tc; a.nu = b.nu;
-        a.u_per = c.upf; a.y_per = c.ypf;
-        a.first = c.first;
-        a.t_index0 = t_index0; a.Ts = b.Ts;
+        UkfArgs a = kf_model_args<UkfArgs>(b, c, t_index0);
         a.gamma = b.w.gamma; a.wm0 = b.w.wm0; a.wc0 = b.w.wc0; a.wi = b.w.wi;
         a.post = c.post;
-        HIPC(launch_ukf(b.model_id, nx, ny, b.d_models, a, b.stream));
+        HIPC(launch_ukf(b.model_id, b.nx, b.ny, b.d_models, a, b.stream));
         return LLPF_OK;
     });
 }
@@ -118,12 +64,11 @@ static int ukf_run(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T
 static int ukf_smooth(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
                       const llpf_kalman_outputs* fwd, const llpf_kalman_smooth_outputs* out) {
     CHK(ukf_check_run(b, U, Y, T, per_filter, t_index0, fwd));
-    const int nx = b.nx, ny = b.ny;
     return kf_smooth(
         b, U, T, per_filter, out, "ukf_smooth",
         [&]() -> int {
             std::string err;
-            if (ukf_smooth_prepare(b.model_id, nx, ny, err) != 0) return fail(LLPF_ERR_HIP, "ukf: " + err);
+            if (ukf_smooth_prepare(b.model_id, b.nx, b.ny, err) != 0) return fail(LLPF_ERR_HIP, "ukf: " + err);
             return LLPF_OK;
         },
         [&](double* post) { return ukf_forward(b, U, Y, T, per_filter, t_index0, ll_total, fwd, post); },
@@ -141,7 +86,7 @@ static int ukf_smooth(llpf_ukf_bank& b, const double* U, const double* Y, int64_
             a.init = c.init;
             a.t_index0 = t_index0; a.Ts = b.Ts;
             a.gamma = b.w.gamma; a.wm0 = b.w.wm0; a.wc0 = b.w.wc0; a.wi = b.w.wi;
-            HIPC(launch_ukf_smooth(b.model_id, nx, ny, b.d_models, a, b.stream));
+            HIPC(launch_ukf_smooth(b.model_id, b.nx, b.ny, b.d_models, a, b.stream));
             return LLPF_OK;
         });
 }

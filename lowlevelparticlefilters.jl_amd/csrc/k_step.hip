@@ -1,11 +1,9 @@
-// k_step.hip — k_step (balanced propagate + weight: every model, every mode), k_max, and the run-time compiled user models
+// k_step.hip — k_step (balanced propagate + weight: every model, every mode), k_max, the run-time compiled user models, and the one hiprtc
+// compile path and module loader of every unit's run-time programs (kernels/jit.hpp: jit_program_compile, jit_program_function)
 // One of the engine's device translation units (kernels.hip has the map); split so that they build in parallel.
 #include <hip/hiprtc.h>
 
 #include <atomic>
-#include <mutex>
-#include <string>
-#include <vector>
 
 #include "engine.hpp"
 #include "jit_prelude.inc"
@@ -24,6 +22,7 @@ namespace llpf {
 #include "kernels/step.hpp"
 #include "kernels/resample.hpp"
 #include "kernels/resfx.hpp"
+#include "kernels/dispatch.hpp"
 #include "kernels/jit.hpp"
 
 bool step_supported(int model_id, int nx, int ny) {
@@ -88,17 +87,6 @@ static hipError_t launch_step_t(const BankDev& b, int mode, const StepArgs& a, h
 }
 
 template <int NX>
-static hipError_t launch_step_lg_ny(const BankDev& b, int mode, const StepArgs& a, hipStream_t s) {
-    switch (b.ny) {
-        case 1: return launch_step_t<LinGauss<NX, 1>, NX, 1>(b, mode, a, s);
-        case 2: return launch_step_t<LinGauss<NX, 2>, NX, 2>(b, mode, a, s);
-        case 3: return launch_step_t<LinGauss<NX, 3>, NX, 3>(b, mode, a, s);
-        case 4: return launch_step_t<LinGauss<NX, 4>, NX, 4>(b, mode, a, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int NX>
 static hipError_t launch_step_rb_ny(const BankDev& b, int mode, const StepArgs& a, hipStream_t s) {
     if (mode == MODE_AUX) return hipErrorInvalidValue;
     switch (b.ny) {
@@ -118,17 +106,7 @@ static hipError_t launch_step_aux2_t(const BankDev& b, const StepArgs& a, hipStr
     return hipGetLastError();
 }
 static hipError_t launch_step_aux2(const BankDev& b, const StepArgs& a, hipStream_t s) {
-    switch (b.nx) {
-        case 1: return launch_step_aux2_t<1>(b, a, s);
-        case 2: return launch_step_aux2_t<2>(b, a, s);
-        case 3: return launch_step_aux2_t<3>(b, a, s);
-        case 4: return launch_step_aux2_t<4>(b, a, s);
-        case 5: return launch_step_aux2_t<5>(b, a, s);
-        case 6: return launch_step_aux2_t<6>(b, a, s);
-        case 7: return launch_step_aux2_t<7>(b, a, s);
-        case 8: return launch_step_aux2_t<8>(b, a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_dim<1, 8>(b.nx, [&](auto NX) { return launch_step_aux2_t<decltype(NX)::value>(b, a, s); });
 }
 
 hipError_t launch_step(const BankDev& b, int mode, const StepArgs& a, hipStream_t s) {
@@ -145,13 +123,10 @@ hipError_t launch_step(const BankDev& b, int mode, const StepArgs& a, hipStream_
             default: return hipErrorInvalidValue;
         }
     }
-    switch (b.nx) {
-        case 1: return launch_step_lg_ny<1>(b, mode, a, s);
-        case 2: return launch_step_lg_ny<2>(b, mode, a, s);
-        case 3: return launch_step_lg_ny<3>(b, mode, a, s);
-        case 4: return launch_step_lg_ny<4>(b, mode, a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_lingauss(b.nx, b.ny, [&](auto m) {
+        using M = decltype(m);
+        return launch_step_t<typename M::Model, M::NX, M::NY>(b, mode, a, s);
+    });
 }
 
 // ---- resampling with source-side dynamics (kernels/resfx.hpp) ----

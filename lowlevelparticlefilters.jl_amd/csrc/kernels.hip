@@ -28,6 +28,7 @@ namespace llpf {
 #include "kernels/access.hpp"
 #include "kernels/smooth.hpp"
 #include "kernels/selftest.hpp"
+#include "kernels/dispatch.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -36,26 +37,10 @@ static inline dim3 grid1(int64_t n, int F) { return dim3((unsigned)((n + BLOCK -
 
 hipError_t launch_init(const BankDev& b, uint32_t step, int init_anc, hipStream_t s) {
     dim3 g = grid1(b.Ns, b.F);
-    switch (b.nx) {
-        case 1: hipLaunchKernelGGL(k_init<1>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 2: hipLaunchKernelGGL(k_init<2>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 3: hipLaunchKernelGGL(k_init<3>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 4: hipLaunchKernelGGL(k_init<4>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 5: hipLaunchKernelGGL(k_init<5>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;   // 5..8: models compiled on demand
-        case 6: hipLaunchKernelGGL(k_init<6>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 7: hipLaunchKernelGGL(k_init<7>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 8: hipLaunchKernelGGL(k_init<8>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 9: hipLaunchKernelGGL(k_init<9>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 10: hipLaunchKernelGGL(k_init<10>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 11: hipLaunchKernelGGL(k_init<11>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 12: hipLaunchKernelGGL(k_init<12>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 13: hipLaunchKernelGGL(k_init<13>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 14: hipLaunchKernelGGL(k_init<14>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 15: hipLaunchKernelGGL(k_init<15>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        case 16: hipLaunchKernelGGL(k_init<16>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_dim<1, MAXD>(b.nx, [&](auto NX) {      // above 4: models compiled on demand
+        hipLaunchKernelGGL(k_init<decltype(NX)::value>, g, dim3(BLOCK), 0, s, b, b.models, b.scal, step, init_anc);
+        return hipGetLastError();
+    });
 }
 
 template <int NX, bool XMEAN>
@@ -67,26 +52,10 @@ static void launch_norm_e2(const BankDev& b, int parity, int need_e2, uint32_t s
 }
 hipError_t launch_norm(const BankDev& b, int parity, int want_xmean, int need_e2, uint32_t step, int only_fallback, int bound, int64_t kstep, hipStream_t s) {
     if (!want_xmean) { launch_norm_e2<0, false>(b, parity, need_e2, step, only_fallback, bound, kstep, s); return hipGetLastError(); }
-    switch (b.nx) {
-        case 1: launch_norm_e2<1, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 2: launch_norm_e2<2, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 3: launch_norm_e2<3, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 4: launch_norm_e2<4, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 5: launch_norm_e2<5, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 6: launch_norm_e2<6, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 7: launch_norm_e2<7, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 8: launch_norm_e2<8, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 9: launch_norm_e2<9, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 10: launch_norm_e2<10, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 11: launch_norm_e2<11, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 12: launch_norm_e2<12, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 13: launch_norm_e2<13, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 14: launch_norm_e2<14, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 15: launch_norm_e2<15, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        case 16: launch_norm_e2<16, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_dim<1, MAXD>(b.nx, [&](auto NX) {
+        launch_norm_e2<decltype(NX)::value, true>(b, parity, need_e2, step, only_fallback, bound, kstep, s);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_ess(const BankDev& b, hipStream_t s) {
     hipLaunchKernelGGL(k_ess, dim3((unsigned)b.F), dim3(BLOCK), 0, s, b);
@@ -155,49 +124,19 @@ static hipError_t launch_smooth_fx_t(const BankDev& b, const SmoothArgs& a, hipS
     hipLaunchKernelGGL((k_smooth_fx<Model, NX, NY>), grid1(b.N, 1), dim3(BLOCK), 0, s, b, b.models, a);
     return hipGetLastError();
 }
-template <int NX>
-static hipError_t launch_smooth_fx_ny(const BankDev& b, const SmoothArgs& a, hipStream_t s) {
-    switch (b.ny) {
-        case 1: return launch_smooth_fx_t<LinGauss<NX, 1>, NX, 1>(b, a, s);
-        case 2: return launch_smooth_fx_t<LinGauss<NX, 2>, NX, 2>(b, a, s);
-        case 3: return launch_smooth_fx_t<LinGauss<NX, 3>, NX, 3>(b, a, s);
-        case 4: return launch_smooth_fx_t<LinGauss<NX, 4>, NX, 4>(b, a, s);
-        default: return hipErrorInvalidValue;
-    }
-}
 hipError_t launch_smooth_fx(const BankDev& b, const SmoothArgs& a, hipStream_t s) {
     if (b.model_id >= LLPF_MODEL_USER_BASE) return launch_smooth_fx_user(b, a, s);     // compiled with the user's dynamics (kernels/jit.hpp)
-    if (b.model_id == LLPF_MODEL_QUADTANK_RK4) return launch_smooth_fx_t<QuadTank<4, 2>, 4, 2>(b, a, s);
-    switch (b.nx) {
-        case 1: return launch_smooth_fx_ny<1>(b, a, s);
-        case 2: return launch_smooth_fx_ny<2>(b, a, s);
-        case 3: return launch_smooth_fx_ny<3>(b, a, s);
-        case 4: return launch_smooth_fx_ny<4>(b, a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_builtin_model(b.model_id, b.nx, b.ny, [&](auto m) {
+        using M = decltype(m);
+        return launch_smooth_fx_t<typename M::Model, M::NX, M::NY>(b, a, s);
+    });
 }
 hipError_t launch_smooth_draw(const BankDev& b, const SmoothArgs& a, hipStream_t s) {
     const dim3 g((unsigned)a.M, 1, 1);
-    switch (b.nx) {
-        case 1: hipLaunchKernelGGL((k_smooth_draw<1>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 2: hipLaunchKernelGGL((k_smooth_draw<2>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 3: hipLaunchKernelGGL((k_smooth_draw<3>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 4: hipLaunchKernelGGL((k_smooth_draw<4>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 5: hipLaunchKernelGGL((k_smooth_draw<5>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 6: hipLaunchKernelGGL((k_smooth_draw<6>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 7: hipLaunchKernelGGL((k_smooth_draw<7>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 8: hipLaunchKernelGGL((k_smooth_draw<8>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 9: hipLaunchKernelGGL((k_smooth_draw<9>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 10: hipLaunchKernelGGL((k_smooth_draw<10>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 11: hipLaunchKernelGGL((k_smooth_draw<11>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 12: hipLaunchKernelGGL((k_smooth_draw<12>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 13: hipLaunchKernelGGL((k_smooth_draw<13>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 14: hipLaunchKernelGGL((k_smooth_draw<14>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 15: hipLaunchKernelGGL((k_smooth_draw<15>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        case 16: hipLaunchKernelGGL((k_smooth_draw<16>), g, dim3(BLOCK), 0, s, b, b.models, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_dim<1, MAXD>(b.nx, [&](auto NX) {
+        hipLaunchKernelGGL((k_smooth_draw<decltype(NX)::value>), g, dim3(BLOCK), 0, s, b, b.models, a);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_bake_weights(const BankDev& b, hipStream_t s) {
     hipLaunchKernelGGL(k_bake_weights, grid1(b.Ns, b.F), dim3(BLOCK), 0, s, b);

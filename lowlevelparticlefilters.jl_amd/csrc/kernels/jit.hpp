@@ -1,4 +1,4 @@
-// kernels/jit.hpp — user-supplied models, compiled at run time (host side; part of kernels.hip, namespace llpf).
+// kernels/jit.hpp — user-supplied models, compiled at run time (host side; part of k_step.hip, namespace llpf).
 // ------------------------------------------------------------------------------------------------
 // The reference's filters take arbitrary `dynamics` / `measurement` callables (src/PFtypes.jl:59-63, 189-193); a Julia
 // closure cannot run on the GPU, but a device-code snippet can: llpf_model_compile() takes HIP source that defines
@@ -13,21 +13,69 @@
 // with hiprtc (--offload-arch of the device, -ffp-contract=off like the engine itself).  Filters with such a model run the
 // balanced form: the precompiled k_resample + the compiled k_step; noise and likelihood stay the Gaussian descriptors.
 // ------------------------------------------------------------------------------------------------
-// (kernels.hip includes <hip/hiprtc.h>, <mutex>, <vector> and jit_prelude.inc before it opens the namespace)
+// (k_step.hip includes <hip/hiprtc.h> and jit_prelude.inc before it opens the namespace)
+
+// ---- the one compile path and the one module loader of every run-time program (declared in engine.hpp) ----
+int jit_program_compile(const std::string& src, const char* file, const std::vector<std::string>& exprs, const std::vector<const char*>& extra_opts,
+                        const char* what, std::unique_ptr<JitProgram>& out, std::string& err) {
+    hiprtcProgram prog = nullptr;
+    if (hiprtcCreateProgram(&prog, src.c_str(), file, 0, nullptr, nullptr) != HIPRTC_SUCCESS) { err = "hiprtcCreateProgram failed"; return -1; }
+    for (const std::string& e : exprs) hiprtcAddNameExpression(prog, e.c_str());
+    int devid = 0;
+    hipDeviceProp_t prop;
+    std::string arch = "gfx950";
+    if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.gcnArchName[0]) arch = prop.gcnArchName;
+    const std::string archopt = "--offload-arch=" + arch;
+    // the options of the engine's own translation units (Makefile): -ffp-contract=off, the same bits
+    std::vector<const char*> opts = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-value"};
+    opts.insert(opts.end(), extra_opts.begin(), extra_opts.end());
+    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
+    if (rc != HIPRTC_SUCCESS) {
+        size_t n = 0;
+        hiprtcGetProgramLogSize(prog, &n);
+        std::string log(n, '\0');
+        if (n) hiprtcGetProgramLog(prog, &log[0]);
+        err = std::string(what) + hiprtcGetErrorString(rc) + "\n" + log;
+        hiprtcDestroyProgram(&prog);
+        return -1;
+    }
+    std::unique_ptr<JitProgram> jp(new JitProgram());
+    size_t sz = 0;
+    hiprtcGetCodeSize(prog, &sz);
+    jp->code.resize(sz);
+    hiprtcGetCode(prog, jp->code.data());
+    for (const std::string& e : exprs) {
+        const char* low = nullptr;
+        if (hiprtcGetLoweredName(prog, e.c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + e; hiprtcDestroyProgram(&prog); return -1; }
+        jp->names.push_back(low);
+    }
+    hiprtcDestroyProgram(&prog);
+    out = std::move(jp);
+    return 0;
+}
+hipError_t jit_program_function(JitProgram& jp, int which, hipFunction_t* fn) {
+    int devid = 0;
+    hipError_t e = hipGetDevice(&devid);
+    if (e != hipSuccess) return e;
+    if ((int)jp.dev.size() <= devid) jp.dev.resize((size_t)devid + 1);
+    JitProgram::PerDevice& pd = jp.dev[(size_t)devid];
+    if (!pd.mod && (e = hipModuleLoadData(&pd.mod, jp.code.data())) != hipSuccess) return e;
+    if (pd.fn.size() < jp.names.size()) pd.fn.resize(jp.names.size(), nullptr);
+    if (!pd.fn[(size_t)which] && (e = hipModuleGetFunction(&pd.fn[(size_t)which], pd.mod, jp.names[(size_t)which].c_str())) != hipSuccess) return e;
+    *fn = pd.fn[(size_t)which];
+    return hipSuccess;
+}
 
 struct JitModel {
     int nx = 0, ny = 0;
     std::string src;                           // the snippet: a second llpf_model_compile of the same (source, nx, ny) returns the same id
-    std::vector<char> code;
     static constexpr int NK = 12;
-    std::string name[NK];                      // lowered names of k_step<UserModel, nx, ny, MODE, STEP_PPT>, MODE = 0..3; [4]: k_user_bound<UserModel>;
+    std::unique_ptr<JitProgram> prog;          // kernels [0..3]: k_step<UserModel, nx, ny, MODE, STEP_PPT>, MODE = 0..3; [4]: k_user_bound<UserModel>;
                                                // [5]: k_smooth_fx<UserModel, nx, ny>; models whose dynamics are worth a table (marks): [6], [7]:
                                                // k_step<..., MODE_PROP / MODE_PROP_WEIGHT, STEP_PPT, true>; [8], [9]: k_resample_fx<UserModel, nx, systematic / stratified>;
                                                // [10]: k_init_user<UserModel, nx>; [11]: k_traits_tag<model_traits<UserModel>::value> (never launched)
     bool marks = false;
     int traits = 0;                            // LLPF_TRAIT_*: the optional members the snippet defines
-    struct PerDevice { hipModule_t mod = nullptr; hipFunction_t fn[NK] = {}; };
-    std::vector<PerDevice> dev;                // indexed by device ordinal, loaded on first use
 };
 static std::mutex g_jit_mutex;
 static std::vector<JitModel*> g_jit_models;
@@ -57,8 +105,6 @@ static int jit_compile_model(const char* device_src, int nx, int ny, bool intern
     src += "\nnamespace llpf {\n";
     src += device_src;
     src += "\n}  // namespace llpf\n";
-    hiprtcProgram prog = nullptr;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "llpf_user_model.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) { err = "hiprtcCreateProgram failed"; return -1; }
     std::string expr[JitModel::NK];
     for (int mode = 0; mode < 4; ++mode)
         expr[mode] = "llpf::k_step<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string(ny) + ", " + std::to_string(mode) + ", " + std::to_string(STEP_PPT) + ">";
@@ -77,48 +123,24 @@ static int jit_compile_model(const char* device_src, int nx, int ny, bool intern
         expr[8] = "llpf::k_resample_fx<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string((int)LLPF_RESAMPLE_SYSTEMATIC) + ">";
         expr[9] = "llpf::k_resample_fx<llpf::UserModel, " + std::to_string(nx) + ", " + std::to_string((int)LLPF_RESAMPLE_STRATIFIED) + ">";
     }
-    for (int mode = 0; mode < nk; ++mode) hiprtcAddNameExpression(prog, expr[mode].c_str());
-    int devid = 0;
-    hipDeviceProp_t prop;
-    std::string arch = "gfx950";
-    if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.gcnArchName[0]) arch = prop.gcnArchName;
-    const std::string archopt = "--offload-arch=" + arch;
     // -disable-machine-licm: as for k_step.hip (Makefile) — the tile loop of k_step<..., MARKS>
     // (-DLLPF_EXP_LDEXP: as for k_step.hip in the Makefile — the same bits, one instruction instead of six for exp's scaling)
-    const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-value", "-DLLPF_EXP_LDEXP=1", "-mllvm", "-disable-machine-licm"};
-    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
-    if (rc != HIPRTC_SUCCESS) {
-        size_t n = 0;
-        hiprtcGetProgramLogSize(prog, &n);
-        std::string log(n, '\0');
-        if (n) hiprtcGetProgramLog(prog, &log[0]);
-        err = std::string("hiprtc: ") + hiprtcGetErrorString(rc) + "\n" + log;
-        hiprtcDestroyProgram(&prog);
-        return -1;
-    }
-    JitModel* jm = new JitModel();
+    std::unique_ptr<JitModel> jm(new JitModel());
+    if (jit_program_compile(src, "llpf_user_model.hip", std::vector<std::string>(expr, expr + nk), {"-DLLPF_EXP_LDEXP=1", "-mllvm", "-disable-machine-licm"},
+                            "hiprtc: ", jm->prog, err) != 0) return -1;
     jm->nx = nx; jm->ny = ny; jm->src = device_src; jm->marks = marks;
-    size_t sz = 0;
-    hiprtcGetCodeSize(prog, &sz);
-    jm->code.resize(sz);
-    hiprtcGetCode(prog, jm->code.data());
-    for (int mode = 0; mode < nk; ++mode) {
-        const char* low = nullptr;
-        if (hiprtcGetLoweredName(prog, expr[mode].c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + expr[mode]; delete jm; hiprtcDestroyProgram(&prog); return -1; }
-        jm->name[mode] = low;
-    }
     if (marks) {      // "...k_traits_tagILi<value>EEEvv": what the snippet provides, without running anything
-        const size_t at = jm->name[11].find("k_traits_tagILi");
-        if (at == std::string::npos) { err = "could not read the model's traits from " + jm->name[11]; delete jm; hiprtcDestroyProgram(&prog); return -1; }
-        jm->traits = atoi(jm->name[11].c_str() + at + 15);
+        const std::string& tag = jm->prog->names[11];
+        const size_t at = tag.find("k_traits_tagILi");
+        if (at == std::string::npos) { err = "could not read the model's traits from " + tag; return -1; }
+        jm->traits = atoi(tag.c_str() + at + 15);
         if (jm->traits & LLPF_TRAIT_NOISE) jm->marks = false;      // a model that forms its own noise needs x next to f(x): inline dynamics
     }
-    hiprtcDestroyProgram(&prog);
     std::lock_guard<std::mutex> lk(g_jit_mutex);
     // two threads may have compiled the same snippet side by side: the first registration wins, "the same (source, nx, ny) returns the same id"
     for (size_t k = 0; k < g_jit_models.size(); ++k)
-        if (g_jit_models[k]->nx == nx && g_jit_models[k]->ny == ny && g_jit_models[k]->src == device_src) { delete jm; return LLPF_MODEL_USER_BASE + (int)k; }
-    g_jit_models.push_back(jm);
+        if (g_jit_models[k]->nx == nx && g_jit_models[k]->ny == ny && g_jit_models[k]->src == device_src) return LLPF_MODEL_USER_BASE + (int)k;
+    g_jit_models.push_back(jm.release());
     return LLPF_MODEL_USER_BASE + (int)g_jit_models.size() - 1;
 }
 
@@ -132,16 +154,8 @@ static bool jit_supported(int model_id, int nx, int ny) {
     return jm && jm->nx == nx && jm->ny == ny;
 }
 static hipError_t jit_function(JitModel* jm, int which, hipFunction_t* fn) {      // this device's handle of kernel `which`
-    int devid = 0;
-    hipError_t e = hipGetDevice(&devid);
-    if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lk(g_jit_mutex);
-    if ((int)jm->dev.size() <= devid) jm->dev.resize((size_t)devid + 1);
-    JitModel::PerDevice& pd = jm->dev[(size_t)devid];
-    if (!pd.mod && (e = hipModuleLoadData(&pd.mod, jm->code.data())) != hipSuccess) return e;
-    if (!pd.fn[which] && (e = hipModuleGetFunction(&pd.fn[which], pd.mod, jm->name[which].c_str())) != hipSuccess) return e;
-    *fn = pd.fn[which];
-    return hipSuccess;
+    return jit_program_function(*jm->prog, which, fn);
 }
 // a user model with a likelihood of its own: its upper bound into every filter's descriptor (see k_user_bound); a no-op kernel otherwise
 hipError_t launch_user_bound(int model_id, ModelD* models, int F, const double* zero_u, hipStream_t s) {
@@ -220,10 +234,7 @@ static hipError_t launch_resample_fx_user(const BankDev& b, const ResArgs& a, co
 // ---- k_rbfull for shapes the library was not precompiled for (kernels/rbfull.hpp is part of the prelude) -----------------------------
 struct JitRbfull {
     int fk = 0, nn = 0, nl = 0, ny = 0;
-    std::vector<char> code;
-    std::string name[3];                       // MODE_WEIGHT, MODE_PROP, MODE_PROP_WEIGHT
-    struct PerDevice { hipModule_t mod = nullptr; hipFunction_t fn[3] = {nullptr, nullptr, nullptr}; };
-    std::vector<PerDevice> dev;
+    std::unique_ptr<JitProgram> prog;          // kernels: MODE_WEIGHT, MODE_PROP, MODE_PROP_WEIGHT
 };
 static std::vector<JitRbfull*> g_jit_rbfull;
 static JitRbfull* jit_rbfull_find(int fk, int nn, int nl, int ny) {
@@ -235,64 +246,27 @@ int jit_prepare_rbfull(int fk, int nn, int nl, int ny, std::string& err) {
         std::lock_guard<std::mutex> lk(g_jit_mutex);
         if (jit_rbfull_find(fk, nn, nl, ny)) return 0;
     }
-    std::string src(LLPF_JIT_PRELUDE);
-    hiprtcProgram prog = nullptr;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "llpf_rbfull_shape.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) { err = "hiprtcCreateProgram failed"; return -1; }
     const std::string model = (fk == 1 ? "llpf::QuadTank<" : "llpf::LinGauss<") + std::to_string(nn) + ", " + std::to_string(ny) + ">";
-    std::string expr[3];
-    for (int mode = 0; mode < 3; ++mode) {
-        expr[mode] = "llpf::k_rbfull<" + model + ", " + std::to_string(nn) + ", " + std::to_string(nl) + ", " + std::to_string(ny) + ", " + std::to_string(mode) + ">";
-        hiprtcAddNameExpression(prog, expr[mode].c_str());
-    }
-    int devid = 0;
-    hipDeviceProp_t prop;
-    std::string arch = "gfx950";
-    if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess && prop.gcnArchName[0]) arch = prop.gcnArchName;
-    const std::string archopt = "--offload-arch=" + arch;
+    std::vector<std::string> exprs;
+    for (int mode = 0; mode < 3; ++mode)
+        exprs.push_back("llpf::k_rbfull<" + model + ", " + std::to_string(nn) + ", " + std::to_string(nl) + ", " + std::to_string(ny) + ", " + std::to_string(mode) + ">");
     // -disable-machine-licm: as for k_rbfull.hip (Makefile) — hoisted out of the persistent loop, the literal constants of the body are spilled
-    const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-value", "-mllvm", "-disable-machine-licm"};
-    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
-    if (rc != HIPRTC_SUCCESS) {
-        size_t n = 0;
-        hiprtcGetProgramLogSize(prog, &n);
-        std::string log(n, '\0');
-        if (n) hiprtcGetProgramLog(prog, &log[0]);
-        err = std::string("hiprtc: ") + hiprtcGetErrorString(rc) + "\n" + log;
-        hiprtcDestroyProgram(&prog);
-        return -1;
-    }
-    JitRbfull* j = new JitRbfull();
+    std::unique_ptr<JitRbfull> j(new JitRbfull());
+    if (jit_program_compile(LLPF_JIT_PRELUDE, "llpf_rbfull_shape.hip", exprs, {"-mllvm", "-disable-machine-licm"}, "hiprtc: ", j->prog, err) != 0) return -1;
     j->fk = fk; j->nn = nn; j->nl = nl; j->ny = ny;
-    size_t sz = 0;
-    hiprtcGetCodeSize(prog, &sz);
-    j->code.resize(sz);
-    hiprtcGetCode(prog, j->code.data());
-    for (int mode = 0; mode < 3; ++mode) {
-        const char* low = nullptr;
-        if (hiprtcGetLoweredName(prog, expr[mode].c_str(), &low) != HIPRTC_SUCCESS || !low) { err = "hiprtcGetLoweredName failed for " + expr[mode]; delete j; hiprtcDestroyProgram(&prog); return -1; }
-        j->name[mode] = low;
-    }
-    hiprtcDestroyProgram(&prog);
     std::lock_guard<std::mutex> lk(g_jit_mutex);
-    if (jit_rbfull_find(fk, nn, nl, ny)) { delete j; return 0; }      // another thread registered the shape meanwhile
-    g_jit_rbfull.push_back(j);
+    if (!jit_rbfull_find(fk, nn, nl, ny)) g_jit_rbfull.push_back(j.release());      // (another thread may have registered the shape meanwhile)
     return 0;
 }
 hipError_t launch_rbfull_jit(int fk, int nn, int nl, int ny, const BankDev& b, int mode, const StepArgs& a, hipStream_t s) {
     if (mode < 0 || mode > 2) return hipErrorInvalidValue;
-    int devid = 0;
-    hipError_t e = hipGetDevice(&devid);
-    if (e != hipSuccess) return e;
     hipFunction_t fn = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_jit_mutex);
         JitRbfull* j = jit_rbfull_find(fk, nn, nl, ny);
         if (!j) return hipErrorInvalidValue;            // jit_prepare_rbfull runs when the bank is built
-        if ((int)j->dev.size() <= devid) j->dev.resize((size_t)devid + 1);
-        JitRbfull::PerDevice& pd = j->dev[(size_t)devid];
-        if (!pd.mod && (e = hipModuleLoadData(&pd.mod, j->code.data())) != hipSuccess) return e;
-        if (!pd.fn[mode] && (e = hipModuleGetFunction(&pd.fn[mode], pd.mod, j->name[mode].c_str())) != hipSuccess) return e;
-        fn = pd.fn[mode];
+        const hipError_t e = jit_program_function(*j->prog, mode, &fn);
+        if (e != hipSuccess) return e;
     }
     BankDev bd = b;
     StepArgs aa = a;
