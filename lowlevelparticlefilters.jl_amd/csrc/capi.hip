@@ -84,6 +84,7 @@ static void test_throw(const char* site) {
     } while (0)
 
 #include "host/densities.hpp"
+#include "host/run_plan.hpp"
 #include "host/bank.hpp"
 #include "host/fallback.hpp"
 #include "host/rbkf.hpp"
@@ -163,9 +164,7 @@ int llpf_run(llpf_filter* f, const double* U, const double* Y, int64_t T, double
              double* ll_total, const llpf_run_outputs* o) LLPF_TRY {
     NEEDF(f);
     double lt = 0.0;
-    int rc = bank_run(f->bank, U, Y, T, t_index0, &lt, o ? o->ll_steps : nullptr, o ? o->xmean : nullptr,
-                      o ? o->x_hist : nullptr, o ? o->w_hist : nullptr, o ? o->we_hist : nullptr, false, o ? o->xcov : nullptr,
-                      o ? o->xquant : nullptr, o ? o->quant_p : nullptr, o ? o->nq : 0);
+    int rc = bank_run(f->bank, U, Y, T, t_index0, &lt, o ? *o : llpf_run_outputs{});
     if (ll_total) *ll_total = lt;
     return rc;
 } LLPF_GUARD(llpf_run)
@@ -189,15 +188,16 @@ int llpf_aux_run(llpf_filter* f, const double* U, const double* Y, int64_t T, in
     NEEDF(f);
     if (o && (o->xcov || o->xquant)) return fail(LLPF_ERR_ARG, "the xcov / xquant outputs are provided by llpf_run only");
     double lt = 0.0;
-    int rc = bank_aux_run(f->bank, U, Y, T, mode, &lt, o ? o->ll_steps : nullptr, o ? o->xmean : nullptr,
-                          o ? o->x_hist : nullptr, o ? o->w_hist : nullptr, o ? o->we_hist : nullptr);
+    int rc = bank_aux_run(f->bank, U, Y, T, mode, &lt, o ? *o : llpf_run_outputs{});
     if (ll_total) *ll_total = lt;
     return rc;
 } LLPF_GUARD(llpf_aux_run)
 int llpf_bank_aux_run(llpf_bank* b, const double* U, const double* Y, int64_t T, int32_t mode,
                       double* ll_total, double* ll_steps) LLPF_TRY {
     if (!b) return fail(LLPF_ERR_ARG, "null bank");
-    return bank_aux_run(b->bank, U, Y, T, mode, ll_total, ll_steps, nullptr, nullptr, nullptr, nullptr);
+    llpf_run_outputs o{};
+    o.ll_steps = ll_steps;
+    return bank_aux_run(b->bank, U, Y, T, mode, ll_total, o);
 } LLPF_GUARD(llpf_bank_aux_run)
 
 int llpf_simulate(llpf_filter* f, int64_t M, int64_t T, const double* U, int32_t u_per_trajectory, double t_index0,
@@ -523,12 +523,16 @@ int llpf_bank_set_models(llpf_bank* b, const llpf_model* models) LLPF_TRY { NEED
 int llpf_bank_run(llpf_bank* b, const double* U, const double* Y, int64_t T, double t_index0,
                   double* ll_total, double* ll_steps) LLPF_TRY {
     NEEDF(b);
-    return bank_run(b->bank, U, Y, T, t_index0, ll_total, ll_steps, nullptr, nullptr, nullptr, nullptr);
+    llpf_run_outputs o{};
+    o.ll_steps = ll_steps;
+    return bank_run(b->bank, U, Y, T, t_index0, ll_total, o);
 } LLPF_GUARD(llpf_bank_run)
 int llpf_bank_run_multi(llpf_bank* b, const double* U, const double* Y, int64_t T, double t_index0,
                         double* ll_total, double* ll_steps, double* xmean) LLPF_TRY {
     NEEDF(b);
-    return bank_run(b->bank, U, Y, T, t_index0, ll_total, ll_steps, xmean, nullptr, nullptr, nullptr, true);
+    llpf_run_outputs o{};
+    o.ll_steps = ll_steps; o.xmean = xmean;
+    return bank_run(b->bank, U, Y, T, t_index0, ll_total, o, true);
 } LLPF_GUARD(llpf_bank_run_multi)
 int llpf_bank_set_profiling(llpf_bank* b, int32_t on) LLPF_TRY { NEEDF(b); return set_prof(b->bank, on); } LLPF_GUARD(llpf_bank_set_profiling)
 int llpf_bank_get_profile(llpf_bank* b, double* ms, int64_t* n) LLPF_TRY { NEEDF(b); return get_prof(b->bank, ms, n); } LLPF_GUARD(llpf_bank_get_profile)

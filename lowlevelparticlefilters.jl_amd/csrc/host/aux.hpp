@@ -58,14 +58,8 @@ static int bank_aux_correct(Bank& b, double* ll_out /* [F] or null */, const Aux
     CHK(use_device(b));
     if (b.aux_pending) {
         CHK(aux_launch_finalize(b, true, 0, 0, row, o));
-        std::vector<int> fl;
-        int64_t kf;
-        CHK(poll_fallback(b, fl, kf));
-        if (!fl.empty()) {   // bound test failed: exact-max normalisation of the same weights (their max is in the slot)
-            CHK(clear_slot_sums(b, (b.parity + ACC_NSLOT - 1) % ACC_NSLOT, fl));
-            CHK(aux_launch_finalize(b, false, 1, 0, row, o));
-            CHK(clear_fallback(b, fl));
-        }
+        // bound test failed: exact-max normalisation of the same weights (their max is in the slot)
+        CHK(redo_if_flagged(b, (b.parity + ACC_NSLOT - 1) % ACC_NSLOT, [&] { return aux_launch_finalize(b, false, 1, 0, row, o); }));
     } else {
         {
             BankDev d = b.dev();
@@ -90,6 +84,21 @@ static int bank_aux_correct(Bank& b, double* ll_out /* [F] or null */, const Aux
     return check_status(b, h);
 }
 
+// expnormalize! of w + lambda (sums in `slot`) and the forced resample, ancestors to HBM; in the exact-max form where the bound test fails
+static int aux_forced_resample(Bank& b, int slot) {
+    BankDev d = b.dev();
+    ResArgs ra{};
+    ra.mode = RES_FINALIZE | RES_RESAMPLE; ra.parity = slot; ra.step = rel_step(b); ra.M = (int32_t)b.N; ra.anc_out = b.d_anc;
+    ra.force = 1; ra.fast_head = 1; ra.u_from_scal = 1; ra.k = 0;
+    HIPC(launch_resample(d, ra, b.stream));
+    return redo_if_flagged(b, slot, [&]() -> int {
+        HIPC(launch_norm(d, slot, 0, 0, rel_step(b), 1, 0, 0, b.stream));
+        ra.fast_head = 0; ra.only_fallback = 1;
+        HIPC(launch_resample(d, ra, b.stream));
+        return LLPF_OK;
+    });
+}
+
 // predict!(pf::AuxiliaryParticleFilter{<:AdvancedParticleFilter}, u, y, p, t) — reference src/filtering.jl:219-234: the look-ahead
 // weights lambda (noise-free prediction) only steer the resampling; the particles are then propagated AGAIN from xprev[j], with
 // noise, and the weights are reset (lambda is discarded: the following correct!, which is logsumexp! only, returns ~0).
@@ -101,21 +110,8 @@ static int aux_predict_dev_advanced(Bank& b, const double* d_u, const double* d_
     const int slot = b.parity;
     b.parity = (b.parity + 1) % ACC_NSLOT;
     b.qcur ^= 1;                                  // the quanta of w + lambda are the current ones; b.cur stays: xnext holds x' and is overwritten
+    CHK(aux_forced_resample(b, slot));
     BankDev d = b.dev();
-    ResArgs ra{};
-    ra.mode = RES_FINALIZE | RES_RESAMPLE; ra.parity = slot; ra.step = rel_step(b); ra.M = (int32_t)b.N; ra.anc_out = b.d_anc;
-    ra.force = 1; ra.fast_head = 1; ra.u_from_scal = 1; ra.k = 0;
-    HIPC(launch_resample(d, ra, b.stream));
-    std::vector<int> fl;
-    int64_t kf;
-    CHK(poll_fallback(b, fl, kf));
-    if (!fl.empty()) {   // expnormalize! of w + lambda in the exact-max form
-        CHK(clear_slot_sums(b, slot, fl));
-        HIPC(launch_norm(d, slot, 0, 0, rel_step(b), 1, 0, 0, b.stream));
-        ra.fast_head = 0; ra.only_fallback = 1;
-        HIPC(launch_resample(d, ra, b.stream));
-        CHK(clear_fallback(b, fl));
-    }
     StepArgs a{};
     a.u = d_u; a.y = nullptr; a.t_prop = t; a.t_meas = t; a.step = rel_step(b); a.has_y = 0; a.parity = b.parity;
     a.K = llpf_qbits(b.N); a.k = 0;
@@ -147,43 +143,15 @@ static int aux_predict_dev(Bank& b, const double* d_u, const double* d_y1, bool 
         // resample(ResampleResidual, ...) (src/resample.jl:63-117) under the auxiliary filter: residual ancestors are not sorted, which
         // the fused second half relies on; the balanced form instead — k_resample (expnormalize! of w + lambda, forced residual
         // resample: ancestors to HBM), then k_step<NoModel, MODE_AUX2>: x = x'[j] + noise, w = lambda - log N, exp-sums
-        const int slot1 = (b.parity + ACC_NSLOT - 1) % ACC_NSLOT;
-        BankDev d = b.dev();
-        ResArgs ra{};
-        ra.mode = RES_FINALIZE | RES_RESAMPLE; ra.parity = slot1; ra.step = rel_step(b); ra.M = (int32_t)b.N; ra.anc_out = b.d_anc;
-        ra.force = 1; ra.fast_head = 1; ra.u_from_scal = 1; ra.k = 0;
-        HIPC(launch_resample(d, ra, b.stream));
-        std::vector<int> fl;
-        int64_t kf;
-        CHK(poll_fallback(b, fl, kf));
-        if (!fl.empty()) {   // expnormalize! of w + lambda in the exact-max form
-            CHK(clear_slot_sums(b, slot1, fl));
-            HIPC(launch_norm(d, slot1, 0, 0, rel_step(b), 1, 0, 0, b.stream));
-            ra.fast_head = 0; ra.only_fallback = 1;
-            HIPC(launch_resample(d, ra, b.stream));
-            CHK(clear_fallback(b, fl));
-        }
+        CHK(aux_forced_resample(b, (b.parity + ACC_NSLOT - 1) % ACC_NSLOT));
         StepArgs st{};
         st.t_prop = t; st.t_meas = t; st.step = rel_step(b); st.has_y = 0; st.parity = b.parity; st.need_e2 = 0; st.K = llpf_qbits(b.N);
         st.k = 0; st.next_step = rel_step(b) + 1; st.want_xmean = want_xm; st.accumulate = 1; st.aux = has_y1 ? 2 : 1;
-        HIPC(launch_step(d, MODE_AUX2, st, b.stream));
-        b.parity = (b.parity + 1) % ACC_NSLOT;
-        b.qcur ^= 1;
-        b.cur ^= 1;
-        b.n_predict++;
-        b.t_index++;
-        b.aux_pending = true;
-        b.we_is_lambda = true;
-        return LLPF_OK;
-    }
-    CHK(aux_launch_resprop(b, has_y1, t, true, 0, 0, want_xm));
-    std::vector<int> fl;
-    int64_t kf;
-    CHK(poll_fallback(b, fl, kf));
-    if (!fl.empty()) {   // expnormalize! of w + lambda in the exact-max form, then the second half again
-        CHK(clear_slot_sums(b, (b.parity + ACC_NSLOT - 1) % ACC_NSLOT, fl));
-        CHK(aux_launch_resprop(b, has_y1, t, false, 1, 0, want_xm));
-        CHK(clear_fallback(b, fl));
+        HIPC(launch_step(b.dev(), MODE_AUX2, st, b.stream));
+    } else {
+        CHK(aux_launch_resprop(b, has_y1, t, true, 0, 0, want_xm));
+        // expnormalize! of w + lambda in the exact-max form, then the second half again
+        CHK(redo_if_flagged(b, (b.parity + ACC_NSLOT - 1) % ACC_NSLOT, [&] { return aux_launch_resprop(b, has_y1, t, false, 1, 0, want_xm); }));
     }
     b.parity = (b.parity + 1) % ACC_NSLOT;
     b.qcur ^= 1;
@@ -198,10 +166,8 @@ static int aux_predict_dev(Bank& b, const double* d_u, const double* d_y1, bool 
 static int bank_aux_predict(Bank& b, const double* u, const double* y1, double t) {
     CHK(use_device(b));
     const bool has_y = (y1 != nullptr) && !(y1[0] != y1[0]);
-    double hbuf[2 * MAXD] = {0};
-    if (u) for (int i = 0; i < b.nu; ++i) hbuf[i] = u[i];
-    if (has_y) for (int i = 0; i < b.ny; ++i) hbuf[MAXD + i] = y1[i];
-    HIPC(hipMemcpyAsync(b.d_uy, hbuf, sizeof(hbuf), hipMemcpyHostToDevice, b.stream));
+    UYRow row;
+    CHK(stage_uy(b, row, u, has_y ? y1 : nullptr));
     CHK(aux_predict_dev(b, b.d_uy, b.d_uy + MAXD, has_y, t, 0));
     HIPC(hipStreamSynchronize(b.stream));
     std::vector<FilterScal> h;
@@ -214,59 +180,27 @@ static int bank_aux_predict(Bank& b, const double* u, const double* y1, double t
 //         of the wrapped ParticleFilter on (u[end], y[end]).
 // Without history outputs all launches are enqueued back to back (three per timestep: look-ahead, resample+propagate,
 // finalize) and the bound-test flag is polled once at the end; a failed test re-drives from that launch in exact form.
-static int bank_aux_run(Bank& b, const double* U, const double* Y, int64_t T, int mode, double* ll_total /* [F] */,
-                        double* ll_steps, double* xmean, double* x_hist, double* w_hist, double* we_hist) {
-    CHK(use_device(b));
-    if (T < 1) return fail(LLPF_ERR_ARG, "T must be >= 1");
-    if (!Y) return fail(LLPF_ERR_ARG, "Y is null");
-    if (b.nu > 0 && !U) return fail(LLPF_ERR_ARG, "U is null");
+// Of `o`: ll_steps, xmean and the history (xcov / xquant are llpf_run's).
+static int bank_aux_run(Bank& b, const double* U, const double* Y, int64_t T, int mode, double* ll_total /* [F] */, const llpf_run_outputs& o) {
+    CHK(run_check_args(b, U, Y, T, o));
     if (mode != 0 && mode != 1) return fail(LLPF_ERR_ARG, "mode must be 0 (forward_trajectory) or 1 (loglik)");
-    if ((x_hist || w_hist || we_hist) && b.F != 1) return fail(LLPF_ERR_ARG, "history outputs need a single filter");
     // refused HERE, before any state of the handle moves (the back-to-back epochs below never pass through aux_predict_dev's own check)
     if (is_rb(b) || is_rbfull(b)) return fail(LLPF_ERR_ARG, "the auxiliary filter is not defined for the Rao-Blackwellized model");
     if (b.nx > 8) return fail(LLPF_ERR_ARG, "the auxiliary filter is compiled for up to 8 states (this filter has " + std::to_string(b.nx) + ")");
-    CHK(b.d_U.ensure((size_t)T * (b.nu > 0 ? b.nu : 1)));
-    CHK(b.d_Y.ensure((size_t)T * b.ny));
-    if (b.nu > 0) HIPC(hipMemcpyAsync(b.d_U, U, sizeof(double) * T * b.nu, hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_Y, Y, sizeof(double) * T * b.ny, hipMemcpyHostToDevice, b.stream));
+    CHK(stage_inputs(b, U, Y, T, false));
     CHK(b.d_ll_steps.ensure((size_t)T * b.F));
-    if (xmean) CHK(b.d_xmean.ensure((size_t)T * b.F * b.nx));
+    if (o.xmean) CHK(b.d_xmean.ensure((size_t)T * b.F * b.nx));
     const bool residual = b.cfg.resampling_strategy == LLPF_RESAMPLE_RESIDUAL;     // balanced form, driven step by step (aux_predict_dev)
     CHK(aux_ensure_lam(b));
     const double Ts = b.cfg.model.Ts;
-    const bool hist = x_hist || w_hist || we_hist;
-    const int want_xm = xmean ? 1 : 0;
+    const bool hist = wants_history(o);
+    const int want_xm = o.xmean ? 1 : 0;
     if (want_xm) CHK(ensure_xmpart(b));
-    b.run_resamples = 0;
     b.last_run_launches = 0;      // counted by aux_launch_resprop; stays 0 where the balanced second half runs (residual resampling)
-    {
-        std::vector<FilterScal> h;
-        CHK(scal_download(b, h));
-        for (int f = 0; f < b.F; ++f) { h[f].ll_total = 0.0; b.run_resamples -= h[f].resample_count; }
-        CHK(scal_upload(b, h));
-    }
+    CHK(run_zero_totals(b, b.step_base));      // (the steps of the auxiliary verbs stay relative to the base they find)
     AuxOuts outs;
-    outs.d_ll_steps = b.d_ll_steps; outs.d_xmean = xmean ? b.d_xmean : nullptr; outs.accumulate = 1;
+    outs.d_ll_steps = b.d_ll_steps; outs.d_xmean = o.xmean ? b.d_xmean : nullptr; outs.accumulate = 1;
     auto has_y = [&](int64_t k) { return !(Y[k * b.ny] != Y[k * b.ny]); };
-    auto record = [&](int64_t k) -> int {     // x[:,t] .= particles(pf); w[:,t] .= weights(pf); we[:,t] .= expweights(pf)
-        BankDev d = b.dev();
-        if (x_hist) {
-            HIPC(launch_soa2aos(d, b.d_x[b.cur], b.d_tmp, b.stream));
-            HIPC(hipMemcpyAsync(x_hist + (size_t)k * b.N * b.nx, b.d_tmp, sizeof(double) * b.N * b.nx, hipMemcpyDeviceToHost, b.stream));
-            HIPC(hipStreamSynchronize(b.stream));
-        }
-        if (w_hist) {
-            HIPC(launch_materialize(d, b.d_tmp, nullptr, b.stream));
-            HIPC(hipMemcpyAsync(w_hist + (size_t)k * b.N, b.d_tmp, sizeof(double) * b.N, hipMemcpyDeviceToHost, b.stream));
-            HIPC(hipStreamSynchronize(b.stream));
-        }
-        if (we_hist) {
-            HIPC(launch_materialize(d, nullptr, b.d_tmp, b.stream));
-            HIPC(hipMemcpyAsync(we_hist + (size_t)k * b.N, b.d_tmp, sizeof(double) * b.N, hipMemcpyDeviceToHost, b.stream));
-            HIPC(hipStreamSynchronize(b.stream));
-        }
-        return LLPF_OK;
-    };
     HIPC(hipEventRecord(b.ev_run0, b.stream));
     const int64_t n_aux = T - 1;                       // aux predict! calls: k = 0 .. T-2
     // correct! of step 0 (synchronous: after reset! the weights are uniform and take the exact-max form).  loglik with
@@ -275,12 +209,12 @@ static int bank_aux_run(Bank& b, const double* U, const double* Y, int64_t T, in
     const bool advanced = b.cfg.filter_kind == LLPF_ADVANCED_PARTICLE_FILTER;     // its predict! is driven synchronously (filtering.jl:219-234)
     if (hist || advanced || residual) {
         // step-synchronous form (history is copied out between correct! and predict!)
-        if (hist && (mode == 0 || T > 1)) CHK(record(0));
+        if (hist && (mode == 0 || T > 1)) CHK(copy_history_row(b, o, 0));
         for (int64_t k = 0; k < n_aux; ++k) {
             CHK(aux_predict_dev(b, b.nu > 0 ? b.d_U + k * b.nu : nullptr, b.d_Y + (k + 1) * b.ny, has_y(k + 1), (double)k * Ts, want_xm));
             if (mode == 1 && k + 1 == T - 1) break;           // loglik: the last step is the wrapped filter's update!
             CHK(bank_aux_correct(b, nullptr, outs, k + 1));
-            if (hist) CHK(record(k + 1));
+            if (hist) CHK(copy_history_row(b, o, k + 1));
         }
     } else if (n_aux > 0) {
         // epochs: e = 3k+1 look-ahead(k), 3k+2 resample+propagate(k), 3k+3 finalize(k+1)
@@ -309,16 +243,15 @@ static int bank_aux_run(Bank& b, const double* U, const double* Y, int64_t T, in
         int64_t e0 = 1;
         while (e0 <= e_last) {
             for (int64_t e = e0; e <= e_last; ++e) CHK(launch_epoch(e, true, 0));
-            std::vector<int> fl;
-            int64_t ef;
-            CHK(poll_fallback(b, fl, ef));
-            if (fl.empty()) break;
-            // launch `ef` of the flagged filters again with an exact-max normalisation of the same weights
-            at_epoch(ef);
-            CHK(clear_slot_sums(b, (b.parity + ACC_NSLOT - 1) % ACC_NSLOT, fl));
-            CHK(launch_epoch(ef, false, 1));
-            CHK(clear_fallback(b, fl));
-            e0 = ef + 1;
+            Flagged fl;
+            CHK(poll_fallback(b, fl));
+            if (!fl.any) break;
+            // launch `fl.step` of the flagged filters again with an exact-max normalisation of the same weights
+            at_epoch(fl.step);
+            CHK(clear_slot_sums(b, (b.parity + ACC_NSLOT - 1) % ACC_NSLOT));
+            CHK(launch_epoch(fl.step, false, 1));
+            CHK(clear_fallback(b));
+            e0 = fl.step + 1;
         }
         at_epoch(3 * n_aux);      // host state after the last resample+propagate launch (a finalize does not advance it)
         b.aux_pending = (mode == 1);
@@ -334,20 +267,15 @@ static int bank_aux_run(Bank& b, const double* U, const double* Y, int64_t T, in
     HIPC(hipEventRecord(b.ev_run1, b.stream));
     std::vector<double> hl((size_t)T * b.F, 0.0);
     HIPC(hipMemcpyAsync(hl.data(), b.d_ll_steps, sizeof(double) * T * b.F, hipMemcpyDeviceToHost, b.stream));
-    if (xmean) HIPC(hipMemcpyAsync(xmean, b.d_xmean, sizeof(double) * T * b.F * b.nx, hipMemcpyDeviceToHost, b.stream));
+    if (o.xmean) HIPC(hipMemcpyAsync(o.xmean, b.d_xmean, sizeof(double) * T * b.F * b.nx, hipMemcpyDeviceToHost, b.stream));
     std::vector<FilterScal> h;
-    CHK(scal_download(b, h));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, b.ev_run0, b.ev_run1));
-    b.last_run_ms = ms;
-    if (b.profiling) prof_collect(b);
+    CHK(run_finish(b, h));
     for (int f = 0; f < b.F; ++f) {
         if (mode == 1) hl[(size_t)(T - 1) * b.F + f] = last[f];
         double tot = 0.0;
         for (int64_t k = 0; k < T; ++k) tot += hl[(size_t)k * b.F + f];     // same left-to-right order as the reference's sum
         if (ll_total) ll_total[f] = tot;
-        b.run_resamples += h[f].resample_count;
     }
-    if (ll_steps) memcpy(ll_steps, hl.data(), sizeof(double) * T * b.F);
+    if (o.ll_steps) memcpy(o.ll_steps, hl.data(), sizeof(double) * T * b.F);
     return check_status(b, h);
 }

@@ -114,7 +114,7 @@ struct Bank : BankStream {
     uint32_t* d_flag = nullptr;
     int64_t last_run_launches = 0, last_run_fx_steps = 0;
     double last_run_surv = -1.0;
-    bool last_run_skip_w = false;     // the last run's fused launches stored no weights (host/run.hpp: skip_w_run)
+    bool last_run_skip_w = false;     // the last run's fused launches stored no weights (host/run_plan.hpp: skip_w_run)
     int64_t last_run_redos = 0;       // failed bound tests the last run's host loop redid in exact form
     DevBuf<double> d_xmpart;
     // Rao-Blackwellized model: host side of the shared covariance recursion (csrc/shared/llpf_rbkf.h)
@@ -126,7 +126,7 @@ struct Bank : BankStream {
     uint64_t* d_rtile = nullptr;      // [F][2][P2] residual resampling: per-tile counts / residual sums and their prefixes
     DevBuf<double> d_lam;             // [F][Ns] lambda of the AuxiliaryParticleFilter predict! (allocated on first use)
     double surv_frac = -1.0;          // distinct ancestors per predict! / N over the last run of a model that can take the source-side form (-1: none yet)
-    bool use_fx = true;               //   ... and the form the next run takes (hysteresis: host/run.hpp)
+    bool use_fx = true;               //   ... and the form the next run takes (hysteresis: host/run_plan.hpp)
     DevBuf<unsigned long long> d_surv;      // [F][P2][4] survivor counters of a run (BankDev::surv)
     DevBuf<int32_t> d_mark;           // [F][Ns] run-start marks / [F][nx][Ns] f(x_j): resampling with source-side dynamics (kernels/resfx.hpp),
     DevBuf<double> d_fxs;             //   allocated on first use (ensure_fx)
@@ -146,13 +146,14 @@ struct Bank : BankStream {
     // Captured run loops (hipGraph): a chain of T dependent launches replays ~1 us per launch faster than it enqueues
     // (tools/launch_floor.hip: 1.6 vs 2.8 us per dependent empty launch).  Keyed by everything a launch argument depends on.
     struct RunGraph {
-        int64_t T; double t_index0; int par0, cur0, qcur0, flags, np_parity;
+        RunForm form;                    // every form decision of the run (host/run_plan.hpp), compared as a whole
+        int64_t T; double t_index0; int par0, cur0, qcur0, np_parity;
         const void *dU, *dY, *dll, *dxm, *dxc, *drb, *dxq, *dqp, *dw, *dws;      // every device buffer a captured launch addresses that ensure() may reallocate
         int nq;
         uint64_t yhash;
         GraphExec exec;
         bool same(const RunGraph& o) const {
-            return T == o.T && t_index0 == o.t_index0 && par0 == o.par0 && cur0 == o.cur0 && qcur0 == o.qcur0 && flags == o.flags &&
+            return form == o.form && T == o.T && t_index0 == o.t_index0 && par0 == o.par0 && cur0 == o.cur0 && qcur0 == o.qcur0 &&
                    np_parity == o.np_parity && dU == o.dU && dY == o.dY && dll == o.dll && dxm == o.dxm && dxc == o.dxc && drb == o.drb && dxq == o.dxq && dqp == o.dqp && dw == o.dw && dws == o.dws && nq == o.nq && yhash == o.yhash;
         }
     };

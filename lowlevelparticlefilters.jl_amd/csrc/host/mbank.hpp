@@ -210,8 +210,8 @@ static int mbank_run(llpf_mbank& m, const double* U, const double* Y, int64_t T,
     for (int s = 0; s < S; ++s) local[s].assign(m.shards[s]->owned.size(), 0.0);
     CHK(mbank_foreach(m, [&](int s) -> int {
         Bank& b = m.shards[s]->bank;
-        if (aux) return bank_aux_run(b, U, Y, T, aux_mode, local[s].data(), nullptr, nullptr, nullptr, nullptr, nullptr);
-        return bank_run(b, U, Y, T, t_index0, local[s].data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (aux) return bank_aux_run(b, U, Y, T, aux_mode, local[s].data(), llpf_run_outputs{});
+        return bank_run(b, U, Y, T, t_index0, local[s].data(), llpf_run_outputs{});
     }));
     m.last_run_ms = 0.0;
     for (int s = 0; s < S; ++s) m.last_run_ms = std::max(m.last_run_ms, m.shards[s]->bank.last_run_ms);

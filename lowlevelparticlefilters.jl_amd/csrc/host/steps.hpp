@@ -1,13 +1,20 @@
 // host/steps.hpp — single-step API: correct!, predict!.  Part of capi.hip (one translation unit).
 // ---- single steps -------------------------------------------------------------------------------
+// One row of u and y (null: zeros) to Bank::d_uy.  The row is the caller's: it has to outlive the copy, which the stream may still read.
+struct UYRow { double v[2 * MAXD]; };
+static int stage_uy(Bank& b, UYRow& row, const double* u, const double* y) {
+    memset(row.v, 0, sizeof(row.v));
+    if (u) for (int i = 0; i < b.nu; ++i) row.v[i] = u[i];
+    if (y) for (int i = 0; i < b.ny; ++i) row.v[MAXD + i] = y[i];
+    HIPC(hipMemcpyAsync(b.d_uy, row.v, sizeof(row.v), hipMemcpyHostToDevice, b.stream));
+    return LLPF_OK;
+}
 static int bank_correct(Bank& b, const double* u, const double* y, double t, double* ll_out /* [F] */) {
     CHK(use_device(b));
     b.aux_pending = false; b.we_is_lambda = false;      // new weights supersede pending aux sums
     const bool has_y = (y != nullptr) && !(y[0] != y[0]);
-    double hbuf[2 * MAXD] = {0};
-    if (u) for (int i = 0; i < b.nu; ++i) hbuf[i] = u[i];
-    if (has_y) for (int i = 0; i < b.ny; ++i) hbuf[MAXD + i] = y[i];
-    HIPC(hipMemcpyAsync(b.d_uy, hbuf, sizeof(hbuf), hipMemcpyHostToDevice, b.stream));
+    UYRow row;
+    CHK(stage_uy(b, row, u, has_y ? y : nullptr));
     const int slot = b.parity;
     {
         BankDev d = b.dev();
@@ -23,16 +30,12 @@ static int bank_correct(Bank& b, const double* u, const double* y, double t, dou
     ResArgs ra{};
     ra.mode = RES_FINALIZE; ra.parity = slot; ra.M = (int32_t)b.N; ra.fast_head = 1; ra.k = 0;
     HIPC(launch_resample(d, ra, b.stream));
-    std::vector<int> fl;
-    int64_t kf;
-    CHK(poll_fallback(b, fl, kf));
-    if (!fl.empty()) {   // bound test failed: exact-max normalisation of the same weights
-        CHK(clear_slot_sums(b, slot, fl));
+    CHK(redo_if_flagged(b, slot, [&]() -> int {      // bound test failed: exact-max normalisation of the same weights
         HIPC(launch_norm(d, slot, 0, 1, rel_step(b), 1, 0, 0, b.stream));
         ra.fast_head = 0; ra.only_fallback = 1;
         HIPC(launch_resample(d, ra, b.stream));
-        CHK(clear_fallback(b, fl));
-    }
+        return LLPF_OK;
+    }));
     std::vector<FilterScal> h;
     CHK(scal_download(b, h));
     if (ll_out) for (int f = 0; f < b.F; ++f) ll_out[f] = h[f].ll;
@@ -41,9 +44,8 @@ static int bank_correct(Bank& b, const double* u, const double* y, double t, dou
 
 static int bank_predict(Bank& b, const double* u, double t) {
     CHK(use_device(b));
-    double hbuf[2 * MAXD] = {0};
-    if (u) for (int i = 0; i < b.nu; ++i) hbuf[i] = u[i];
-    HIPC(hipMemcpyAsync(b.d_uy, hbuf, sizeof(hbuf), hipMemcpyHostToDevice, b.stream));
+    UYRow row;
+    CHK(stage_uy(b, row, u, nullptr));
     BankDev d = b.dev();
     ResArgs ra{};
     ra.mode = RES_RESAMPLE; ra.parity = (b.parity + ACC_NSLOT - 1) % ACC_NSLOT; ra.step = rel_step(b); ra.M = (int32_t)b.N;

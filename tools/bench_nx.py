@@ -1,7 +1,7 @@
 """The timestep of a single linear-Gaussian filter (N = 1e6, resample every step) against the state dimension and the schedule:
   fused      one launch (k_resprop), precompiled for nx <= 4                                   LLPF_UNFUSED=0
   balanced   k_resample + k_step, ancestors through HBM                                        LLPF_UNFUSED=1
-  default    what the engine picks with no switch set (host/run.hpp: fused for nx <= 2, balanced from nx = 3 on)
+  default    what the engine picks with no switch set (host/run_plan.hpp: fused for nx <= 2, balanced from nx = 3 on)
 nx >= 5 is compiled on demand (hiprtc) and has the balanced form only.  The round-3 review asked for the step between nx = 4 and nx = 5
 to be visible: measuring it showed the cliff was at nx = 3 — the fused kernel needs three waves per SIMD there — which is why those
 dimensions now run balanced.  (The source-side form of the quad-tank, k_resample_fx + k_step<MARKS>, was measured for this model too and
