@@ -315,6 +315,7 @@ struct JitCache {
 };
 
 #include "kernels/sim_args.hpp"
+#include "kernels/kf_model_args.hpp"
 #include "kernels/ukf_args.hpp"
 #include "kernels/ekf_args.hpp"
 // arguments of k_kalman (kernels/kalman.hpp): one launch is one chunk of steps [t0, t0 + Tc) of F Kalman filters, one thread per filter.

@@ -223,10 +223,9 @@ struct KfChunk {
     double* post;             // null, or where the posterior of the chunk's steps goes: [tc][nx + np][F]
 };
 
-// the arguments of one chunk that the kernels of the model-driven banks have in common (UkfArgs, EkfArgs)
-template <class Args>
-static Args kf_model_args(const KfModelBank& b, const KfChunk& c, double t_index0) {
-    Args a{};
+// the arguments of one chunk that the kernels of the model-driven banks have in common (the base of UkfArgs and EkfArgs)
+static KfModelArgs kf_model_args(const KfModelBank& b, const KfChunk& c, double t_index0) {
+    KfModelArgs a{};
     a.par = b.d_par; a.state = b.d_state; a.zero_u = b.d_zero;
     a.u = c.u;
     a.y = c.y;

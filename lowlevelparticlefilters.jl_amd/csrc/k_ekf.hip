@@ -23,11 +23,10 @@ namespace llpf {
 // ia: null for the plain kernel, or the arguments of the iterated one, k_ekf<..., IekfArgs> (its EkfArgs part is `a`)
 template <class Model, int NX, int NY>
 static hipError_t launch_ekf_t(const ModelD* models, const EkfArgs& a, const IekfArgs* ia, hipStream_t s) {
-    const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
     if (ia)
-        hipLaunchKernelGGL((k_ekf<Model, NX, NY, IekfArgs>), g, dim3(KF_BLOCK), 0, s, models, *ia);
+        hipLaunchKernelGGL((k_ekf<Model, NX, NY, IekfArgs>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, models, *ia);
     else
-        hipLaunchKernelGGL((k_ekf<Model, NX, NY>), g, dim3(KF_BLOCK), 0, s, models, a);
+        hipLaunchKernelGGL((k_ekf<Model, NX, NY>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, models, a);
     return hipGetLastError();
 }
 // ---- run-time compiled models (kernels/jit_bank.hpp) ----
@@ -49,13 +48,8 @@ int iekf_prepare(int model_id, int nx, int ny, std::string& err) { return ekf_co
 
 static hipError_t launch_ekf_any(int model_id, int nx, int ny, const ModelD* models, const EkfArgs& a, const IekfArgs* ia, hipStream_t s) {
     if (!jit_bank_builtin(model_id, nx, ny)) {
-        hipFunction_t fn = nullptr;
-        const hipError_t e = g_ekf.function(jit_bank_key(model_id, nx, ny, ia ? ":iterated" : ""), 0, &fn);
-        if (e != hipSuccess) return e;
-        EkfArgs aa = a;
-        IekfArgs iaa = ia ? *ia : IekfArgs{};
-        void* args[] = {&models, ia ? (void*)&iaa : (void*)&aa};
-        return hipModuleLaunchKernel(fn, (unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1, KF_BLOCK, 1, 1, 0, s, args, nullptr);
+        const std::string key = jit_bank_key(model_id, nx, ny, ia ? ":iterated" : "");
+        return ia ? jit_bank_launch(g_ekf, key, 0, models, *ia, a.F, s) : jit_bank_launch(g_ekf, key, 0, models, a, a.F, s);
     }
     return dispatch_builtin_model(model_id, nx, ny, [&](auto m) {
         using M = decltype(m);

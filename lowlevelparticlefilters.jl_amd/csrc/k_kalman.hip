@@ -12,14 +12,14 @@ namespace llpf {
 #include "kernels/kf_store.hpp"
 #include "kernels/kalman.hpp"
 #include "kernels/dispatch.hpp"
+#include "kernels/jit_bank.hpp"      // kf_grid
 
 template <int NX, int NY>
 static hipError_t launch_kalman_t(const KalmanArgs& a, hipStream_t s) {
-    const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
     if (a.post)
-        hipLaunchKernelGGL((k_kalman<NX, NY, true>), g, dim3(KF_BLOCK), 0, s, a);
+        hipLaunchKernelGGL((k_kalman<NX, NY, true>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, a);
     else
-        hipLaunchKernelGGL((k_kalman<NX, NY, false>), g, dim3(KF_BLOCK), 0, s, a);
+        hipLaunchKernelGGL((k_kalman<NX, NY, false>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_kalman(int nx, int ny, const KalmanArgs& a, hipStream_t s) {
@@ -28,8 +28,7 @@ hipError_t launch_kalman(int nx, int ny, const KalmanArgs& a, hipStream_t s) {
 
 template <int NX>
 static hipError_t launch_kalman_smooth_t(const KalmanSmoothArgs& a, hipStream_t s) {
-    const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
-    hipLaunchKernelGGL((k_kalman_smooth<NX>), g, dim3(KF_BLOCK), 0, s, a);
+    hipLaunchKernelGGL((k_kalman_smooth<NX>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -22,17 +22,15 @@ namespace llpf {
 
 template <class Model, int NX, int NY>
 static hipError_t launch_ukf_t(const ModelD* models, const UkfArgs& a, hipStream_t s) {
-    const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
     if (a.post)
-        hipLaunchKernelGGL((k_ukf<Model, NX, NY, true>), g, dim3(KF_BLOCK), 0, s, models, a);
+        hipLaunchKernelGGL((k_ukf<Model, NX, NY, true>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, models, a);
     else
-        hipLaunchKernelGGL((k_ukf<Model, NX, NY, false>), g, dim3(KF_BLOCK), 0, s, models, a);
+        hipLaunchKernelGGL((k_ukf<Model, NX, NY, false>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, models, a);
     return hipGetLastError();
 }
 template <class Model, int NX>
 static hipError_t launch_ukf_smooth_t(const ModelD* models, const UkfSmoothArgs& a, hipStream_t s) {
-    const dim3 g((unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1);
-    hipLaunchKernelGGL((k_ukf_smooth<Model, NX>), g, dim3(KF_BLOCK), 0, s, models, a);
+    hipLaunchKernelGGL((k_ukf_smooth<Model, NX>), kf_grid(a.F), dim3(KF_BLOCK), 0, s, models, a);
     return hipGetLastError();
 }
 // ---- run-time compiled models (kernels/jit_bank.hpp) ----
@@ -56,14 +54,8 @@ int ukf_prepare(int model_id, int nx, int ny, std::string& err) { return ukf_com
 int ukf_smooth_prepare(int model_id, int nx, int ny, std::string& err) { return ukf_compile(model_id, nx, ny, true, err); }
 
 hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const UkfArgs& a, hipStream_t s) {
-    if (!jit_bank_builtin(model_id, nx, ny)) {
-        hipFunction_t fn = nullptr;      // with a.post: the smoother's forward kernel k_ukf<..., true>
-        const hipError_t e = g_ukf.function(jit_bank_key(model_id, nx, ny, a.post ? ":smooth" : ""), a.post ? 1 : 0, &fn);
-        if (e != hipSuccess) return e;
-        UkfArgs aa = a;
-        void* args[] = {&models, &aa};
-        return hipModuleLaunchKernel(fn, (unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1, KF_BLOCK, 1, 1, 0, s, args, nullptr);
-    }
+    if (!jit_bank_builtin(model_id, nx, ny))      // with a.post: the smoother's forward kernel k_ukf<..., true>
+        return jit_bank_launch(g_ukf, jit_bank_key(model_id, nx, ny, a.post ? ":smooth" : ""), a.post ? 1 : 0, models, a, a.F, s);
     return dispatch_builtin_model(model_id, nx, ny, [&](auto m) {
         using M = decltype(m);
         return launch_ukf_t<typename M::Model, M::NX, M::NY>(models, a, s);
@@ -71,14 +63,7 @@ hipError_t launch_ukf(int model_id, int nx, int ny, const ModelD* models, const 
 }
 
 hipError_t launch_ukf_smooth(int model_id, int nx, int ny, const ModelD* models, const UkfSmoothArgs& a, hipStream_t s) {
-    if (!jit_bank_builtin(model_id, nx, ny)) {
-        hipFunction_t fn = nullptr;
-        const hipError_t e = g_ukf.function(jit_bank_key(model_id, nx, ny, ":smooth"), 0, &fn);
-        if (e != hipSuccess) return e;
-        UkfSmoothArgs aa = a;
-        void* args[] = {&models, &aa};
-        return hipModuleLaunchKernel(fn, (unsigned)((a.F + KF_BLOCK - 1) / KF_BLOCK), 1, 1, KF_BLOCK, 1, 1, 0, s, args, nullptr);
-    }
+    if (!jit_bank_builtin(model_id, nx, ny)) return jit_bank_launch(g_ukf, jit_bank_key(model_id, nx, ny, ":smooth"), 0, models, a, a.F, s);
     return dispatch_builtin_model(model_id, nx, ny, [&](auto m) {
         using M = decltype(m);
         return launch_ukf_smooth_t<typename M::Model, M::NX>(models, a, s);

@@ -1,6 +1,10 @@
-// kernels/jit_bank.hpp — what the run-time programs of the model-driven Kalman banks share (host side; part of k_ukf.hip and k_ekf.hip,
-// namespace llpf): which models have precompiled kernels, the key of a cache entry, and the source of one program around a model's snippet.
+// kernels/jit_bank.hpp — what the launchers of the one-thread-per-filter banks share (host side; part of k_kalman.hip, k_ukf.hip and
+// k_ekf.hip, namespace llpf, after kernels/kf_store.hpp): the grid of a bank and, for the model-driven banks, which models have precompiled
+// kernels, the key of a cache entry, the source of one program around a model's snippet, and the launch of a kernel of such a program.
 // ------------------------------------------------------------------------------------------------
+// one thread per filter, KF_BLOCK of them per workgroup
+static dim3 kf_grid(int64_t F) { return dim3((unsigned)((F + KF_BLOCK - 1) / KF_BLOCK), 1, 1); }
+
 // A program is the prelude, the bank's shared headers at file scope, then inside namespace llpf the snippet and the bank's kernel text.
 // It is compiled by jit_program_compile without extra options and kept in the unit's own JitCache (engine.hpp).
 static bool jit_bank_builtin(int model_id, int nx, int ny) {
@@ -23,4 +27,14 @@ static std::unique_ptr<JitProgram> jit_bank_build(int model_id, int nx, int ny, 
     std::unique_ptr<JitProgram> p;
     jit_program_compile(src, file, exprs, {}, what, p, err);
     return p;
+}
+
+// launches kernel `which` of the entry `key` of the unit's cache (its prepare compiled it) as k(models, args) over F filters
+template <class Args>
+static hipError_t jit_bank_launch(JitCache& cache, const std::string& key, int which, const ModelD* models, Args args, int64_t F, hipStream_t s) {
+    hipFunction_t fn = nullptr;
+    const hipError_t e = cache.function(key, which, &fn);
+    if (e != hipSuccess) return e;
+    void* params[] = {&models, &args};
+    return hipModuleLaunchKernel(fn, kf_grid(F).x, 1, 1, KF_BLOCK, 1, 1, 0, s, params, nullptr);
 }

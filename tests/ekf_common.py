@@ -3,19 +3,14 @@ csrc/shared/llpf_ekf.h and csrc/shared/llpf_quadtank_jac.h (tests/ekf_host.c), t
 whose C twins that file holds, and a numpy restatement of the textbook first-order extended Kalman filter in its literal formulas
 (np.linalg.inv, dense symmetrize, slogdet) that shares nothing with the header and runs in float64 and np.longdouble."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 
 from llpf_amd import _structs as S
+import kf_host as kh
+from kf_host import ROOT, SHARED, _dp, _p
 import ukf_common as uc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHARED = os.path.join(ROOT, "lowlevelparticlefilters.jl_amd", "csrc", "shared")
-SHIM = os.path.join(ROOT, "tests", "ekf_host.c")
-_dp = C.POINTER(C.c_double)
 KIND_LG, KIND_QUADTANK, KIND_PENDULUM, KIND_SQUARE = 0, 1, 2, 3
 
 # the pendulum of tests/user_models.py (PENDULUM_SRC) with the two Jacobian members: the expressions of ekf_host.c's twin
@@ -97,50 +92,34 @@ struct UserModel {
 
 
 def build_host(outdir):
-    """cc -O2 -ffp-contract=off of tests/ekf_host.c into outdir; returns the loaded library"""
-    cc = shutil.which("cc") or shutil.which("gcc")
-    so = os.path.join(str(outdir), "libekf_host.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", SHARED, "-I", os.path.join(ROOT, "include"),
-                    SHIM, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.ekf_host_run.restype = C.c_int
-    L.ekf_host_run.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(S.Model)] + [_dp] * 6 + [C.c_int64, C.c_int, C.c_double]
-                               + [_dp] * 7)
-    L.ekf_host_qt_jac.restype = None
-    L.ekf_host_qt_jac.argtypes = [C.POINTER(S.Model), _dp, C.c_double, _dp, _dp, _dp]
-    return L
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(_dp)
+    """the host build of tests/ekf_host.c in outdir (ekf_host_run, iekf_host_run and ekf_host_qt_jac)"""
+    run = kh.MODEL_HEAD + [_dp] * 2 + kh.RUN_TAIL
+    return kh.build(outdir, "ekf_host.c", {"ekf_host_run": run, "iekf_host_run": run + [C.c_int, C.c_double, C.POINTER(C.c_int32)],
+                                           "ekf_host_qt_jac": (None, [C.POINTER(S.Model), _dp, C.c_double, _dp, _dp, _dp])})
 
 
 def kind_of(model):
     return {S.MODEL_LINEAR_GAUSSIAN: KIND_LG, S.MODEL_QUADTANK_RK4: KIND_QUADTANK}[model.model_id]
 
 
-def host_run(L, models, U, Y, T, per_filter=0, t_index0=0.0, state=None, kind=None):
+def host_run(L, models, U, Y, T, per_filter=0, t_index0=0.0, state=None, kind=None, iterations=None):
     """the host build of the header over the filters `models` (llpf_model descriptors); kind: KIND_* (default: by the model id of the
-    first); state = (x0 [F, nx], P0 [F, nx, nx]) or None (reset).  Returns the outputs in the device's layout and the final state."""
+    first); state = (x0 [F, nx], P0 [F, nx, nx]) or None (reset); iterations: None, or (maxiters, epsilon) of the iterated filter, whose
+    outputs have "iters" [T, F] as well.  Returns the outputs in the device's layout and the final state."""
     F = len(models)
     m0 = models[0]
     nx, ny, nu = m0.nx, m0.ny, m0.nu
     kind = kind_of(m0) if kind is None else kind
     arr = (S.Model * F)(*models)
-    R1 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.dynamics_density) for m in models]), dtype=np.float64)
-    R2 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.measurement_density) for m in models]), dtype=np.float64)
-    if state is None:
-        x0 = np.ascontiguousarray(np.stack([S.gaussian_mean(m.initial_density) for m in models]), dtype=np.float64)
-        P0 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.initial_density) for m in models]), dtype=np.float64)
-    else:
-        x0, P0 = np.array(state[0], dtype=np.float64), np.array(state[1], dtype=np.float64)
-    U = np.ascontiguousarray(U, dtype=np.float64) if nu > 0 else np.zeros(1)
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    out = dict(ll=np.empty(F), ll_steps=np.empty((T, F)), x=np.empty((T, F, nx)), xt=np.empty((T, F, nx)), R=np.empty((T, F, nx, nx)),
-               Rt=np.empty((T, F, nx, nx)), e=np.empty((T, F, ny)))
+    R1, R2, x0, P0 = kh.pack_models(models, state)
+    out, outp = kh.outputs(T, F, nx, ny)
     f, g = uc.oracle_fns() if kind == KIND_LG else (None, None)
-    rc = L.ekf_host_run(F, nx, ny, nu, f, g, kind, arr, _p(R1), _p(R2), _p(x0), _p(P0), _p(U), _p(Y), T, per_filter, float(t_index0),
-                        _p(out["ll"]), _p(out["ll_steps"]), _p(out["x"]), _p(out["xt"]), _p(out["R"]), _p(out["Rt"]), _p(out["e"]))
+    args = [F, nx, ny, nu, f, g, kind, arr, _p(R1), _p(R2), _p(x0), _p(P0), _p(kh.inputs(U, nu)), _p(kh.f64(Y)), T, per_filter, float(t_index0)] + outp
+    if iterations is None:
+        rc = L.ekf_host_run(*args)
+    else:
+        out["iters"] = np.full((T, F), -1, dtype=np.int32)
+        rc = L.iekf_host_run(*args, int(iterations[0]), float(iterations[1]), out["iters"].ctypes.data_as(C.POINTER(C.c_int32)))
     assert rc == 0, rc
     return out, (x0, P0)
 

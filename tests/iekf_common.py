@@ -1,65 +1,20 @@
 """Shared pieces of the iterated-extended-Kalman-bank tests (test_iekf.py, test_gpu_iekf.py) and of tools/bench_ekf.py --iterated: the
-host build of the iterated filter of csrc/shared/llpf_ekf.h (tests/iekf_host.c, which holds tests/ekf_host.c's plain filter as well) and
-a numpy restatement of the textbook iterated extended Kalman filter (Bell & Cathey 1993) in its literal formulas (np.linalg.inv,
-K = R C' inv(S), (I - K C) R, slogdet) that shares nothing with the header and runs in float64 and np.longdouble."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
+host build of the iterated filter of csrc/shared/llpf_ekf.h (tests/ekf_host.c: iekf_host_run) and a numpy restatement of the textbook
+iterated extended Kalman filter (Bell & Cathey 1993) in its literal formulas (np.linalg.inv, K = R C' inv(S), (I - K C) R, slogdet) that
+shares nothing with the header and runs in float64 and np.longdouble."""
 import numpy as np
 
 from llpf_amd import _structs as S
 import ekf_common as ec
 import ukf_common as uc
 
-SHIM = os.path.join(ec.ROOT, "tests", "iekf_host.c")
-_dp = ec._dp
-_p = ec._p
-
-
-def build_host(outdir):
-    """cc -O2 -ffp-contract=off of tests/iekf_host.c into outdir; returns the loaded library (iekf_host_run and ekf_host_run)"""
-    cc = shutil.which("cc") or shutil.which("gcc")
-    so = os.path.join(str(outdir), "libiekf_host.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", ec.SHARED, "-I", os.path.join(ec.ROOT, "include"),
-                    SHIM, "-o", so], check=True)
-    L = C.CDLL(so)
-    run_args = [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(S.Model)] + [_dp] * 6 + [C.c_int64, C.c_int, C.c_double] + [_dp] * 7
-    L.ekf_host_run.restype = C.c_int
-    L.ekf_host_run.argtypes = run_args
-    L.iekf_host_run.restype = C.c_int
-    L.iekf_host_run.argtypes = run_args + [C.c_int, C.c_double, C.POINTER(C.c_int32)]
-    return L
+build_host = ec.build_host      # the extended twin is one library: iekf_host_run is in it
 
 
 def host_run(L, models, U, Y, T, maxiters, epsilon, per_filter=0, t_index0=0.0, state=None, kind=None):
     """ekf_common.host_run for the iterated filter at (maxiters, epsilon): the outputs in the device's layout, with "iters" [T, F] (the
     linearisations each step ran, 0 at a missing row), and the final state"""
-    F = len(models)
-    m0 = models[0]
-    nx, ny, nu = m0.nx, m0.ny, m0.nu
-    kind = ec.kind_of(m0) if kind is None else kind
-    arr = (S.Model * F)(*models)
-    R1 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.dynamics_density) for m in models]), dtype=np.float64)
-    R2 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.measurement_density) for m in models]), dtype=np.float64)
-    if state is None:
-        x0 = np.ascontiguousarray(np.stack([S.gaussian_mean(m.initial_density) for m in models]), dtype=np.float64)
-        P0 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.initial_density) for m in models]), dtype=np.float64)
-    else:
-        x0, P0 = np.array(state[0], dtype=np.float64), np.array(state[1], dtype=np.float64)
-    U = np.ascontiguousarray(U, dtype=np.float64) if nu > 0 else np.zeros(1)
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    out = dict(ll=np.empty(F), ll_steps=np.empty((T, F)), x=np.empty((T, F, nx)), xt=np.empty((T, F, nx)), R=np.empty((T, F, nx, nx)),
-               Rt=np.empty((T, F, nx, nx)), e=np.empty((T, F, ny)))
-    iters = np.full((T, F), -1, dtype=np.int32)
-    f, g = uc.oracle_fns() if kind == ec.KIND_LG else (None, None)
-    rc = L.iekf_host_run(F, nx, ny, nu, f, g, kind, arr, _p(R1), _p(R2), _p(x0), _p(P0), _p(U), _p(Y), T, per_filter, float(t_index0),
-                         _p(out["ll"]), _p(out["ll_steps"]), _p(out["x"]), _p(out["xt"]), _p(out["R"]), _p(out["Rt"]), _p(out["e"]),
-                         int(maxiters), float(epsilon), iters.ctypes.data_as(C.POINTER(C.c_int32)))
-    assert rc == 0, rc
-    out["iters"] = iters
-    return out, (x0, P0)
+    return ec.host_run(L, models, U, Y, T, per_filter, t_index0, state, kind, iterations=(maxiters, epsilon))
 
 
 def pendulum_bank_models(n, model_id=None):

@@ -2,34 +2,20 @@
 csrc/shared/llpf_kalman.h (tests/kalman_host.c), random stable linear-Gaussian systems in every covariance kind, and a numpy
 restatement of the reference's correct! / predict! in its literal formulas (src/filtering.jl, src/kalman.jl)."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 
 from llpf_amd import _structs as S
+import kf_host as kh
+from kf_host import ROOT, SHARED, _dp, _p
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHARED = os.path.join(ROOT, "lowlevelparticlefilters.jl_amd", "csrc", "shared")
-SHIM = os.path.join(ROOT, "tests", "kalman_host.c")
 KINDS = (S.COV_SCAL, S.COV_DIAG, S.COV_FULL)
-_dp = C.POINTER(C.c_double)
 
 
 def build_host(outdir):
-    """cc -O2 -ffp-contract=off of tests/kalman_host.c into outdir; returns the loaded library"""
-    cc = shutil.which("cc") or shutil.which("gcc")
-    so = os.path.join(str(outdir), "libkalman_host.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", SHARED, SHIM, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.kf_host_run.restype = C.c_int
-    L.kf_host_run.argtypes = [C.c_int] * 4 + [_dp] * 8 + [_dp, _dp, C.c_int64, C.c_int] + [_dp] * 7
-    return L
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(_dp)
+    """the host build of tests/kalman_host.c in outdir (kf_host_run and kf_host_smooth)"""
+    return kh.build(outdir, "kalman_host.c", {"kf_host_run": [C.c_int] * 4 + [_dp] * 8 + [_dp, _dp, C.c_int64, C.c_int] + [_dp] * 7,
+                                              "kf_host_smooth": [C.c_int] * 4 + [_dp] * 6 + [_dp, C.c_int64, C.c_int] + [_dp] * 4})
 
 
 def _gauss(rng, n, kind, scale=1.0, mu=None):
@@ -65,6 +51,12 @@ def matrices(m, D):
                 P0=S.gaussian_cov_matrix(m.initial_density))
 
 
+def stacked_matrices(systems):
+    """A [F, nx, nx], B [F, nx, nu], C [F, ny, nx], D [F, ny, nu] of the filters `systems` [(model, D)], as the host twin takes them"""
+    mats = [matrices(m, D) for m, D in systems]
+    return [kh.f64(np.stack([mm[k] for mm in mats])) for k in ("A", "B", "C", "D")]
+
+
 def simulate(rng, mats, T, missing=()):
     """data from the model (numpy), U [T, nu], Y [T, ny]; rows in `missing` get a NaN first element"""
     A, B, Cm, D = mats["A"], mats["B"], mats["C"], mats["D"]
@@ -87,20 +79,10 @@ def host_run(L, systems, U, Y, T, per_filter=0, state=None):
     F = len(systems)
     m0 = systems[0][0]
     nx, ny, nu = m0.nx, m0.ny, m0.nu
-    mats = [matrices(m, D) for m, D in systems]
-    st = lambda k, shape: np.ascontiguousarray(np.stack([mm[k].reshape(shape) for mm in mats]), dtype=np.float64)
-    A, B, Cm, D = st("A", (nx, nx)), st("B", (nx, nu)), st("C", (ny, nx)), st("D", (ny, nu))
-    R1, R2 = st("R1", (nx, nx)), st("R2", (ny, ny))
-    if state is None:
-        x0, P0 = st("x0", (nx,)), st("P0", (nx, nx))
-    else:
-        x0, P0 = np.array(state[0], dtype=np.float64), np.array(state[1], dtype=np.float64)
-    U = np.ascontiguousarray(U, dtype=np.float64) if nu > 0 else np.zeros(1)
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    out = dict(ll=np.empty(F), ll_steps=np.empty((T, F)), x=np.empty((T, F, nx)), xt=np.empty((T, F, nx)), R=np.empty((T, F, nx, nx)),
-               Rt=np.empty((T, F, nx, nx)), e=np.empty((T, F, ny)))
-    rc = L.kf_host_run(F, nx, ny, nu, _p(A), _p(B), _p(Cm), _p(D), _p(R1), _p(R2), _p(x0), _p(P0), _p(U), _p(Y), T, per_filter,
-                       _p(out["ll"]), _p(out["ll_steps"]), _p(out["x"]), _p(out["xt"]), _p(out["R"]), _p(out["Rt"]), _p(out["e"]))
+    ABCD = stacked_matrices(systems)
+    R1, R2, x0, P0 = kh.pack_models([m for m, _ in systems], state)
+    out, outp = kh.outputs(T, F, nx, ny)
+    rc = L.kf_host_run(F, nx, ny, nu, *map(_p, ABCD), _p(R1), _p(R2), _p(x0), _p(P0), _p(kh.inputs(U, nu)), _p(kh.f64(Y)), T, per_filter, *outp)
     assert rc == 0
     return out, (x0, P0)
 

@@ -1,60 +1,71 @@
-/* kalman_host.c — a host build of csrc/shared/llpf_kalman.h (the device order of the Kalman bank), for the tests and for
- * tools/bench_kalman.py.  Build: cc -O2 -ffp-contract=off -shared -fPIC -I <csrc>/shared kalman_host.c -o libkalman_host.so
+/* kalman_host.c — a host build of csrc/shared/llpf_kalman.h (the device order of the Kalman bank and of its smoother), for the tests and
+ * for tools/bench_kalman.py.  Build: cc -O2 -ffp-contract=off -shared -fPIC -I <csrc>/shared kalman_host.c -o libkalman_host.so
+ * The loops, the layouts and the optional outputs are those of tests/kf_host_frame.h.
  *
- * kf_host_run: T steps of F filters from x0, P0 (the lower triangle of P0 is read), exactly as llpf_kalman_bank_run after
- * llpf_kalman_bank_set_state(x0, P0).  Matrices per filter, row-major: A [F][nx][nx], B [F][nx][nu], C [F][ny][nx], D [F][ny][nu],
- * R1 [F][nx][nx], R2 [F][ny][ny].  U [T][nu] or [F][T][nu] (per_filter bit 0), Y [T][ny] or [F][T][ny] (bit 1).  Outputs (each
- * optional) time-major as the device writes them: ll_steps [T][F], x, xt [T][F][nx], R, Rt [T][F][nx][nx], e [T][F][ny]; ll_total [F];
- * x0, P0 receive the final state (the prior of step T). */
-#include <stdint.h>
-#include <string.h>
+ * kf_host_run: T steps of F filters from x0, P0, exactly as llpf_kalman_bank_run after llpf_kalman_bank_set_state(x0, P0).  Matrices per
+ * filter, row-major: A [F][nx][nx], B [F][nx][nu], C [F][ny][nx], D [F][ny][nu], R1 [F][nx][nx], R2 [F][ny][ny].
+ * kf_host_smooth: the backward pass of F filters over the posterior xt, Rt of a forward pass, exactly as llpf_kalman_bank_smooth runs it
+ * on the device. */
+#include "kf_host_frame.h"
 
-#include "llpf_kalman.h"
+typedef struct {
+    int nx, ny, nu;
+    const double *A, *B, *C, *D, *R1, *R2;
+    double P[LLPF_KF_NPAR(LLPF_KF_MAXX, LLPF_KF_MAXY, LLPF_KF_MAXU)];
+} kf_ctx;
 
-static void dense(int nx, const double* Rp, double* out) {
-    for (int r = 0; r < nx; ++r)
-        for (int c = 0; c < nx; ++c) out[r * nx + c] = Rp[llpf_kf_idx(r, c)];
+static double kf_begin(void* ctx, int f) {
+    kf_ctx* k = ctx;
+    const int nx = k->nx, ny = k->ny, nu = k->nu;
+    double* P = k->P;
+    memset(P, 0, sizeof(k->P));
+    for (int i = 0; i < nx * nx; ++i) P[LLPF_KF_OFF_A + i] = k->A[(size_t)f * nx * nx + i];
+    for (int i = 0; i < ny * nx; ++i) P[LLPF_KF_OFF_C(nx) + i] = k->C[(size_t)f * ny * nx + i];
+    kf_host_pack(nx, k->R1 + (size_t)f * nx * nx, P + LLPF_KF_OFF_R1(nx, ny));
+    kf_host_pack(ny, k->R2 + (size_t)f * ny * ny, P + LLPF_KF_OFF_R2(nx, ny));
+    for (int i = 0; i < nx * nu; ++i) P[LLPF_KF_OFF_B(nx, ny) + i] = k->B[(size_t)f * nx * nu + i];
+    for (int i = 0; i < ny * nu; ++i) P[LLPF_KF_OFF_D(nx, ny, nu) + i] = k->D[(size_t)f * ny * nu + i];
+    return 0.0;      /* constant matrices: no tau */
+}
+static double kf_correct(void* ctx, const double* u, const double* y, double tau, double* x, double* R, double* e, int* done) {
+    const kf_ctx* k = ctx;
+    (void)tau; (void)done;
+    return llpf_kf_correct(k->nx, k->ny, k->nu, k->P, 1, u, y, x, R, e);
+}
+static void kf_predict(void* ctx, const double* u, double tau, double* x, double* R) {
+    const kf_ctx* k = ctx;
+    (void)tau;
+    llpf_kf_predict(k->nx, k->ny, k->nu, k->P, 1, u, x, R);
+}
+static void kf_smooth(void* ctx, const double* u, double tau, const double* xf, const double* Rf, double* xs, double* Rs) {
+    const kf_ctx* k = ctx;
+    (void)tau;
+    llpf_kf_smooth(k->nx, k->ny, k->nu, k->P, 1, u, xf, Rf, xs, Rs);
+}
+static const kf_host_family kf_family = {kf_begin, kf_correct, kf_predict, kf_smooth};
+
+static int kf_dims_ok(int nx, int ny, int nu) {
+    return nx >= 1 && nx <= LLPF_KF_MAXX && ny >= 1 && ny <= LLPF_KF_MAXY && nu >= 0 && nu <= LLPF_KF_MAXU;
 }
 
 int kf_host_run(int F, int nx, int ny, int nu, const double* A, const double* B, const double* C, const double* D, const double* R1,
                 const double* R2, double* x0, double* P0, const double* U, const double* Y, int64_t T, int per_filter,
                 double* ll_total, double* ll_steps, double* xo, double* xto, double* Ro, double* Rto, double* eo) {
-    if (nx < 1 || nx > LLPF_KF_MAXX || ny < 1 || ny > LLPF_KF_MAXY || nu < 0 || nu > LLPF_KF_MAXU) return -1;
-    const int npar = LLPF_KF_NPAR(nx, ny, nu);
-    double P[LLPF_KF_NPAR(LLPF_KF_MAXX, LLPF_KF_MAXY, LLPF_KF_MAXU)];
-    for (int f = 0; f < F; ++f) {
-        memset(P, 0, sizeof(P));
-        for (int i = 0; i < nx * nx; ++i) P[LLPF_KF_OFF_A + i] = A[(size_t)f * nx * nx + i];
-        for (int i = 0; i < ny * nx; ++i) P[LLPF_KF_OFF_C(nx) + i] = C[(size_t)f * ny * nx + i];
-        for (int r = 0; r < nx; ++r)
-            for (int c = 0; c <= r; ++c) P[LLPF_KF_OFF_R1(nx, ny) + llpf_kf_idx(r, c)] = R1[((size_t)f * nx + r) * nx + c];
-        for (int r = 0; r < ny; ++r)
-            for (int c = 0; c <= r; ++c) P[LLPF_KF_OFF_R2(nx, ny) + llpf_kf_idx(r, c)] = R2[((size_t)f * ny + r) * ny + c];
-        for (int i = 0; i < nx * nu; ++i) P[LLPF_KF_OFF_B(nx, ny) + i] = B[(size_t)f * nx * nu + i];
-        for (int i = 0; i < ny * nu; ++i) P[LLPF_KF_OFF_D(nx, ny, nu) + i] = D[(size_t)f * ny * nu + i];
-        (void)npar;
-        double x[LLPF_KF_MAXX], R[LLPF_KF_NP(LLPF_KF_MAXX)], e[LLPF_KF_MAXY];
-        for (int i = 0; i < nx; ++i) x[i] = x0[(size_t)f * nx + i];
-        for (int r = 0; r < nx; ++r)
-            for (int c = 0; c <= r; ++c) R[llpf_kf_idx(r, c)] = P0[((size_t)f * nx + r) * nx + c];
-        double llt = 0.0;
-        for (int64_t t = 0; t < T; ++t) {
-            const size_t tf = (size_t)t * F + f;
-            const double* u = nu > 0 ? U + ((per_filter & 1) ? ((size_t)f * T + t) : (size_t)t) * nu : U;
-            const double* y = Y + ((per_filter & 2) ? ((size_t)f * T + t) : (size_t)t) * ny;
-            if (xo) memcpy(xo + tf * nx, x, sizeof(double) * nx);
-            if (Ro) dense(nx, R, Ro + tf * nx * nx);
-            const double ll = llpf_kf_correct(nx, ny, nu, P, 1, u, y, x, R, e);
-            llt = llt + ll;
-            if (ll_steps) ll_steps[tf] = ll;
-            if (eo) memcpy(eo + tf * ny, e, sizeof(double) * ny);
-            if (xto) memcpy(xto + tf * nx, x, sizeof(double) * nx);
-            if (Rto) dense(nx, R, Rto + tf * nx * nx);
-            llpf_kf_predict(nx, ny, nu, P, 1, u, x, R);
-        }
-        if (ll_total) ll_total[f] = llt;
-        for (int i = 0; i < nx; ++i) x0[(size_t)f * nx + i] = x[i];
-        dense(nx, R, P0 + (size_t)f * nx * nx);
-    }
+    if (!kf_dims_ok(nx, ny, nu)) return -1;
+    kf_ctx k = {nx, ny, nu, A, B, C, D, R1, R2, {0.0}};
+    const kf_host_io io = {.F = F, .nx = nx, .ny = ny, .nu = nu, .T = T, .per_filter = per_filter, .U = U, .Y = Y, .x0 = x0, .P0 = P0,
+                           .ll_total = ll_total, .ll_steps = ll_steps, .x = xo, .xt = xto, .R = Ro, .Rt = Rto, .e = eo};
+    kf_host_forward(&io, &kf_family, &k);
+    return 0;
+}
+
+int kf_host_smooth(int F, int nx, int ny, int nu, const double* A, const double* B, const double* C, const double* D, const double* R1,
+                   const double* R2, const double* U, int64_t T, int per_filter, const double* xt, const double* Rt, double* xTo,
+                   double* RTo) {
+    if (!kf_dims_ok(nx, ny, nu) || T < 1) return -1;
+    kf_ctx k = {nx, ny, nu, A, B, C, D, R1, R2, {0.0}};
+    const kf_host_io io = {.F = F, .nx = nx, .ny = ny, .nu = nu, .T = T, .per_filter = per_filter, .U = U, .post_x = xt, .post_R = Rt,
+                           .xT = xTo, .RT = RTo};
+    kf_host_backward(&io, &kf_family, &k);
     return 0;
 }

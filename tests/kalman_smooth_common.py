@@ -1,33 +1,14 @@
 """Shared pieces of the Kalman-smoother tests (test_kalman_smooth.py, test_gpu_kalman_smooth.py) and of tools/bench_kalman.py --smooth:
-the host build of llpf_kf_smooth (tests/kalman_smooth_host.c), a numpy restatement of the reference's RTS smoother in its literal formulas
+the host build of llpf_kf_smooth (tests/kalman_host.c), a numpy restatement of the reference's RTS smoother in its literal formulas
 (src/smoothing.jl:10-102), and an oracle that shares nothing with the recursion: the conditional mean and covariance of every state under
 the dense joint Gaussian of all states and all measurements."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
 import numpy as np
 
 import kalman_common as kc
+import kf_host as kh
+from kf_host import _p
 
-SHIM = os.path.join(kc.ROOT, "tests", "kalman_smooth_host.c")
-_dp = C.POINTER(C.c_double)
-
-
-def build_host_smooth(outdir):
-    """cc -O2 -ffp-contract=off of tests/kalman_smooth_host.c into outdir; returns the loaded library"""
-    cc = shutil.which("cc") or shutil.which("gcc")
-    so = os.path.join(str(outdir), "libkalman_smooth_host.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", kc.SHARED, SHIM, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.kf_host_smooth.restype = C.c_int
-    L.kf_host_smooth.argtypes = [C.c_int] * 4 + [_dp] * 6 + [_dp, C.c_int64, C.c_int] + [_dp] * 4
-    return L
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(_dp)
+build_host_smooth = kc.build_host      # the Kalman twin is one library: kf_host_smooth is in it
 
 
 def host_smooth(L, systems, U, fw, T, per_filter=0):
@@ -36,16 +17,9 @@ def host_smooth(L, systems, U, fw, T, per_filter=0):
     F = len(systems)
     m0 = systems[0][0]
     nx, ny, nu = m0.nx, m0.ny, m0.nu
-    mats = [kc.matrices(m, D) for m, D in systems]
-    st = lambda k, shape: np.ascontiguousarray(np.stack([mm[k].reshape(shape) for mm in mats]), dtype=np.float64)
-    A, B, Cm, D = st("A", (nx, nx)), st("B", (nx, nu)), st("C", (ny, nx)), st("D", (ny, nu))
-    R1, R2 = st("R1", (nx, nx)), st("R2", (ny, ny))
-    U = np.ascontiguousarray(U, dtype=np.float64) if nu > 0 else np.zeros(1)
-    xt = np.ascontiguousarray(fw["xt"], dtype=np.float64)
-    Rt = np.ascontiguousarray(fw["Rt"], dtype=np.float64)
-    out = dict(xT=np.empty((T, F, nx)), RT=np.empty((T, F, nx, nx)))
-    rc = L.kf_host_smooth(F, nx, ny, nu, _p(A), _p(B), _p(Cm), _p(D), _p(R1), _p(R2), _p(U), T, per_filter, _p(xt), _p(Rt),
-                          _p(out["xT"]), _p(out["RT"]))
+    R1, R2, _, _ = kh.pack_models([m for m, _ in systems])
+    out, iop = kh.smooth_io(fw, T, F, nx)
+    rc = L.kf_host_smooth(F, nx, ny, nu, *map(_p, kc.stacked_matrices(systems)), _p(R1), _p(R2), _p(kh.inputs(U, nu)), T, per_filter, *iop)
     assert rc == 0
     return out
 

@@ -1,5 +1,5 @@
 """Banks of iterated extended Kalman filters on the device (llpf_ekf_bank_set_iterations; kernels/ekf.hpp, host/ekf.hpp): the GPU
-reproduces the host build of the iterated filter of csrc/shared/llpf_ekf.h (tests/iekf_host.c) bit for bit — precompiled and run-time
+reproduces the host build of the iterated filter of csrc/shared/llpf_ekf.h (tests/ekf_host.c) bit for bit — precompiled and run-time
 compiled models, lanes of one wave that stop after different numbers of linearisations, whatever the bank, the chunking of T or the
 split of a run — and the Python API (IteratedExtendedKalmanFilter, IteratedExtendedKalmanFilterBank) is the filter the CPU tests pin
 down."""

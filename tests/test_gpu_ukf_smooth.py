@@ -1,5 +1,5 @@
 """The unscented Rauch-Tung-Striebel smoother on the device (llpf_ukf_bank_smooth; kernels/ukf.hpp: k_ukf_smooth, host/ukf.hpp: ukf_smooth):
-the GPU reproduces the host build of csrc/shared/llpf_ukf.h (tests/ukf_host.c, tests/ukf_smooth_host.c around the oracle's model
+the GPU reproduces the host build of csrc/shared/llpf_ukf.h (tests/ukf_host.c around the oracle's model
 functions) bit for bit in every output — smoothed and forward, precompiled and run-time compiled models, whatever the bank, the chunking
 of T or the split of a run — the state after a smooth is the state after a run, and the Python API is the smoother the CPU tests pin
 down."""

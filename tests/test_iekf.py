@@ -1,5 +1,5 @@
 """Banks of iterated extended Kalman filters, the part that needs no GPU: the iterated correct! of csrc/shared/llpf_ekf.h (the device
-order, built for the host by tests/iekf_host.c) against the plain filter of the same header where the two must coincide, against a numpy
+order, built for the host by tests/ekf_host.c) against the plain filter of the same header where the two must coincide, against a numpy
 restatement of the textbook Gauss-Newton formulas where they do not, the posterior mode as a known answer, and the argument checks of
 llpf_ekf_bank_set_iterations."""
 import ctypes as C

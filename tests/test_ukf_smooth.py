@@ -1,5 +1,5 @@
 """The unscented Rauch-Tung-Striebel smoother of the unscented bank (llpf_ukf_smooth_finish, llpf_ukf_bank_smooth), the checks that need no
-GPU: the host build of the header's backward step (tests/ukf_smooth_host.c) — the definition the device reproduces bit for bit
+GPU: the host build of the header's backward step (tests/ukf_host.c) — the definition the device reproduces bit for bit
 (tests/test_gpu_ukf_smooth.py) — is the RTS smoother on linear models, the conditional law of the joint Gaussian, and the textbook
 formulas (ukf_smooth_common.numpy_ukf_smooth) on nonlinear ones; the ABI is declared, exported, bound, guarded and mirrored in Julia;
 arguments are refused before a device is looked for."""

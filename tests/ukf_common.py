@@ -4,19 +4,14 @@ restatement of the textbook additive-noise unscented Kalman filter in its litera
 symmetrize) that shares nothing with the header.  The restatement also runs in np.longdouble with hand-written factorisations, which
 measures its own rounding error."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 
 from llpf_amd import _structs as S
+import kf_host as kh
+from kf_host import ROOT, SHARED, _dp, _p
 import oracle_binding as ob
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHARED = os.path.join(ROOT, "lowlevelparticlefilters.jl_amd", "csrc", "shared")
-SHIM = os.path.join(ROOT, "tests", "ukf_host.c")
-_dp = C.POINTER(C.c_double)
 TWIN_PENDULUM, TWIN_SQUARE = 1, 2
 
 # f(x) = x, g(x) = x_0^2: the unscented transform of a quadratic is exact (tests/ukf_host.c: square_f / square_g)
@@ -48,20 +43,9 @@ def merwe_set(L, abk):
 
 # ---- the host build of the header ----
 def build_host(outdir):
-    """cc -O2 -ffp-contract=off of tests/ukf_host.c into outdir; returns the loaded library"""
-    cc = shutil.which("cc") or shutil.which("gcc")
-    so = os.path.join(str(outdir), "libukf_host.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", SHARED, "-I", os.path.join(ROOT, "include"),
-                    SHIM, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.ukf_host_run.restype = C.c_int
-    L.ukf_host_run.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(S.Model)] + [_dp] * 7 + [C.c_int64, C.c_int, C.c_double]
-                               + [_dp] * 7)
-    return L
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(_dp)
+    """the host build of tests/ukf_host.c in outdir (ukf_host_run and ukf_host_smooth)"""
+    smooth = [C.c_int] * 3 + [C.c_void_p, C.c_int, C.POINTER(S.Model)] + [_dp] * 3 + [C.c_int64, C.c_int, C.c_double] + [_dp] * 4
+    return kh.build(outdir, "ukf_host.c", {"ukf_host_run": kh.MODEL_HEAD + [_dp] * 3 + kh.RUN_TAIL, "ukf_host_smooth": smooth})
 
 
 def oracle_fns():
@@ -78,21 +62,12 @@ def host_run(L, models, w, U, Y, T, per_filter=0, t_index0=0.0, state=None, twin
     m0 = models[0]
     nx, ny, nu = m0.nx, m0.ny, m0.nu
     arr = (S.Model * F)(*models)
-    R1 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.dynamics_density) for m in models]), dtype=np.float64)
-    R2 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.measurement_density) for m in models]), dtype=np.float64)
-    if state is None:
-        x0 = np.ascontiguousarray(np.stack([S.gaussian_mean(m.initial_density) for m in models]), dtype=np.float64)
-        P0 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.initial_density) for m in models]), dtype=np.float64)
-    else:
-        x0, P0 = np.array(state[0], dtype=np.float64), np.array(state[1], dtype=np.float64)
-    U = np.ascontiguousarray(U, dtype=np.float64) if nu > 0 else np.zeros(1)
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    R1, R2, x0, P0 = kh.pack_models(models, state)
     wv = np.array(w, dtype=np.float64)
-    out = dict(ll=np.empty(F), ll_steps=np.empty((T, F)), x=np.empty((T, F, nx)), xt=np.empty((T, F, nx)), R=np.empty((T, F, nx, nx)),
-               Rt=np.empty((T, F, nx, nx)), e=np.empty((T, F, ny)))
+    out, outp = kh.outputs(T, F, nx, ny)
     f, g = (None, None) if twin else oracle_fns()
-    rc = L.ukf_host_run(F, nx, ny, nu, f, g, twin, arr, _p(R1), _p(R2), _p(wv), _p(x0), _p(P0), _p(U), _p(Y), T, per_filter, float(t_index0),
-                        _p(out["ll"]), _p(out["ll_steps"]), _p(out["x"]), _p(out["xt"]), _p(out["R"]), _p(out["Rt"]), _p(out["e"]))
+    rc = L.ukf_host_run(F, nx, ny, nu, f, g, twin, arr, _p(R1), _p(R2), _p(wv), _p(x0), _p(P0), _p(kh.inputs(U, nu)), _p(kh.f64(Y)), T,
+                        per_filter, float(t_index0), *outp)
     assert rc == 0
     return out, (x0, P0)
 

@@ -1,19 +1,17 @@
-/* ukf_host.c — a host build of csrc/shared/llpf_ukf.h (the device order of the unscented Kalman bank) around model functions given as
- * pointers, for the tests and for tools/bench_ukf.py.
+/* ukf_host.c — a host build of csrc/shared/llpf_ukf.h (the device order of the unscented Kalman bank and of its smoother) around model
+ * functions given as pointers, for the tests and for tools/bench_ukf.py.
  * Build: cc -O2 -ffp-contract=off -shared -fPIC -I <csrc>/shared -I <root>/include ukf_host.c -o libukf_host.so
+ * The loops, the layouts and the optional outputs are those of tests/kf_host_frame.h.
  *
- * ukf_host_run: T steps of F filters from x0, P0 (the lower triangle of P0 is read), exactly as llpf_ukf_bank_run after
- * llpf_ukf_bank_set_state(x0, P0).  f / g: dynamics and measurement (model, x, u, tau, out) — the tests pass the addresses of the
- * oracle's orc_dynamics / orc_measurement, the device's models in the device's order — or NULL with `twin` naming one of the C twins
- * below of the tests' device snippets.  models [F] are the llpf_model descriptors (the model's own parameters); R1 [F][nx][nx],
- * R2 [F][ny][ny] dense row-major (the lower triangles are read); w = gamma, wm0, wc0, wi.  U [T][nu] or [F][T][nu] (per_filter bit 0),
- * Y [T][ny] or [F][T][ny] (bit 1); step t runs at tau = (t_index0 + t) * models[f].Ts.  Outputs (each optional) time-major as the device
- * writes them: ll_steps [T][F], x, xt [T][F][nx], R, Rt [T][F][nx][nx], e [T][F][ny]; ll_total [F]; x0, P0 receive the final state. */
-#include <stdint.h>
-#include <string.h>
-
+ * ukf_host_run: T steps of F filters from x0, P0, exactly as llpf_ukf_bank_run after llpf_ukf_bank_set_state(x0, P0).  f / g: dynamics
+ * and measurement (model, x, u, tau, out) — the tests pass the addresses of the oracle's orc_dynamics / orc_measurement, the device's
+ * models in the device's order — or NULL with `twin` naming one of the C twins below of the tests' device snippets.  models [F] are the
+ * llpf_model descriptors (the model's own parameters, Ts among them); w = gamma, wm0, wc0, wi.
+ * ukf_host_smooth: the backward pass of F filters over the posterior xt, Rt of a forward pass, exactly as llpf_ukf_bank_smooth runs it
+ * on the device; of the model it takes the dynamics only. */
 #include "llpf.h"
 #include "llpf_ukf.h"
+#include "kf_host_frame.h"
 
 typedef void (*ukf_fn)(const llpf_model* m, const double* x, const double* u, double t, double* out);
 
@@ -44,69 +42,85 @@ static void square_g(const llpf_model* m, const double* x, const double* u, doub
     out[0] = x[0] * x[0];
 }
 
-static void dense(int nx, const double* Rp, double* out) {
-    for (int r = 0; r < nx; ++r)
-        for (int c = 0; c < nx; ++c) out[r * nx + c] = Rp[llpf_kf_idx(r, c)];
+typedef struct {
+    int nx, ny;
+    ukf_fn f, g;
+    const llpf_model *models, *m;      /* m: the filter in hand */
+    const double *R1, *R2;             /* R2 null: the smoother's, which reads R1 only */
+    double gamma, wm0, wc0, wi;
+    double P[LLPF_UKF_NPAR(LLPF_KF_MAXX, LLPF_KF_MAXY)];
+    double Cf[LLPF_KF_NP(LLPF_KF_MAXX)], Z[LLPF_UKF_NPTS(LLPF_KF_MAXX) * LLPF_KF_MAXX], X[LLPF_KF_MAXX];
+} ukf_ctx;
+
+/* 0, or the entry point's error; the model functions of a twin replace f / g */
+static int ukf_ctx_set(ukf_ctx* k, int nx, int ny, ukf_fn f, ukf_fn g, int twin, const llpf_model* models, const double* R1, const double* R2,
+                       const double* w) {
+    if (twin == 1) { f = pendulum_f; g = pendulum_g; }
+    if (twin == 2) { f = square_f; g = square_g; }
+    if (!f || !g) return -2;
+    k->nx = nx; k->ny = ny; k->f = f; k->g = g; k->models = models; k->R1 = R1; k->R2 = R2;
+    k->gamma = w[0]; k->wm0 = w[1]; k->wc0 = w[2]; k->wi = w[3];
+    return 0;
 }
+static double ukf_begin(void* ctx, int f) {
+    ukf_ctx* k = ctx;
+    k->m = k->models + f;
+    kf_host_pack(k->nx, k->R1 + (size_t)f * k->nx * k->nx, k->P + LLPF_UKF_OFF_R1);
+    if (k->R2) kf_host_pack(k->ny, k->R2 + (size_t)f * k->ny * k->ny, k->P + LLPF_UKF_OFF_R2(k->nx));
+    return k->m->Ts;
+}
+/* Z = fn at the sigma points of (x, R), `dim` values each; returns llpf_ukf_factor's status */
+static int ukf_propagate(ukf_ctx* k, ukf_fn fn, int dim, const double* u, double tau, const double* x, const double* R) {
+    const int ok = llpf_ukf_factor(k->nx, R, k->Cf);
+    for (int i = 0; i < LLPF_UKF_NPTS(k->nx); ++i) {
+        llpf_ukf_point(k->nx, k->gamma, x, k->Cf, i, k->X);
+        fn(k->m, k->X, u, tau, k->Z + i * dim);
+    }
+    return ok;
+}
+static double ukf_correct(void* ctx, const double* u, const double* y, double tau, double* x, double* R, double* e, int* done) {
+    ukf_ctx* k = ctx;
+    (void)done;
+    if (!(y[0] == y[0])) {
+        for (int r = 0; r < k->ny; ++r) e[r] = llpf_kf_nan();
+        return 0.0;
+    }
+    const int ok = ukf_propagate(k, k->g, k->ny, u, tau, x, R);
+    return llpf_ukf_correct_finish(k->nx, k->ny, k->gamma, k->wm0, k->wc0, k->wi, k->P, 1, ok, k->Cf, k->Z, 1, y, x, R, e);
+}
+static void ukf_predict(void* ctx, const double* u, double tau, double* x, double* R) {
+    ukf_ctx* k = ctx;
+    const int ok = ukf_propagate(k, k->f, k->nx, u, tau, x, R);
+    llpf_ukf_predict_finish(k->nx, k->wm0, k->wc0, k->wi, k->P, 1, ok, k->Z, 1, x, R);
+}
+static void ukf_smooth(void* ctx, const double* u, double tau, const double* xf, const double* Rf, double* xs, double* Rs) {
+    ukf_ctx* k = ctx;
+    const int ok = ukf_propagate(k, k->f, k->nx, u, tau, xf, Rf);
+    llpf_ukf_smooth_finish(k->nx, k->gamma, k->wm0, k->wc0, k->wi, k->P, 1, ok, k->Cf, k->Z, 1, xf, Rf, xs, Rs);
+}
+static const kf_host_family ukf_family = {ukf_begin, ukf_correct, ukf_predict, ukf_smooth};
 
 int ukf_host_run(int F, int nx, int ny, int nu, ukf_fn f, ukf_fn g, int twin, const llpf_model* models, const double* R1, const double* R2,
                  const double* w, double* x0, double* P0, const double* U, const double* Y, int64_t T, int per_filter, double t_index0,
                  double* ll_total, double* ll_steps, double* xo, double* xto, double* Ro, double* Rto, double* eo) {
     if (nx < 1 || nx > LLPF_KF_MAXX || ny < 1 || ny > LLPF_KF_MAXY || nu < 0 || nu > LLPF_KF_MAXU) return -1;
-    if (twin == 1) { f = pendulum_f; g = pendulum_g; }
-    if (twin == 2) { f = square_f; g = square_g; }
-    if (!f || !g) return -2;
-    const double gamma = w[0], wm0 = w[1], wc0 = w[2], wi = w[3];
-    const double zero_u[LLPF_KF_MAXU] = {0.0};
-    const int npt = LLPF_UKF_NPTS(nx);
-    double P[LLPF_UKF_NPAR(LLPF_KF_MAXX, LLPF_KF_MAXY)];
-    for (int k = 0; k < F; ++k) {
-        const llpf_model* m = models + k;
-        for (int r = 0; r < nx; ++r)
-            for (int c = 0; c <= r; ++c) P[LLPF_UKF_OFF_R1 + llpf_kf_idx(r, c)] = R1[((size_t)k * nx + r) * nx + c];
-        for (int r = 0; r < ny; ++r)
-            for (int c = 0; c <= r; ++c) P[LLPF_UKF_OFF_R2(nx) + llpf_kf_idx(r, c)] = R2[((size_t)k * ny + r) * ny + c];
-        double x[LLPF_KF_MAXX], R[LLPF_KF_NP(LLPF_KF_MAXX)], Cf[LLPF_KF_NP(LLPF_KF_MAXX)], e[LLPF_KF_MAXY];
-        double Z[LLPF_UKF_NPTS(LLPF_KF_MAXX) * LLPF_KF_MAXX], X[LLPF_KF_MAXX];
-        for (int i = 0; i < nx; ++i) x[i] = x0[(size_t)k * nx + i];
-        for (int r = 0; r < nx; ++r)
-            for (int c = 0; c <= r; ++c) R[llpf_kf_idx(r, c)] = P0[((size_t)k * nx + r) * nx + c];
-        double llt = 0.0;
-        for (int64_t t = 0; t < T; ++t) {
-            const size_t tf = (size_t)t * F + k;
-            const double* u = nu > 0 ? U + ((per_filter & 1) ? ((size_t)k * T + t) : (size_t)t) * nu : zero_u;
-            const double* y = Y + ((per_filter & 2) ? ((size_t)k * T + t) : (size_t)t) * ny;
-            const double tau = (t_index0 + (double)t) * m->Ts;
-            if (xo) memcpy(xo + tf * nx, x, sizeof(double) * nx);
-            if (Ro) dense(nx, R, Ro + tf * nx * nx);
-            double ll = 0.0;
-            if (!(y[0] == y[0])) {
-                for (int r = 0; r < ny; ++r) e[r] = llpf_kf_nan();
-            } else {
-                const int ok = llpf_ukf_factor(nx, R, Cf);
-                for (int i = 0; i < npt; ++i) {
-                    llpf_ukf_point(nx, gamma, x, Cf, i, X);
-                    g(m, X, u, tau, Z + i * ny);
-                }
-                ll = llpf_ukf_correct_finish(nx, ny, gamma, wm0, wc0, wi, P, 1, ok, Cf, Z, 1, y, x, R, e);
-            }
-            llt = llt + ll;
-            if (ll_steps) ll_steps[tf] = ll;
-            if (eo) memcpy(eo + tf * ny, e, sizeof(double) * ny);
-            if (xto) memcpy(xto + tf * nx, x, sizeof(double) * nx);
-            if (Rto) dense(nx, R, Rto + tf * nx * nx);
-            {
-                const int ok = llpf_ukf_factor(nx, R, Cf);
-                for (int i = 0; i < npt; ++i) {
-                    llpf_ukf_point(nx, gamma, x, Cf, i, X);
-                    f(m, X, u, tau, Z + i * nx);
-                }
-                llpf_ukf_predict_finish(nx, wm0, wc0, wi, P, 1, ok, Z, 1, x, R);
-            }
-        }
-        if (ll_total) ll_total[k] = llt;
-        for (int i = 0; i < nx; ++i) x0[(size_t)k * nx + i] = x[i];
-        dense(nx, R, P0 + (size_t)k * nx * nx);
-    }
+    ukf_ctx k;
+    const int rc = ukf_ctx_set(&k, nx, ny, f, g, twin, models, R1, R2, w);
+    if (rc) return rc;
+    const kf_host_io io = {.F = F, .nx = nx, .ny = ny, .nu = nu, .T = T, .per_filter = per_filter, .t_index0 = t_index0, .U = U, .Y = Y,
+                           .x0 = x0, .P0 = P0, .ll_total = ll_total, .ll_steps = ll_steps, .x = xo, .xt = xto, .R = Ro, .Rt = Rto, .e = eo};
+    kf_host_forward(&io, &ukf_family, &k);
+    return 0;
+}
+
+int ukf_host_smooth(int F, int nx, int nu, ukf_fn f, int twin, const llpf_model* models, const double* R1, const double* w, const double* U,
+                    int64_t T, int per_filter, double t_index0, const double* xt, const double* Rt, double* xTo, double* RTo) {
+    if (nx < 1 || nx > LLPF_KF_MAXX || nu < 0 || nu > LLPF_KF_MAXU || T < 1) return -1;
+    ukf_ctx k;
+    const int rc = ukf_ctx_set(&k, nx, 0, f, f, twin, models, R1, NULL, w);
+    if (rc) return rc;
+    const kf_host_io io = {.F = F, .nx = nx, .nu = nu, .T = T, .per_filter = per_filter, .t_index0 = t_index0, .U = U, .post_x = xt,
+                           .post_R = Rt, .xT = xTo, .RT = RTo};
+    kf_host_backward(&io, &ukf_family, &k);
     return 0;
 }

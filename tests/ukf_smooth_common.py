@@ -1,36 +1,15 @@
 """Shared pieces of the unscented-smoother tests (test_ukf_smooth.py, test_gpu_ukf_smooth.py) and of tools/bench_ukf.py --smooth: the host
-build of llpf_ukf_smooth_finish (tests/ukf_smooth_host.c) around the oracle's dynamics or the C twins of the test snippets, and a numpy
+build of llpf_ukf_smooth_finish (tests/ukf_host.c) around the oracle's dynamics or the C twins of the test snippets, and a numpy
 restatement of the textbook additive-noise unscented Rauch-Tung-Striebel smoother (Sarkka 2008) in its literal formulas, in float64
 (ukf_common.Lin64) and in np.longdouble (ukf_common.LinLong), that shares nothing with the header."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
 import numpy as np
 
 from llpf_amd import _structs as S
+import kf_host as kh
+from kf_host import _p
 import ukf_common as uc
 
-SHIM = os.path.join(uc.ROOT, "tests", "ukf_smooth_host.c")
-_dp = C.POINTER(C.c_double)
-
-
-def build_host_smooth(outdir):
-    """cc -O2 -ffp-contract=off of tests/ukf_smooth_host.c into outdir; returns the loaded library"""
-    cc = shutil.which("cc") or shutil.which("gcc")
-    so = os.path.join(str(outdir), "libukf_smooth_host.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", uc.SHARED, "-I", os.path.join(uc.ROOT, "include"),
-                    SHIM, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.ukf_host_smooth.restype = C.c_int
-    L.ukf_host_smooth.argtypes = ([C.c_int] * 3 + [C.c_void_p, C.c_int, C.POINTER(S.Model)] + [_dp] * 3 + [C.c_int64, C.c_int, C.c_double]
-                                  + [_dp] * 4)
-    return L
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(_dp)
+build_host_smooth = uc.build_host      # the unscented twin is one library: ukf_host_smooth is in it
 
 
 def host_smooth(L, models, w, U, fw, T, per_filter=0, t_index0=0.0, twin=0):
@@ -40,16 +19,11 @@ def host_smooth(L, models, w, U, fw, T, per_filter=0, t_index0=0.0, twin=0):
     m0 = models[0]
     nx, nu = m0.nx, m0.nu
     arr = (S.Model * F)(*models)
-    R1 = np.ascontiguousarray(np.stack([S.gaussian_cov_matrix(m.dynamics_density) for m in models]), dtype=np.float64)
-    U = np.ascontiguousarray(U, dtype=np.float64) if nu > 0 else np.zeros(1)
+    R1 = kh.pack_models(models)[0]
     wv = np.array(w, dtype=np.float64)
-    xt = np.ascontiguousarray(fw["xt"], dtype=np.float64)
-    Rt = np.ascontiguousarray(fw["Rt"], dtype=np.float64)
-    assert xt.shape == (T, F, nx) and Rt.shape == (T, F, nx, nx)
-    out = dict(xT=np.empty((T, F, nx)), RT=np.empty((T, F, nx, nx)))
+    out, iop = kh.smooth_io(fw, T, F, nx)
     f = None if twin else uc.oracle_fns()[0]
-    rc = L.ukf_host_smooth(F, nx, nu, f, twin, arr, _p(R1), _p(wv), _p(U), T, per_filter, float(t_index0), _p(xt), _p(Rt),
-                           _p(out["xT"]), _p(out["RT"]))
+    rc = L.ukf_host_smooth(F, nx, nu, f, twin, arr, _p(R1), _p(wv), _p(kh.inputs(U, nu)), T, per_filter, float(t_index0), *iop)
     assert rc == 0
     return out
 

@@ -8,7 +8,7 @@ Prints one JSON line per configuration.
 --iterated: the iterated extended Kalman filter (llpf_ekf_bank_set_iterations, maxiters 10, epsilon 1e-8) beside the plain one instead
 of the unscented bank — the same bank handle, ll_total only, plain then iterated in the same process — on the same models and sizes and
 on a bank of pendulum snippets with per-filter priors (tests/ekf_common.py: PENDULUM_JAC_SRC), the one case whose lanes iterate more
-than twice; its mean linearisations per step come from the host build (tests/iekf_host.c) over --host-filters filters.  In a rocprofv3
+than twice; its mean linearisations per step come from the host build (tests/ekf_host.c) over --host-filters filters.  In a rocprofv3
 run the plain kernel is k_ekf<..., EkfArgs> and the iterated one k_ekf<..., IekfArgs>."""
 import argparse
 import json

@@ -6,7 +6,7 @@ Prints one JSON line per configuration.
 
 --smooth: the same for llpf_kalman_bank_smooth (forward pass plus the RTS smoother's backward pass) at (nx, ny) in {(4, 2), (8, 4)} by
 default, in two forms: ll + xT, and xT + RT; the host baseline is one thread running the header's forward step with the posterior stored
-and its backward step (tests/kalman_host.c, tests/kalman_smooth_host.c)."""
+and its backward step (tests/kalman_host.c)."""
 import argparse
 import json
 import os

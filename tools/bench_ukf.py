@@ -7,8 +7,7 @@ the single-thread host build of the same header (tests/ukf_host.c, cc -O2).  End
 cost the unscented bank replaces.  Prints one JSON line per configuration.
 
 --smooth: the same for llpf_ukf_bank_smooth (forward pass plus the unscented RTS smoother's backward pass) in two forms, ll + xT and
-xT + RT; the host baseline is one thread running the header's forward step and its backward step (tests/ukf_host.c,
-tests/ukf_smooth_host.c)."""
+xT + RT; the host baseline is one thread running the header's forward step and its backward step (tests/ukf_host.c)."""
 import argparse
 import json
 import os
