@@ -199,8 +199,79 @@ def device_count():
     return n.value
 
 
-class FilterHandle:
+class _Handle:
+    """What every handle shares.  `_SYM`: the prefix of the handle's symbols, so that verb `v` is the export `_SYM_v` (llpf_<verb> for the
+    filter, llpf_<kind>_<verb> for the banks); `h`: the handle, destroyed by close() or with the object."""
+    _SYM = None
+
+    def _call(self, verb, *args):
+        check(getattr(self.L, "%s_%s" % (self._SYM, verb))(self.h, *args))
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.L, self._SYM + "_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._call("reset")
+
+    def _scalar(self, verb, ctype):
+        """a getter whose one output is a scalar of `ctype`"""
+        v = ctype(0)
+        self._call(verb, C.byref(v))
+        return v.value
+
+    def _profile(self, *lead):
+        ms = np.zeros(PROF_CLASSES)
+        n = np.zeros(PROF_CLASSES, dtype=np.int64)
+        self._call("get_profile", *lead, dptr(ms), iptr(n))
+        return ms, n
+
+    def _io(self, U, Y):
+        """the inputs every filter shares: U [T, nu] (None without inputs), Y [T, ny], T"""
+        Y = f64(Y).reshape(-1, self.ny)
+        T = Y.shape[0]
+        U = f64(U).reshape(T, self.nu) if self.nu else None
+        return U, Y, T
+
+
+class _PfHandle(_Handle):
+    """... and what the handles of particle filters share beyond that: the seed, the profile and the counters of the last run."""
+
+    def seed(self, s):
+        self._call("seed", int(s) & 0xFFFFFFFFFFFFFFFF)
+
+    def set_profiling(self, on):
+        self._call("set_profiling", 1 if on else 0)
+
+    def profile(self):
+        return self._profile()
+
+    def last_run_ms(self):
+        return self._scalar("last_run_ms", C.c_double)
+
+    def resample_count(self):
+        return self._scalar("resample_count", C.c_int64)
+
+
+def _models_or_replicas(base_cfg, models, n_filters):
+    """F, the (S.Model * F) array or None, and filter 0's model: one llpf_model per filter, or None with n_filters, where every filter uses
+    base_cfg.model (Monte-Carlo replicas)"""
+    if models is None:
+        return int(n_filters), None, base_cfg.model
+    F = len(models)
+    return F, (S.Model * F)(*models), models[0]
+
+
+class FilterHandle(_PfHandle):
     """RAII wrapper of an `llpf_filter*` (one filter on one device)."""
+    _SYM = "llpf"
 
     def __init__(self, cfg):
         self.L = lib()
@@ -212,27 +283,10 @@ class FilterHandle:
         if cfg.model.model_id == S.MODEL_RB_BILINEAR:      # particles, history and means are [xn; xl] (RBParticle, reference src/rbpf.jl:24-30)
             self.nx = cfg.model.nx + cfg.model.rb.nxl
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.llpf_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # --- step ---
-    def reset(self):
-        check(self.L.llpf_reset(self.h))
-
-    def seed(self, s):
-        check(self.L.llpf_seed(self.h, int(s) & 0xFFFFFFFFFFFFFFFF))
-
     def set_model(self, model):
         """new parameters, same model family and dimensions (the reference's filter_from_parameters(theta, pf)): nothing is reallocated"""
-        check(self.L.llpf_set_model(self.h, C.byref(model)))
+        self._call("set_model", C.byref(model))
 
     def _u(self, u):
         if self.nu == 0:
@@ -250,27 +304,28 @@ class FilterHandle:
             raise ValueError("y must have %d elements" % self.ny)
         return y
 
+    def _step_ll(self, verb, *args):
+        """a step whose last argument is the log-likelihood it returns"""
+        ll = C.c_double(0)
+        self._call(verb, *args, C.byref(ll))
+        return ll.value
+
     def correct(self, u, y, t):
         u, y = self._u(u), self._y(y)
-        ll = C.c_double(0)
-        check(self.L.llpf_correct(self.h, dptr(u), dptr(y), float(t), C.byref(ll)))
-        return ll.value
+        return self._step_ll("correct", dptr(u), dptr(y), float(t))
 
     def predict(self, u, t):
         u = self._u(u)
-        check(self.L.llpf_predict(self.h, dptr(u), float(t)))
+        self._call("predict", dptr(u), float(t))
 
     def update(self, u, y, t):
         u, y = self._u(u), self._y(y)
-        ll = C.c_double(0)
-        check(self.L.llpf_update(self.h, dptr(u), dptr(y), float(t), C.byref(ll)))
-        return ll.value
+        return self._step_ll("update", dptr(u), dptr(y), float(t))
 
-    def run(self, U, Y, t_index0=0.0, ll_steps=False, xmean=False, history=False, xcov=False, quantiles=None):
-        """quantiles: probabilities q -> res["xquant"] [T, nx, len(q)], weighted_quantile of every timestep's state on the device"""
-        Y = f64(Y).reshape(-1, self.ny)
-        T = Y.shape[0]
-        U = f64(U).reshape(T, self.nu) if self.nu else None
+    def _run(self, verb, U, Y, arg, ll_steps, xmean, history, xcov=False, quantiles=None):
+        """llpf_run / llpf_aux_run: the outputs asked for, as the RunOutputs of the call and as the dictionary it returns; `arg`: the
+        argument between T and ll_total (t_index0, or the mode)"""
+        U, Y, T = self._io(U, Y)
         outs = S.RunOutputs()
         res = {}
         if quantiles is not None:
@@ -292,9 +347,13 @@ class FilterHandle:
             res["we"] = np.zeros((T, self.N))
             outs.x_hist, outs.w_hist, outs.we_hist = dptr(res["x"]), dptr(res["w"]), dptr(res["we"])
         ll = C.c_double(0)
-        check(self.L.llpf_run(self.h, dptr(U), dptr(Y), T, float(t_index0), C.byref(ll), C.byref(outs)))
+        self._call(verb, dptr(U), dptr(Y), T, arg, C.byref(ll), C.byref(outs))
         res["ll"] = ll.value
         return res
+
+    def run(self, U, Y, t_index0=0.0, ll_steps=False, xmean=False, history=False, xcov=False, quantiles=None):
+        """quantiles: probabilities q -> res["xquant"] [T, nx, len(q)], weighted_quantile of every timestep's state on the device"""
+        return self._run("run", U, Y, float(t_index0), ll_steps, xmean, history, xcov, quantiles)
 
     def simulate(self, M, T, U=None, u_per_trajectory=False, t_index0=0.0, seed=0, step0=0, flags=SIM_DYNAMICS_NOISE | SIM_MEASUREMENT_NOISE,
                  states=True, measurements=True):
@@ -304,11 +363,14 @@ class FilterHandle:
                          states, measurements)
         return (None if X is None else X[0]), (None if Y is None else Y[0])
 
+    def _get(self, verb, a):
+        """an accessor that fills the array `a` (float64, or int64)"""
+        self._call(verb, iptr(a) if a.dtype == np.int64 else dptr(a))
+        return a
+
     def weighted_cov(self):
         """weighted_cov of the current particles under the current weights (reference src/filtering.jl:571-581), on the device"""
-        a = np.zeros((self.nx, self.nx))
-        check(self.L.llpf_weighted_cov(self.h, dptr(a)))
-        return a
+        return self._get("weighted_cov", np.zeros((self.nx, self.nx)))
 
     def weighted_quantile(self, q):
         """weighted_quantile of the current particles under the current weights (reference src/filtering.jl:583-595), on the device.
@@ -316,22 +378,20 @@ class FilterHandle:
         to the reference's [state][q] nesting."""
         q = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64)
         out = np.empty((q.size, self.nx))
-        check(self.L.llpf_weighted_quantile(self.h, dptr(q), q.size, dptr(out)))
+        self._call("weighted_quantile", dptr(q), q.size, dptr(out))
         return out
 
     def rb_covariance(self):
         """x[1].R of an RBPF: the covariance of the linear substate shared by all particles."""
         nl = self.nx - self.cfg.model.nxn
-        a = np.zeros((nl, nl))
-        check(self.L.llpf_rb_get_covariance(self.h, dptr(a)))
-        return a
+        return self._get("rb_get_covariance", np.zeros((nl, nl)))
 
     def rb_linear_state(self):
         """per-particle Kalman state of LLPF_MODEL_RB_BILINEAR: xl [N, nxl], R [N, nxl, nxl] (fields of RBParticle)."""
         nl = self.cfg.model.rb.nxl
         xl = np.zeros((self.N, nl))
         R = np.zeros((self.N, nl, nl))
-        check(self.L.llpf_rb_get_linear_state(self.h, dptr(xl), dptr(R)))
+        self._call("rb_get_linear_state", dptr(xl), dptr(R))
         return xl, R
 
     def smooth(self, M, U, xf, wf, wef):
@@ -341,153 +401,88 @@ class FilterHandle:
         U = f64(U).reshape(T, self.nu) if self.nu else None
         xb = np.zeros((T, int(M), self.nx))
         idx = np.zeros((T, int(M)), dtype=np.int64)
-        check(self.L.llpf_smooth(self.h, int(M), dptr(U), T, dptr(xf), dptr(wf), dptr(wef), dptr(xb), iptr(idx)))
+        self._call("smooth", int(M), dptr(U), T, dptr(xf), dptr(wf), dptr(wef), dptr(xb), iptr(idx))
         return xb, idx
 
     # --- AuxiliaryParticleFilter verbs (reference src/filtering.jl:170-217) ---
     def aux_correct(self):
-        ll = C.c_double(0)
-        check(self.L.llpf_aux_correct(self.h, C.byref(ll)))
-        return ll.value
+        return self._scalar("aux_correct", C.c_double)
 
     def aux_predict(self, u, y1, t):
         u, y1 = self._u(u), self._y(y1)
-        check(self.L.llpf_aux_predict(self.h, dptr(u), dptr(y1), float(t)))
+        self._call("aux_predict", dptr(u), dptr(y1), float(t))
 
     def aux_update(self, u, y1, t):
         u, y1 = self._u(u), self._y(y1)
-        ll = C.c_double(0)
-        check(self.L.llpf_aux_update(self.h, dptr(u), dptr(y1), float(t), C.byref(ll)))
-        return ll.value
+        return self._step_ll("aux_update", dptr(u), dptr(y1), float(t))
 
     def run_aux(self, U, Y, mode=0, ll_steps=False, xmean=False, history=False):
         """mode 0: forward_trajectory loop, mode 1: loglik loop of the AuxiliaryParticleFilter (after reset)."""
-        Y = f64(Y).reshape(-1, self.ny)
-        T = Y.shape[0]
-        U = f64(U).reshape(T, self.nu) if self.nu else None
-        outs = S.RunOutputs()
-        res = {}
-        if ll_steps:
-            res["ll_steps"] = np.zeros(T)
-            outs.ll_steps = dptr(res["ll_steps"])
-        if xmean:
-            res["xmean"] = np.zeros((T, self.nx))
-            outs.xmean = dptr(res["xmean"])
-        if history:
-            res["x"] = np.zeros((T, self.N, self.nx))
-            res["w"] = np.zeros((T, self.N))
-            res["we"] = np.zeros((T, self.N))
-            outs.x_hist, outs.w_hist, outs.we_hist = dptr(res["x"]), dptr(res["w"]), dptr(res["we"])
-        ll = C.c_double(0)
-        check(self.L.llpf_aux_run(self.h, dptr(U), dptr(Y), T, int(mode), C.byref(ll), C.byref(outs)))
-        res["ll"] = ll.value
-        return res
+        return self._run("aux_run", U, Y, int(mode), ll_steps, xmean, history)
 
     # --- accessors ---
     def index(self):
-        t = C.c_int64(0)
-        check(self.L.llpf_index(self.h, C.byref(t)))
-        return t.value
+        return self._scalar("index", C.c_int64)
 
     def set_index(self, t):
-        check(self.L.llpf_set_index(self.h, int(t)))
+        self._call("set_index", int(t))
 
     def particles(self):
-        a = np.empty((self.N, self.nx))
-        check(self.L.llpf_get_particles(self.h, dptr(a)))
-        return a
+        return self._get("get_particles", np.empty((self.N, self.nx)))
 
     def weights(self):
-        a = np.empty(self.N)
-        check(self.L.llpf_get_weights(self.h, dptr(a)))
-        return a
+        return self._get("get_weights", np.empty(self.N))
 
     def expweights(self):
-        a = np.empty(self.N)
-        check(self.L.llpf_get_expweights(self.h, dptr(a)))
-        return a
+        return self._get("get_expweights", np.empty(self.N))
 
     def ancestors(self):
-        a = np.empty(self.N, dtype=np.int64)
-        check(self.L.llpf_get_ancestors(self.h, iptr(a)))
-        return a
+        return self._get("get_ancestors", np.empty(self.N, dtype=np.int64))
 
     def bins(self):
-        a = np.empty(self.N)
-        check(self.L.llpf_get_bins(self.h, dptr(a)))
-        return a
+        return self._get("get_bins", np.empty(self.N))
 
     def set_particles(self, x):
         x = f64(x).reshape(self.N, self.nx)
-        check(self.L.llpf_set_particles(self.h, dptr(x)))
+        self._call("set_particles", dptr(x))
 
     def set_weights(self, w):
         w = f64(w).reshape(self.N)
-        check(self.L.llpf_set_weights(self.h, dptr(w)))
+        self._call("set_weights", dptr(w))
 
     def ess(self):
-        v = C.c_double(0)
-        check(self.L.llpf_effective_particles(self.h, C.byref(v)))
-        return v.value
+        return self._scalar("effective_particles", C.c_double)
 
     def shouldresample(self):
-        v = C.c_int32(0)
-        check(self.L.llpf_shouldresample(self.h, C.byref(v)))
-        return bool(v.value)
+        return bool(self._scalar("shouldresample", C.c_int32))
 
     def last_resampled(self):
-        v = C.c_int32(0)
-        check(self.L.llpf_last_resampled(self.h, C.byref(v)))
-        return bool(v.value)
+        return bool(self._scalar("last_resampled", C.c_int32))
 
     def maxw(self):
-        v = C.c_double(0)
-        check(self.L.llpf_maxw(self.h, C.byref(v)))
-        return v.value
+        return self._scalar("maxw", C.c_double)
 
     def weighted_mean(self):
-        a = np.empty(self.nx)
-        check(self.L.llpf_weighted_mean(self.h, dptr(a)))
-        return a
-
-    def resample_count(self):
-        v = C.c_int64(0)
-        check(self.L.llpf_resample_count(self.h, C.byref(v)))
-        return v.value
-
-    def last_run_ms(self):
-        v = C.c_double(0)
-        check(self.L.llpf_last_run_ms(self.h, C.byref(v)))
-        return v.value
+        return self._get("weighted_mean", np.empty(self.nx))
 
     def last_run_stats(self):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
-        check(self.L.llpf_last_run_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        self._call("last_run_stats", C.byref(a), C.byref(b), C.byref(c))
         return {"fused_launches": a.value, "source_side_timesteps": b.value, "survivor_fraction": c.value}
 
     def last_run_form(self):
         a, b = C.c_int32(0), C.c_int64(0)
-        check(self.L.llpf_last_run_form(self.h, C.byref(a), C.byref(b)))
+        self._call("last_run_form", C.byref(a), C.byref(b))
         return {"weights_not_stored": bool(a.value), "exact_redos": b.value}
-
-    def set_profiling(self, on):
-        check(self.L.llpf_set_profiling(self.h, 1 if on else 0))
-
-    def profile(self):
-        ms = np.zeros(PROF_CLASSES)
-        n = np.zeros(PROF_CLASSES, dtype=np.int64)
-        check(self.L.llpf_get_profile(self.h, dptr(ms), iptr(n)))
-        return ms, n
 
 
 KALMAN_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
 KALMAN_SMOOTH_OUTPUTS = ("xT", "RT")
 
 
-class _KfBankHandle:
-    """What the handles of the one-thread-per-filter Kalman banks share.  `_SYM`: the prefix of the bank's symbols; `times`: the arguments
-    the bank's run and smooth take between per_filter and ll_total (none, or t_index0)."""
-    _SYM = None
+class _KfBankHandle(_Handle):
+    """What the handles of the one-thread-per-filter Kalman banks share.  `times`: the arguments the bank's run and smooth take between
+    per_filter and ll_total (none, or t_index0)."""
 
     def _open(self, models):
         self.L = lib()
@@ -496,23 +491,6 @@ class _KfBankHandle:
         m0 = models[0]
         self.nx, self.nu, self.ny = m0.nx, m0.nu, m0.ny
         return (S.Model * self.F)(*models)
-
-    def _call(self, verb, *args):
-        check(getattr(self.L, "%s_%s" % (self._SYM, verb))(self.h, *args))
-
-    def close(self):
-        if getattr(self, "h", None):
-            getattr(self.L, self._SYM + "_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self._call("reset")
 
     def _inputs(self, U, Y, u_per_filter, y_per_filter):
         F, nu, ny = self.F, self.nu, self.ny
@@ -655,60 +633,33 @@ class EkfBankHandle(_KfBankHandle):
         return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
 
 
-class BankHandle:
+class BankHandle(_PfHandle):
     """RAII wrapper of an `llpf_bank*` (many independent filters on one device)."""
+    _SYM = "llpf_bank"
 
     def __init__(self, base_cfg, models=None, n_filters=None):
         """models: one llpf_model per filter, or None with n_filters: every filter uses base_cfg.model (Monte-Carlo replicas)."""
         self.L = lib()
         self.cfg = base_cfg
         self.h = _vp()
-        if models is None:
-            self.F = int(n_filters)
-            self._models = None
-            check(self.L.llpf_bank_create(C.byref(base_cfg), None, self.F, C.byref(self.h)))
-            m0 = base_cfg.model
-        else:
-            self.F = len(models)
-            arr = (S.Model * self.F)(*models)
-            self._models = arr
-            check(self.L.llpf_bank_create(C.byref(base_cfg), arr, self.F, C.byref(self.h)))
-            m0 = models[0]
+        self.F, self._models, m0 = _models_or_replicas(base_cfg, models, n_filters)
+        check(self.L.llpf_bank_create(C.byref(base_cfg), self._models, self.F, C.byref(self.h)))
         self.N = int(base_cfg.n_particles)
         self.nx, self.nu, self.ny = m0.nx, m0.nu, m0.ny
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.llpf_bank_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        check(self.L.llpf_bank_reset(self.h))
-
-    def seed(self, s):
-        check(self.L.llpf_bank_seed(self.h, int(s) & 0xFFFFFFFFFFFFFFFF))
 
     def set_models(self, models):
         """new parameters for every filter of the bank (len(models) == n_filters), same model family and dimensions"""
         if len(models) != self.F:
             raise ValueError("set_models: %d models for a bank of %d filters" % (len(models), self.F))
         arr = (S.Model * self.F)(*models)
-        check(self.L.llpf_bank_set_models(self.h, arr))
+        self._call("set_models", arr)
         self._models = arr
 
     def run(self, U, Y, t_index0=0.0, ll_steps=False):
-        Y = f64(Y).reshape(-1, self.ny)
-        T = Y.shape[0]
-        U = f64(U).reshape(T, self.nu) if self.nu else None
+        U, Y, T = self._io(U, Y)
         ll = np.zeros(self.F)
         lls = np.zeros((T, self.F)) if ll_steps else None
-        check(self.L.llpf_bank_run(self.h, dptr(U), dptr(Y), T, float(t_index0), dptr(ll), dptr(lls)))
+        self._call("run", dptr(U), dptr(Y), T, float(t_index0), dptr(ll), dptr(lls))
         return {"ll": ll, "ll_steps": lls}
 
     def run_multi(self, U, Y, t_index0=0.0, ll_steps=False, xmean=False):
@@ -719,16 +670,14 @@ class BankHandle:
         ll = np.zeros(self.F)
         lls = np.zeros((T, self.F)) if ll_steps else None
         xm = np.zeros((T, self.F, self.nx)) if xmean else None
-        check(self.L.llpf_bank_run_multi(self.h, dptr(U), dptr(Y), T, float(t_index0), dptr(ll), dptr(lls), dptr(xm)))
+        self._call("run_multi", dptr(U), dptr(Y), T, float(t_index0), dptr(ll), dptr(lls), dptr(xm))
         return {"ll": ll, "ll_steps": lls, "xmean": xm}
 
     def run_aux(self, U, Y, mode=1, ll_steps=False):
-        Y = f64(Y).reshape(-1, self.ny)
-        T = Y.shape[0]
-        U = f64(U).reshape(T, self.nu) if self.nu else None
+        U, Y, T = self._io(U, Y)
         ll = np.zeros(self.F)
         lls = np.zeros((T, self.F)) if ll_steps else None
-        check(self.L.llpf_bank_aux_run(self.h, dptr(U), dptr(Y), T, int(mode), dptr(ll), dptr(lls)))
+        self._call("aux_run", dptr(U), dptr(Y), T, int(mode), dptr(ll), dptr(lls))
         return {"ll": ll, "ll_steps": lls}
 
     def simulate(self, M, T, U=None, u_per_trajectory=False, t_index0=0.0, seed=0, step0=0, flags=SIM_DYNAMICS_NOISE | SIM_MEASUREMENT_NOISE,
@@ -738,24 +687,6 @@ class BankHandle:
         return _simulate(self.L.llpf_bank_simulate, self.h, self.F, self.nx, self.nu, self.ny, M, T, U, u_per_trajectory, t_index0, seed, step0,
                          flags, states, measurements)
 
-    def last_run_ms(self):
-        v = C.c_double(0)
-        check(self.L.llpf_bank_last_run_ms(self.h, C.byref(v)))
-        return v.value
-
-    def resample_count(self):
-        v = C.c_int64(0)
-        check(self.L.llpf_bank_resample_count(self.h, C.byref(v)))
-        return v.value
-
-    def set_profiling(self, on):
-        check(self.L.llpf_bank_set_profiling(self.h, 1 if on else 0))
-
-    def profile(self):
-        ms = np.zeros(PROF_CLASSES)
-        n = np.zeros(PROF_CLASSES, dtype=np.int64)
-        check(self.L.llpf_bank_get_profile(self.h, dptr(ms), iptr(n)))
-        return ms, n
 
 MBANK_ID_BYTES = 128
 MBANK_COLL = {0: "none", 1: "rccl", 2: "host", 3: "external"}
@@ -768,26 +699,20 @@ def mbank_unique_id():
     return bytes(buf)
 
 
-class MBankHandle:
+class MBankHandle(_PfHandle):
     """RAII wrapper of an `llpf_mbank*`: a sweep of independent filters sharded over GPUs, filter k on shard k mod n_shards;
     the exchange of the log-likelihood vector (RCCL) happens inside run().
 
     devices=[...]             : this process drives all listed GPUs (llpf_mbank_create)
     rank=, world=, unique_id= : one process per GPU (llpf_mbank_create_rank); unique_id None with world > 1 leaves the
                                 exchange to the caller (run() then returns this rank's slots, zeros elsewhere)"""
+    _SYM = "llpf_mbank"
 
     def __init__(self, base_cfg, models=None, n_filters=None, devices=None, rank=None, world=None, unique_id=None):
         self.L = lib()
         self.cfg = base_cfg
         self.h = _vp()
-        if models is None:
-            self.F = int(n_filters)
-            arr = None
-            m0 = base_cfg.model
-        else:
-            self.F = len(models)
-            arr = (S.Model * self.F)(*models)
-            m0 = models[0]
+        self.F, arr, m0 = _models_or_replicas(base_cfg, models, n_filters)
         self._models = arr
         if rank is None:
             devs = list(devices if devices is not None else [base_cfg.device])
@@ -803,58 +728,34 @@ class MBankHandle:
         self.N = int(base_cfg.n_particles)
         self.nx, self.nu, self.ny = m0.nx, m0.nu, m0.ny
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.llpf_mbank_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        check(self.L.llpf_mbank_reset(self.h))
-
-    def seed(self, s):
-        check(self.L.llpf_mbank_seed(self.h, int(s) & 0xFFFFFFFFFFFFFFFF))
-
     def set_models(self, models):
         """new parameters for every filter of the sweep (all n_filters descriptors, on every rank)"""
         if len(models) != self.F:
             raise ValueError("set_models: %d models for a sweep of %d filters" % (len(models), self.F))
         arr = (S.Model * self.F)(*models)
-        check(self.L.llpf_mbank_set_models(self.h, arr))
+        self._call("set_models", arr)
         self._models = arr
 
-    def _io(self, U, Y):
-        Y = f64(Y).reshape(-1, self.ny)
-        T = Y.shape[0]
-        U = f64(U).reshape(T, self.nu) if self.nu else None
-        return U, Y, T
+    def _sweep(self, verb, U, Y, arg):
+        U, Y, T = self._io(U, Y)
+        ll = np.zeros(self.F)
+        tot = C.c_double(0)
+        self._call(verb, dptr(U), dptr(Y), T, arg, dptr(ll), C.byref(tot))
+        return {"ll": ll, "ll_sum": tot.value}
 
     def run(self, U, Y, t_index0=0.0):
-        U, Y, T = self._io(U, Y)
-        ll = np.zeros(self.F)
-        tot = C.c_double(0)
-        check(self.L.llpf_mbank_run(self.h, dptr(U), dptr(Y), T, float(t_index0), dptr(ll), C.byref(tot)))
-        return {"ll": ll, "ll_sum": tot.value}
+        return self._sweep("run", U, Y, float(t_index0))
 
     def run_aux(self, U, Y, mode=1):
-        U, Y, T = self._io(U, Y)
-        ll = np.zeros(self.F)
-        tot = C.c_double(0)
-        check(self.L.llpf_mbank_aux_run(self.h, dptr(U), dptr(Y), T, int(mode), dptr(ll), C.byref(tot)))
-        return {"ll": ll, "ll_sum": tot.value}
+        return self._sweep("aux_run", U, Y, int(mode))
 
     def info(self):
         i = S.MBankInfo()
-        check(self.L.llpf_mbank_info(self.h, C.byref(i)))
+        self._call("info", C.byref(i))
         d = {k: getattr(i, k) for k, _ in S.MBankInfo._fields_}
         d["collective"] = MBANK_COLL.get(d["collective"], d["collective"])
         devs = (C.c_int32 * max(1, i.n_local_shards))()
-        check(self.L.llpf_mbank_local_devices(self.h, devs))
+        self._call("local_devices", devs)
         d["local_devices"] = list(devs)[: i.n_local_shards]
         return d
 
@@ -864,14 +765,8 @@ class MBankHandle:
     def resample_count(self):
         return self.info()["resample_count"]
 
-    def set_profiling(self, on):
-        check(self.L.llpf_mbank_set_profiling(self.h, 1 if on else 0))
-
     def profile(self, local_shard=0):
-        ms = np.zeros(PROF_CLASSES)
-        n = np.zeros(PROF_CLASSES, dtype=np.int64)
-        check(self.L.llpf_mbank_get_profile(self.h, int(local_shard), dptr(ms), iptr(n)))
-        return ms, n
+        return self._profile(int(local_shard))
 
 
 def mbank_partition(n_filters, shard, n_shards):

@@ -208,11 +208,38 @@ static int use_device(const Bank& b) {
     return LLPF_OK;
 }
 
-static int scal_download(Bank& b, std::vector<FilterScal>& h) {
-    h.resize(b.F);
-    HIPC(hipMemcpyAsync(h.data(), b.d_scal, sizeof(FilterScal) * b.F, hipMemcpyDeviceToHost, b.stream));
+// the devices the runtime shows: none when it cannot be asked
+static int device_count() {
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
+}
+// There is no CPU implementation behind the ABI: whatever needs a device starts here.  *ndev: how many there are.
+static int need_device(int* ndev = nullptr) {
+    const int n = device_count();
+    if (n < 1) return fail(LLPF_ERR_NO_DEVICE, "no HIP device visible; this engine has no CPU fallback");
+    if (ndev) *ndev = n;
+    return LLPF_OK;
+}
+// the device and the stream of a new bank of any kind: the one place a bank's stream is created (~BankStream destroys it)
+static int open_stream(BankStream& b, int device) {
+    int ndev = 0;
+    CHK(need_device(&ndev));
+    if (device < 0 || device >= ndev) return fail(LLPF_ERR_ARG, "device ordinal out of range");
+    b.device = device;
+    HIPC(hipSetDevice(device));
+    HIPC(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    return LLPF_OK;
+}
+// the end of an accessor: bytes of device memory to the caller's, complete on return
+static int bank_to_host(Bank& b, void* dst, const void* src, size_t bytes) {
+    HIPC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b.stream));
     HIPC(hipStreamSynchronize(b.stream));
     return LLPF_OK;
+}
+
+static int scal_download(Bank& b, std::vector<FilterScal>& h) {
+    h.resize(b.F);
+    return bank_to_host(b, h.data(), b.d_scal, sizeof(FilterScal) * b.F);
 }
 static int scal_upload(Bank& b, const std::vector<FilterScal>& h) {
     HIPC(hipMemcpyAsync(b.d_scal, h.data(), sizeof(FilterScal) * b.F, hipMemcpyHostToDevice, b.stream));
@@ -235,6 +262,13 @@ static void set_keys(Bank& b, std::vector<FilterScal>& h, uint64_t seed) {
         h[f].k0 = (uint32_t)s;
         h[f].k1 = (uint32_t)(s >> 32);
     }
+}
+static int bank_seed(Bank& b, uint64_t seed) {
+    CHK(use_device(b));
+    std::vector<FilterScal> h;
+    CHK(scal_download(b, h));
+    set_keys(b, h, seed);
+    return scal_upload(b, h);
 }
 
 // profiling helpers ------------------------------------------------------------------------------
@@ -265,6 +299,15 @@ static void prof_collect(Bank& b) {
     }
     b.pending.clear();
 }
+static int set_prof(Bank& b, int on) {
+    b.profiling = on != 0;
+    for (int i = 0; i < LLPF_PROF_CLASSES; ++i) { b.prof_ms[i] = 0.0; b.prof_n[i] = 0; }
+    return LLPF_OK;
+}
+static int get_prof(Bank& b, double* ms, int64_t* n) {
+    for (int i = 0; i < LLPF_PROF_CLASSES; ++i) { if (ms) ms[i] = b.prof_ms[i]; if (n) n[i] = b.prof_n[i]; }
+    return LLPF_OK;
+}
 
 // the scratch of the resampling with source-side dynamics: marks (zero between timesteps) and the plane of f(x_j)
 // per-block parts of the weighted mean, one set per accumulator slot: [ACC_NSLOT][F][P1][MAXD] — 400 MB for a filter near 2^29 particles,
@@ -290,14 +333,29 @@ static int ensure_fx(Bank& b) {
 }
 
 static bool is_rbfull(const Bank& b) { return b.cfg.model.model_id == LLPF_MODEL_RB_BILINEAR; }
-static int bank_init_particles(Bank& b, bool is_reset) {
-    b.aux_pending = false; b.we_is_lambda = false;
-    for (size_t f = 0; f < b.rb.size(); ++f) {              // reset!(pf::RBPF): R = copy(pf.kf.d0.Sigma), src/rbpf.jl:152 (pf.kf itself is not reset)
+
+// LLPF_MODEL_RB_LINEAR (b.rb is empty otherwise), every filter: x[1].R = copy(d0.Sigma); with_kf: also the inner KalmanFilter object,
+// kf.x = d0.mu, kf.R = d0.Sigma
+static void rb_kf_init(Bank& b, bool with_kf) {
+    const int nl = b.nx - b.cfg.model.nxn;
+    for (size_t f = 0; f < b.rb.size(); ++f) {
         double S0[16];
         gauss_cov_dense(&b.hmodels[f].linear_initial, S0);
-        const int nl = b.nx - b.cfg.model.nxn;
-        for (int i = 0; i < nl * nl; ++i) b.rb[f].R[i] = S0[i];
+        for (int i = 0; i < nl * nl; ++i) { b.rb[f].R[i] = S0[i]; if (with_kf) b.rb[f].kfR[i] = S0[i]; }
+        if (with_kf) for (int i = 0; i < nl; ++i) b.rb[f].kfx[i] = b.hmodels[f].linear_initial.mu[i];
     }
+}
+// the accumulators and the tile sums empty, the next weighting kernel writes slot 0
+static int bank_zero_acc(Bank& b) {
+    HIPC(hipMemsetAsync(b.d_acc, 0, sizeof(uint64_t) * (size_t)b.F * ACC_WORDS, b.stream));
+    HIPC(hipMemsetAsync(b.d_tileq, 0, sizeof(uint64_t) * (size_t)ACC_NSLOT * b.F * b.P2, b.stream));
+    b.parity = 0;
+    return LLPF_OK;
+}
+
+static int bank_init_particles(Bank& b, bool is_reset) {
+    b.aux_pending = false; b.we_is_lambda = false;
+    rb_kf_init(b, false);              // reset!(pf::RBPF): R = copy(pf.kf.d0.Sigma), src/rbpf.jl:152 (pf.kf itself is not reset)
     // constructor (src/PFtypes.jl:65-75): x ~ d0, w = log(1/N), j = 1:N, t = 0
     // reset!      (src/filtering.jl:4-14): x ~ d0, w = -log N, we = 1/N, t = 1   (j untouched)
     std::vector<FilterScal> h;
@@ -318,10 +376,8 @@ static int bank_init_particles(Bank& b, bool is_reset) {
         if (!is_reset) { s.anc_ident_s[0] = s.anc_ident_s[1] = 1; s.last_resampled = 0; s.resample_count = 0; s.ll_total = 0.0; }
     }
     CHK(scal_upload(b, h));
-    HIPC(hipMemsetAsync(b.d_acc, 0, sizeof(uint64_t) * (size_t)b.F * ACC_WORDS, b.stream));
-    HIPC(hipMemsetAsync(b.d_tileq, 0, sizeof(uint64_t) * (size_t)ACC_NSLOT * b.F * b.P2, b.stream));
+    CHK(bank_zero_acc(b));
     HIPC(hipMemsetAsync(b.d_flag, 0, sizeof(uint32_t) * 4, b.stream));
-    b.parity = 0;
     if (b.cfg.model.model_id >= LLPF_MODEL_USER_BASE && (jit_model_traits(b.cfg.model.model_id) & LLPF_TRAIT_INITIAL) > 0) {
         // an initial density of the model's own: prepare() sees u = 0 — whatever the single-step verbs staged in d_uy last (a reset! after
         // predict!/correct! must equal the reset! of a fresh handle)
@@ -334,6 +390,58 @@ static int bank_init_particles(Bank& b, bool is_reset) {
     b.t_index = is_reset ? 1 : 0;
     HIPC(hipStreamSynchronize(b.stream));
     return LLPF_OK;
+}
+static int bank_reset(Bank& b) {
+    CHK(use_device(b));
+    return bank_init_particles(b, true);
+}
+
+// The filters of a bank share one kernel instance: the shape, the nonlinear part, the rows of a particle plane and BankDev::pad0 are
+// taken from filter 0's model m0.  0 when mf fits; otherwise which of the caller's three messages applies: 1 the model id or a
+// dimension differs, 2 LLPF_MODEL_RB_BILINEAR's rb.nxl / rb.fn_kind, 3 LLPF_MODEL_RB_LINEAR's nxn
+static int same_family(const llpf_model& m0, const llpf_model& mf) {
+    if (mf.model_id != m0.model_id || mf.nx != m0.nx || mf.nu != m0.nu || mf.ny != m0.ny) return 1;
+    if (m0.model_id == LLPF_MODEL_RB_BILINEAR && (mf.rb.nxl != m0.rb.nxl || mf.rb.fn_kind != m0.rb.fn_kind)) return 2;
+    if (m0.model_id == LLPF_MODEL_RB_LINEAR && mf.nxn != m0.nxn) return 3;
+    return 0;
+}
+
+// The pool: one device allocation for every buffer of a bank whose size is known at creation (a filter is often built per Monte-Carlo
+// run or per parameter candidate: 17 hipMalloc + as many memsets and hipFree cost more than a short run), zero-filled once.  Its layout
+// is written once and walked twice: without a base take() only adds up the sizes, each rounded up to 256 bytes; with the pool's
+// address it places the pointers.  A buffer of no elements is absent: it takes no bytes and its pointer stays null.
+struct PoolCarve {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    void take(T*& p, size_t n) {
+        if (!n) return;
+        if (base) p = reinterpret_cast<T*>(base + off);
+        off += (sizeof(T) * n + 255) / 256 * 256;
+    }
+};
+static size_t bank_carve(Bank& b, char* base) {
+    const size_t F = (size_t)b.F, FN = F * (size_t)b.Ns, P2 = (size_t)b.P2;
+    const bool two_level = b.P2 > 4 * BLOCK;           // (kernels/resample.hpp: TQ_GROUP) launch_tile_prefix tests d_tpre / d_gsum for null
+    PoolCarve c{base};
+    c.take(b.d_models, F);
+    c.take(b.d_scal, F);
+    c.take(b.d_x[0], FN * b.xrows);
+    c.take(b.d_x[1], FN * b.xrows);
+    c.take(b.d_w, FN);
+    c.take(b.d_anc, FN);
+    c.take(b.d_acc, F * ACC_WORDS);
+    c.take(b.d_quanta[0], FN);
+    c.take(b.d_quanta[1], FN);
+    c.take(b.d_tileq, (size_t)ACC_NSLOT * F * P2);
+    c.take(b.d_flag, 4);
+    c.take(b.d_rtile, F * 2 * P2);      // (xmpart: on the first run that asks for weighted means, ensure_xmpart)
+    c.take(b.d_rb, b.cfg.model.model_id == LLPF_MODEL_RB_LINEAR ? 2 * F : 0);
+    c.take(b.d_tpre, two_level ? F * P2 : 0);
+    c.take(b.d_gsum, two_level ? F * ((P2 + 4 * BLOCK - 1) / (4 * BLOCK)) : 0);
+    c.take(b.d_uy, 4 * MAXD);
+    c.take(b.d_tmp, F * (size_t)b.N * (b.nxp > 1 ? b.nxp : 1) + 64 / sizeof(double));
+    return c.off;
 }
 
 static int bank_create(const llpf_config* cfg, const llpf_model* models, int F, Bank& b, uint64_t key_off = 0, uint64_t key_stride = 1) {
@@ -382,10 +490,7 @@ static int bank_create(const llpf_config* cfg, const llpf_model* models, int F, 
     if (!(cfg->resample_threshold >= 0.0 && cfg->resample_threshold <= 1.0)) return fail(LLPF_ERR_ARG, "resample_threshold must be in [0,1]");
     if (cfg->filter_kind != LLPF_PARTICLE_FILTER && cfg->filter_kind != LLPF_ADVANCED_PARTICLE_FILTER)
         return fail(LLPF_ERR_ARG, "filter_kind must be LLPF_PARTICLE_FILTER or LLPF_ADVANCED_PARTICLE_FILTER");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(LLPF_ERR_NO_DEVICE, "no HIP device visible; this engine has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(LLPF_ERR_ARG, "device ordinal out of range");
+    CHK(open_stream(b, cfg->device));
 
     b.cfg = *cfg;
     b.cfg.model = m0;
@@ -398,7 +503,6 @@ static int bank_create(const llpf_config* cfg, const llpf_model* models, int F, 
     b.nxp = (m0.model_id == LLPF_MODEL_RB_BILINEAR) ? m0.nx + m0.rb.nxl : b.nx;
     b.P1 = (int)(b.Ns / BLOCK);          // entries of the per-block weighted-mean partials of one filter (finest block granularity)
     b.P2 = (int)(b.Ns / TILE);
-    b.device = cfg->device;
     // replicas (models == NULL): one descriptor is prepared and uploaded, the device copies it F times (a bank of
     // thousands of Monte-Carlo replicas otherwise spends its construction on host copies of identical 8 KB structs)
     const bool replicas = (models == nullptr) && m0.model_id != LLPF_MODEL_RB_LINEAR;
@@ -408,59 +512,21 @@ static int bank_create(const llpf_config* cfg, const llpf_model* models, int F, 
     for (int f = 0; f < FH; ++f) {
         const llpf_model& mf = models ? models[f] : cfg->model;
         b.hmodels[f] = mf;
-        if (mf.model_id != m0.model_id || mf.nx != m0.nx || mf.nu != m0.nu || mf.ny != m0.ny)
-            return fail(LLPF_ERR_ARG, "all filters of a bank must share model id and dimensions");
-        // the kernel instance (shape, nonlinear part), the rows of a particle plane and BankDev::pad0 are taken from models[0]
-        if (m0.model_id == LLPF_MODEL_RB_BILINEAR && (mf.rb.nxl != m0.rb.nxl || mf.rb.fn_kind != m0.rb.fn_kind))
-            return fail(LLPF_ERR_ARG, "all filters of a bank must share model id and dimensions (LLPF_MODEL_RB_BILINEAR: also rb.nxl and rb.fn_kind)");
-        if (m0.model_id == LLPF_MODEL_RB_LINEAR && mf.nxn != m0.nxn)
-            return fail(LLPF_ERR_ARG, "all filters of a bank must share model id and dimensions (LLPF_MODEL_RB_LINEAR: also nxn)");
+        static const char* const differs[] = {"all filters of a bank must share model id and dimensions",
+                                              "all filters of a bank must share model id and dimensions (LLPF_MODEL_RB_BILINEAR: also rb.nxl and rb.fn_kind)",
+                                              "all filters of a bank must share model id and dimensions (LLPF_MODEL_RB_LINEAR: also nxn)"};
+        if (const int d = same_family(m0, mf)) return fail(LLPF_ERR_ARG, differs[d - 1]);
         int rc = model_prepare(&mf, &hm[f]);
         if (rc) return fail(LLPF_ERR_ARG, "invalid density (covariance not positive definite or dimension mismatch), code " + std::to_string(rc));
     }
-    HIPC(hipSetDevice(b.device));
-    HIPC(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
-    const size_t FN = (size_t)F * b.Ns;
-    {   // one device allocation for everything whose size is known here (a filter is often built per Monte-Carlo run or per
-        // parameter candidate: 17 hipMalloc + as many memsets and hipFree cost more than a short run), zero-filled once
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-        const size_t o_models = take(sizeof(ModelD) * F), o_scal = take(sizeof(FilterScal) * F);
-        const size_t o_x0 = take(sizeof(double) * FN * b.xrows), o_x1 = take(sizeof(double) * FN * b.xrows);
-        const size_t o_w = take(sizeof(double) * FN), o_anc = take(sizeof(int32_t) * FN);
-        const size_t o_acc = take(sizeof(uint64_t) * (size_t)F * ACC_WORDS);
-        const size_t o_q0 = take(sizeof(uint64_t) * FN), o_q1 = take(sizeof(uint64_t) * FN);
-        const size_t o_tileq = take(sizeof(uint64_t) * (size_t)ACC_NSLOT * F * b.P2), o_flag = take(sizeof(uint32_t) * 4);
-        const size_t o_rtile = take(sizeof(uint64_t) * (size_t)F * 2 * b.P2);      // (xmpart: on the first run that asks for weighted means, ensure_xmpart)
-        const size_t o_rb = take(m0.model_id == LLPF_MODEL_RB_LINEAR ? sizeof(RBStep) * 2 * (size_t)F : 0);
-        const bool two_level = b.P2 > 4 * BLOCK;           // (kernels/resample.hpp: TQ_GROUP)
-        const size_t o_tpre = take(two_level ? sizeof(uint64_t) * (size_t)F * b.P2 : 0), o_gsum = take(two_level ? sizeof(uint64_t) * (size_t)F * ((b.P2 + 4 * BLOCK - 1) / (4 * BLOCK)) : 0);
-        const size_t o_uy = take(sizeof(double) * 4 * MAXD);
-        const size_t o_tmp = take(sizeof(double) * (size_t)F * b.N * (b.nxp > 1 ? b.nxp : 1) + 64);
-        CHK(b.d_pool.ensure(off));
-        test_throw("pool");
-        HIPC(hipMemsetAsync(b.d_pool, 0, off, b.stream));
-        char* base = b.d_pool;
-        b.d_models = reinterpret_cast<ModelD*>(base + o_models); b.d_scal = reinterpret_cast<FilterScal*>(base + o_scal);
-        b.d_x[0] = reinterpret_cast<double*>(base + o_x0); b.d_x[1] = reinterpret_cast<double*>(base + o_x1);
-        b.d_w = reinterpret_cast<double*>(base + o_w); b.d_anc = reinterpret_cast<int32_t*>(base + o_anc);
-        b.d_acc = reinterpret_cast<uint64_t*>(base + o_acc);
-        b.d_quanta[0] = reinterpret_cast<uint64_t*>(base + o_q0); b.d_quanta[1] = reinterpret_cast<uint64_t*>(base + o_q1);
-        b.d_tileq = reinterpret_cast<uint64_t*>(base + o_tileq); b.d_flag = reinterpret_cast<uint32_t*>(base + o_flag);
-        b.d_rtile = reinterpret_cast<uint64_t*>(base + o_rtile);
-        if (m0.model_id == LLPF_MODEL_RB_LINEAR) b.d_rb = reinterpret_cast<RBStep*>(base + o_rb);
-        if (two_level) { b.d_tpre = reinterpret_cast<uint64_t*>(base + o_tpre); b.d_gsum = reinterpret_cast<uint64_t*>(base + o_gsum); }
-        b.d_uy = reinterpret_cast<double*>(base + o_uy); b.d_tmp = reinterpret_cast<double*>(base + o_tmp);
-    }
+    const size_t pool_bytes = bank_carve(b, nullptr);
+    CHK(b.d_pool.ensure(pool_bytes));
+    test_throw("pool");
+    HIPC(hipMemsetAsync(b.d_pool, 0, pool_bytes, b.stream));
+    bank_carve(b, b.d_pool);
     if (m0.model_id == LLPF_MODEL_RB_LINEAR) {
         b.rb.resize(F);
-        for (int f = 0; f < F; ++f) {                       // the inner KalmanFilter object: kf.x = d0.mu, kf.R = d0.Sigma
-            double S0[16];
-            gauss_cov_dense(&b.hmodels[f].linear_initial, S0);
-            const int nl = m0.nx - m0.nxn;
-            for (int i = 0; i < nl * nl; ++i) { b.rb[f].R[i] = S0[i]; b.rb[f].kfR[i] = S0[i]; }
-            for (int i = 0; i < nl; ++i) b.rb[f].kfx[i] = b.hmodels[f].linear_initial.mu[i];
-        }
+        rb_kf_init(b, true);
     }
     HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * FH, hipMemcpyHostToDevice, b.stream));
     if (FH < F) HIPC(launch_replicate_models(b.d_models, F, b.stream));
@@ -496,11 +562,10 @@ static int bank_set_models(Bank& b, const llpf_model* models) {
             const int id = jit_builtin_lg(mf.nx, mf.ny, err);
             if (id == m0.model_id) mf.model_id = id;
         }
-        if (mf.model_id != m0.model_id || mf.nx != m0.nx || mf.nu != m0.nu || mf.ny != m0.ny)
-            return fail(LLPF_ERR_ARG, "set_model: the new model must have the model id and the dimensions the handle was created with");
-        if (m0.model_id == LLPF_MODEL_RB_BILINEAR && (mf.rb.nxl != m0.rb.nxl || mf.rb.fn_kind != m0.rb.fn_kind))
-            return fail(LLPF_ERR_ARG, "set_model: LLPF_MODEL_RB_BILINEAR must keep rb.nxl and rb.fn_kind");
-        if (m0.model_id == LLPF_MODEL_RB_LINEAR && mf.nxn != m0.nxn) return fail(LLPF_ERR_ARG, "set_model: LLPF_MODEL_RB_LINEAR must keep nxn");
+        static const char* const differs[] = {"set_model: the new model must have the model id and the dimensions the handle was created with",
+                                              "set_model: LLPF_MODEL_RB_BILINEAR must keep rb.nxl and rb.fn_kind",
+                                              "set_model: LLPF_MODEL_RB_LINEAR must keep nxn"};
+        if (const int d = same_family(m0, mf)) return fail(LLPF_ERR_ARG, differs[d - 1]);
         const int rc = model_prepare(&mf, &hm[f]);
         if (rc) return fail(LLPF_ERR_ARG, "invalid density (covariance not positive definite or dimension mismatch), code " + std::to_string(rc) + ", in filter " + std::to_string(f));
     }
@@ -513,15 +578,7 @@ static int bank_set_models(Bank& b, const llpf_model* models) {
         HIPC(launch_user_bound(m0.model_id, b.d_models, F, b.d_uy, b.stream));
     }
     HIPC(hipStreamSynchronize(b.stream));
-    if (m0.model_id == LLPF_MODEL_RB_LINEAR) {               // the inner KalmanFilter object of the new filter: kf.x = d0.mu, kf.R = d0.Sigma
-        for (int f = 0; f < F; ++f) {
-            double S0[16];
-            gauss_cov_dense(&b.hmodels[f].linear_initial, S0);
-            const int nl = m0.nx - m0.nxn;
-            for (int i = 0; i < nl * nl; ++i) { b.rb[f].R[i] = S0[i]; b.rb[f].kfR[i] = S0[i]; }
-            for (int i = 0; i < nl; ++i) b.rb[f].kfx[i] = b.hmodels[f].linear_initial.mu[i];
-        }
-    }
+    rb_kf_init(b, true);               // the inner KalmanFilter object of the new filter
     return LLPF_OK;
 }
 

@@ -98,18 +98,12 @@ static int kf_pack_models(const char* who, const char* filter_name, int need_tra
 
 // the device, the dimensions (b.nx, ny, nu are the pack's) and the stream of a new bank; `site`: the bank's create site of test_throw
 static int kf_open(KfBank& b, int32_t device, int32_t F, int npar, const char* site) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(LLPF_ERR_NO_DEVICE, "no HIP device visible; this engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LLPF_ERR_ARG, "device ordinal out of range");
+    CHK(open_stream(b, device));
     test_throw(site);
     b.F = F;
     b.np = LLPF_KF_NP(b.nx);
     b.npar = npar;
     b.nstate = b.nx + b.np + 1;
-    b.device = device;
-    HIPC(hipSetDevice(device));
-    HIPC(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
     return LLPF_OK;
 }
 

@@ -165,6 +165,125 @@ static int mbank_build(llpf_mbank* m, const llpf_config* base, const llpf_model*
     return LLPF_OK;
 }
 
+// which exchange a sweep without an id uses: none for one shard (LLPF_MBANK_FORCE_RCCL=1: a communicator of one rank), RCCL between
+// distinct GPUs, the host sum when the device list names one GPU twice
+static int mbank_env_collective(bool distinct, int n_shards_total) {
+    if (n_shards_total == 1) { const char* e = getenv("LLPF_MBANK_FORCE_RCCL"); return (e && atoi(e)) ? MBANK_COLL_RCCL : MBANK_COLL_NONE; }
+    return distinct ? MBANK_COLL_RCCL : MBANK_COLL_HOST;
+}
+
+// one process, n_devices GPUs: the shards, then (ncclCommInitAll) their communicators
+static int mbank_create(llpf_mbank& m, const llpf_config* base, const llpf_model* models, int32_t n_filters, const int32_t* devices,
+                        int32_t n_devices) {
+    if (!devices || n_devices < 1) return fail(LLPF_ERR_ARG, "empty device list");
+    int ndev = 0;
+    CHK(need_device(&ndev));
+    bool distinct = true;
+    for (int i = 0; i < n_devices; ++i) {
+        if (devices[i] < 0 || devices[i] >= ndev) return fail(LLPF_ERR_ARG, "device ordinal out of range");
+        for (int j = 0; j < i; ++j) if (devices[j] == devices[i]) distinct = false;
+    }
+    CHK(mbank_build(&m, base, models, n_filters, devices, n_devices, 0, n_devices));
+    m.collective = mbank_env_collective(distinct, n_devices);
+    if (m.collective == MBANK_COLL_RCCL) {
+        rccl_dl::Api* R = rccl_dl::api();
+        if (!R->handle) return fail(LLPF_ERR_HIP, R->err);
+        std::vector<rccl_dl::comm_t> comms((size_t)n_devices, nullptr);
+        std::vector<int> devs(devices, devices + n_devices);
+        (void)hipGetLastError();      // RCCL reads the runtime's sticky last-error after its own launches: start clean
+        rccl_dl::result_t r = R->CommInitAll(comms.data(), n_devices, devs.data());
+        if (r != rccl_dl::Success) return fail(LLPF_ERR_HIP, std::string("ncclCommInitAll: ") + R->GetErrorString(r));
+        for (int i = 0; i < n_devices; ++i) m.shards[i]->comm = comms[i];
+    }
+    return LLPF_OK;
+}
+// one process per GPU, rank `rank` of `world`: the shard on base->device, then (ncclCommInitRank) its communicator from the id the host
+// distributed; id == NULL with world > 1 leaves the exchange to the caller
+static int mbank_create_rank(llpf_mbank& m, const llpf_config* base, const llpf_model* models, int32_t n_filters, int32_t rank, int32_t world,
+                             const uint8_t* id) {
+    if (!base) return fail(LLPF_ERR_ARG, "null config");
+    if (world < 1 || rank < 0 || rank >= world) return fail(LLPF_ERR_ARG, "rank / world out of range");
+    CHK(need_device());
+    const int32_t dev = base->device;
+    CHK(mbank_build(&m, base, models, n_filters, &dev, 1, rank, world));
+    m.collective = id ? MBANK_COLL_RCCL : (world > 1 ? MBANK_COLL_EXTERNAL : mbank_env_collective(true, 1));
+    if (m.collective == MBANK_COLL_RCCL) {
+        rccl_dl::Api* R = rccl_dl::api();
+        if (!R->handle) return fail(LLPF_ERR_HIP, R->err);
+        rccl_dl::unique_id u;
+        if (id) memcpy(u.internal, id, LLPF_MBANK_ID_BYTES);
+        else { rccl_dl::result_t r0 = R->GetUniqueId(&u); if (r0 != rccl_dl::Success) return fail(LLPF_ERR_HIP, std::string("ncclGetUniqueId: ") + R->GetErrorString(r0)); }
+        hipSetDevice(dev);
+        (void)hipGetLastError();
+        rccl_dl::result_t r = R->CommInitRank(&m.shards[0]->comm, world, u, rank);
+        if (r != rccl_dl::Success) return fail(LLPF_ERR_HIP, std::string("ncclCommInitRank: ") + R->GetErrorString(r));
+    }
+    return LLPF_OK;
+}
+static int mbank_unique_id(uint8_t* id) {
+    if (!id) return fail(LLPF_ERR_ARG, "null id");
+    rccl_dl::Api* R = rccl_dl::api();
+    if (!R->handle) return fail(LLPF_ERR_HIP, R->err);
+    rccl_dl::unique_id u;
+    RCCLC(R->GetUniqueId(&u));
+    memcpy(id, u.internal, LLPF_MBANK_ID_BYTES);
+    return LLPF_OK;
+}
+// the partition the two creates use (mbank_owned), as an entry point of its own: pure host code, needs no device
+static int mbank_partition(int32_t n_filters, int32_t shard, int32_t n_shards, int32_t* owned, int32_t* n_owned) {
+    if (n_filters < 0 || n_shards < 1 || shard < 0 || shard >= n_shards || !n_owned) return fail(LLPF_ERR_ARG, "partition: bad arguments");
+    std::vector<int> o;
+    mbank_owned(n_filters, shard, n_shards, o);
+    *n_owned = (int32_t)o.size();
+    if (owned) for (size_t i = 0; i < o.size(); ++i) owned[i] = (int32_t)o[i];
+    return LLPF_OK;
+}
+
+static int mbank_reset(llpf_mbank& m) {
+    return mbank_foreach(m, [&](int s) -> int { return bank_reset(m.shards[s]->bank); });
+}
+static int mbank_seed(llpf_mbank& m, uint64_t seed) {
+    return mbank_foreach(m, [&](int s) -> int { return bank_seed(m.shards[s]->bank, seed); });
+}
+static int mbank_set_models(llpf_mbank& m, const llpf_model* models) {
+    if (!models) return fail(LLPF_ERR_ARG, "null models");
+    return mbank_foreach(m, [&](int s) -> int {
+        MShard& sh = *m.shards[s];
+        std::vector<llpf_model> mine;
+        mine.reserve(sh.owned.size());
+        for (int k : sh.owned) mine.push_back(models[k]);      // the same partition as at creation: filter k lives on shard k mod n_shards
+        return bank_set_models(sh.bank, mine.data());
+    });
+}
+static int mbank_info(llpf_mbank& m, llpf_mbank_info_t* info) {
+    if (!info) return fail(LLPF_ERR_ARG, "null info");
+    info->n_filters = m.n_filters;
+    info->n_shards = m.n_shards_total;
+    info->n_local_shards = (int32_t)m.shards.size();
+    info->first_local_shard = m.first_shard;
+    info->collective = m.collective;
+    info->n_local_filters = 0;
+    for (auto& sp : m.shards) info->n_local_filters += (int32_t)sp->owned.size();
+    info->last_run_ms = m.last_run_ms;
+    info->last_collective_ms = m.last_coll_ms;
+    info->resample_count = 0;
+    for (auto& sp : m.shards) info->resample_count += sp->bank.run_resamples;
+    return LLPF_OK;
+}
+static int mbank_local_devices(llpf_mbank& m, int32_t* devices) {
+    if (!devices) return fail(LLPF_ERR_ARG, "devices is NULL");
+    for (size_t s = 0; s < m.shards.size(); ++s) devices[s] = m.shards[s]->device;
+    return LLPF_OK;
+}
+static int mbank_set_prof(llpf_mbank& m, int on) {
+    for (auto& sp : m.shards) set_prof(sp->bank, on);
+    return LLPF_OK;
+}
+static int mbank_get_prof(llpf_mbank& m, int32_t local_shard, double* ms, int64_t* n) {
+    if (local_shard < 0 || local_shard >= (int32_t)m.shards.size()) return fail(LLPF_ERR_ARG, "local shard out of range");
+    return get_prof(m.shards[local_shard]->bank, ms, n);
+}
+
 // the exchange: on return h_ll holds every filter's log-likelihood (or, MBANK_COLL_EXTERNAL, this process's slots and zeros)
 static int mbank_exchange(llpf_mbank& m, const std::vector<std::vector<double>>& local) {
     const size_t nb = sizeof(double) * (size_t)m.n_filters;

@@ -65,3 +65,32 @@ def test_bad_arguments_are_rejected():
     cfg = S.make_config(M.lg_test_model(), 100, strategy=7)
     assert L.llpf_create(C.byref(cfg), C.byref(h)) == _capi.ERR_ARG
     assert L.llpf_reset(None) == _capi.ERR_ARG
+
+
+def _null_args(argtypes):
+    # a null pointer for every pointer argument, a zero of its ctype for every other
+    return [None if issubclass(t, (C._Pointer, C.c_void_p, C.c_char_p)) else t(0) for t in argtypes]
+
+
+def test_a_null_handle_is_an_argument_error():
+    """Every export that takes a handle answers a null one with LLPF_ERR_ARG and "null handle" (a destroy: LLPF_OK, like free(NULL)),
+    every create a null out pointer with LLPF_ERR_ARG and "null out pointer".  llpf_ekf_bank_set_iterations checks its two numbers
+    before the handle, so its message starts with the bank's name."""
+    L = _capi.lib()
+    takes_handle = [n for n, a in _capi.SYMBOLS.items() if a and a[0] is C.c_void_p]
+    creates = [n for n in _capi.SYMBOLS if "create" in n]
+    assert len(takes_handle) >= 83 and len(creates) >= 7 and not set(takes_handle) & set(creates)
+    for name in takes_handle:
+        rc = getattr(L, name)(*_null_args(_capi.SYMBOLS[name]))
+        if name.endswith("_destroy"):
+            assert rc == _capi.OK, name
+            continue
+        msg = L.llpf_last_error().decode()
+        assert rc == _capi.ERR_ARG, (name, rc, msg)
+        if name == "llpf_ekf_bank_set_iterations":
+            assert msg.startswith("ekf"), msg
+        else:
+            assert "null handle" in msg, (name, msg)
+    for name in creates:
+        rc = getattr(L, name)(*_null_args(_capi.SYMBOLS[name]))
+        assert rc == _capi.ERR_ARG and b"null out pointer" in L.llpf_last_error(), (name, rc, L.llpf_last_error())
