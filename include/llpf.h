@@ -493,6 +493,47 @@ int  llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64
 int  llpf_ekf_bank_get_state(llpf_ekf_bank* b, double* x, double* R);
 int  llpf_ekf_bank_set_state(llpf_ekf_bank* b, const double* x, const double* R);
 
+/* ---- banks of ensemble Kalman filters -----------------------------------------------------------------------------------------------
+ * n_filters independent stochastic (perturbed-observation) ensemble Kalman filters of n_members members each, one GPU workgroup per
+ * filter, in the operation order of csrc/shared/llpf_enkf.h (that header is the definition, the order of every sum over the ensemble
+ * included: a host build of it around the same model functions and the same generator gives the same bits).  UNVERIFIED against the
+ * reference's EnsembleKalmanFilter, whose source was not available: the choices of that header are this project's.
+ *   reset!    member i is the draw reset! gives particle i of a particle filter with the same key;
+ *   correct!  Y_i = g(x_i); Pxy, S = cov(Y) + R2 from the ensemble (divisor N - 1); ll = logpdf(N(0, S), y - mean(Y)); every member moves
+ *             by Pxy S^-1 (y - Y_i - v_i), v_i its own draw of the measurement noise (the one llpf_simulate gives trajectory i);
+ *   predict!  x_i = f(x_i) + w_i, the process noise predict! gives particle i at the same step (the Gaussian descriptor, or the model's
+ *             own `noise`); then x_i = mean + rho (x_i - mean) when the inflation rho is not 1.
+ * The descriptors and dimensions are those of llpf_ukf_bank_create; a model of llpf_model_compile may have `noise` and `initial`
+ * members of its own (multiplicative or Laplace process noise, a box prior), `loglik` stays refused (there is no Gaussian R2), the
+ * Rao-Blackwellized model ids too.  2 <= n_members <= 65536 (LLPF_ENKF_MAX_MEMBERS).  Filter f's key is seed + f: a filter's bits do
+ * not depend on the bank it sits in.  The counters are the particle bank's: every reset draws the next ensemble, every predict! moves
+ * the step counter, llpf_enkf_bank_seed zeroes both and draws the first ensemble of the new seed (the bank a create with that seed gives).
+ * A filter whose S loses definiteness, or that holds a NaN member at a correct!, is NaN from that step on; the others are unaffected.
+ * Steps, missing rows, the outputs and ll_total are those of llpf_kalman_bank_run: x, R are mean and sample covariance of the prior
+ * members, xt, Rt of the updated ones; step t evaluates the model at tau = (t_index0 + t) * Ts.  get_state gives mean and sample
+ * covariance of the current members. */
+typedef struct llpf_enkf_bank llpf_enkf_bank;
+int  llpf_enkf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, int32_t n_members, uint64_t seed, llpf_enkf_bank** out);
+int  llpf_enkf_bank_destroy(llpf_enkf_bank* b);
+int  llpf_enkf_bank_reset(llpf_enkf_bank* b);
+int  llpf_enkf_bank_seed(llpf_enkf_bank* b, uint64_t seed);
+/* new parameters for every filter (same model id and dimensions, nothing reallocated; the members are left as they are) */
+int  llpf_enkf_bank_set_models(llpf_enkf_bank* b, const llpf_model* models);
+/* the inflation rho of every later predict!: finite and >= 1, else LLPF_ERR_ARG; 1 (the value after create) is no inflation */
+int  llpf_enkf_bank_set_inflation(llpf_enkf_bank* b, double rho);
+/* T steps of every filter; U, Y, per_filter, ll_total and out as llpf_kalman_bank_run takes them */
+int  llpf_enkf_bank_run(llpf_enkf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                        double* ll_total, const llpf_kalman_outputs* out);
+/* correct!(u, y) and predict!(u) of every filter at tau = t_index * Ts; correct then predict is a run of one step, bit for bit.
+ * u is [nu] or [F][nu] (per_filter bit 0), y [ny] or [F][ny] (bit 1); ll [F] (optional), e [F][ny] (optional) */
+int  llpf_enkf_bank_correct(llpf_enkf_bank* b, const double* u, const double* y, int32_t per_filter, double t_index, double* ll, double* e);
+int  llpf_enkf_bank_predict(llpf_enkf_bank* b, const double* u, int32_t per_filter, double t_index);
+/* mean and sample covariance of every ensemble: x [F][nx], R [F][nx][nx] (either NULL) */
+int  llpf_enkf_bank_get_state(llpf_enkf_bank* b, double* x, double* R);
+/* the members, X [F][n_members][nx] */
+int  llpf_enkf_bank_get_members(llpf_enkf_bank* b, double* X);
+int  llpf_enkf_bank_set_members(llpf_enkf_bank* b, const double* X);
+
 /* ---- sweeps sharded over the GPUs of one node (multi-GPU banks) ------------------------------
  * The same sweep as llpf_bank_*, with filter k on shard k mod n_shards (one shard = one GPU, one stream): the reference's
  * one-filter-per-thread layout (src/smoothing.jl:335-347, test/runtests.jl:412-417) with GPUs for threads.  Filters never

@@ -64,6 +64,18 @@ SYMBOLS = {
     "llpf_ekf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
     "llpf_ekf_bank_get_state": [_vp, _dp, _dp],
     "llpf_ekf_bank_set_state": [_vp, _dp, _dp],
+    "llpf_enkf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(_vp)],
+    "llpf_enkf_bank_destroy": [_vp],
+    "llpf_enkf_bank_reset": [_vp],
+    "llpf_enkf_bank_seed": [_vp, C.c_uint64],
+    "llpf_enkf_bank_set_models": [_vp, C.POINTER(S.Model)],
+    "llpf_enkf_bank_set_inflation": [_vp, C.c_double],
+    "llpf_enkf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_enkf_bank_correct": [_vp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp],
+    "llpf_enkf_bank_predict": [_vp, _dp, C.c_int32, C.c_double],
+    "llpf_enkf_bank_get_state": [_vp, _dp, _dp],
+    "llpf_enkf_bank_get_members": [_vp, _dp],
+    "llpf_enkf_bank_set_members": [_vp, _dp],
     "llpf_num_particles": [_vp, _ip],
     "llpf_index": [_vp, _ip],
     "llpf_get_particles": [_vp, _dp],
@@ -631,6 +643,63 @@ class EkfBankHandle(_KfBankHandle):
     def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
         """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""
         return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
+
+
+class EnkfBankHandle(_KfBankHandle):
+    """RAII wrapper of an `llpf_enkf_bank*` (independent ensemble Kalman filters of `n_members` members on one device; filter f's key is
+    seed + f)."""
+    _SYM = "llpf_enkf_bank"
+
+    def __init__(self, device, models, n_members, seed=0):
+        arr = self._open(models)
+        self.N = int(n_members)
+        check(self.L.llpf_enkf_bank_create(int(device), arr, self.F, self.N, int(seed), C.byref(self.h)))
+
+    def set_models(self, models):
+        self._call("set_models", (S.Model * self.F)(*models))
+
+    def set_inflation(self, rho):
+        """the inflation of every later predict!: x_i = mean + rho (x_i - mean); finite and >= 1"""
+        self._call("set_inflation", float(rho))
+
+    def seed(self, seed):
+        """zeroes the counters of the generator and draws the first ensemble of `seed`: the bank a create with that seed gives"""
+        self._call("seed", int(seed))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
+        """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""
+        return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
+
+    def _u(self, u, u_per_filter):
+        if self.nu == 0:
+            return None, False
+        return f64(u).reshape((self.F, self.nu) if u_per_filter else (self.nu,)), u_per_filter
+
+    def correct(self, u, y, u_per_filter=False, y_per_filter=False, t_index=0.0):
+        """correct!(u, y) of every filter at time t_index Ts: (ll [F], e [F, ny]); u [nu] or [F, nu], y [ny] or [F, ny]"""
+        u, u_per_filter = self._u(u, u_per_filter)
+        y = f64(y).reshape((self.F, self.ny) if y_per_filter else (self.ny,))
+        ll, e = np.empty(self.F), np.empty((self.F, self.ny))
+        self._call("correct", dptr(u), dptr(y), (1 if u_per_filter else 0) | (2 if y_per_filter else 0), float(t_index), dptr(ll), dptr(e))
+        return ll, e
+
+    def predict(self, u, u_per_filter=False, t_index=0.0):
+        """predict!(u) of every filter at time t_index Ts"""
+        u, u_per_filter = self._u(u, u_per_filter)
+        self._call("predict", dptr(u), 1 if u_per_filter else 0, float(t_index))
+
+    def get_members(self):
+        """the members of every filter, [F, N, nx]"""
+        X = np.empty((self.F, self.N, self.nx))
+        self._call("get_members", dptr(X))
+        return X
+
+    def set_members(self, X):
+        X = f64(X).reshape(self.F, self.N, self.nx)
+        self._call("set_members", dptr(X))
+
+    def set_state(self, x, R):
+        raise TypeError("an ensemble Kalman filter's state is its members: use set_members")
 
 
 class BankHandle(_PfHandle):

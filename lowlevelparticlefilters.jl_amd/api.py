@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -444,7 +444,8 @@ class KalmanSmoothingSolution(KalmanFilteringSolution):
 
 
 def covariance(kf):
-    """covariance(kf) — the covariance R of the current estimate of a KalmanFilter, an UnscentedKalmanFilter or an ExtendedKalmanFilter"""
+    """covariance(kf) — the covariance R of the current estimate of a KalmanFilter, an UnscentedKalmanFilter, an ExtendedKalmanFilter or an
+    EnsembleKalmanFilter (its sample covariance)"""
     return kf.R
 
 
@@ -808,6 +809,111 @@ class IteratedExtendedKalmanFilterBank(ExtendedKalmanFilterBank):
         self.maxiters, self.epsilon = int(maxiters), float(epsilon)
 
 
+def _check_inflation(rho):
+    rho = float(rho)
+    if not np.isfinite(rho) or rho < 1.0:
+        raise ValueError("enkf: the inflation must be finite and >= 1")
+    return rho
+
+
+class EnsembleKalmanFilter(_NonlinearKalmanFilter):
+    """EnsembleKalmanFilter(dynamics, measurement, R1, R2, d0, N; inflation=1.0, Ts, nu, ny, p, seed, device) — the stochastic
+    (perturbed-observation) ensemble Kalman filter with N members: every member is propagated through the dynamics with its own process
+    noise, and one ny x ny solve from the ensemble's sample moments moves every member towards its own perturbed measurement
+    (csrc/shared/llpf_enkf.h is the definition; unverified against the reference's EnsembleKalmanFilter).  The arguments are
+    UnscentedKalmanFilter's, with two additions a ParticleFilter has: R1 may be a UserNoise and d0 a UserInitial when the UserDynamics
+    snippet has a `noise` / `initial` member of its own (multiplicative or Laplace process noise, a box prior).  R2 stays Gaussian.
+    state(f) is the ensemble mean, covariance(f) the sample covariance, particles(f) the members [N, nx].  Runs on the device as a bank of
+    one filter (llpf_enkf_bank_*), created on first use.  nx <= 8, ny <= 4, nu <= 8, 2 <= N <= 65536."""
+
+    def __init__(self, dynamics, measurement, R1, R2, d0, N, *, inflation=1.0, Ts=1.0, nu=-1, ny=-1, p=None, seed=0, device=0):
+        if (isinstance(R1, UserNoise) or isinstance(d0, UserInitial)) and not isinstance(dynamics, UserDynamics):
+            raise TypeError("UserNoise / UserInitial are members of a UserDynamics snippet")
+        nx = dynamics.nx if isinstance(dynamics, UserDynamics) else len(d0)
+        if ny < 0 and np.ndim(R2) >= 1:
+            ny = np.asarray(R2).shape[0]
+        if _is_plain_callable(dynamics):
+            if ny < 0:
+                raise ValueError("pass ny= with callable dynamics and a scalar R2")
+            dynamics, measurement, _ = _trace_callables(dynamics, measurement, None, nx, nu, ny, p)
+        if isinstance(dynamics, UserDynamics):
+            ny = dynamics.ny
+        elif isinstance(measurement, LinearMeasurement):
+            ny = measurement.C.shape[0]
+        elif isinstance(measurement, QuadTankMeasurement):
+            ny = 2
+        cov = lambda c, n: MvNormal(np.zeros(n), c if np.ndim(c) < 2 else np.atleast_2d(np.asarray(c, float)))
+        self.dynamics, self.measurement, self.R1, self.R2, self.d0 = dynamics, measurement, R1, R2, d0
+        self.dynamics_density = R1 if isinstance(R1, UserNoise) else cov(R1, nx)
+        self.measurement_density, self.initial_density = cov(R2, ny), d0
+        self.p, self.Ts, self.device = p, float(Ts), int(device)
+        self._model = _build_model(dynamics, measurement, self.dynamics_density, self.measurement_density, d0, Ts)
+        self.nx, self.nu, self.ny = self._model.nx, self._model.nu, self._model.ny
+        self._handle = None
+        self._index = 0
+        self.N, self.seed, self.inflation = int(N), int(seed), _check_inflation(inflation)
+
+    def _open(self):
+        h = _capi.EnkfBankHandle(self.device, [self._model], self.N, self.seed)
+        if self.inflation != 1.0:
+            h.set_inflation(self.inflation)
+        return h
+
+    def set_inflation(self, rho):
+        self.inflation = _check_inflation(rho)
+        self._h.set_inflation(self.inflation)
+
+    def members(self):
+        """the members, [N, nx]"""
+        return self._h.get_members()[0]
+
+
+class EnsembleKalmanFilterBank(_KfBank):
+    """n independent ensemble Kalman filters of N members each, of the same model family and dimensions, on one device, one GPU workgroup
+    each (llpf_enkf_bank_*): a log-likelihood per parameter set without resampling, weights or ancestors, for every model a FilterBank
+    takes except one with a likelihood of its own.  `filters_spec` is a list of EnsembleKalmanFilter or of (dynamics, measurement, R1, R2,
+    d0) tuples; filter k's key is seed + k."""
+    _AT_LOGLIK, _AT_FORWARD = {"t_index0": 1.0}, {"t_index0": 0.0}
+
+    def __init__(self, filters_spec, N, device=0, seed=0, inflation=1.0, Ts=1.0):
+        self._init(self._models(filters_spec, N, Ts), N, device, seed, inflation)
+
+    def _init(self, models, N, device, seed, inflation):
+        self.device, self.N, self.seed, self.inflation = int(device), int(N), int(seed), _check_inflation(inflation)
+        self._h = _capi.EnkfBankHandle(self.device, models, self.N, self.seed)
+        if self.inflation != 1.0:
+            self._h.set_inflation(self.inflation)
+        self.n_filters = len(models)
+        self.Ts = float(models[0].Ts)
+
+    @staticmethod
+    def _models(filters_spec, N, Ts):
+        return [(f if isinstance(f, EnsembleKalmanFilter) else EnsembleKalmanFilter(*f, N, Ts=Ts))._model for f in filters_spec]
+
+    @classmethod
+    def from_filter_bank(cls, bank, device=None, inflation=1.0):
+        """the ensemble twin of a FilterBank: the same descriptors (any model that is not Rao-Blackwellized and has no likelihood of its
+        own), N members where the bank has N particles, the bank's seed; loglik and forward at the times FilterBank's use"""
+        self = cls.__new__(cls)
+        self._init(list(bank._models), bank.N, bank._h.cfg.device if device is None else device, bank.rng, inflation)
+        return self
+
+    def set_parameters(self, filters_spec):
+        """new parameters for every filter (same model and dimensions, nothing reallocated: llpf_enkf_bank_set_models)"""
+        self._h.set_models(self._models(filters_spec, self.N, self.Ts))
+
+    def set_inflation(self, rho):
+        self.inflation = _check_inflation(rho)
+        self._h.set_inflation(self.inflation)
+
+    def members(self):
+        """the members of every filter, [F, N, nx]"""
+        return self._h.get_members()
+
+    def smooth(self, u, y, outputs=None, forward=()):
+        raise TypeError("the ensemble Kalman filter has no smoother")
+
+
 class RBMeasurementModel:
     """RBMeasurementModel(measurement, R2, ny) — reference src/rbpf.jl:36-60; `measurement` is a LinearMeasurement
     descriptor of the nonlinear state's contribution y = Gn xn (+ C xl + e)."""
@@ -962,6 +1068,11 @@ def _pt(args, kw, skip):
 def predict(pf, u, *args, **kw):
     """predict!(pf, u, p, t = index(pf)*Ts) — reference src/filtering.jl:140-153;
     predict!(pf::AuxiliaryParticleFilter, u, y1, p, t) — :195-217 (y1 = the NEXT measurement)."""
+    if isinstance(pf, EnsembleKalmanFilter):        # the bank's own verb: the members move, the step counter grows
+        t = _pt(args, kw, 0)[1]
+        pf._h.predict(u, t_index=float(pf._index) if t is None else float(t) / pf.Ts)
+        pf._index += 1
+        return
     if isinstance(pf, _NonlinearKalmanFilter):      # a step whose measurement is missing: correct! is skipped, predict! runs
         pf._step(u, None, _pt(args, kw, 0)[1], ())
         return
@@ -975,6 +1086,11 @@ def predict(pf, u, *args, **kw):
 def correct(pf, u, y, p=None, t=None):
     """ll, 0 = correct!(pf, u, y, p, t) — reference src/filtering.jl:164-168.  y=None means missing.
     For an AuxiliaryParticleFilter (:170-174) only logsumexp! runs: the measurement update was done in predict!."""
+    if isinstance(pf, EnsembleKalmanFilter):
+        if y is None:
+            return 0.0, np.full(pf.ny, np.nan)
+        ll, e = pf._h.correct(u, y, t_index=float(pf._index) if t is None else float(t) / pf.Ts)
+        return float(ll[0]), e[0]
     if isinstance(pf, _NonlinearKalmanFilter):
         # the posterior of a one-step run put back as the state: the same numbers (the packed lower triangle of Rt is what the step holds)
         i = pf._index
@@ -1269,6 +1385,8 @@ def smooth(pf, *args):
         pf._index += yy.shape[0]
         sol = KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
         return KalmanSmoothingSolution(sol, r["xT"][:, 0], r["RT"][:, 0])
+    if isinstance(pf, EnsembleKalmanFilter):
+        raise TypeError("the ensemble Kalman filter has no smoother")
     if isinstance(pf, ExtendedKalmanFilter):
         raise TypeError("the extended Kalman filter has no smoother yet: smooth an UnscentedKalmanFilter of the same model")
     if len(args) >= 7:
@@ -1318,6 +1436,8 @@ def mean_trajectory(pf, u=None, y=None, p=None):
 
 # accessors — reference src/PFtypes.jl:296-334
 def particles(pf):
+    if isinstance(pf, EnsembleKalmanFilter):
+        return pf.members()
     return pf._h.particles()
 
 

@@ -19,6 +19,7 @@
 #include "shared/llpf_kalman.h"
 #include "shared/llpf_ukf.h"
 #include "shared/llpf_ekf.h"
+#include "shared/llpf_enkf.h"
 
 using namespace llpf;
 
@@ -103,6 +104,7 @@ static void test_throw(const char* site) {
 #include "host/kalman.hpp"
 #include "host/ukf.hpp"
 #include "host/ekf.hpp"
+#include "host/enkf.hpp"
 
 // A new handle: `build` fills it, a status other than LLPF_OK frees it again.  No handler here: what build throws is caught by the
 // export's own function-try-block (which names the export), the half-built handle freed on the way.
@@ -270,6 +272,37 @@ int llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64_
 } LLPF_GUARD(llpf_ekf_bank_run)
 int llpf_ekf_bank_get_state(llpf_ekf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_get_state)
 int llpf_ekf_bank_set_state(llpf_ekf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_set_state)
+
+// ---- banks of ensemble Kalman filters (host/kfbank.hpp, host/enkf.hpp) ----
+int llpf_enkf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, int32_t n_members, uint64_t seed, llpf_enkf_bank** out) LLPF_TRY {
+    return make_handle(out, [&](llpf_enkf_bank& b) { return enkf_create(b, device, models, n_filters, n_members, seed); });
+} LLPF_GUARD(llpf_enkf_bank_create)
+int llpf_enkf_bank_destroy(llpf_enkf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_enkf_bank_destroy)
+int llpf_enkf_bank_reset(llpf_enkf_bank* b) LLPF_TRY { NEEDF(b); return enkf_reset(*b); } LLPF_GUARD(llpf_enkf_bank_reset)
+int llpf_enkf_bank_seed(llpf_enkf_bank* b, uint64_t seed) LLPF_TRY { NEEDF(b); return enkf_seed(*b, seed); } LLPF_GUARD(llpf_enkf_bank_seed)
+int llpf_enkf_bank_set_models(llpf_enkf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return kf_model_set_models(*b, models); } LLPF_GUARD(llpf_enkf_bank_set_models)
+int llpf_enkf_bank_set_inflation(llpf_enkf_bank* b, double rho) LLPF_TRY {
+    NEEDF(b);
+    CHK(enkf_check_inflation(rho));
+    b->rho = rho;
+    return LLPF_OK;
+} LLPF_GUARD(llpf_enkf_bank_set_inflation)
+int llpf_enkf_bank_run(llpf_enkf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                       const llpf_kalman_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return enkf_run(*b, U, Y, T, per_filter, t_index0, ll_total, out);
+} LLPF_GUARD(llpf_enkf_bank_run)
+int llpf_enkf_bank_correct(llpf_enkf_bank* b, const double* u, const double* y, int32_t per_filter, double t_index, double* ll, double* e) LLPF_TRY {
+    NEEDF(b);
+    return enkf_correct(*b, u, y, per_filter, t_index, ll, e);
+} LLPF_GUARD(llpf_enkf_bank_correct)
+int llpf_enkf_bank_predict(llpf_enkf_bank* b, const double* u, int32_t per_filter, double t_index) LLPF_TRY {
+    NEEDF(b);
+    return enkf_predict(*b, u, per_filter, t_index);
+} LLPF_GUARD(llpf_enkf_bank_predict)
+int llpf_enkf_bank_get_state(llpf_enkf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_enkf_bank_get_state)
+int llpf_enkf_bank_get_members(llpf_enkf_bank* b, double* X) LLPF_TRY { NEEDF(b); return enkf_get_members(*b, X); } LLPF_GUARD(llpf_enkf_bank_get_members)
+int llpf_enkf_bank_set_members(llpf_enkf_bank* b, const double* X) LLPF_TRY { NEEDF(b); return enkf_set_members(*b, X); } LLPF_GUARD(llpf_enkf_bank_set_members)
 
 // ---- the state of a filter (host/access.hpp) ----
 int llpf_rb_get_covariance(llpf_filter* f, double* R) LLPF_TRY { NEEDF(f); return bank_rb_covariance(f->bank, R); } LLPF_GUARD(llpf_rb_get_covariance)

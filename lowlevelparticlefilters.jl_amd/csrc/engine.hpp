@@ -318,6 +318,7 @@ struct JitCache {
 #include "kernels/kf_model_args.hpp"
 #include "kernels/ukf_args.hpp"
 #include "kernels/ekf_args.hpp"
+#include "kernels/enkf_args.hpp"
 // arguments of k_kalman (kernels/kalman.hpp): one launch is one chunk of steps [t0, t0 + Tc) of F Kalman filters, one thread per filter.
 // Device arrays are SoA / time-major: a wave's 64 lanes read and write whole lines.
 struct KalmanArgs {
@@ -428,6 +429,13 @@ hipError_t launch_ekf(int model_id, int nx, int ny, const ModelD* models, const 
 // run-time compiled model on the first iterated use of the model, into a cache entry of its own; launch_iekf runs one chunk of steps
 int iekf_prepare(int model_id, int nx, int ny, std::string& err);
 hipError_t launch_iekf(int model_id, int nx, int ny, const ModelD* models, const EkfArgs& a, int32_t maxiters, double epsilon, hipStream_t s);
+// banks of ensemble Kalman filters (k_enkf.hip; kernels/enkf.hpp), one workgroup per filter: enkf_prepare compiles k_enkf and k_enkf_init of
+// a run-time compiled model on its first bank (0, or -1 with `err` set); launch_enkf runs one chunk of steps, launch_enkf_init draws the
+// ensembles of a reset!, launch_enkf_moments puts mean and packed sample covariance of every ensemble into the state (nx in 1..8)
+int enkf_prepare(int model_id, int nx, int ny, std::string& err);
+hipError_t launch_enkf(int model_id, int nx, int ny, const ModelD* models, const EnkfArgs& a, hipStream_t s);
+hipError_t launch_enkf_init(int model_id, int nx, int ny, const ModelD* models, int F, const EnkfInitArgs& a, hipStream_t s);
+hipError_t launch_enkf_moments(int nx, const double* members, double* state, int64_t F, int N, int zero_ll, hipStream_t s);
 // kernels/jit.hpp: the snippet and shape of a run-time compiled model (false: unknown id), and the prelude its programs start with
 bool jit_model_source(int model_id, std::string& src, int& nx, int& ny);
 const char* jit_prelude();

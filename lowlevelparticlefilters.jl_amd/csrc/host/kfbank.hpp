@@ -1,4 +1,4 @@
-// host/kfbank.hpp — what the banks of one-thread-per-filter Kalman filters share (host/kalman.hpp, host/ukf.hpp, host/ekf.hpp): the bank, its state, the
+// host/kfbank.hpp — what the banks of Kalman filters share (host/kalman.hpp, host/ukf.hpp, host/ekf.hpp, host/enkf.hpp): the bank, its state, the
 // checks of a run's arguments and the drivers of the forward and the backward pass; for the two model-driven banks also their models
 // (KfModelBank).  Part of capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
@@ -49,8 +49,9 @@ static int kf_pack_filter(const llpf_model& m, const std::string& at, int f, int
 // The pack of a bank whose filters are driven by a model's own functions (the unscented and the extended bank): models -> the descriptors
 // ModelD[F], the SoA covariances par [np(nx) + np(ny)][F] (R1 packed, then R2 packed) and the initial state; every check that needs no
 // device.  `who`: the prefix of every message; `filter_name`: what the Rao-Blackwellized ids are said not to have; `need_traits`: the
-// optional members (LLPF_TRAIT_DYNAMICS_JAC, LLPF_TRAIT_MEASUREMENT_JAC) a compiled model must define for this bank
-static int kf_pack_models(const char* who, const char* filter_name, int need_traits, const llpf_model* models, int32_t F, int& model_id, int& nx,
+// optional members (LLPF_TRAIT_DYNAMICS_JAC, LLPF_TRAIT_MEASUREMENT_JAC) a compiled model must define for this bank; `allow_traits`: which
+// of LLPF_TRAIT_NOISE and LLPF_TRAIT_INITIAL the bank admits (the ensemble bank draws through the model's own members; the others: 0)
+static int kf_pack_models(const char* who, const char* filter_name, int need_traits, int allow_traits, const llpf_model* models, int32_t F, int& model_id, int& nx,
                           int& ny, int& nu, std::vector<ModelD>& hm, std::vector<double>& par, std::vector<double>& init) {
     const std::string w = std::string(who) + ": ";
     if (!models) return fail(LLPF_ERR_ARG, w + "models is null");
@@ -69,8 +70,8 @@ static int kf_pack_models(const char* who, const char* filter_name, int need_tra
         if (sx != nx || sy != ny) return fail(LLPF_ERR_ARG, w + "nx, ny differ from the dimensions the model was compiled for");
         const int traits = jit_model_traits(model_id);
         if (traits & LLPF_TRAIT_LOGLIK) return fail(LLPF_ERR_ARG, w + "the model has a likelihood of its own (loglik): there is no Gaussian R2");
-        if (traits & LLPF_TRAIT_NOISE) return fail(LLPF_ERR_ARG, w + "the model forms its own noise (noise): only additive noise is supported");
-        if (traits & LLPF_TRAIT_INITIAL) return fail(LLPF_ERR_ARG, w + "the model has an initial density of its own (initial): d0 must be Gaussian");
+        if (traits & LLPF_TRAIT_NOISE & ~allow_traits) return fail(LLPF_ERR_ARG, w + "the model forms its own noise (noise): only additive noise is supported");
+        if (traits & LLPF_TRAIT_INITIAL & ~allow_traits) return fail(LLPF_ERR_ARG, w + "the model has an initial density of its own (initial): d0 must be Gaussian");
         if (need_traits & LLPF_TRAIT_DYNAMICS_JAC & ~traits)
             return fail(LLPF_ERR_ARG, w + "the model has no dynamics_jac(x, fx, J): add the member to the snippet, or trace the callable with jacobians = true");
         if (need_traits & LLPF_TRAIT_MEASUREMENT_JAC & ~traits)
@@ -113,6 +114,7 @@ static int kf_open(KfBank& b, int32_t device, int32_t F, int npar, const char* s
 struct KfModelBank : KfBank {
     const char* filter_name;          // kf_pack_models: what the Rao-Blackwellized ids are said not to have
     int need_traits;                  // ... and the optional members a compiled model must define for this bank
+    int allow_traits = 0;             // ... and which of `noise` and `initial` it admits (host/enkf.hpp)
     int model_id = 0;
     double Ts = 1.0;
     DevBuf<ModelD> d_models;
@@ -126,7 +128,7 @@ static int kf_model_create(KfModelBank& b, int32_t device, const llpf_model* mod
                            int (*prepare)(int, int, int, std::string&)) {
     std::vector<ModelD> hm;
     std::vector<double> par;
-    CHK(kf_pack_models(b.who, b.filter_name, b.need_traits, models, F, b.model_id, b.nx, b.ny, b.nu, hm, par, b.h_init));
+    CHK(kf_pack_models(b.who, b.filter_name, b.need_traits, b.allow_traits, models, F, b.model_id, b.nx, b.ny, b.nu, hm, par, b.h_init));
     CHK(kf_open(b, device, F, LLPF_KF_NP(b.nx) + LLPF_KF_NP(b.ny), site));
     b.Ts = models[0].Ts;
     {
@@ -149,7 +151,7 @@ static int kf_model_set_models(KfModelBank& b, const llpf_model* models) {
     std::vector<ModelD> hm;
     std::vector<double> par, init;
     int id = 0, nx = 0, ny = 0, nu = 0;
-    CHK(kf_pack_models(b.who, b.filter_name, b.need_traits, models, b.F, id, nx, ny, nu, hm, par, init));
+    CHK(kf_pack_models(b.who, b.filter_name, b.need_traits, b.allow_traits, models, b.F, id, nx, ny, nu, hm, par, init));
     if (id != b.model_id || nx != b.nx || ny != b.ny || nu != b.nu) return kf_fail(b.who, "set_models must keep the model id and the dimensions of the bank");
     HIPC(hipSetDevice(b.device));
     HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));

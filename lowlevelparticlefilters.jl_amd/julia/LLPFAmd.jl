@@ -37,7 +37,8 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
        GPUKalmanFilter, GPUKalmanFilterBank, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
-       ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank, set_iterations!
+       ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank, set_iterations!,
+       GPUEnsembleKalmanFilter, GPUEnsembleKalmanFilterBank, set_inflation!, members, set_members!
 
 const LIB = get(ENV, "LLPF_HIP_LIB", joinpath(@__DIR__, "..", "libllpf_hip.so"))
 const MAXD = 16          # LLPF_MAX_DIM: states / outputs
@@ -1443,6 +1444,142 @@ covariance(kf::GPUExtendedKalmanFilter) = state(kf.bank)[2][:, :, 1]
 function forward_trajectory(kf::GPUExtendedKalmanFilter, u, y, p = NullParameters())
     reset!(kf.bank)
     ll, o = ekf_run(kf.bank, u, y; outputs = true)
+    T = length(y)
+    kf.index = T
+    KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                            [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+end
+
+# ---- banks of ensemble Kalman filters (stochastic, perturbed observations; csrc/shared/llpf_enkf.h is the definition): llpf_enkf_bank_* ----
+mutable struct GPUEnsembleKalmanFilterBank
+    h::Ptr{Cvoid}
+    F::Int
+    N::Int
+    nx::Int
+    nu::Int
+    ny::Int
+    Ts::Float64
+end
+"""
+    GPUEnsembleKalmanFilterBank(filters, N; Ts = 1.0, device = 0, seed = 0, inflation = 1.0)
+
+Independent ensemble Kalman filters of `N` members each on the device, one GPU workgroup per filter; `filters` is a vector of
+(dynamics, measurement, R1, R2, d0) tuples as `GPUUnscentedKalmanFilterBank` takes them.  Filter k's key is `seed + k - 1`; every
+`reset!` draws the next ensemble, `seed!` zeroes the counters and draws the first one again.  `loglik(bank, u, y)` is the vector of
+every filter's log-likelihood.  Unverified against the reference's `EnsembleKalmanFilter` (its source was not available when this was
+written).
+"""
+function GPUEnsembleKalmanFilterBank(filters::Vector, N::Integer; Ts = 1.0, device = 0, seed = 0, inflation = 1.0)
+    cms = [ukf_model(f, Ts) for f in filters]
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_enkf_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Int32, Int32, UInt64, Ref{Ptr{Cvoid}}), device, cms, length(cms),
+                Int32(N), UInt64(seed), h))
+    b = GPUEnsembleKalmanFilterBank(h[], length(cms), Int(N), cms[1].nx, cms[1].nu, cms[1].ny, Float64(Ts))
+    finalizer(x -> ccall((:llpf_enkf_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    inflation == 1.0 || set_inflation!(b, inflation)
+    b
+end
+"set_inflation!(bank, rho): x_i = mean + rho (x_i - mean) after every later predict!; rho finite and >= 1"
+function set_inflation!(b::GPUEnsembleKalmanFilterBank, rho)
+    check(ccall((:llpf_enkf_bank_set_inflation, LIB), Cint, (Ptr{Cvoid}, Float64), b.h, Float64(rho)))
+    b
+end
+function set_parameters!(b::GPUEnsembleKalmanFilterBank, filters::Vector)
+    cms = [ukf_model(f, b.Ts) for f in filters]
+    length(cms) == b.F || throw(ArgumentError("set_parameters!: $(length(cms)) filters for a bank of $(b.F)"))
+    check(ccall((:llpf_enkf_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}), b.h, cms))
+    b
+end
+reset!(b::GPUEnsembleKalmanFilterBank) = check(ccall((:llpf_enkf_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+seed!(b::GPUEnsembleKalmanFilterBank, seed) = check(ccall((:llpf_enkf_bank_seed, LIB), Cint, (Ptr{Cvoid}, UInt64), b.h, UInt64(seed)))
+# u, y: vectors of T vectors shared by every filter (a missing y is `missing` / a NaN first element); step t runs at time (t_index0 + t - 1) Ts
+function enkf_run(b::GPUEnsembleKalmanFilterBank, u, y; outputs = false, t_index0 = 0.0)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        check(ccall((:llpf_enkf_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Ptr{CKalmanOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), Float64(t_index0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+"loglik(bank, u, y): every filter's log-likelihood (reset! first, then T update! steps, the first at t = 1 Ts as the particle filters' loglik)"
+loglik(b::GPUEnsembleKalmanFilterBank, u, y) = (reset!(b); enkf_run(b, u, y; t_index0 = 1.0)[1])
+"ensemble mean x (nx x F) and sample covariance R (nx x nx x F) of every filter"
+function state(b::GPUEnsembleKalmanFilterBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_enkf_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, x, R))
+    x, R
+end
+covariance(b::GPUEnsembleKalmanFilterBank) = state(b)[2]
+"members(bank): the members of every filter, nx x N x F"
+function members(b::GPUEnsembleKalmanFilterBank)
+    X = zeros(b.nx, b.N, b.F)
+    check(ccall((:llpf_enkf_bank_get_members, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.h, X))
+    X
+end
+function set_members!(b::GPUEnsembleKalmanFilterBank, X)
+    Xm = Array{Float64}(reshape(X, b.nx, b.N, b.F))
+    check(ccall((:llpf_enkf_bank_set_members, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.h, Xm))
+    b
+end
+
+"""
+    GPUEnsembleKalmanFilter(dynamics, measurement, R1, R2, d0, N; Ts = 1.0, device = 0, seed = 0, inflation = 1.0)
+
+The stochastic ensemble Kalman filter with `N` members on the device (a bank of one filter, llpf_enkf_bank_*): `forward_trajectory`
+returns the reference's `KalmanFilteringSolution` (means and sample covariances of the members); `loglik`, `reset!`, `update!`,
+`correct!`, `predict!`, `state`, `covariance`, `members`.
+"""
+mutable struct GPUEnsembleKalmanFilter
+    bank::GPUEnsembleKalmanFilterBank
+    Ts::Float64
+    index::Int
+end
+GPUEnsembleKalmanFilter(dynamics, measurement, R1, R2, d0, N::Integer; Ts = 1.0, device = 0, seed = 0, inflation = 1.0) =
+    GPUEnsembleKalmanFilter(GPUEnsembleKalmanFilterBank([(dynamics, measurement, R1, R2, d0)], N; Ts = Ts, device = device, seed = seed,
+                                                        inflation = inflation), Float64(Ts), 0)
+set_inflation!(kf::GPUEnsembleKalmanFilter, rho) = (set_inflation!(kf.bank, rho); kf)
+reset!(kf::GPUEnsembleKalmanFilter) = (reset!(kf.bank); kf.index = 1; nothing)
+loglik(kf::GPUEnsembleKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
+members(kf::GPUEnsembleKalmanFilter) = members(kf.bank)[:, :, 1]
+"correct!(enkf, u, y): the members move; returns (ll, e)"
+function correct!(kf::GPUEnsembleKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    b = kf.bank
+    ismissingy(y) && return 0.0, fill(NaN, b.ny)
+    uu = b.nu > 0 ? Vector{Float64}(u) : Float64[]; yy = Vector{Float64}(y)
+    ll = zeros(1); e = zeros(b.ny)
+    check(ccall((:llpf_enkf_bank_correct, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Ptr{Float64}),
+                b.h, b.nu > 0 ? uu : C_NULL, yy, Int32(0), t / kf.Ts, ll, e))
+    ll[1], e
+end
+"predict!(enkf, u): dynamics and process noise of every member; the step counter grows by one"
+function predict!(kf::GPUEnsembleKalmanFilter, u, p = NullParameters(), t = kf.index * kf.Ts)
+    b = kf.bank
+    uu = b.nu > 0 ? Vector{Float64}(u) : Float64[]
+    check(ccall((:llpf_enkf_bank_predict, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Float64), b.h, b.nu > 0 ? uu : C_NULL, Int32(0), t / kf.Ts))
+    kf.index += 1
+    nothing
+end
+"update!(enkf, u, y): correct! then predict! at time t; returns (ll, e)"
+function update!(kf::GPUEnsembleKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    r = correct!(kf, u, y, p, t)
+    predict!(kf, u, p, t)
+    r
+end
+state(kf::GPUEnsembleKalmanFilter) = state(kf.bank)[1][:, 1]
+covariance(kf::GPUEnsembleKalmanFilter) = state(kf.bank)[2][:, :, 1]
+function forward_trajectory(kf::GPUEnsembleKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o = enkf_run(kf.bank, u, y; outputs = true)
     T = length(y)
     kf.index = T
     KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
