@@ -189,7 +189,9 @@ typedef struct llpf_run_outputs {
  *   forward_trajectory(pf,u,y,p) — reference src/filtering.jl:343-365: llpf_reset, then t_index0 = 0
  *   loglik(pf,u,y,p)             — reference src/smoothing.jl:227-230: llpf_reset, then t_index0 = 1
  * U is T x nu row-major, Y is T x ny row-major; a row of Y whose first element is NaN is "missing".
- * *ll_total receives the sum of the per-step log-likelihoods. */
+ * *ll_total receives the sum of the per-step log-likelihoods.
+ * A non-zero status leaves the handle's particles, weights and ancestors as the step that failed left them (the ancestors possibly those of
+ * an earlier step of the run): llpf_reset before the handle is used again. */
 int  llpf_run(llpf_filter* f, const double* U, const double* Y, int64_t T, double t_index0,
               double* ll_total, const llpf_run_outputs* outs);
 
@@ -624,7 +626,9 @@ int  llpf_last_run_ms(llpf_filter* f, double* ms);
 int  llpf_last_run_stats(llpf_filter* f, int64_t* fused_launches, int64_t* source_side_timesteps, double* survivor_fraction);
 /* two more facts about the last llpf_run: whether its fused launches left the weights they formed unstored (a merged-schedule run of
  * filters of several tiles at resample_threshold 1: every step resamples and nobody reads them; LLPF_SKIP_W=0 pins the storing form), and
- * how many failed bound tests its host loop redid in the exact-max form.  Results do not depend on either. */
+ * how many failed bound tests its host loop redid in the exact-max form.  Results do not depend on either.
+ * *weights_not_stored is a set of bits: 1 = the weights were not stored; 2 = nor were, in every launch but the run's last, the ancestors
+ * (the same runs; LLPF_SKIP_ANC=0 pins the ancestor-storing form): the ancestors a run leaves are those of its last predict! either way. */
 int  llpf_last_run_form(llpf_filter* f, int32_t* weights_not_stored, int64_t* exact_redos);
 int  llpf_bank_last_run_ms(llpf_bank* b, double* ms);
 

@@ -251,7 +251,7 @@ struct ResArgs {
     int64_t k;             // epoch of this launch within a run (for the bank_flag stop test; recorded by a failed bound test)
     int64_t row;           // row of ll_steps / xmean this finalize writes
     int32_t count_surv;    // k_resample: add the number of distinct ancestors to BankDev::surv (models that could take the source-side form)
-    int32_t ablate;        // developer aid (LLPF_ABLATE): bit0 skip RNG, bit1 skip owner search, bit2 skip model math, bit3 skip the weight store; results invalid
+    int32_t ablate;        // developer aid (LLPF_ABLATE): bit0 skip RNG, bit1 skip owner search, bit2 skip model math, bit3 skip the weight store, bit4 skip the ancestor store of the rounds with an owner; results invalid
     int32_t nt_id;         // k_resprop (split schedule): the steps that do not resample read and store nontemporal — set by the host for working sets well
                            // beyond the Infinity Cache (host/run.hpp: below ~7 M particles plain accesses are up to 11 % faster, above nontemporal ones)
     int32_t lazy_q;        // k_resprop (split schedule): the k_norm in front of it stored no quanta — BankDev::quanta points at the WEIGHTS and the scan
@@ -259,6 +259,8 @@ struct ResArgs {
     int32_t skip_w;        // k_resprop (merged schedule, resample_threshold 1, several tiles): the weights this launch forms are not stored — the next
                            // step resamples whatever they are and reads only their sums and quanta; the exact redo of a failed bound test forms
                            // them again first (host/run.hpp)
+    int32_t skip_anc;      // ... and neither are the ancestors of the outputs with an owner, except output M - 1's (kernels/resprop.hpp, SKIPA): the next
+                           // launch overwrites them; set only together with skip_w, never on a run's last launch (in the padding in front of dbg)
     uint64_t* dbg;         // optional [P2][8] phase timestamps of one launch (s_memrealtime, 100 MHz), or nullptr
 };
 

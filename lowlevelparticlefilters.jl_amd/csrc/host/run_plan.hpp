@@ -17,6 +17,7 @@ struct RunSwitches {
     int unfused = -1, source_fx = -1, nt_id = -1;      // LLPF_UNFUSED, LLPF_SOURCE_FX, LLPF_NT_ID = 0/1
     int schedule = -1;                                 // LLPF_SCHEDULE: 1 for "merged", 0 for anything else (the split schedule)
     int lazy_q = -1, skip_w = -1, graph = -1;          // LLPF_LAZY_Q=0: the stored form; LLPF_SKIP_W=0: the storing form; LLPF_GRAPH=0: every run is enqueued
+    int skip_anc = -1;                                 // LLPF_SKIP_ANC=0: a run without the weight store still stores every ancestor
     int ablate = 0;                                    // LLPF_ABLATE (DEVTOOLS builds)
     bool debug_timing = false;                         // LLPF_DEBUG_TIMING=k: the fused launch of step k leaves its per-tile clock readings behind; no graphs
     int64_t debug_step = 0;
@@ -35,6 +36,7 @@ static inline RunSwitches read_run_switches() {
     s.nt_id = env_flag(getenv("LLPF_NT_ID"));
     s.lazy_q = env_flag(getenv("LLPF_LAZY_Q"));
     s.skip_w = env_flag(getenv("LLPF_SKIP_W"));
+    s.skip_anc = env_flag(getenv("LLPF_SKIP_ANC"));
     s.graph = env_flag(graph_env);
     s.ablate = abl_env ? atoi(abl_env) : 0;
     s.debug_timing = dbg_env != nullptr;
@@ -70,7 +72,8 @@ struct RunForm {
     int fx_capable;           // the balanced form of a model whose dynamics are worth a table: the launches count surviving sources
     int source_fx;            // f(x_j) once per surviving source in the resampling launch (kernels/resfx.hpp)
     int lazy_run;             // split schedule, fused: k_norm stores no quanta, two weight buffers
-    int skip_w_run;           // merged fused run at threshold 1: the fused launches store no weights
+    int skip_w_run : 16;      // merged fused run at threshold 1: the fused launches store no weights
+    int skip_anc_run : 16;    // ... and no ancestors but output M - 1's, except the run's last launch (the two share one int: all 32 bits are theirs)
     int nt_id;                // nontemporal accesses on the steps that do not resample
     int want_xm;              // weighted means out of the normalise / weighting kernels
     int xm_launch;            // weighted means by a k_wmean launch per step (per-particle covariance)
@@ -149,6 +152,11 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
     // kernel redoes a failed test in place, from the stored weights) nor for the Rao-Blackwellized model (its weighting also updates the
     // linear substate).  LLPF_SKIP_W=0: the storing form.
     p.skip_w_run = !p.unfused && p.acc_in_weighting && !rbm && f.thr == 1.0 && f.P2 > 1 && s.skip_w != 0;
+    // ... nor the ancestors of the outputs with an owner (k_resprop<..., SKIPA>: 4 more bytes, one more store).  Every launch of such a run
+    // rewrites all N entries, so only those of the run's last launch — which has no weighting phase and keeps storing — reach the accessor,
+    // the "stale j" rule of later verbs or k_resample; inside the run the one reader is the next launch's rounds of [c_end, M), for which
+    // the entry of output M - 1 is kept current (kernels/resprop.hpp).  LLPF_SKIP_ANC=0: every launch stores its ancestors.
+    p.skip_anc_run = p.skip_w_run && s.skip_anc != 0;
     // nontemporal accesses on the steps that do not resample: working sets well beyond the Infinity Cache (LLPF_NT_ID=0|1 pins it)
     p.nt_id = s.nt_id >= 0 ? s.nt_id : (FNs >= ((int64_t)7 << 20) ? 1 : 0);
     // weighted means come out of the normalise / weighting kernels (partial sums over the nx rows they read anyway); the

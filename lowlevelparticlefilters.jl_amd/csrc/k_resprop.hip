@@ -42,7 +42,11 @@ static hipError_t launch_resprop_t(const BankDev& b, const ResArgs& a, const Ste
     else if (st.aux) hipLaunchKernelGGL((k_resprop<NoModel<NX>, NX, 1, true, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
     else if (weight && st.accumulate && one) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
     else if (weight && st.accumulate && a.skip_w) {      // ResArgs::skip_w: the weights are not stored (kernels/resprop.hpp, SKIPW)
-        if constexpr (!Model::RB) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
+        if constexpr (!Model::RB) {
+            // ResArgs::skip_anc: nor are the ancestors of the rounds with an owner (SKIPA)
+            if (a.skip_anc) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
+            else hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
+        }
         else return hipErrorInvalidValue;
     }
     else if (weight && st.accumulate) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);

@@ -184,7 +184,12 @@ static_assert(TILE == 1024, "TileSum assumes 1024-particle tiles");
 // consumes only the integer sums and the quanta): the weights formed here are not stored — 8 of the 44 bytes an output writes, one of its
 // five stores.  The only reader of those weights, the exact redo of a failed bound test, has the host form them again first, from the
 // states in memory.  A head that would not resample (no quanta at all) asks for that redo instead of reading the weights.
-template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, bool SKIPW = false>
+// SKIPA (only with SKIPW, and never a run's last launch, which is WEIGHT = false): the rounds with an owner store no ancestor either — 4 of
+// the remaining 36 bytes, one of the four stores.  The next launch of the run overwrites all of them unread, with one exception: its
+// rounds of [c_end, M) read the previous ancestor of their own output, and only output M - 1 can be such an output (its threshold is the
+// only one that can reach bins[N]: tests/test_stale_corner.py).  That entry is kept current: stored once behind the loop by the block
+// that owns output M - 1, and by the rounds of [c_end, M) as ever.
+template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, bool SKIPW = false, bool SKIPA = false>
 // amdgpu_waves_per_eu(4): the ~3.8 blocks per CU of a 10^6-particle filter must be resident together (<= 128 VGPRs); the
 // larger state dimensions would spill under that cap and keep the compiler's choice; the Rao-Blackwellized propagate uses
 // 130-156 VGPRs and is pinned to three waves per SIMD (<= 168): twice in this round an unrelated change pushed it past 170 and
@@ -260,6 +265,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
         }
     };
     static_assert(!SKIPW || (WEIGHT && ACC && !AUX && !ONE && !Model::RB), "the form without the weight store: merged schedule, several tiles");
+    static_assert(!SKIPA || SKIPW, "the form without the ancestor store exists only where the weights are not stored either");
     const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
     if (h.status) return;
     // Values of FilterScal fetched above with the head's loads but wanted only from here on.  FilterScal is written by this
@@ -373,6 +379,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     // gfx950, so each round's owner lookup and gather waited for the previous round's write-through stores to be acknowledged
     // (profiles/loop_chain_isa.txt).  A thread still visits its outputs in increasing order (TileSum sees the same sequence), and the
     // body is the same text.
+    // SKIPA: only the rounds of [c_end, M) store their ancestor (a compile-time choice: a test in the loop costs more than the store)
+#ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 4: the same behind a run-time test, and without the entry kept behind the loop (results invalid) */
+#define LLPF_ANC_KEPT(STALE) ((STALE) == 1 || (!SKIPA && !(a.ablate & 16)))
+#else
+#define LLPF_ANC_KEPT(STALE) ((STALE) == 1 || !SKIPA)
+#endif
 #define LLPF_OUTPUT_ROUNDS(RESX, NTLX, STALE, OEND) \
 _Pragma("unroll 1") \
     for (; o < (OEND); o += BLOCK) { \
@@ -381,7 +393,7 @@ _Pragma("unroll 1") \
         if (RESX) { \
             if ((STALE) == 0 || ((STALE) == 2 && o < ucend)) src = tile0 + owner_of(o); \
             else src = anc_ident_prev ? o : (uint32_t)ld_off(anc, o << 2); \
-            Mem<LLPF_STCOH0>::st_off(anc, o << 2, (int32_t)src); \
+            if (LLPF_ANC_KEPT(STALE)) Mem<LLPF_STCOH0>::st_off(anc, o << 2, (int32_t)src); \
             if (AUX) wprev = ld_off(lamp, o << 3) - lN; \
         } else if (AUX) { \
             wprev = ld_off(lamp, o << 3) - lN; \
@@ -501,9 +513,16 @@ _Pragma("unroll") \
 #undef LLPF_OUTPUT_LOOP
 #undef LLPF_OUTPUT_ROUNDS
 #undef LLPF_OUTPUT_STALE
+#undef LLPF_ANC_KEPT
 #undef LLPF_OUTPUT_ACC
 #undef LLPF_OUTPUT_LOOP_PF
 #undef LLPF_OUTPUT_LOOP_ID2
+    if constexpr (SKIPA) {
+        // the one entry the next launch may read (its rounds of [c_end, M)): the ancestor of output M - 1, by the block that owns it
+        static_assert(PEEL, "SKIPA: the rounds with and without an owner are separate loops");
+        if (res && ucend == (uint32_t)a.M && (uint32_t)first < ucend && threadIdx.x == 0)
+            Mem<LLPF_STCOH0>::st_off(anc, (ucend - 1u) << 2, (int32_t)(tile0 + owner_of(ucend - 1u)));
+    }
     if (WEIGHT && ACC) ts.flush(sh_tq, tq_next, tbase);
     __builtin_amdgcn_s_setprio(3);
     LLPF_STAMP(3);
