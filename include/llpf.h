@@ -628,7 +628,9 @@ int  llpf_last_run_stats(llpf_filter* f, int64_t* fused_launches, int64_t* sourc
  * filters of several tiles at resample_threshold 1: every step resamples and nobody reads them; LLPF_SKIP_W=0 pins the storing form), and
  * how many failed bound tests its host loop redid in the exact-max form.  Results do not depend on either.
  * *weights_not_stored is a set of bits: 1 = the weights were not stored; 2 = nor were, in every launch but the run's last, the ancestors
- * (the same runs; LLPF_SKIP_ANC=0 pins the ancestor-storing form): the ancestors a run leaves are those of its last predict! either way. */
+ * (the same runs; LLPF_SKIP_ANC=0 pins the ancestor-storing form): the ancestors a run leaves are those of its last predict! either way;
+ * 4 = those launches were the kernel compiled for systematic resampling without weighted means (the runs of bit 2 that resample
+ * systematically and ask for no xmean; LLPF_LEAN=0 pins the kernel that tests both at run time). */
 int  llpf_last_run_form(llpf_filter* f, int32_t* weights_not_stored, int64_t* exact_redos);
 int  llpf_bank_last_run_ms(llpf_bank* b, double* ms);
 

@@ -259,8 +259,11 @@ struct ResArgs {
     int32_t skip_w;        // k_resprop (merged schedule, resample_threshold 1, several tiles): the weights this launch forms are not stored — the next
                            // step resamples whatever they are and reads only their sums and quanta; the exact redo of a failed bound test forms
                            // them again first (host/run.hpp)
-    int32_t skip_anc;      // ... and neither are the ancestors of the outputs with an owner, except output M - 1's (kernels/resprop.hpp, SKIPA): the next
+    int16_t skip_anc;      // ... and neither are the ancestors of the outputs with an owner, except output M - 1's (kernels/resprop.hpp, SKIPA): the next
                            // launch overwrites them; set only together with skip_w, never on a run's last launch (in the padding in front of dbg)
+    int16_t lean;          // ... and the run resamples systematically and wants no weighted means (kernels/resprop.hpp, LEAN): the kernel that holds
+                           // neither the stratified counts nor the means; set only together with skip_anc, with which it shares four bytes (the
+                           // struct keeps its size and the layout of everything else)
     uint64_t* dbg;         // optional [P2][8] phase timestamps of one launch (s_memrealtime, 100 MHz), or nullptr
 };
 

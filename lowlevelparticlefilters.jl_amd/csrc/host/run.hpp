@@ -202,6 +202,7 @@ struct RunLoop {
         ra.lazy_q = lazy_q ? 1 : 0;
         ra.skip_w = (p.skip_w_run && fast) ? 1 : 0;      // (the exact redo of a failed step keeps the storing form)
         ra.skip_anc = (p.skip_anc_run && fast && weight) ? 1 : 0;      // (... and so does the run's last launch, whose ancestors the run leaves)
+        ra.lean = (p.lean_form() && ra.skip_anc) ? 1 : 0;              // (... and both keep the kernel with the run-time tests)
         ra.nt_id = p.nt_id;
         if (!fast) {
             ProfScope ps(b, LLPF_PROF_NORMALISE);
@@ -408,7 +409,7 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     const RunPlan plan = make_run_plan(facts);
     b.use_fx = plan.use_fx;
     b.last_run_launches = 0; b.last_run_fx_steps = plan.source_fx ? T : 0; b.last_run_surv = -1.0;
-    b.last_run_skip_w = plan.skip_w_run; b.last_run_skip_anc = plan.skip_anc_run; b.last_run_redos = 0;
+    b.last_run_skip_w = plan.skip_w_run; b.last_run_skip_anc = plan.skip_anc_run; b.last_run_lean = plan.lean_form(); b.last_run_redos = 0;
 
     // 4. what the plan needs
     if (o.ll_steps) CHK(b.d_ll_steps.ensure((size_t)T * b.F));

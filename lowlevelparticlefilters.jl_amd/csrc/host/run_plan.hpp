@@ -18,6 +18,7 @@ struct RunSwitches {
     int schedule = -1;                                 // LLPF_SCHEDULE: 1 for "merged", 0 for anything else (the split schedule)
     int lazy_q = -1, skip_w = -1, graph = -1;          // LLPF_LAZY_Q=0: the stored form; LLPF_SKIP_W=0: the storing form; LLPF_GRAPH=0: every run is enqueued
     int skip_anc = -1;                                 // LLPF_SKIP_ANC=0: a run without the weight store still stores every ancestor
+    int lean = -1;                                     // LLPF_LEAN=0: such a run keeps the kernel that tests the strategy and the means at run time
     int ablate = 0;                                    // LLPF_ABLATE (DEVTOOLS builds)
     bool debug_timing = false;                         // LLPF_DEBUG_TIMING=k: the fused launch of step k leaves its per-tile clock readings behind; no graphs
     int64_t debug_step = 0;
@@ -37,6 +38,7 @@ static inline RunSwitches read_run_switches() {
     s.lazy_q = env_flag(getenv("LLPF_LAZY_Q"));
     s.skip_w = env_flag(getenv("LLPF_SKIP_W"));
     s.skip_anc = env_flag(getenv("LLPF_SKIP_ANC"));
+    s.lean = env_flag(getenv("LLPF_LEAN"));
     s.graph = env_flag(graph_env);
     s.ablate = abl_env ? atoi(abl_env) : 0;
     s.debug_timing = dbg_env != nullptr;
@@ -72,8 +74,12 @@ struct RunForm {
     int fx_capable;           // the balanced form of a model whose dynamics are worth a table: the launches count surviving sources
     int source_fx;            // f(x_j) once per surviving source in the resampling launch (kernels/resfx.hpp)
     int lazy_run;             // split schedule, fused: k_norm stores no quanta, two weight buffers
+    // The kernel relies on this: k_resprop<..., SKIPW> holds no arm for a step that does not resample and accumulates no sum of squares
+    // (kernels/resprop.hpp) — skip_w_run is set at resample_threshold exactly 1 and nowhere else.
     int skip_w_run : 16;      // merged fused run at threshold 1: the fused launches store no weights
-    int skip_anc_run : 16;    // ... and no ancestors but output M - 1's, except the run's last launch (the two share one int: all 32 bits are theirs)
+    int skip_anc_run : 8;     // ... and no ancestors but output M - 1's, except the run's last launch
+    int lean_run : 8;         // ... and, where they store no ancestors, are the kernel compiled for systematic resampling without weighted means
+                              // (lean_form(); the three share one int: all 32 bits are theirs)
     int nt_id;                // nontemporal accesses on the steps that do not resample
     int want_xm;              // weighted means out of the normalise / weighting kernels
     int xm_launch;            // weighted means by a k_wmean launch per step (per-particle covariance)
@@ -81,6 +87,7 @@ struct RunForm {
     int ablate;
     int ll_steps, multi, xcov, xquant;      // outputs and input layout the launch arguments depend on
     bool operator==(const RunForm& o) const { return memcmp(this, &o, sizeof(RunForm)) == 0; }
+    bool lean_form() const { return skip_anc_run && lean_run; }      // the run's fused launches but the last are k_resprop<..., LEAN>
 };
 static_assert(std::has_unique_object_representations<RunForm>::value, "RunForm is compared bytewise: ints only, no padding");
 
@@ -163,6 +170,12 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
     // model with per-particle covariance takes them from a k_wmean launch per step over its [xn; xl] rows instead
     p.want_xm = f.xmean && !rbfull;
     p.xm_launch = f.xmean && rbfull;
+    // ... and what else such a run knows before its first launch: it resamples systematically and wants no weighted means — the launches
+    // that store no ancestors are then k_resprop<..., LEAN>, which holds neither the stratified counts (a Philox block per threshold) nor
+    // the means and tests neither (the same bits; LinGauss with one or two states, every other shape keeps the form above).  The field
+    // follows skip_w_run, not skip_anc_run, so that two plans which differ only in LLPF_SKIP_ANC differ only in skip_anc_run; the launches
+    // take the form where both hold (lean_form()).  LLPF_LEAN=0: the kernel with the run-time tests.
+    p.lean_run = p.skip_w_run && f.strategy == LLPF_RESAMPLE_SYSTEMATIC && !p.want_xm && s.lean != 0;
     // The run ends in the buffer it began in (a handle's weights do not move between runs: one captured graph per shape, not two that
     // alternate): T - 1 steps have a weighting phase; when that number is odd, step 0 keeps the stored form and weights in place.
     p.k_pp0 = (p.lazy_run && ((f.T - 1) & 1)) ? 1 : 0;

@@ -43,7 +43,14 @@ static hipError_t launch_resprop_t(const BankDev& b, const ResArgs& a, const Ste
     else if (weight && st.accumulate && one) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
     else if (weight && st.accumulate && a.skip_w) {      // ResArgs::skip_w: the weights are not stored (kernels/resprop.hpp, SKIPW)
         if constexpr (!Model::RB) {
-            // ResArgs::skip_anc: nor are the ancestors of the rounds with an owner (SKIPA)
+            // ResArgs::skip_anc: nor are the ancestors of the rounds with an owner (SKIPA); ResArgs::lean: systematic resampling and no weighted
+            // means, compiled in (LEAN) — the shapes a run takes fused by default; every other shape keeps the form with the run-time tests
+            if constexpr (std::is_same<Model, LinGauss<NX, NY>>::value && NX <= 2) {
+                if (a.skip_anc && a.lean) {
+                    hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
+                    return hipGetLastError();
+                }
+            }
             if (a.skip_anc) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
             else hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
         }

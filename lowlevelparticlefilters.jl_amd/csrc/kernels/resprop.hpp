@@ -189,7 +189,13 @@ static_assert(TILE == 1024, "TileSum assumes 1024-particle tiles");
 // rounds of [c_end, M) read the previous ancestor of their own output, and only output M - 1 can be such an output (its threshold is the
 // only one that can reach bins[N]: tests/test_stale_corner.py).  That entry is kept current: stored once behind the loop by the block
 // that owns output M - 1, and by the rounds of [c_end, M) as ever.
-template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, bool SKIPW = false, bool SKIPA = false>
+// What SKIPW says about the run is compiled in: past the head every launch resamples (threshold 1: decide_resample returns 1, and a head
+// whose quanta sum to zero has asked for the redo, NO_TOT0), so there is no arm for a step that does not — it could not run anyway, the
+// weights it would read were never stored — and no sum of squares (host/fallback.hpp: need_e2 is 0 at threshold 1).
+// LEAN (only with SKIPW and SKIPA; host/run_plan.hpp: lean_run): the run also resamples systematically and wants no weighted means — only
+// res_counts<LLPF_RESAMPLE_SYSTEMATIC> is instantiated, and there is no xm[], no block_store_xm and no test of either.  The same
+// arithmetic, counters, stores and visiting order: the form only drops tests and arms that such a run never takes.
+template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, bool SKIPW = false, bool SKIPA = false, bool LEAN = false>
 // amdgpu_waves_per_eu(4): the ~3.8 blocks per CU of a 10^6-particle filter must be resident together (<= 128 VGPRs); the
 // larger state dimensions would spill under that cap and keep the compiler's choice; the Rao-Blackwellized propagate uses
 // 130-156 VGPRs and is pinned to three waves per SIMD (<= 168): twice in this round an unrelated change pushed it past 170 and
@@ -266,6 +272,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     };
     static_assert(!SKIPW || (WEIGHT && ACC && !AUX && !ONE && !Model::RB), "the form without the weight store: merged schedule, several tiles");
     static_assert(!SKIPA || SKIPW, "the form without the ancestor store exists only where the weights are not stored either");
+    static_assert(!LEAN || (SKIPW && SKIPA), "the lean form exists only where neither weights nor ancestors are stored");
+    // SKIPW means that host/run_plan.hpp saw resample_threshold == 1 (RunForm::skip_w_run): every step of the run resamples, none needs E2
+    constexpr bool ALWAYS_RES = SKIPW;
+    static_assert(!ALWAYS_RES || (WEIGHT && ACC && !AUX), "a launch that always resamples: the merged schedule's weighting form, never forced");
     const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
     if (h.status) return;
     // Values of FilterScal fetched above with the head's loads but wanted only from here on.  FilterScal is written by this
@@ -295,7 +305,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     //                j[i] untouched (resample.jl:25-34) -> previous ancestor (identity if the last predict! did
     //                not resample)
     //   otherwise  : s.j .= 1:N, the tile's own particles (padding lanes included so that their weight stays -Inf)
-    const bool res = (h.dr || a.force) && h.tot != 0;
+    const bool res = ALWAYS_RES || ((h.dr || a.force) && h.tot != 0);
+    // (tested where they are used, as ever: read once up here the two arguments stay in SGPRs across the whole kernel, which the forms
+    // that do test them pay for in lanes)
+#define LLPF_NEED_E2 (!ALWAYS_RES && st.need_e2 != 0)
+#define LLPF_WANT_XM (!LEAN && st.want_xmean)
     int64_t first, last;
     int32_t c_end = 0;
     double l = 0.0;
@@ -322,19 +336,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
                 }
             }
         }
-        if (b.strategy == LLPF_RESAMPLE_SYSTEMATIC) res_counts<LLPF_RESAMPLE_SYSTEMATIC>(b, a, f, tile, h, qv, sh, c_start, c_end);
-        else res_counts<LLPF_RESAMPLE_STRATIFIED>(b, a, f, tile, h, qv, sh, c_start, c_end);
+        if (LEAN || b.strategy == LLPF_RESAMPLE_SYSTEMATIC) res_counts<LLPF_RESAMPLE_SYSTEMATIC>(b, a, f, tile, h, qv, sh, c_start, c_end);
+        else if constexpr (!LEAN) res_counts<LLPF_RESAMPLE_STRATIFIED>(b, a, f, tile, h, qv, sh, c_start, c_end);
         first = c_start;
         last = (tile == b.P2 - 1) ? (int64_t)a.M : (int64_t)c_end;
         if (OWN_TABLE) res_owner_table(sh, sh, sh_own, c_start);
-    } else {
+    } else if constexpr (!ALWAYS_RES) {
         l = head_log(h);
         first = (int64_t)tile * TILE;
         last = first + TILE;
         if (!RBFAT) __syncthreads();      // generator tables in LDS
     }
     {   // bound of the weights produced below: max of the previous (normalised) weights + the density's peak
-        const double wmx = res ? b.log1N : (h.mtrue - h.a) - l;
+        const double wmx = (ALWAYS_RES || res) ? b.log1N : (h.mtrue - h.a) - l;
         if constexpr (Model::RB) {     // peak of N(0, S) of the coming correct! (or of R2 when C == 0)
             const double c0w = md->rb_zeroC ? md->dg.c0 : (st.rb_corr + f)->dS.c0;
             pc.off = (WEIGHT && st.has_y) ? wmx + c0w : wmx;
@@ -397,7 +411,7 @@ _Pragma("unroll 1") \
             if (AUX) wprev = ld_off(lamp, o << 3) - lN; \
         } else if (AUX) { \
             wprev = ld_off(lamp, o << 3) - lN; \
-        } else if (WEIGHT) { \
+        } else if (WEIGHT && !ALWAYS_RES) { \
             wprev = (ld_off(pc.w, o << 3) - h.a) - l; \
         } \
         double xs[NX]; \
@@ -408,10 +422,10 @@ _Pragma("unroll 1") \
 #define LLPF_OUTPUT_ACC(o, wv, xs) \
         if (WEIGHT && ACC) { \
             double e; \
-            const uint64_t q = wacc.add(wv, pc.off, st.K, st.need_e2 != 0, &e); \
+            const uint64_t q = wacc.add(wv, pc.off, st.K, LLPF_NEED_E2, &e); \
             Mem<LLPF_STCOH0>::st_off(pc.qnext, (o) << 3, q); \
             ts.add(o, q, sh_tq, tq_next, tbase); \
-            if (st.want_xmean) { \
+            if (LLPF_WANT_XM) { \
 _Pragma("unroll") \
                 for (int d = 0; d < NX; ++d) xm[d] = xm[d] + xs[d] * e; \
             } \
@@ -554,10 +568,10 @@ _Pragma("unroll") \
                 for (uint32_t o = (uint32_t)first + threadIdx.x; o < ulast; o += BLOCK) {
                     const double wv = ld_off(pc.wn, o << 3);
                     double e;
-                    const uint64_t q = wacc.add(wv, mx, st.K, st.need_e2 != 0, &e);
+                    const uint64_t q = wacc.add(wv, mx, st.K, LLPF_NEED_E2, &e);
                     st_off(pc.qnext, o << 3, q);
                     ts.add(o, q, sh_tq, tq_next, tbase);
-                    if (st.want_xmean) {
+                    if (LLPF_WANT_XM) {
 #pragma unroll
                         for (int d = 0; d < NX; ++d) xm[d] = xm[d] + ld_off(pc.xn + (size_t)d * Ns, o << 3) * e;
                     }
@@ -566,11 +580,11 @@ _Pragma("unroll") \
             }
         }
         if (ACC) {
-            wacc.flush(b.acc + (size_t)f * ACC_WORDS, st.parity, st.need_e2 != 0, sm_acc);
+            wacc.flush(b.acc + (size_t)f * ACC_WORDS, st.parity, LLPF_NEED_E2, sm_acc);
             __syncthreads();
             if (threadIdx.x < 8 && sh_tq[threadIdx.x])
                 atomicAdd(reinterpret_cast<unsigned long long*>(tq_next + tbase + threadIdx.x), (unsigned long long)sh_tq[threadIdx.x]);
-            if (st.want_xmean) block_store_xm<NX>(xm, xmpart_slot(b, st.parity, f) + (size_t)tile * MAXD, sm_x);
+            if (LLPF_WANT_XM) block_store_xm<NX>(xm, xmpart_slot(b, st.parity, f) + (size_t)tile * MAXD, sm_x);
         }
         if (tile == 0 && threadIdx.x == 0) {
             if (AUX) {     // the weights just written are final values (no pending normalisation); aux_off bounds them
@@ -588,6 +602,8 @@ _Pragma("unroll") \
     __syncthreads();
     LLPF_STAMP(4);
 #undef LLPF_STAMP
+#undef LLPF_NEED_E2
+#undef LLPF_WANT_XM
     if (tile == b.P2 - 1 && threadIdx.x == 0) {        // bookkeeping of this predict! (by the only block that reads anc_ident)
         const int r = res ? 1 : 0;
         sc->anc_ident_s[b.anc_slot ^ 1] = r ? 0 : 1;
