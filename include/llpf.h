@@ -624,13 +624,13 @@ int  llpf_last_run_ms(llpf_filter* f, double* ms);
  * the survivor fraction the choice for the NEXT run is made by (distinct ancestors per predict! / N, a step that did not resample
  * counting as 1; -1 when the model cannot take the source-side form).  Results do not depend on the form: the choice is a schedule. */
 int  llpf_last_run_stats(llpf_filter* f, int64_t* fused_launches, int64_t* source_side_timesteps, double* survivor_fraction);
-/* two more facts about the last llpf_run: whether its fused launches left the weights they formed unstored (a merged-schedule run of
- * filters of several tiles at resample_threshold 1: every step resamples and nobody reads them; LLPF_SKIP_W=0 pins the storing form), and
- * how many failed bound tests its host loop redid in the exact-max form.  Results do not depend on either.
- * *weights_not_stored is a set of bits: 1 = the weights were not stored; 2 = nor were, in every launch but the run's last, the ancestors
- * (the same runs; LLPF_SKIP_ANC=0 pins the ancestor-storing form): the ancestors a run leaves are those of its last predict! either way;
- * 4 = those launches were the kernel compiled for systematic resampling without weighted means (the runs of bit 2 that resample
- * systematically and ask for no xmean; LLPF_LEAN=0 pins the kernel that tests both at run time). */
+/* two more facts about the last llpf_run: what its fused launches left out, and how many failed bound tests its host loop redid in the
+ * exact-max form.  Results do not depend on either.
+ * *weights_not_stored is (1 << level) - 1: 0, 1, 3 or 7.  A merged-schedule run of filters of several tiles at resample_threshold 1
+ * resamples at every step, so nobody reads what its launches form between the steps, and each level leaves out one thing more: bit 1 =
+ * the weights were not stored (LLPF_SKIP_W=0 pins level 0); bit 2 = nor were, in every launch but the run's last, the ancestors — those
+ * a run leaves are its last predict!'s either way (LLPF_SKIP_ANC=0 pins level 1); bit 4 = those launches were the kernel compiled for
+ * systematic resampling without weighted means (linear-Gaussian models of one or two states, no xmean; LLPF_LEAN=0 pins level 2). */
 int  llpf_last_run_form(llpf_filter* f, int32_t* weights_not_stored, int64_t* exact_redos);
 int  llpf_bank_last_run_ms(llpf_bank* b, double* ms);
 

@@ -256,16 +256,12 @@ struct ResArgs {
                            // beyond the Infinity Cache (host/run.hpp: below ~7 M particles plain accesses are up to 11 % faster, above nontemporal ones)
     int32_t lazy_q;        // k_resprop (split schedule): the k_norm in front of it stored no quanta — BankDev::quanta points at the WEIGHTS and the scan
                            // forms the tile's quanta itself, floor(exp(w - offset) 2^K): the same function of the same numbers (host/run.hpp)
-    int32_t skip_w;        // k_resprop (merged schedule, resample_threshold 1, several tiles): the weights this launch forms are not stored — the next
-                           // step resamples whatever they are and reads only their sums and quanta; the exact redo of a failed bound test forms
-                           // them again first (host/run.hpp)
-    int16_t skip_anc;      // ... and neither are the ancestors of the outputs with an owner, except output M - 1's (kernels/resprop.hpp, SKIPA): the next
-                           // launch overwrites them; set only together with skip_w, never on a run's last launch (in the padding in front of dbg)
-    int16_t lean;          // ... and the run resamples systematically and wants no weighted means (kernels/resprop.hpp, LEAN): the kernel that holds
-                           // neither the stratified counts nor the means; set only together with skip_anc, with which it shares four bytes (the
-                           // struct keeps its size and the layout of everything else)
+    int32_t level;         // k_resprop (merged schedule, resample_threshold 1, several tiles): what this launch leaves out, a RunLevel (host/run_plan.hpp:
+                           // launch_level) — from 1 the weights it forms are not stored, from 2 nor the ancestors of the outputs with an owner except
+                           // output M - 1's, 3 is the kernel for systematic resampling without weighted means (kernels/resprop.hpp)
     uint64_t* dbg;         // optional [P2][8] phase timestamps of one launch (s_memrealtime, 100 MHz), or nullptr
 };
+static_assert(__builtin_offsetof(ResArgs, dbg) == 136 && sizeof(ResArgs) == 144, "ResArgs is a kernel argument: its layout is part of every launch");
 
 // ---- end of the part the run-time compiled user-model kernels see (tools/gen_jit_prelude.py cuts here) ----
 }  // namespace llpf

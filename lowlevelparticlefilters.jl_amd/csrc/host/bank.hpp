@@ -114,9 +114,7 @@ struct Bank : BankStream {
     uint32_t* d_flag = nullptr;
     int64_t last_run_launches = 0, last_run_fx_steps = 0;
     double last_run_surv = -1.0;
-    bool last_run_skip_w = false;     // the last run's fused launches stored no weights (host/run_plan.hpp: skip_w_run)
-    bool last_run_skip_anc = false;   // ... and, but for its last launch, no ancestors (skip_anc_run)
-    bool last_run_lean = false;       // ... and those launches were the kernel for systematic resampling without weighted means (lean_form())
+    int last_run_level = 0;           // the RunLevel of the last run's plan (host/run_plan.hpp)
     int64_t last_run_redos = 0;       // failed bound tests the last run's host loop redid in exact form
     DevBuf<double> d_xmpart;
     // Rao-Blackwellized model: host side of the shared covariance recursion (csrc/shared/llpf_rbkf.h)

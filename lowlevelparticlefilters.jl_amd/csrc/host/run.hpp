@@ -200,9 +200,7 @@ struct RunLoop {
             HIPC(launch_norm(d, ra.parity, p.want_xm, ne2, rel_step(b), 0, lazy_q ? 3 : 1, k, b.stream));
         }
         ra.lazy_q = lazy_q ? 1 : 0;
-        ra.skip_w = (p.skip_w_run && fast) ? 1 : 0;      // (the exact redo of a failed step keeps the storing form)
-        ra.skip_anc = (p.skip_anc_run && fast && weight) ? 1 : 0;      // (... and so does the run's last launch, whose ancestors the run leaves)
-        ra.lean = (p.lean_form() && ra.skip_anc) ? 1 : 0;              // (... and both keep the kernel with the run-time tests)
+        ra.level = launch_level(p, fast, weight);
         ra.nt_id = p.nt_id;
         if (!fast) {
             ProfScope ps(b, LLPF_PROF_NORMALISE);
@@ -348,7 +346,7 @@ struct RunLoop {
             // step kf of the flagged filters: exact-max normalisation of the same weights, then the step again
             const int64_t kf = fl.step;
             b.last_run_redos += 1;
-            if (p.skip_w_run && kf > 0) CHK(reweight_flagged(kf));
+            if (p.level >= RUN_SKIP_W && kf > 0) CHK(reweight_flagged(kf));
             CHK(clear_slot_sums(b, head_slot(e, kf)));
             CHK(timestep(kf, false, 1));
             CHK(clear_fallback(b));
@@ -409,7 +407,7 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     const RunPlan plan = make_run_plan(facts);
     b.use_fx = plan.use_fx;
     b.last_run_launches = 0; b.last_run_fx_steps = plan.source_fx ? T : 0; b.last_run_surv = -1.0;
-    b.last_run_skip_w = plan.skip_w_run; b.last_run_skip_anc = plan.skip_anc_run; b.last_run_lean = plan.lean_form(); b.last_run_redos = 0;
+    b.last_run_level = plan.level; b.last_run_redos = 0;
 
     // 4. what the plan needs
     if (o.ll_steps) CHK(b.d_ll_steps.ensure((size_t)T * b.F));

@@ -63,6 +63,17 @@ struct RunFacts {
     RunSwitches sw;
 };
 
+// What the fused launches of a merged run at resample_threshold 1 leave out — all of them but the exact redo of a failed bound test and
+// the run's last launch (launch_level).  Ordered: each level is the one below it and one thing more.  Plain ints, so that the kernel's
+// template argument and ResArgs::level are the same values (kernels/resprop.hpp).  The kernel relies on this: a level above RUN_STORES
+// holds no arm for a step that does not resample and accumulates no sum of squares — it is planned at threshold exactly 1 and nowhere else.
+enum RunLevel : int {
+    RUN_STORES = 0,           // weights and ancestors are stored
+    RUN_SKIP_W = 1,           // no weights are stored
+    RUN_SKIP_ANC = 2,         // ... and no ancestor but output M - 1's
+    RUN_LEAN = 3,             // ... by the kernel for systematic resampling without weighted means
+};
+
 // Everything a captured launch sequence depends on besides its buffers, its length and the entry state: the key of a captured graph
 // holds one and compares it as a whole (Bank::RunGraph), so a switch added here is part of the key without further ado.  Plain ints
 // (0/1 where the name is a yes/no), no padding: equality is equality of the bytes.
@@ -74,12 +85,7 @@ struct RunForm {
     int fx_capable;           // the balanced form of a model whose dynamics are worth a table: the launches count surviving sources
     int source_fx;            // f(x_j) once per surviving source in the resampling launch (kernels/resfx.hpp)
     int lazy_run;             // split schedule, fused: k_norm stores no quanta, two weight buffers
-    // The kernel relies on this: k_resprop<..., SKIPW> holds no arm for a step that does not resample and accumulates no sum of squares
-    // (kernels/resprop.hpp) — skip_w_run is set at resample_threshold exactly 1 and nowhere else.
-    int skip_w_run : 16;      // merged fused run at threshold 1: the fused launches store no weights
-    int skip_anc_run : 8;     // ... and no ancestors but output M - 1's, except the run's last launch
-    int lean_run : 8;         // ... and, where they store no ancestors, are the kernel compiled for systematic resampling without weighted means
-                              // (lean_form(); the three share one int: all 32 bits are theirs)
+    int level;                // RunLevel of the run's fused launches (launch_level() gives each launch's own)
     int nt_id;                // nontemporal accesses on the steps that do not resample
     int want_xm;              // weighted means out of the normalise / weighting kernels
     int xm_launch;            // weighted means by a k_wmean launch per step (per-particle covariance)
@@ -87,7 +93,6 @@ struct RunForm {
     int ablate;
     int ll_steps, multi, xcov, xquant;      // outputs and input layout the launch arguments depend on
     bool operator==(const RunForm& o) const { return memcmp(this, &o, sizeof(RunForm)) == 0; }
-    bool lean_form() const { return skip_anc_run && lean_run; }      // the run's fused launches but the last are k_resprop<..., LEAN>
 };
 static_assert(std::has_unique_object_representations<RunForm>::value, "RunForm is compared bytewise: ints only, no padding");
 
@@ -154,16 +159,16 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
     p.lazy_run = !p.merged && !p.unfused && !p.no_bound && f.thr < 1.0 && s.lazy_q != 0;
     // Merged fused run at threshold 1: every step resamples, so the weights a launch forms are never read again — the next step's prior is
     // log(1/N), its head consumes their integer sums and quanta, and the run ends uniform (k_post_predict) — and the fused launches do not
-    // store them (k_resprop<..., SKIPW>: 8 of the 44 bytes an output writes).  Their one reader is the exact redo of a failed bound test, in
+    // store them (k_resprop<..., RUN_SKIP_W>: 8 of the 44 bytes an output writes).  Their one reader is the exact redo of a failed bound test, in
     // front of which the weights of the flagged filters are formed again (host/run.hpp: reweight_flagged).  Not for one-tile filters (their
     // kernel redoes a failed test in place, from the stored weights) nor for the Rao-Blackwellized model (its weighting also updates the
     // linear substate).  LLPF_SKIP_W=0: the storing form.
-    p.skip_w_run = !p.unfused && p.acc_in_weighting && !rbm && f.thr == 1.0 && f.P2 > 1 && s.skip_w != 0;
-    // ... nor the ancestors of the outputs with an owner (k_resprop<..., SKIPA>: 4 more bytes, one more store).  Every launch of such a run
-    // rewrites all N entries, so only those of the run's last launch — which has no weighting phase and keeps storing — reach the accessor,
+    const bool skip_w = !p.unfused && p.acc_in_weighting && !rbm && f.thr == 1.0 && f.P2 > 1 && s.skip_w != 0;
+    // ... nor the ancestors of the outputs with an owner (k_resprop<..., RUN_SKIP_ANC>: 4 more bytes, one more store).  Every launch of such a
+    // run rewrites all N entries, so only those of the run's last launch — which has no weighting phase and keeps storing — reach the accessor,
     // the "stale j" rule of later verbs or k_resample; inside the run the one reader is the next launch's rounds of [c_end, M), for which
     // the entry of output M - 1 is kept current (kernels/resprop.hpp).  LLPF_SKIP_ANC=0: every launch stores its ancestors.
-    p.skip_anc_run = p.skip_w_run && s.skip_anc != 0;
+    const bool skip_anc = skip_w && s.skip_anc != 0;
     // nontemporal accesses on the steps that do not resample: working sets well beyond the Infinity Cache (LLPF_NT_ID=0|1 pins it)
     p.nt_id = s.nt_id >= 0 ? s.nt_id : (FNs >= ((int64_t)7 << 20) ? 1 : 0);
     // weighted means come out of the normalise / weighting kernels (partial sums over the nx rows they read anyway); the
@@ -171,11 +176,11 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
     p.want_xm = f.xmean && !rbfull;
     p.xm_launch = f.xmean && rbfull;
     // ... and what else such a run knows before its first launch: it resamples systematically and wants no weighted means — the launches
-    // that store no ancestors are then k_resprop<..., LEAN>, which holds neither the stratified counts (a Philox block per threshold) nor
-    // the means and tests neither (the same bits; LinGauss with one or two states, every other shape keeps the form above).  The field
-    // follows skip_w_run, not skip_anc_run, so that two plans which differ only in LLPF_SKIP_ANC differ only in skip_anc_run; the launches
-    // take the form where both hold (lean_form()).  LLPF_LEAN=0: the kernel with the run-time tests.
-    p.lean_run = p.skip_w_run && f.strategy == LLPF_RESAMPLE_SYSTEMATIC && !p.want_xm && s.lean != 0;
+    // that store no ancestors are then k_resprop<..., RUN_LEAN>, which holds neither the stratified counts (a Philox block per threshold) nor
+    // the means and tests neither (the same bits).  The kernel exists for the linear-Gaussian model with one or two states; every other
+    // shape keeps the level below.  LLPF_LEAN=0: the kernel with the run-time tests.
+    const bool lean = skip_anc && f.strategy == LLPF_RESAMPLE_SYSTEMATIC && !p.want_xm && f.model_id == LLPF_MODEL_LINEAR_GAUSSIAN && f.nx <= 2 && s.lean != 0;
+    p.level = lean ? RUN_LEAN : skip_anc ? RUN_SKIP_ANC : skip_w ? RUN_SKIP_W : RUN_STORES;
     // The run ends in the buffer it began in (a handle's weights do not move between runs: one captured graph per shape, not two that
     // alternate): T - 1 steps have a weighting phase; when that number is odd, step 0 keeps the stored form and weights in place.
     p.k_pp0 = (p.lazy_run && ((f.T - 1) & 1)) ? 1 : 0;
@@ -184,6 +189,11 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
     // a captured graph holds no host round trip: not with history (row copies, or staging that is freed), not while events are collected
     p.use_graph = !f.hist && !f.profiling && !s.debug_timing && s.graph != 0;
     return p;
+}
+// The level of one fused launch of the run: the exact redo of a failed bound test (`fast` false) reads stored weights and keeps the
+// storing form; the run's last launch (`weight` false: no weighting phase) forms no weights and leaves the ancestors the run ends with.
+static inline int launch_level(const RunForm& p, bool fast, bool weight) {
+    return !fast ? RUN_STORES : !weight ? std::min<int>(p.level, RUN_SKIP_W) : p.level;
 }
 
 // ---- the host-side state of a run's timesteps (the device may have to be re-driven from a step whose bound test failed) ----

@@ -7,6 +7,7 @@
 #define LLPF_HORNER_C(c) "v"(c)
 #endif
 #include "engine.hpp"
+#include "host/run_plan.hpp"      // RunLevel
 
 namespace llpf {
 
@@ -41,22 +42,18 @@ static hipError_t launch_resprop_t(const BankDev& b, const ResArgs& a, const Ste
     if (st.aux && one) hipLaunchKernelGGL((k_resprop<NoModel<NX>, NX, 1, true, true, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
     else if (st.aux) hipLaunchKernelGGL((k_resprop<NoModel<NX>, NX, 1, true, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
     else if (weight && st.accumulate && one) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
-    else if (weight && st.accumulate && a.skip_w) {      // ResArgs::skip_w: the weights are not stored (kernels/resprop.hpp, SKIPW)
-        if constexpr (!Model::RB) {
-            // ResArgs::skip_anc: nor are the ancestors of the rounds with an owner (SKIPA); ResArgs::lean: systematic resampling and no weighted
-            // means, compiled in (LEAN) — the shapes a run takes fused by default; every other shape keeps the form with the run-time tests
-            if constexpr (std::is_same<Model, LinGauss<NX, NY>>::value && NX <= 2) {
-                if (a.skip_anc && a.lean) {
-                    hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
-                    return hipGetLastError();
-                }
-            }
-            if (a.skip_anc) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
-            else hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
+    else if (weight && st.accumulate) {
+        // ResArgs::level: what the launch leaves out (kernels/resprop.hpp).  The Rao-Blackwellized model has only level 0 (its weighting also
+        // updates the linear substate), level 3 exists for LinGauss with one or two states: the plan asks for neither elsewhere
+        constexpr bool skips = !Model::RB, lean = std::is_same<Model, LinGauss<NX, NY>>::value && NX <= 2;
+        switch (a.level) {
+            case RUN_STORES: hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); break;
+            case RUN_SKIP_W: if constexpr (skips) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_SKIP_W>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
+            case RUN_SKIP_ANC: if constexpr (skips) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_SKIP_ANC>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
+            case RUN_LEAN: if constexpr (lean) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_LEAN>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
+            default: return hipErrorInvalidValue;
         }
-        else return hipErrorInvalidValue;
     }
-    else if (weight && st.accumulate) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st);
     else return launch_resprop_split(b, a, st, weight, s);      // the split-schedule forms live in k_resprop_split.hip
     return hipGetLastError();
 }

@@ -276,7 +276,7 @@ __global__ void k_fb_clear(BankDev b, int slot, int mode) {
         for (int i = threadIdx.x; i < 7 * NSHARD * ACC_STRIDE; i += blockDim.x)
             acc[(size_t)words[i / (NSHARD * ACC_STRIDE)] * NSHARD * ACC_STRIDE + (i % (NSHARD * ACC_STRIDE))] = 0;
     } else if (mode == 2) {
-        // a run whose fused launches store no weights (ResArgs::skip_w): the step in front of the failed head resampled, so the prior of the
+        // a run whose fused launches store no weights (ResArgs::level >= 1): the step in front of the failed head resampled, so the prior of the
         // weights the host is about to form again (k_step<MODE_WEIGHT>) is log(1/N); the redo's head clears `uniform` again
         if (threadIdx.x == 0) { sc->uniform = 1; sc->wconst = b.log1N; }
     } else if (threadIdx.x == 0) {

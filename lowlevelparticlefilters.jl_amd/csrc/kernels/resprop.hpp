@@ -47,7 +47,7 @@ template <class T> DEV void st_off(T* base, uint32_t byte_off, T v) {
 #endif
 #define LLPF_STCOH ((LLPF_WT && !LLPF_RB_PLAIN_ST) ? STP : COH)
 #define LLPF_STCOH0 ((LLPF_WT && !LLPF_RB_PLAIN_ST) ? LLPF_RESPROP_ST : 0)
-// STW = false: the weights formed here are not stored (k_resprop<..., SKIPW>: nobody reads them)
+// STW = false: the weights formed here are not stored (k_resprop<..., LEVEL >= 1>: nobody reads them)
 template <class Model, int NX, int NY, bool WEIGHT, bool COH = false, bool LTAB = false, bool STW = true>
 struct PropCtx {
     const BankDev& b;
@@ -180,11 +180,13 @@ static_assert(TILE == 1024, "TileSum assumes 1024-particle tiles");
 #define LLPF_HOT_ARGS(b, a) (b).acc, (b).tileq, (b).scal, (b).bank_flag, (b).quanta, (b).F, (b).P2, (a).parity
 
 // ONE: the filter is a single tile (launched only when P2 == 1): a failed bound test is redone inside this kernel
-// SKIPW: a run at resample_threshold 1 (host/run.hpp: every step resamples, so the prior of every weight is log(1/N) and the next head
+// LEVEL: what the launch leaves out, a RunLevel (host/run_plan.hpp: planned by make_run_plan, per launch by launch_level).  Each level is
+// the one below it and one thing more; SKIPW, SKIPA and LEAN below are LEVEL >= 1, >= 2 and >= 3.
+// SKIPW: a run at resample_threshold 1 (every step resamples, so the prior of every weight is log(1/N) and the next head
 // consumes only the integer sums and the quanta): the weights formed here are not stored — 8 of the 44 bytes an output writes, one of its
 // five stores.  The only reader of those weights, the exact redo of a failed bound test, has the host form them again first, from the
 // states in memory.  A head that would not resample (no quanta at all) asks for that redo instead of reading the weights.
-// SKIPA (only with SKIPW, and never a run's last launch, which is WEIGHT = false): the rounds with an owner store no ancestor either — 4 of
+// SKIPA (never a run's last launch, which is WEIGHT = false): the rounds with an owner store no ancestor either — 4 of
 // the remaining 36 bytes, one of the four stores.  The next launch of the run overwrites all of them unread, with one exception: its
 // rounds of [c_end, M) read the previous ancestor of their own output, and only output M - 1 can be such an output (its threshold is the
 // only one that can reach bins[N]: tests/test_stale_corner.py).  That entry is kept current: stored once behind the loop by the block
@@ -192,15 +194,16 @@ static_assert(TILE == 1024, "TileSum assumes 1024-particle tiles");
 // What SKIPW says about the run is compiled in: past the head every launch resamples (threshold 1: decide_resample returns 1, and a head
 // whose quanta sum to zero has asked for the redo, NO_TOT0), so there is no arm for a step that does not — it could not run anyway, the
 // weights it would read were never stored — and no sum of squares (host/fallback.hpp: need_e2 is 0 at threshold 1).
-// LEAN (only with SKIPW and SKIPA; host/run_plan.hpp: lean_run): the run also resamples systematically and wants no weighted means — only
+// LEAN: the run also resamples systematically and wants no weighted means — only
 // res_counts<LLPF_RESAMPLE_SYSTEMATIC> is instantiated, and there is no xm[], no block_store_xm and no test of either.  The same
 // arithmetic, counters, stores and visiting order: the form only drops tests and arms that such a run never takes.
-template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, bool SKIPW = false, bool SKIPA = false, bool LEAN = false>
+template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, int LEVEL = 0>
 // amdgpu_waves_per_eu(4): the ~3.8 blocks per CU of a 10^6-particle filter must be resident together (<= 128 VGPRs); the
 // larger state dimensions would spill under that cap and keep the compiler's choice; the Rao-Blackwellized propagate uses
 // 130-156 VGPRs and is pinned to three waves per SIMD (<= 168): twice in this round an unrelated change pushed it past 170 and
 // cost it 28 %
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model::RB || (model_lean<Model>::value && LLPF_RBX_W4)) && NX <= 2 && NY <= 2 && !ONE) ? 4 : (Model::RB ? 3 : 1)))) void k_resprop(LLPF_HOT_PARAMS, BankDev b_in, const ModelD* __restrict__ models, ResArgs a_in, StepArgs st) {
+    constexpr bool SKIPW = LEVEL >= 1, SKIPA = LEVEL >= 2, LEAN = LEVEL >= 3;
     // what the head's first loads are addressed with arrives in SGPRs with the wave (kernarg preload) instead of through a
     // scalar load of the argument block: one memory round trip less at the start of every launch
     BankDev b = b_in;
@@ -271,9 +274,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
         }
     };
     static_assert(!SKIPW || (WEIGHT && ACC && !AUX && !ONE && !Model::RB), "the form without the weight store: merged schedule, several tiles");
-    static_assert(!SKIPA || SKIPW, "the form without the ancestor store exists only where the weights are not stored either");
-    static_assert(!LEAN || (SKIPW && SKIPA), "the lean form exists only where neither weights nor ancestors are stored");
-    // SKIPW means that host/run_plan.hpp saw resample_threshold == 1 (RunForm::skip_w_run): every step of the run resamples, none needs E2
+    // SKIPW means that host/run_plan.hpp saw resample_threshold == 1 (RunForm::level): every step of the run resamples, none needs E2
     constexpr bool ALWAYS_RES = SKIPW;
     static_assert(!ALWAYS_RES || (WEIGHT && ACC && !AUX), "a launch that always resamples: the merged schedule's weighting form, never forced");
     const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);

@@ -12,16 +12,15 @@ import pytest
 from llpf_amd import _capi, _structs as S
 import oracle_binding as ob
 from gpu_common import assert_state_equal, assert_steps_equal
-from test_gpu_skip_weight_store import _bits, _c2, _oracle, _set_form
+from thr1_common import OWN_CAP, bits, oracle, peaked_workload, set_form, workload
 
 pytestmark = pytest.mark.gpu
 
 T = 12
-OWN_CAP = 2048          # entries of the owner table (csrc/engine.hpp); beyond it a round finds its source by descent
 
 
 def _assert_equal(rg, g, ro, o, what):
-    assert _bits(rg["ll"]) == _bits(ro["ll"]), "%s: ll %r against %r" % (what, rg["ll"], ro["ll"])
+    assert bits(rg["ll"]) == bits(ro["ll"]), "%s: ll %r against %r" % (what, rg["ll"], ro["ll"])
     assert_steps_equal(rg["ll_steps"], ro["ll_steps"], what + " ll_steps", resamples=(g.resample_count(), o.resample_count()))
     assert g.resample_count() == o.resample_count(), what
     assert_state_equal(g.particles(), o.particles(), what + " particles")
@@ -35,9 +34,9 @@ _reference = {}
 def _c2_reference(N, thr):
     """the oracle's run of the C2 system, computed once per (N, threshold) and left unchanged"""
     if (N, thr) not in _reference:
-        cfg, U, Y = _c2(N, T, thr)
+        cfg, U, Y = workload(N, T, thr=thr)
         try:
-            o = _oracle(cfg, 16)
+            o = oracle(cfg, 16)
             ro = o.run(U, Y, 1.0, ll_steps=True)
         finally:
             ob.set_threads(1)
@@ -49,7 +48,7 @@ def _c2_reference(N, thr):
 @pytest.mark.parametrize("N", [1025, 2049, 70001])
 def test_merged_runs_equal_the_oracle(N, form, thr, monkeypatch):
     cfg, U, Y, o, ro = _c2_reference(N, thr)
-    _set_form(monkeypatch, form)
+    set_form(monkeypatch, "LLPF_SKIP_W", form)
     g = _capi.FilterHandle(cfg)
     g.reset()
     rg = g.run(U, Y, 1.0, ll_steps=True)
@@ -66,20 +65,11 @@ def test_one_source_owns_more_outputs_than_the_owner_table_holds(monkeypatch):
     """Measurement noise of standard deviation 1e-4 on the C2 system: the particle nearest the measurement takes most of the weight, its
     block runs many rounds, looks sources up by descent beyond the owner table and flushes its tile sums to the global ones (the first
     step gives all 5000 outputs to one source; one later step fails its bound test and is redone in exact form)."""
-    import models as M
     N = 5000
-    base = M.lg_test_model()
-    nx, nu, ny = base.nx, base.nu, base.ny
-    A = np.array(base.A[:nx * nx]).reshape(nx, nx)
-    B = np.array(base.B[:nx * nu]).reshape(nx, nu)
-    Cm = np.array(base.C[:ny * nx]).reshape(ny, nx)
-    g0 = S.make_gaussian
-    model = S.make_lg_model(A, B, Cm, g0(np.zeros(2), 0.1 ** 2), g0(np.zeros(1), np.full(1, 1e-8)), g0(np.array([0.3, -0.5]), 4.0), 1.0)
-    _, U, Y = M.simulate_lg(model, T, seed=1)
-    cfg = S.make_config(model, N, S.PARTICLE_FILTER, S.RESAMPLE_SYSTEMATIC, 1.0, 1000, 0)
+    cfg, U, Y = peaked_workload(N, T)
     heaviest = []
     for k in range(1, T + 1):          # the ancestors of step k are what a run of k steps leaves
-        o = _oracle(cfg)
+        o = oracle(cfg)
         ro = o.run(U[:k], Y[:k], 1.0, ll_steps=True)
         heaviest.append(int(np.bincount(o.ancestors()).max()))
     assert sum(h > OWN_CAP for h in heaviest) >= 3, "sources own at most %r outputs" % (heaviest,)
@@ -97,7 +87,7 @@ def test_rao_blackwellized_form(thr):
     import bench
     model, U, Y, kind, _, _ = bench.build_workload("rbpf", 2049, T)
     cfg = S.make_config(model, 2049, kind, S.RESAMPLE_SYSTEMATIC, thr, 1000, 0)
-    o = _oracle(cfg)
+    o = oracle(cfg)
     ro = o.run(U, Y, 1.0, ll_steps=True)
     g = _capi.FilterHandle(cfg)
     g.reset()
@@ -109,8 +99,8 @@ def test_rao_blackwellized_form(thr):
 
 def test_auxiliary_form():
     """the auxiliary filter's loglik loop on the C2 system: its second half is the fused kernel with the look-ahead weights as priors"""
-    cfg, U, Y = _c2(2049, T, 0.1)
-    o = _oracle(cfg)
+    cfg, U, Y = workload(2049, T, thr=0.1)
+    o = oracle(cfg)
     ro = o.run_aux(U, Y, 1, ll_steps=True)
     g = _capi.FilterHandle(cfg)
     g.reset()

@@ -1,4 +1,4 @@
-"""The fused timestep at resample_threshold 1 without its weight store (host/run.hpp: skip_w_run; kernels/resprop.hpp: SKIPW).
+"""The fused timestep at resample_threshold 1 without its weight store (host/run_plan.hpp: RUN_SKIP_W; kernels/resprop.hpp: SKIPW).
 
 Every step of such a run resamples, so the weights a fused launch forms are read by nobody: the run's fused launches do not store
 them, and the exact redo of a failed bound test has them formed again first.  LLPF_SKIP_W=0 pins the storing form.  Everything here
@@ -6,42 +6,18 @@ is bit for bit (uint64 views, no tolerance): both forms against the device-order
 import numpy as np
 import pytest
 
-from llpf_amd import _capi, _structs as S
+from llpf_amd import _capi
 import oracle_binding as ob
 from gpu_common import assert_state_equal, assert_steps_equal
+from thr1_common import FORMS, assert_form, bits, oracle, outlier_that_fails_exactly_step, set_form, workload
 
 pytestmark = pytest.mark.gpu
 
-FORMS = ("default", "0")       # LLPF_SKIP_W unset / LLPF_SKIP_W=0
-
-
-def _c2(N, T, thr=1.0):
-    """the system of the headline workload (bench.build_workload("lg"): linear-Gaussian, nx = 2), seeded as bench.py seeds it"""
-    import bench
-    model, U, Y, kind, _, _ = bench.build_workload("lg", N, T)
-    return S.make_config(model, N, kind, S.RESAMPLE_SYSTEMATIC, thr, 1000, 0), U, Y
-
-
-def _set_form(monkeypatch, form):
-    if form == "default":
-        monkeypatch.delenv("LLPF_SKIP_W", raising=False)
-    else:
-        monkeypatch.setenv("LLPF_SKIP_W", form)
-
-
-def _oracle(cfg, threads=1):
-    ob.set_threads(threads)
-    o = ob.OracleFilter(cfg, ob.ORDER_DEVICE)
-    o.reset()
-    return o
-
-
-def _bits(v):
-    return np.float64(v).view(np.uint64)
+SWITCH = "LLPF_SKIP_W"
 
 
 def _assert_run_equal(rg, g, ro, o, what):
-    assert _bits(rg["ll"]) == _bits(ro["ll"]), "%s: ll %r against %r" % (what, rg["ll"], ro["ll"])
+    assert bits(rg["ll"]) == bits(ro["ll"]), "%s: ll %r against %r" % (what, rg["ll"], ro["ll"])
     assert_steps_equal(rg["ll_steps"], ro["ll_steps"], what + " ll_steps", resamples=(g.resample_count(), o.resample_count()))
     assert g.resample_count() == o.resample_count(), what
     assert_state_equal(g.particles(), o.particles(), what + " particles")
@@ -51,66 +27,43 @@ def _assert_run_equal(rg, g, ro, o, what):
 @pytest.mark.parametrize("N", [1025, 70001, 10**6])       # one tile + 1, ragged, the headline size
 def test_plain_runs_equal_the_oracle_and_the_storing_form(N, monkeypatch):
     T = 50
-    cfg, U, Y = _c2(N, T)
+    cfg, U, Y = workload(N, T)
     try:
-        o = _oracle(cfg, 16)
+        o = oracle(cfg, 16)
         ro = o.run(U, Y, 1.0, ll_steps=True)
     finally:
         ob.set_threads(1)
     got = {}
     for form in FORMS:
-        _set_form(monkeypatch, form)
+        set_form(monkeypatch, SWITCH, form)
         g = _capi.FilterHandle(cfg)
         g.reset()
         rg = g.run(U, Y, 1.0, ll_steps=True)
-        assert g.last_run_form()["weights_not_stored"] == (form == "default")
+        assert_form(g, SWITCH, form)
         assert g.last_run_stats()["fused_launches"] == T
         _assert_run_equal(rg, g, ro, o, "LLPF_SKIP_W %s" % form)
         got[form] = (rg["ll"], rg["ll_steps"].copy(), g.particles(), g.weights())
     a, b = got["default"], got["0"]
-    assert _bits(a[0]) == _bits(b[0])
+    assert bits(a[0]) == bits(b[0])
     for x, y, what in zip(a[1:], b[1:], ("ll_steps", "particles", "weights()")):
         assert_state_equal(x, y, "the two forms: " + what)
-
-
-def _outlier_that_fails_exactly_step(cfg, U, Y, kf):
-    """Measurements with an outlier at step kf, chosen on the CPU with the device-order oracle so that the bound test of exactly that
-    step fails (S < 2^-10): no exact step without the outlier, none in the steps before kf, one in the whole run."""
-    o = _oracle(cfg)
-    o.run(U, Y, 1.0)
-    assert o.exact_steps() == 0, "the plain data already fail a bound test"
-    for amp in (6.0, 8.0, 10.0, 12.0, 16.0, 20.0, 30.0):
-        Yo = Y.copy()
-        Yo[kf] += amp
-        o = _oracle(cfg)
-        o.run(U[:kf], Yo[:kf], 1.0)
-        before = o.exact_steps()
-        o = _oracle(cfg)
-        o.run(U[:kf + 1], Yo[:kf + 1], 1.0)
-        upto = o.exact_steps()
-        o = _oracle(cfg)
-        o.run(U, Yo, 1.0)
-        if (before, upto, o.exact_steps()) == (0, 1, 1):
-            return Yo
-    raise AssertionError("no outlier amplitude makes exactly step %d fail" % kf)
 
 
 @pytest.mark.parametrize("N", [1025, 70001])
 def test_failed_bound_test_in_mid_run(N, monkeypatch):
     T, kf = 60, 23
-    cfg, U, Y = _c2(N, T)
-    Yo = _outlier_that_fails_exactly_step(cfg, U, Y, kf)
-    o = _oracle(cfg)
+    cfg, U, Y = workload(N, T)
+    Yo = outlier_that_fails_exactly_step(cfg, U, Y, kf)
+    o = oracle(cfg)
     ro = o.run(U, Yo, 1.0, ll_steps=True)
     assert o.exact_steps() == 1
     got = {}
     for form in FORMS:
-        _set_form(monkeypatch, form)
+        set_form(monkeypatch, SWITCH, form)
         g = _capi.FilterHandle(cfg)
         g.reset()
         rg = g.run(U, Yo, 1.0, ll_steps=True)
-        f = g.last_run_form()
-        assert f["weights_not_stored"] == (form == "default")
+        f = assert_form(g, SWITCH, form)
         assert f["exact_redos"] == 1, "the exact redo was not taken exactly once: %r" % (f,)
         _assert_run_equal(rg, g, ro, o, "LLPF_SKIP_W %s" % form)
         got[form] = (rg["ll_steps"].copy(), g.particles(), g.weights())
@@ -163,8 +116,8 @@ def _after_the_run_trace(h, U, Y, Yo, engine):
 
 def test_after_the_run(monkeypatch):
     N, T, kf = 70001, 40, 17
-    cfg, U, Y = _c2(N, T)
-    o = _oracle(cfg)
+    cfg, U, Y = workload(N, T)
+    o = oracle(cfg)
     o.run(U, Y, 1.0)
     assert o.exact_steps() == 0
     Yo = Y.copy()
@@ -174,11 +127,11 @@ def test_after_the_run(monkeypatch):
 
     traces = {}
     for form in FORMS:
-        _set_form(monkeypatch, form)
+        set_form(monkeypatch, SWITCH, form)
         g = _capi.FilterHandle(cfg)
         traces[form], redos = _after_the_run_trace(g, U, Y, Yo, True)
         assert redos == n_exact, "exact redos: %d against the oracle's %d exact steps" % (redos, n_exact)
-        assert g.last_run_form()["weights_not_stored"] == (form == "default")
+        assert_form(g, SWITCH, form)
         for (tag, a), (_, b) in zip(traces[form], want):
             assert_state_equal(a, b, "LLPF_SKIP_W %s, %s" % (form, tag))
     for (tag, a), (_, b) in zip(traces["default"], traces["0"]):
@@ -188,12 +141,12 @@ def test_after_the_run(monkeypatch):
 @pytest.mark.parametrize("N,thr", [(70001, 0.1), (1000, 1.0)])
 def test_form_is_not_selected_below_threshold_one_or_for_one_tile(N, thr, monkeypatch):
     monkeypatch.delenv("LLPF_SKIP_W", raising=False)
-    cfg, U, Y = _c2(N, 20, thr)
+    cfg, U, Y = workload(N, 20, thr=thr)
     g = _capi.FilterHandle(cfg)
     g.reset()
     rg = g.run(U, Y, 1.0, ll_steps=True)
     assert g.last_run_stats()["fused_launches"] > 0
     assert not g.last_run_form()["weights_not_stored"]
-    o = _oracle(cfg)
+    o = oracle(cfg)
     ro = o.run(U, Y, 1.0, ll_steps=True)
     _assert_run_equal(rg, g, ro, o, "N = %d, threshold %g" % (N, thr))
