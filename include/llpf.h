@@ -240,7 +240,11 @@ int  llpf_rb_get_linear_state(llpf_filter* f, double* xl, double* R);
  * The time-T indices are j = resample(strategy, wef[:,T], M) (:123); for t = T-1 .. 1 and every trajectory m:
  * wb[n] = wf[n,t] + logpdf(df, xb[m,t+1] - f(xf[n,t],u[t],p,(t-1)Ts)), i = draw_one_categorical(wb)
  * (src/resample.jl:128-152), xb[m,t] = xf[i,t] — O(M N T) density evaluations, one block per trajectory.
- * xb is [T*M*nx] (time-major), idx (optional) [T*M] the 0-based particle index behind every sample.  M <= N. */
+ * xb is [T*M*nx] (time-major), idx (optional) [T*M] the 0-based particle index behind every sample.  M <= N.
+ * LLPF_ERR_ARG, with the reason in llpf_last_error(), for: a Rao-Blackwellized model; a run-time compiled model that forms its own
+ * process noise (LLPF_TRAIT_NOISE: its transition density is not logpdf(dynamics_density, .), so the backward weights would be those of a
+ * model it is not — a measurement likelihood of the model's own, LLPF_TRAIT_LOGLIK, does not enter the backward pass and is fine); a
+ * value of xf that is not finite; NaN or +inf in wf (-inf, the log of a weight that is zero, is fine). */
 int  llpf_smooth(llpf_filter* f, int64_t M, const double* U, int64_t T, const double* xf, const double* wf,
                  const double* wef, double* xb, int64_t* idx);
 
@@ -282,8 +286,9 @@ int  llpf_model_compile(const char* device_src, int32_t nx, int32_t ny, int32_t*
  *       uniforms uu in [0,1) of the particle's own Philox streams; replaces out = fx + rand(dynamics_density).  The reference's
  *       AdvancedParticleFilter hands the noise to the user the same way — dynamics(x, u, p, t, noise = true), src/PFtypes.jl:242-259,
  *       test/runtests.jl:553-599 — and its ParticleFilter draws from ANY dynamics_density (rand!(rng, d, noise), src/PFtypes.jl:122-139).
- *       (dynamics_density is then unused by the propagate but must still be a valid Gaussian; the FFBS smoother, whose backward weights
- *       are logpdf(dynamics_density, .), and the auxiliary filter over a LLPF_PARTICLE_FILTER, whose add_noise! draws from it, keep using it.)
+ *       (dynamics_density is then unused by the propagate but must still be a valid Gaussian: the auxiliary filter over a
+ *       LLPF_PARTICLE_FILTER, whose add_noise! draws from it, keeps using it.  The FFBS smoother, whose backward weights are
+ *       logpdf(dynamics_density, .), has no transition density to weight with and refuses such a model: llpf_smooth.)
  *   DEV void initial(const double* xi, const double* uu, double* out) const;
  *       one draw of the initial density: x_i = rand(rng, initial_density) of reset! / the constructor (src/filtering.jl:4-14, src/PFtypes.jl:66).
  * llpf_model_traits reports which optional members a compiled model has (bit set of LLPF_TRAIT_*), so that a binding can refuse a

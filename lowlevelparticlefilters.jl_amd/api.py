@@ -198,7 +198,8 @@ class UserNoise:
     """dynamics_density of a filter whose model adds its own process noise: the `noise(x, fx, xi, uu, out)` member of the paired
     UserDynamics snippet — the reference's AdvancedParticleFilter contract, dynamics(x, u, p, t, noise = true) (src/PFtypes.jl:242-259),
     or a ParticleFilter with a dynamics_density that is not Gaussian (rand!(rng, d, noise), :122-139).  `gaussian`: the MvNormal the
-    FFBS smoother and the auxiliary filter's add_noise! keep using (default: standard normal)."""
+    auxiliary filter's add_noise! keeps using (default: standard normal).  The FFBS smoother weights with logpdf(dynamics_density, .),
+    which such a model does not have: smooth(pf, ...) raises."""
 
     def __init__(self, gaussian=None, host=None):
         self.gaussian, self.host = gaussian, host
@@ -1389,6 +1390,9 @@ def smooth(pf, *args):
         raise TypeError("the ensemble Kalman filter has no smoother")
     if isinstance(pf, ExtendedKalmanFilter):
         raise TypeError("the extended Kalman filter has no smoother yet: smooth an UnscentedKalmanFilter of the same model")
+    if isinstance(getattr(pf, "dynamics_density", None), UserNoise):      # before the forward pass: llpf_smooth would refuse after it
+        raise TypeError("smooth is not defined for a model with process noise of its own (UserNoise): the backward weights are "
+                        "logpdf(dynamics_density, .), and the model's transition density is not that Gaussian")
     if len(args) >= 7:
         xf, wf, wef, ll, M, u, y = args[:7]
     else:

@@ -7,11 +7,21 @@ static int bank_smooth(Bank& b, int64_t M, const double* U, int64_t T, const dou
     CHK(use_device(b));
     if (b.F != 1) return fail(LLPF_ERR_ARG, "smooth needs a single filter");
     if (is_rb(b) || is_rbfull(b)) return fail(LLPF_ERR_ARG, "smooth is not defined for the Rao-Blackwellized model");
+    // the backward weights are logpdf(dynamics_density, .): a model that forms its own process noise (UserModel::noise) has no such
+    // density — its dynamics_density is a placeholder — and the draws would follow a transition the model does not have
+    if (b.cfg.model.model_id >= LLPF_MODEL_USER_BASE && (jit_model_traits(b.cfg.model.model_id) & LLPF_TRAIT_NOISE) > 0)
+        return fail(LLPF_ERR_ARG, "smooth is not defined for a model with process noise of its own (noise): its transition density is not the Gaussian dynamics_density");
     if (M < 1 || M > b.N) return fail(LLPF_ERR_ARG, "M must be in 1..N (reference src/smoothing.jl:121)");
     if (T < 1 || !xf || !wf || !wef || !xb) return fail(LLPF_ERR_ARG, "bad arguments");
     if (b.nu > 0 && !U) return fail(LLPF_ERR_ARG, "U is null");
     const int64_t N = b.N;
     const int nx = b.nx;
+    // max(wb) is a chain of a > b ? a : b: with a NaN in it the result depends on the order of the reduction (strided over the block
+    // here, serial in the oracle), and every quantum after it is garbage.  -inf log-weights (a likelihood of bounded support) are fine.
+    for (size_t i = 0; i < (size_t)T * N * nx; ++i)
+        if (!std::isfinite(xf[i])) return fail(LLPF_ERR_ARG, "smooth: xf holds a value that is not finite");
+    for (size_t i = 0; i < (size_t)T * N; ++i)
+        if (!(wf[i] < LLPF_INF)) return fail(LLPF_ERR_ARG, "smooth: wf holds NaN or +inf");
     // j = resample(pf.resampling_strategy, wef[:,T], M) with the Philox stream SMOOTH_INIT under the filter's key
     std::vector<FilterScal> h;
     CHK(scal_download(b, h));

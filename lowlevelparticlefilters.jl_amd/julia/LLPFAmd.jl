@@ -283,8 +283,9 @@ UserLikelihood() = UserLikelihood(nothing)
 
 `dynamics_density` of a filter whose model adds its own process noise: the `noise(x, fx, xi, uu, out)` member of the paired `UserDynamics`
 snippet — the reference's `AdvancedParticleFilter` contract, `dynamics(x, u, p, t, noise = true)` (src/PFtypes.jl:242-259), or a
-`ParticleFilter` whose `dynamics_density` is not Gaussian (`rand!(rng, d, noise)`, :122-139).  `gaussian`: the density the FFBS smoother
-and the auxiliary filter's `add_noise!` keep using (default: standard normal)."""
+`ParticleFilter` whose `dynamics_density` is not Gaussian (`rand!(rng, d, noise)`, :122-139).  `gaussian`: the density the auxiliary
+filter's `add_noise!` keeps using (default: standard normal).  The FFBS smoother weights with `logpdf(dynamics_density, .)`, which such a
+model does not have: `smooth(pf, ...)` throws (`llpf_smooth` returns `LLPF_ERR_ARG`)."""
 struct UserNoise
     gaussian
     host

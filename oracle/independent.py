@@ -18,6 +18,9 @@ numpy exp / log, Python loops over particles.  It follows the reference line by 
                        Gaussian logpdf     src/utils.jl:252-257;  rk4 src/utils.jl:220-237;  quad-tank examples/example_quadtank.jl:8-35
   RBPF, !singleR       reset! src/rbpf.jl:146-160, predict! :163-232, correct! :235-283 with
                        correct!(kf, ...) src/filtering.jl:100-128
+  FFBS smoother        one backward step of smooth, src/smoothing.jl:128-141, draw_one_categorical src/resample.jl:128-152: the
+                       distribution of every draw in numpy.longdouble (smoother_backward_step) and how far an fp64 implementation
+                       may be from it (backward_step_slack), at the end of this file
 
 The reference's own random streams (Xoshiro randn, global rand()) are unpinned by its tests; the normals and uniforms are
 INPUTS here (callables `normals(step, n, nd)` / `uniforms(step, n)`), supplied by the tests from the Philox generator that the
@@ -130,7 +133,8 @@ class LinearModel:
     def f(self, x, u, t):
         out = x @ self.A.T
         if self.B.shape[1]:
-            out = out + self.B @ np.asarray(u, dtype=np.float64).reshape(-1)
+            u = np.asarray(u)
+            out = out + self.B @ (u if u.dtype == np.longdouble else u.astype(np.float64)).reshape(-1)
         return out
 
     def g(self, x, u, t):
@@ -359,3 +363,127 @@ class RBPF:
             self.predict(u, t, normals(step0 + k, self.N, self.xn.shape[1]), uniforms(step0 + k, self.N))
             nres += int(self.resampled)
         return ll_steps, nres
+
+
+# ---- FFBS particle smoother: one backward step (src/smoothing.jl:128-141, draw_one_categorical src/resample.jl:128-152) -------------
+# For every trajectory m the reference draws i ~ Categorical(softmax_n(wb[m, n])), wb[m, n] = wf[n, t] + logpdf(df, xb[m, t+1] -
+# f(xf[n, t], u[t], p, t Ts)), by the inverse CDF of one uniform.  Restated here in numpy.longdouble (64-bit significand on x86: 2^11
+# times finer than anything the engine or the C oracle compute), from the fp64 history and the model objects above; nothing is shared
+# with either but the uniform.  The check is teacher forced: xb[t+1] is what the implementation under test produced itself.
+LD = np.longdouble
+LOG2PI_LD = np.log(LD(2) * LD("3.14159265358979323846264338327950288"))
+U53 = 2.0 ** -53                 # unit roundoff of fp64
+
+
+def _chol_ld(S):
+    """lower Cholesky factor of S in long double (numpy.linalg has no long double)"""
+    k = S.shape[0]
+    L = np.zeros((k, k), dtype=LD)
+    for i in range(k):
+        for j in range(i + 1):
+            s = LD(S[i, j]) - np.sum(L[i, :j] * L[j, :j])
+            L[i, j] = np.sqrt(s) if i == j else s / L[j, j]
+    return L
+
+
+def gaussian_logpdf_ld(df, v):
+    """Gaussian.logpdf of v [..., k] in long double: -(k log 2 pi + logdet Sigma) / 2 - v' Sigma^-1 v / 2 through the long-double Cholesky
+    factor.  Returns (logpdf, g) with g = Sigma^-1 (v - mu), the gradient of the quadratic form / 2 (what backward_step_slack needs)."""
+    k = df.mu.size
+    L = _chol_ld(df.Sigma)
+    d = np.asarray(v, dtype=LD) - df.mu.astype(LD)
+    z = np.empty_like(d)
+    for i in range(k):                                   # L z = d
+        z[..., i] = (d[..., i] - np.sum(z[..., :i] * L[i, :i], axis=-1)) / L[i, i]
+    g = np.empty_like(d)
+    for i in range(k - 1, -1, -1):                       # L' g = z
+        g[..., i] = (z[..., i] - np.sum(g[..., i + 1:] * L[i + 1:, i], axis=-1)) / L[i, i]
+    logdet = 2 * np.sum(np.log(np.diag(L)))
+    return -(k * LOG2PI_LD + logdet) / 2 - np.sum(z * z, axis=-1) / 2, g
+
+
+def smoother_backward_step(xf_t, wf_t, model, df, u_t, t, xb_next, logpdf=gaussian_logpdf_ld):
+    """The distribution the backward draw at time index t samples from, for every trajectory: xf_t [N, nx], wf_t [N] the filter's
+    particles and log-weights, model (LinearModel / QuadTank) and df (Gaussian) the transition, u_t the input, t = index * Ts the time the
+    dynamics are evaluated at, xb_next [M, nx] the smoothed samples of index t + 1.
+    Returns a dict: cdf [M, N] (long double, cdf[:, -1] = 1), p [M, N] the probabilities, and what backward_step_slack takes."""
+    x = np.asarray(xf_t, dtype=LD)
+    fx = model.f(x, None if u_t is None else np.asarray(u_t, dtype=LD), LD(t))                  # [N, nx], long double throughout
+    xq = np.asarray(xb_next, dtype=LD)
+    lp, g = logpdf(df, xq[:, None, :] - fx[None, :, :])                                          # [M, N], [M, N, nx]
+    wb = np.asarray(wf_t, dtype=LD)[None, :] + lp
+    mx = np.max(wb, axis=1, keepdims=True)
+    e = np.exp(wb - mx)
+    tot = np.sum(e, axis=1, keepdims=True)
+    cdf = np.cumsum(e, axis=1) / tot
+    cdf[:, -1] = 1
+    return dict(cdf=cdf, p=e / tot, wb=wb, mx=mx, lp=lp, g=g, fx=fx, x=x, xq=xq, u=u_t, wf=np.asarray(wf_t, dtype=LD))
+
+
+def qbits(N):
+    """K = 62 - ceil(log2 N): the engine adds N quanta floor(e 2^K), e <= 1, in 64 bits"""
+    return 62 - int(math.ceil(math.log2(N))) if N > 1 else 62
+
+
+def backward_step_slack(step, model, df, fixed_point=True):
+    """delta [M]: how far the CDF an fp64 implementation draws from can lie from step["cdf"].  Derived, not fitted:
+
+      1. quanta.  The engine replaces e_n = exp(wb_n - max wb) by floor(e_n 2^K) 2^-K, K = qbits(N): each e_n shrinks by less than
+         2^-K, the largest e_n is exactly 1 so the total E is at least 1; Q_i / Q then lies in [(E_i - i 2^-K) / E, E_i / (E - N 2^-K)],
+         within N 2^-K (1 + N 2^-K) of E_i / E.  An implementation that sums in fp64 instead (fixed_point=False: the reference order,
+         a serial cumsum of N terms that never exceeds 1) is within (N - 1) 2^-53 on both the partial sum and the total: 2 N 2^-53.
+      2. from sums to the comparison.  bins_i = fl(fl(Q_i) fl(1 / fl(Q))), s = fl(u fl(fl(Q) fl(1 / fl(Q)))): five roundings and a
+         division, each relative 2^-53 on numbers <= 1 — 8 * 2^-53 covers them.
+      3. the log-weights.  An absolute error d_n of wb_n multiplies e_n by (1 + d_n); a perturbation p_n -> p_n (1 + d_n) of a
+         normalised distribution moves no partial sum by more than 2 sum_n p_n |d_n| (numerator and denominator).  With u = 2^-53,
+         v = xq - fl(f(x_n)) and g = Sigma^-1 v:
+            d_n / u <=   3 (1 + |wf_n| + |c0| + q_n / 2)          wf + (c0 - q/2): two additions and the halving
+                       + |wb_n - mx| + 2                          the subtraction of the maximum; exp itself (< 1 ulp, llpf_detmath.h) and
+                                                                   its quantum's truncation of the significand
+                       + 2 (k + 2) cond(Sigma) q_n                the whitening L z = v and the sum of squares (backward error (k+2) u
+                                                                   of a triangular solve, amplified by at most cond)
+                       + sum_k |g_k| (|xq_k| + |fx_k| + c_f F_k)  the cancellation in v: q/2 moves by g . dv, dv_k = the rounding of
+                                                                   the subtraction plus f's own error c_f u F_k
+         F = |A| |x| + |B| |u| and c_f = nx + nu + 1 for a LinearModel (a dot product of nx + nu terms); for QuadTank (rk4, `supersample`
+         substeps of four right-hand sides: about 40 operations on numbers of the size of x per substep, none cancelling) F = |x| + |fx|
+         and c_f = 64 * supersample.  A common error of mx shifts every wb alike and cancels.
+         Particles with p_n = 0 (a log-weight of -inf, or e_n below the long double's underflow) contribute nothing.
+    Terms of second order in 2^-53 are dropped: they are 2^-40 of the first-order terms."""
+    p, wb, mx, g = step["p"], step["wb"], step["mx"], step["g"]
+    M, N = p.shape
+    k = df.mu.size
+    absx, absfx = np.abs(step["x"]), np.abs(step["fx"])
+    if isinstance(model, LinearModel):
+        F = absx @ np.abs(model.A).T.astype(LD)
+        if model.B.shape[1]:
+            F = F + np.abs(model.B).astype(LD) @ np.abs(np.asarray(step["u"], dtype=LD).reshape(-1))
+        cf = model.A.shape[0] + model.B.shape[1] + 1
+    else:
+        F, cf = absx + absfx, 64 * model.ss
+    c0s = -(k * LOG2PI + float(np.linalg.slogdet(df.Sigma)[1])) / 2.0
+    c0 = abs(c0s)
+    cond = float(np.linalg.cond(df.Sigma))
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.abs(2 * (LD(c0s) - step["lp"]))                                                   # v' Sigma^-1 v
+        d = (3 * (1 + np.abs(step["wf"])[None, :] + c0 + q / 2) + np.abs(wb - mx) + 2 + 2 * (k + 2) * cond * q
+             + np.sum(np.abs(g) * (np.abs(step["xq"])[:, None, :] + absfx[None, :, :] + cf * F[None, :, :]), axis=2))
+        contrib = np.where(p > 0, p * d, 0)
+    rounding = 2 * U53 * np.sum(contrib, axis=1)
+    quanta = N * 2.0 ** -qbits(N) * (1 + N * 2.0 ** -qbits(N)) if fixed_point else 2 * N * U53
+    return (quanta + 8 * U53 + rounding).astype(np.float64)
+
+
+def check_draws(cdf, u, idx, delta):
+    """The assertion of the smoother's check for M draws: index i is right iff cdf[i-1] - delta <= u <= cdf[i] + delta (cdf[-1] = 0).
+    Returns (need [M], excused [M], edge [M]): need = how much slack the reported index needs (0: inside its interval), excused = u lies
+    within delta of an interior edge of the distribution, where either neighbour is accepted and the draw tests nothing, edge = the
+    distance from u to the nearest interior edge."""
+    M, N = cdf.shape
+    u = np.asarray(u, dtype=LD)
+    idx = np.asarray(idx, dtype=np.int64)
+    rows = np.arange(M)
+    hi = cdf[rows, idx]
+    lo = np.where(idx > 0, cdf[rows, np.maximum(idx - 1, 0)], LD(0))
+    need = np.maximum(np.maximum(lo - u, u - hi), 0).astype(np.float64)
+    edge = np.min(np.abs(cdf[:, :-1] - u[:, None]), axis=1).astype(np.float64) if N > 1 else np.full(M, np.inf)
+    return need, edge <= delta, edge

@@ -1623,6 +1623,11 @@ int orc_smooth(orc_filter* f, int64_t M, const double* U, int64_t T, const doubl
     const int64_t N = f->N;
     const int nx = f->nx;
     if (M < 1 || M > N || T < 1) return -1;                   /* @assert M <= N, src/smoothing.jl:121 */
+    /* the engine's refusals (host/smooth.hpp): -2 a model with process noise of its own has no Gaussian transition density; -3 a xf
+     * that is not finite, or NaN / +inf in wf: the maximum below is a chain of a > b ? a : b, whose result then depends on the order */
+    if (f->user_noise_kind) return -2;
+    for (size_t i = 0; i < (size_t)T * N * nx; ++i) if (!isfinite(xf[i])) return -3;
+    for (size_t i = 0; i < (size_t)T * N; ++i) if (!(wf[i] < LLPF_INF)) return -3;
     const int strategy = f->cfg.resampling_strategy;
     double* Ures = (double*)malloc(8 * (size_t)(M > 1 ? M : 1));
     if (strategy == LLPF_RESAMPLE_SYSTEMATIC) Ures[0] = llpf_uniform_step((uint32_t)T, LLPF_STREAM_SMOOTH_INIT, f->k0, f->k1);

@@ -61,7 +61,9 @@ double orc_aux_update(orc_filter* f, const double* u, const double* y1, double t
 double orc_run_aux(orc_filter* f, const double* U, const double* Y, int64_t T, int mode,
                    double* ll_steps, double* xmean, double* x_hist, double* w_hist, double* we_hist);
 
-/* FFBS particle smoother: smooth(pf, xf, wf, wef, ll, M, u, y, p) and draw_one_categorical (0-based) */
+/* FFBS particle smoother: smooth(pf, xf, wf, wef, ll, M, u, y, p) and draw_one_categorical (0-based).  orc_smooth returns 0, or what the
+ * engine refuses with LLPF_ERR_ARG: -1 M or T out of range, -2 a model with process noise of its own (orc_set_user_noise), -3 a xf that is
+ * not finite or a wf that holds NaN / +inf */
 int64_t orc_draw_one_categorical(double* w, double* bins, int64_t n, double u, int order);
 int    orc_smooth(orc_filter* f, int64_t M, const double* U, int64_t T, const double* xf, const double* wf,
                   const double* wef, double* xb, int64_t* idx);
