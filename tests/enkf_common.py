@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from llpf_amd import _structs as S
+from llpf_amd import _capi, _structs as S
 import kf_host as kh
 from kf_host import _dp, _p
 import oracle_binding as ob
@@ -15,7 +15,7 @@ import ukf_common as uc
 KIND_ORACLE, KIND_PENDULUM, KIND_SQUARE, KIND_LINEAR = 0, 2, 3, 4
 CORRECT, PREDICT = 1, 2
 STREAM_INIT, STREAM_DYNAMICS, STREAM_MEASURE = 0, 1, 4
-OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTPUTS = _capi.KALMAN_OUTPUTS
 
 
 def build_host(outdir):

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from llpf_amd import _structs as S
+from llpf_amd import _capi, _structs as S
 import kf_host as kh
 from kf_host import ROOT, SHARED, _dp, _p
 
@@ -144,7 +144,7 @@ def bits_equal(a, b):
 # ------------------------------------------------------------------------------------------------
 # helpers of the GPU tests of the Kalman and the unscented banks
 # ------------------------------------------------------------------------------------------------
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTS = _capi.KALMAN_OUTPUTS
 
 
 def _data(rng, T, nu, ny, missing=()):

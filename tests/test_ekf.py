@@ -18,7 +18,7 @@ import ukf_common as uc
 import user_models as UM
 from test_ukf import linear_systems, T_LIN
 
-OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTPUTS = _capi.KALMAN_OUTPUTS
 
 
 @pytest.fixture(scope="module")

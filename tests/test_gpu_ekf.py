@@ -8,13 +8,14 @@ import llpf_amd
 from llpf_amd import _capi, _structs as S
 import ekf_common as ec
 import kalman_common as kc
-from kalman_common import _data, _same
+from kalman_common import _same
 from gpu_common import _Inject
+import kf_gpu_frame as kg
+from kf_gpu_frame import OUTS, lg_models, quadtank_models, with_id
 import models as M
 import ukf_common as uc
 
 pytestmark = pytest.mark.gpu
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
 
 
 @pytest.fixture(scope="module")
@@ -26,20 +27,7 @@ def _bank(models):
     return _capi.EkfBankHandle(0, list(models))
 
 
-def _with_id(m, model_id):
-    c = S.Model.from_buffer_copy(bytes(m))
-    c.model_id = model_id
-    return c
-
-
-def _lg_models(rng, F, nx, ny, nu):
-    return [kc.random_system(rng, nx, ny, nu, k % 3, D=False)[0] for k in range(F)]
-
-
-def _quadtank_models(F):
-    base = M.quadtank_model()
-    return [S.make_quadtank_model(base.dynamics_density, base.measurement_density, base.initial_density, 1.0, 2,
-                                  gamma1=0.2 + 0.001 * (k % 50), a1=0.03 + 0.0001 * (k % 7)) for k in range(F)]
+EKF = kg.Family("ekf", _bank, ec.host_run, lg_models, True)
 
 
 @pytest.mark.parametrize("nx", range(1, 5))
@@ -48,12 +36,7 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
     for ny in range(1, 5):
         rng = np.random.default_rng(10 * nx + ny)
         nu = int(rng.integers(0, 4))
-        models = _lg_models(rng, 1000, nx, ny, nu)
-        U, Y = _data(rng, 200, nu, ny, missing=(50, 51, 120))
-        b = _bank(models)
-        g = b.run(U, Y, outputs=OUTS)
-        h, st = ec.host_run(host, models, U, Y, 200)
-        _same(g, h, what=(nx, ny))
+        b, g, _, st, _, _ = kg.check_shape(EKF, host, rng, F=1000, T=200, nx=nx, ny=ny, nu=nu, missing=(50, 51, 120), what=(nx, ny))
         assert np.isfinite(g["ll"]).all()
         x, R = b.get_state()
         assert kc.bits_equal(x, st[0]) and kc.bits_equal(R, st[1]), (nx, ny, "final state")
@@ -63,7 +46,7 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
 def test_quadtank_precompiled_shape_and_the_switch_time(host):
     """1., 2. the 17th shape: the built-in quad-tank, F = 1000 with per-filter parameters over T = 200 with missing rows, and across
     tau = TSWITCH = 500 (t_index0 = 470, T = 60): the device's RK4 and its Jacobian in the shared header's order"""
-    models = _quadtank_models(1000)
+    models = quadtank_models(1000)
     U, Y = M.quadtank_data(200)
     Y = Y.copy()
     Y[[5, 120, 121], 0] = np.nan
@@ -85,91 +68,26 @@ def test_quadtank_precompiled_shape_and_the_switch_time(host):
 @pytest.mark.parametrize("F", [1, 63, 64, 65, 1000])
 def test_bank_sizes_and_chunk_edges(host, F):
     """3. per-filter parameters at every bank size around the wave, T around the 256-step chunk of the staging pipe"""
-    rng = np.random.default_rng(100 + F)
-    models = _lg_models(rng, F, 2, 1, 1)
-    U, Y = _data(rng, 700, 1, 1, missing=(0, 255, 256, 699))
-    b = _bank(models)
-    for T in (1, 255, 256, 257, 700):
-        b.reset()
-        g = b.run(U[:T], Y[:T], outputs=OUTS)
-        h, st = ec.host_run(host, models, U[:T], Y[:T], T)
-        _same(g, h, what=(F, T))
-        x, R = b.get_state()
-        assert kc.bits_equal(x, st[0]) and kc.bits_equal(R, st[1]), (F, T, "final state")
+    kg.check_bank_sizes_and_chunk_edges(EKF, host, seed=100 + F, F=F, nx=2, ny=1, nu=1, missing=(0, 255, 256, 699), Ts=(1, 255, 256, 257, 700))
 
 
 def test_continuation_set_models_and_state(host):
     """4., 5. run(a) then run(b) is run(a + b); set_state / get_state round trip; set_models is a fresh bank"""
-    rng = np.random.default_rng(5)
-    models = _lg_models(rng, 300, 3, 2, 2)
-    U, Y = _data(rng, 600, 2, 2, missing=(255, 256, 500))
-    b = _bank(models)
-    whole = b.run(U, Y, outputs=OUTS)
-    b.reset()
-    first = b.run(U[:300], Y[:300], outputs=OUTS)
-    x, R = b.get_state()
-    second = b.run(U[300:], Y[300:], outputs=OUTS, t_index0=300.0)
-    for k in OUTS:
-        assert kc.bits_equal(np.concatenate([first[k], second[k]]), whole[k]), k
-    h2, _ = ec.host_run(host, models, U[300:], Y[300:], 300, state=(x, R), t_index0=300.0)
-    _same(second, h2, what="second half")
-    fresh = _bank(models)
-    fresh.set_state(x, R)
-    xs, Rs = fresh.get_state()
-    assert kc.bits_equal(xs, x) and kc.bits_equal(np.tril(Rs), np.tril(R))
-    again = fresh.run(U[300:], Y[300:], outputs=OUTS, t_index0=300.0)
-    _same(again, second, what="set_state")
-    b.reset()
-    bare = b.run(U, Y)                                  # ll only: nothing is staged per step
-    assert kc.bits_equal(bare["ll"], whole["ll"])
-    other = _lg_models(rng, 300, 3, 2, 2)
+    rng, b, U, Y = kg.check_continuation(EKF, host, seed=5, F=300, T=600, nx=3, ny=2, nu=2, missing=(255, 256, 500), cut=300)
+    other = lg_models(rng, 300, 3, 2, 2)
     b.set_models(other)
     b.reset()
     g = b.run(U, Y, outputs=OUTS)
     h, _ = ec.host_run(host, other, U, Y, 600)
     _same(g, h, what="set_models vs host")
     with pytest.raises(_capi.LLPFError):
-        b.set_models(_lg_models(rng, 300, 2, 2, 2))
+        b.set_models(lg_models(rng, 300, 2, 2, 2))
 
 
 def test_per_filter_inputs_missing_rows_and_a_nan_filter_beside_healthy_ones(host):
     """6., 9. per-filter U and Y over 4000 filters; a filter made NaN through set_state beside healthy ones whose bits do not move"""
-    rng = np.random.default_rng(6)
-    F = 4000
-    models = _lg_models(rng, F, 2, 1, 1)
-    U = rng.standard_normal((F, 40, 1))
-    Y = 2.0 * rng.standard_normal((F, 40, 1))
-    Y[:, [5, 6, 30], 0] = np.nan
-    Y[::7, 11, 0] = np.nan
-    b = _bank(models)
-    x, R = b.get_state()
-    ok = b.run(U, Y, True, True, outputs=OUTS)
-    assert np.all(ok["ll_steps"][[5, 6, 30]] == 0.0) and np.all(np.isnan(ok["e"][[5, 6, 30]]))
-    h, _ = ec.host_run(host, models, U, Y, 40, per_filter=3)
-    _same(ok, h, what="per-filter inputs")
-    R[77] = -100.0 * np.eye(2)
-    b.set_state(x, R)
-    bad = b.run(U, Y, True, True, outputs=OUTS)
-    assert np.isnan(bad["ll"][77]) and np.all(np.isnan(bad["xt"][:, 77])) and np.all(np.isnan(bad["R"][1:, 77]))
-    assert np.all(bad["ll_steps"][[5, 6, 30], 77] == 0.0)
-    keep = [f for f in range(F) if f != 77]
-    for k in OUTS:
-        assert kc.bits_equal(bad[k][:, keep], ok[k][:, keep]), k
-    hb, _ = ec.host_run(host, models, U, Y, 40, per_filter=3, state=(x, R))
-    _same(bad, hb, what="NaN filter")
-
-
-def _pendulum_models(n):
-    out = []
-    for k in range(n):
-        m = uc.pendulum_model()
-        m.qt[0], m.qt[1] = 9.81 * (1 + 0.002 * k), 0.05 + 0.001 * (k % 10)
-        out.append(m)
-    return out
-
-
-def _square_models(n):
-    return [ec.square_model(1.0 + 0.01 * k, 0.36) for k in range(n)]
+    kg.check_per_filter_inputs_and_a_nan_filter(EKF, host, seed=6, F=4000, T=40, nx=2, ny=1, nu=1, missing=(5, 6, 30), stride=7, row=11,
+                                                nan_filter=77)
 
 
 def test_runtime_compiled_shapes(host):
@@ -177,31 +95,27 @@ def test_runtime_compiled_shapes(host):
     with hand-written members against their C twins"""
     rng = np.random.default_rng(21)
     for nx, ny, nu in ((5, 1, 0), (6, 3, 2), (8, 4, 1)):
-        models = _lg_models(rng, 130, nx, ny, nu)
-        U, Y = _data(rng, 60, nu, ny, missing=(7,))
-        g = _bank(models).run(U, Y, outputs=OUTS)
-        h, _ = ec.host_run(host, models, U, Y, 60)
-        _same(g, h, what=("LG", nx, ny))
+        kg.check_shape(EKF, host, rng, F=130, T=60, nx=nx, ny=ny, nu=nu, missing=(7,), what=("LG", nx, ny))
     pid = _capi.model_compile(ec.PENDULUM_JAC_SRC, 2, 1)
-    pend = _pendulum_models(100)
+    pend = kg.pendulum_models(100)
     U, Y = uc.pendulum_data(300)
     Y = Y.copy()
     Y[[3, 256], 0] = np.nan
-    g = _bank([_with_id(m, pid) for m in pend]).run(U, Y, outputs=OUTS)
+    g = _bank([with_id(m, pid) for m in pend]).run(U, Y, outputs=OUTS)
     h, _ = ec.host_run(host, pend, U, Y, 300, kind=ec.KIND_PENDULUM)
     _same(g, h, what="pendulum")
     assert np.isfinite(g["ll"]).all()
-    sq = _square_models(64)
+    sq = kg.square_models(64)
     Y = 3.0 + 0.5 * rng.standard_normal((80, 1))
     h, _ = ec.host_run(host, sq, None, Y, 80, kind=ec.KIND_SQUARE)
     sid = _capi.model_compile(ec.SQUARE_JAC_SRC, 1, 1)
-    g = _bank([_with_id(m, sid) for m in sq]).run(None, Y, outputs=OUTS)
+    g = _bank([with_id(m, sid) for m in sq]).run(None, Y, outputs=OUTS)
     _same(g, h, what="square snippet")
 
 
 def test_a_filter_alone_equals_its_column_of_the_bank_and_a_throw_is_a_status():
     """8., 10. one filter is its column of the bank; LLPF_TEST_THROW=error:ekf_run gives a status with the process alive"""
-    models = _quadtank_models(70)
+    models = quadtank_models(70)
     U, Y = M.quadtank_data(100)
     b = _bank(models)
     g = b.run(U, Y, outputs=OUTS, t_index0=1.0)
@@ -223,19 +137,10 @@ def test_a_filter_alone_equals_its_column_of_the_bank_and_a_throw_is_a_status():
     _same(again, g, what="after the throw")
 
 
-def _c1_specs(n):
-    specs = []
-    for k in range(n):
-        mt = kc.matrices(M.lg_c1_model(seed=k), np.zeros((2, 2)))
-        specs.append((llpf_amd.LinearDynamics(mt["A"], mt["B"]), llpf_amd.LinearMeasurement(mt["C"]), llpf_amd.MvNormal(np.zeros(2), mt["R1"]),
-                      llpf_amd.MvNormal(np.zeros(2), mt["R2"]), llpf_amd.MvNormal(mt["x0"], mt["P0"])))
-    return specs
-
-
 def test_ekf_bank_on_the_linear_c1_model_is_the_kalman_bank():
     """11. from_filter_bank of the C1 linear bank against KalmanFilterBank: every output to 1e-10, R and Rt bit for bit"""
     _, U, Y = M.simulate_lg(M.lg_c1_model(0), 200)
-    pf = llpf_amd.FilterBank(1000, _c1_specs(16), rng=1)
+    pf = llpf_amd.FilterBank(1000, kg.c1_specs(16), rng=1)
     kb = llpf_amd.KalmanFilterBank.from_filter_bank(pf)
     eb = llpf_amd.ExtendedKalmanFilterBank.from_filter_bank(pf)
     lk, le = kb.loglik(U, Y), eb.loglik(U, Y)

@@ -14,6 +14,7 @@ import enkf_common as nc
 import kalman_common as kc
 from kalman_common import _data, _same
 from gpu_common import _Inject, cfg_of
+from kf_gpu_frame import c1_specs, lg_models, pendulum_models, quadtank_models, square_models, with_id
 import models as M
 import ukf_common as uc
 import user_models as UM
@@ -29,22 +30,6 @@ def host(tmp_path_factory):
 
 def _bank(models, N, seed=0):
     return _capi.EnkfBankHandle(0, list(models), N, seed)
-
-
-def _with_id(m, model_id):
-    c = S.Model.from_buffer_copy(bytes(m))
-    c.model_id = model_id
-    return c
-
-
-def _lg_models(rng, F, nx, ny, nu):
-    return [kc.random_system(rng, nx, ny, nu, k % 3, D=False)[0] for k in range(F)]
-
-
-def _quadtank_models(F):
-    base = M.quadtank_model()
-    return [S.make_quadtank_model(base.dynamics_density, base.measurement_density, base.initial_density, 1.0, 2,
-                                  gamma1=0.2 + 0.001 * (k % 50), a1=0.03 + 0.0001 * (k % 7)) for k in range(F)]
 
 
 def _against_the_twin(host, b, models, U, Y, seed, what, twin_models=None, kind=None, outputs=OUTS, **kw):
@@ -67,7 +52,7 @@ def test_lingauss_bit_identical_to_the_twin_for_every_precompiled_shape(host, nx
     for ny in range(1, 5):
         rng = np.random.default_rng(10 * nx + ny)
         nu = int(rng.integers(0, 4))
-        models = _lg_models(rng, 5, nx, ny, nu)
+        models = lg_models(rng, 5, nx, ny, nu)
         U, Y = _data(rng, 40, nu, ny, missing=(5, 6, 30))
         b = _bank(models, 300, seed=77)
         assert kc.bits_equal(b.get_members(), nc.host_init(host, models, 300, 77)), (nx, ny, "reset")
@@ -78,7 +63,7 @@ def test_lingauss_bit_identical_to_the_twin_for_every_precompiled_shape(host, nx
 
 def test_quadtank_precompiled_shape_across_the_switch_time(host):
     """1b. the built-in quad-tank at F = 3, N = 128, T = 520 from t_index0 = 1 (three chunks, across tau = TSWITCH)"""
-    models = _quadtank_models(3)
+    models = quadtank_models(3)
     U, Y = M.quadtank_data(520)
     Y = Y.copy()
     Y[[5, 256, 511], 0] = np.nan
@@ -86,33 +71,24 @@ def test_quadtank_precompiled_shape_across_the_switch_time(host):
     assert np.isfinite(g["ll"]).all() and len(set(g["ll"].tolist())) == 3
 
 
-def _pendulum_models(n):
-    out = []
-    for k in range(n):
-        m = uc.pendulum_model()
-        m.qt[0], m.qt[1] = 9.81 * (1 + 0.002 * k), 0.05 + 0.001 * (k % 10)
-        out.append(m)
-    return out
-
-
 def test_runtime_compiled_models(host):
     """1c. k_enkf from a hiprtc program of the model's own at F = 4, N = 100: the linear-Gaussian model at (5, 1) and (8, 4), the pendulum
     and x0^2 as snippets against their C twins, and a traced callable (x0^2 again, through the tracer)"""
     rng = np.random.default_rng(21)
     for nx, ny, nu in ((5, 1, 0), (8, 4, 1)):
-        models = _lg_models(rng, 4, nx, ny, nu)
+        models = lg_models(rng, 4, nx, ny, nu)
         U, Y = _data(rng, 30, nu, ny, missing=(7,))
         _against_the_twin(host, _bank(models, 100, seed=5), models, U, Y, 5, ("LG", nx, ny))
     pid = _capi.model_compile(UM.PENDULUM_SRC, 2, 1)
-    pend = _pendulum_models(4)
+    pend = pendulum_models(4)
     U, Y = uc.pendulum_data(60)
-    g, _ = _against_the_twin(host, _bank([_with_id(m, pid) for m in pend], 100, seed=6), pend, U, Y, 6, "pendulum", twin_models=pend,
+    g, _ = _against_the_twin(host, _bank([with_id(m, pid) for m in pend], 100, seed=6), pend, U, Y, 6, "pendulum", twin_models=pend,
                              kind=nc.KIND_PENDULUM)
     assert np.isfinite(g["ll"]).all()
-    sq = [ec.square_model(1.0 + 0.01 * k, 0.36) for k in range(4)]
+    sq = square_models(4)
     Y = 3.0 + 0.5 * rng.standard_normal((40, 1))
     sid = _capi.model_compile(ec.SQUARE_JAC_SRC, 1, 1)
-    _against_the_twin(host, _bank([_with_id(m, sid) for m in sq], 100, seed=7), sq, None, Y, 7, "square snippet", twin_models=sq, kind=nc.KIND_SQUARE)
+    _against_the_twin(host, _bank([with_id(m, sid) for m in sq], 100, seed=7), sq, None, Y, 7, "square snippet", twin_models=sq, kind=nc.KIND_SQUARE)
     f = llpf_amd.EnsembleKalmanFilter(lambda x, u, p, t: [x[0]], lambda x, u, p, t: [x[0] * x[0]], 0.1, 0.25, llpf_amd.MvNormal(np.array([1.0]), 0.36),
                                       100, nu=0, ny=1, seed=7)
     sol = llpf_amd.forward_trajectory(f, None, Y)
@@ -125,7 +101,7 @@ def test_runtime_compiled_models(host):
 def test_ensemble_sizes_around_the_wave_and_the_workgroup(host, N):
     """2a. N around 64 and 256 (a slot with none, one or several members) at F = 3, T = 20"""
     rng = np.random.default_rng(300 + N)
-    models = _lg_models(rng, 3, 2, 1, 1)
+    models = lg_models(rng, 3, 2, 1, 1)
     U, Y = _data(rng, 20, 1, 1, missing=(3,))
     _against_the_twin(host, _bank(models, N, seed=N), models, U, Y, N, N)
 
@@ -133,7 +109,7 @@ def test_ensemble_sizes_around_the_wave_and_the_workgroup(host, N):
 def test_chunk_edges_with_outputs_and_without(host):
     """2b. T around the 256-step chunk of the staging pipe at F = 2, N = 65; ll alone is the ll of a run with every output"""
     rng = np.random.default_rng(41)
-    models = _lg_models(rng, 2, 2, 1, 1)
+    models = lg_models(rng, 2, 2, 1, 1)
     U, Y = _data(rng, 600, 1, 1, missing=(0, 255, 256, 599))
     b = _bank(models, 65, seed=9)
     for T in (1, 255, 256, 257, 600):
@@ -148,7 +124,7 @@ def test_shared_and_per_filter_inputs_split_runs_and_the_step_verbs(host):
     """2c. shared and per-filter U / Y give the same bits; run(a) then run(b) is run(a + b); correct + predict is update; reset draws
     the next ensemble and seed restores the first"""
     rng = np.random.default_rng(42)
-    models = _lg_models(rng, 3, 3, 2, 2)
+    models = lg_models(rng, 3, 3, 2, 2)
     U, Y = _data(rng, 50, 2, 2, missing=(4,))
     b = _bank(models, 130, seed=12)
     X0 = b.get_members()
@@ -194,7 +170,7 @@ def _simulated(models, N, T, seed, U, t_index0=0.0):
 def _box_models(mid, F):
     out = []
     for k in range(F):
-        m = _with_id(M.lg_test_model(), mid)
+        m = with_id(M.lg_test_model(), mid)
         for i, v in enumerate((0.05 + 0.01 * k, 0.1, -1.0, -2.0, 1.0, 2.0)):
             m.qt[i] = v
         out.append(m)
@@ -211,7 +187,7 @@ def test_the_members_are_the_particle_banks_draws(host):
     b = _bank(lg, N, seed=31)
     b.run(U[:T], np.full((T, 1), np.nan))
     assert kc.bits_equal(b.get_members(), _simulated(lg, N, T, 31, U)), "LG"
-    qt = _quadtank_models(2)
+    qt = quadtank_models(2)
     Uq, _ = M.quadtank_data(T + 1)
     b = _bank(qt, N, seed=32)
     b.run(Uq[:T], np.full((T, 2), np.nan), t_index0=1.0)
@@ -233,7 +209,7 @@ def test_a_filter_alone_has_the_bits_it_has_in_a_bank(host):
     """4. filters 0, 2 and 4 of F = 5 alone with seed + f; a NaN member makes its filter NaN from that step on and leaves the neighbours'
     bits alone; set_models and set_inflation between calls equal a fresh bank"""
     rng = np.random.default_rng(44)
-    models = _lg_models(rng, 5, 2, 2, 1)
+    models = lg_models(rng, 5, 2, 2, 1)
     U, Y = _data(rng, 30, 1, 2, missing=(9,))
     b = _bank(models, 200, seed=50)
     X0 = b.get_members()
@@ -256,7 +232,7 @@ def test_a_filter_alone_has_the_bits_it_has_in_a_bank(host):
     for k in OUTS:
         assert kc.bits_equal(bad[k][:, keep], g[k][:, keep]), k
     _same(bad, nc.host_run(host, models, Xn, U, Y, 30, 50), what="NaN member vs twin")
-    other = _lg_models(rng, 5, 2, 2, 1)
+    other = lg_models(rng, 5, 2, 2, 1)
     b.seed(50)
     b.set_models(other)
     b.set_inflation(1.25)
@@ -271,14 +247,14 @@ def test_a_filter_alone_has_the_bits_it_has_in_a_bank(host):
     for rho in (0.5, float("nan"), float("inf")):
         assert L.llpf_enkf_bank_set_inflation(b.h, C.c_double(rho)) == _capi.ERR_ARG and L.llpf_last_error().decode().startswith("enkf")
     with pytest.raises(_capi.LLPFError):
-        b.set_models(_lg_models(rng, 5, 3, 2, 1))
+        b.set_models(lg_models(rng, 5, 3, 2, 1))
 
 
 def test_a_throw_and_a_refused_allocation_leave_a_usable_handle(host):
     """5. error:enkf_run is a status, a failed allocation (injected: the run's staging is chunked, so no T makes it large) is
     LLPF_ERR_ALLOC; the members are untouched by either and the handle goes on working; alloc:enkf_create frees the half-built bank"""
     rng = np.random.default_rng(45)
-    models = _lg_models(rng, 3, 2, 1, 1)
+    models = lg_models(rng, 3, 2, 1, 1)
     U, Y = _data(rng, 10, 1, 1)
     b = _bank(models, 64, seed=1)
     X0 = b.get_members()
@@ -300,11 +276,7 @@ def test_a_throw_and_a_refused_allocation_leave_a_usable_handle(host):
 
 def test_python_api():
     """6. from_filter_bank(...).loglik equals a loop of single filters; forward_trajectory has the documented shapes; smooth raises"""
-    specs = []
-    for k in range(3):
-        mt = kc.matrices(M.lg_c1_model(seed=k), np.zeros((2, 2)))
-        specs.append((llpf_amd.LinearDynamics(mt["A"], mt["B"]), llpf_amd.LinearMeasurement(mt["C"]), llpf_amd.MvNormal(np.zeros(2), mt["R1"]),
-                      llpf_amd.MvNormal(np.zeros(2), mt["R2"]), llpf_amd.MvNormal(mt["x0"], mt["P0"])))
+    specs = c1_specs(3)
     rng = np.random.default_rng(3)
     U, Y = rng.standard_normal((25, 2)), rng.standard_normal((25, 2))
     pf = llpf_amd.FilterBank(256, specs, rng=9)

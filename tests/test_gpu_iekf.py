@@ -11,13 +11,14 @@ from llpf_amd import _capi, _structs as S
 import ekf_common as ec
 import iekf_common as ic
 import kalman_common as kc
-from kalman_common import _data, _same
+from kalman_common import _same
 from gpu_common import _Inject
+import kf_gpu_frame as kg
+from kf_gpu_frame import OUTS, lg_models, quadtank_models, with_id
 import models as M
 import ukf_common as uc
 
 pytestmark = pytest.mark.gpu
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
 ITER = (10, 1e-8)
 
 
@@ -43,20 +44,7 @@ def _bank(models, iterations=ITER):
     return b
 
 
-def _with_id(m, model_id):
-    c = S.Model.from_buffer_copy(bytes(m))
-    c.model_id = model_id
-    return c
-
-
-def _lg_models(rng, F, nx, ny, nu):
-    return [kc.random_system(rng, nx, ny, nu, k % 3, D=False)[0] for k in range(F)]
-
-
-def _quadtank_models(F):
-    base = M.quadtank_model()
-    return [S.make_quadtank_model(base.dynamics_density, base.measurement_density, base.initial_density, 1.0, 2,
-                                  gamma1=0.2 + 0.001 * (k % 50), a1=0.03 + 0.0001 * (k % 7)) for k in range(F)]
+IEKF = kg.Family("iekf", _bank, lambda host, models, U, Y, T, **kw: ic.host_run(host, models, U, Y, T, *ITER, **kw), lg_models, True)
 
 
 @pytest.mark.parametrize("nx", range(1, 5))
@@ -66,12 +54,7 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
     for ny in range(1, 5):
         rng = np.random.default_rng(10 * nx + ny)
         nu = int(rng.integers(0, 4))
-        models = _lg_models(rng, 200, nx, ny, nu)
-        U, Y = _data(rng, 60, nu, ny, missing=(0, 20, 21, 59))
-        b = _bank(models)
-        g = b.run(U, Y, outputs=OUTS)
-        h, st = ic.host_run(host, models, U, Y, 60, *ITER)
-        _same(g, h, what=(nx, ny))
+        b, g, h, st, _, _ = kg.check_shape(IEKF, host, rng, F=200, T=60, nx=nx, ny=ny, nu=nu, missing=(0, 20, 21, 59), what=(nx, ny))
         assert np.isfinite(g["ll"]).all() and h["iters"].max() == 2
         x, R = b.get_state()
         assert kc.bits_equal(x, st[0]) and kc.bits_equal(R, st[1]), (nx, ny, "final state")
@@ -80,7 +63,7 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
 
 def test_quadtank_precompiled_shape_across_the_switch_time(host):
     """6. the 17th shape: the built-in quad-tank, F = 200 with per-filter parameters, T = 60 across tau = TSWITCH = 500 with missing rows"""
-    models = _quadtank_models(200)
+    models = quadtank_models(200)
     U, Y = M.quadtank_data(60)
     Y = Y.copy()
     Y[[5, 30, 31], 0] = np.nan
@@ -116,7 +99,7 @@ def test_pendulum_lanes_stop_after_different_iteration_counts(host, pendulum_id,
     if F > 1:
         counts = whole["iters"][0, :min(F, 64)]
         assert len(set(counts.tolist())) >= 3 and counts.max() > 2, counts
-    dev = [_with_id(m, pendulum_id) for m in models[:F]]
+    dev = [with_id(m, pendulum_id) for m in models[:F]]
     b = _bank(dev)
     one = _bank(dev[:1])
     for T in (1, 255, 256, 257):
@@ -144,10 +127,10 @@ def test_square_snippet_traced_callable_and_lingauss_through_hiprtc(host, square
     """8. x0^2 as a snippet against its C twin bit for bit, the same model as a traced callable against the snippet to 1e-10, and the
     linear-Gaussian model at (5, 1), above the precompiled dimensions, bit for bit"""
     rng = np.random.default_rng(21)
-    sq = [ec.square_model(1.0 + 0.01 * k, 0.36) for k in range(64)]
+    sq = kg.square_models(64)
     Y = 3.0 + 0.5 * rng.standard_normal((80, 1))
     h, _ = ic.host_run(host, sq, None, Y, 80, *ITER, kind=ec.KIND_SQUARE)
-    g = _bank([_with_id(m, square_id) for m in sq]).run(None, Y, outputs=OUTS)
+    g = _bank([with_id(m, square_id) for m in sq]).run(None, Y, outputs=OUTS)
     _same(g, h, what="square snippet")
     assert h["iters"].max() > 2
     d1 = llpf_amd.MvNormal(np.array([1.0]), 0.36)
@@ -158,11 +141,7 @@ def test_square_snippet_traced_callable_and_lingauss_through_hiprtc(host, square
     for k in ("x", "xt", "R", "Rt", "e"):
         assert kc.close(getattr(st, k), getattr(ss, k)), ("square", k)
     assert abs(st.ll - ss.ll) <= 1e-10 * abs(ss.ll)
-    models = _lg_models(rng, 130, 5, 1, 0)
-    U, Y = _data(rng, 60, 0, 1, missing=(7,))
-    g = _bank(models).run(U, Y, outputs=OUTS)
-    h, _ = ic.host_run(host, models, U, Y, 60, *ITER)
-    _same(g, h, what=("LG", 5, 1))
+    kg.check_shape(IEKF, host, rng, F=130, T=60, nx=5, ny=1, nu=0, missing=(7,), what=("LG", 5, 1))
 
 
 def test_set_iterations_between_runs(host, pendulum_id, pendulum_case):
@@ -170,7 +149,7 @@ def test_set_iterations_between_runs(host, pendulum_id, pendulum_case):
     keep the setting; a refused setting changes nothing; LLPF_TEST_THROW=error:ekf_run leaves a usable handle"""
     models, U, Y, whole = pendulum_case
     models, T = models[:100], 257
-    dev = [_with_id(m, pendulum_id) for m in models]
+    dev = [with_id(m, pendulum_id) for m in models]
     b = _bank(dev)
     it = b.run(U, Y, outputs=OUTS)
     for k in OUTS:
@@ -198,7 +177,7 @@ def test_set_iterations_between_runs(host, pendulum_id, pendulum_case):
     fresh.set_state(x, R)
     again = fresh.run(U[130:], Y[130:], outputs=OUTS, t_index0=130.0)
     _same(again, second, what="set_state keeps the setting")
-    other = [_with_id(m, pendulum_id) for m in ic.pendulum_bank_models(200)[100:]]
+    other = [with_id(m, pendulum_id) for m in ic.pendulum_bank_models(200)[100:]]
     b.set_models(other)
     b.reset()
     g = b.run(U, Y, outputs=OUTS)

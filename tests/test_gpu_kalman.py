@@ -10,12 +10,13 @@ import llpf_amd
 from llpf_amd import _capi, _structs as S
 import kalman_common as kc
 from kalman_common import _data, _same
+import kf_gpu_frame as kg
+from kf_gpu_frame import OUTS
 import models as M
 import oracle_binding as ob
 import ukf_common as uc
 
 pytestmark = pytest.mark.gpu
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
 
 
 @pytest.fixture(scope="module")
@@ -27,22 +28,21 @@ def _bank(systems):
     return _capi.KalmanBankHandle(0, [m for m, _ in systems], np.stack([D for _, D in systems]))
 
 
+def _family(D):
+    """the Kalman bank over random systems, filter k with a direct term where D(k)"""
+    return kg.Family("kalman", _bank, kc.host_run, lambda rng, F, nx, ny, nu: [kc.random_system(rng, nx, ny, nu, k % 3, D=D(k)) for k in range(F)],
+                     False)
+
+
 @pytest.mark.parametrize("nx", range(1, 9))
 def test_bit_identical_to_the_host_header_for_every_shape(host, nx):
     """F = 1000 random filters, T = 200, every output; shared and per-filter inputs give the same bits"""
+    fam = _family(lambda k: k % 5 != 0)
     for ny in range(1, 5):
         rng = np.random.default_rng(10 * nx + ny)
         nu = int(rng.integers(0, 4))
-        systems = [kc.random_system(rng, nx, ny, nu, k % 3, D=k % 5 != 0) for k in range(1000)]
-        U, Y = _data(rng, 200, nu, ny, missing=(50, 51, 120))
-        b = _bank(systems)
-        g = b.run(U, Y, outputs=OUTS)
-        h, _ = kc.host_run(host, systems, U, Y, 200)
-        _same(g, h, OUTS + ("ll",), (nx, ny))
-        b.reset()
-        gp = b.run(np.broadcast_to(U, (1000,) + U.shape), np.broadcast_to(Y, (1000,) + Y.shape), u_per_filter=nu > 0, y_per_filter=True,
-                   outputs=OUTS)
-        _same(gp, g, OUTS + ("ll",), (nx, ny, "per-filter"))
+        b, g, _, _, U, Y = kg.check_shape(fam, host, rng, F=1000, T=200, nx=nx, ny=ny, nu=nu, missing=(50, 51, 120), what=(nx, ny))
+        kg.check_broadcast_inputs(fam, b, g, U, Y, F=1000, nu=nu, what=(nx, ny, "per-filter"))
         b.close()
 
 

@@ -2,22 +2,20 @@
 host/kalman.hpp): the GPU reproduces the host build of csrc/shared/llpf_kalman.h bit for bit — forward outputs, ll and the smoothed xT, RT —
 whatever the shape, the bank or the chunking; the handle's state after a smooth is the state after a run; and the Python API
 (smooth(kf, u, y), KalmanFilterBank.smooth) computes the reference's smoother."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import llpf_amd
-from llpf_amd import _capi, _structs as S
-from gpu_common import _Inject
+from llpf_amd import _capi
 import kalman_common as kc
 from kalman_common import _data, _same
+import kf_gpu_frame as kg
+from kf_gpu_frame import OUTS, SOUTS
 import kalman_smooth_common as ks
 import models as M
+from test_gpu_kalman import _bank, _family as _kalman_family
 
 pytestmark = pytest.mark.gpu
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
-SOUTS = ("xT", "RT")
 
 
 @pytest.fixture(scope="module")
@@ -30,27 +28,22 @@ def hsmooth(tmp_path_factory):
     return ks.build_host_smooth(tmp_path_factory.mktemp("kalman_smooth_host"))
 
 
-def _bank(systems):
-    return _capi.KalmanBankHandle(0, [m for m, _ in systems], np.stack([D for _, D in systems]))
+def _family(D):
+    """the Kalman bank over random systems, filter k with a direct term where D(k), and its smoother"""
+    def host_smooth(L, systems, U, fw, T, per_filter=0, state=None):
+        return ks.host_smooth(L, systems, U, fw, T, per_filter=per_filter & 1)
+    return _kalman_family(D)._replace(host_smooth=host_smooth)
 
 
 @pytest.mark.parametrize("nx", range(1, 9))
 def test_bit_identical_to_the_host_header_for_every_shape(host, hsmooth, nx):
     """F = 1000 random filters, T = 200, missing rows: xT, RT, ll and every forward output; shared and per-filter inputs give the same bits"""
+    fam = _family(lambda k: k % 5 != 0)
     for ny in range(1, 5):
         rng = np.random.default_rng(1000 + 10 * nx + ny)
         nu = int(rng.integers(0, 4))
-        systems = [kc.random_system(rng, nx, ny, nu, k % 3, D=k % 5 != 0) for k in range(1000)]
-        U, Y = _data(rng, 200, nu, ny, missing=(50, 51, 120, 199))
-        b = _bank(systems)
-        g = b.smooth(U, Y, forward=OUTS)
-        h, _ = kc.host_run(host, systems, U, Y, 200)
-        h.update(ks.host_smooth(hsmooth, systems, U, h, 200))
-        _same(g, h, OUTS + SOUTS + ("ll",), (nx, ny))
-        b.reset()
-        gp = b.smooth(np.broadcast_to(U, (1000,) + U.shape), np.broadcast_to(Y, (1000,) + Y.shape), u_per_filter=nu > 0, y_per_filter=True,
-                      forward=OUTS)
-        _same(gp, g, OUTS + SOUTS + ("ll",), (nx, ny, "per-filter"))
+        b, g, _, _, U, Y = kg.check_shape(fam, (host, hsmooth), rng, F=1000, T=200, nx=nx, ny=ny, nu=nu, missing=(50, 51, 120, 199), what=(nx, ny))
+        kg.check_broadcast_inputs(fam, b, g, U, Y, F=1000, nu=nu, what=(nx, ny, "per-filter"))
         b.close()
 
 
@@ -213,34 +206,5 @@ def test_from_filter_bank_smooths_like_each_filter():
 
 
 def test_a_throw_and_a_refused_allocation_leave_a_usable_handle():
-    rng = np.random.default_rng(45)
-    systems = [kc.random_system(rng, 2, 1, 0, k % 3) for k in range(64)]
-    U, Y = _data(rng, 50, 0, 1)
-    b = _bank(systems)
-    ref = b.smooth(None, Y)
-    b.reset()
-    xi, Ri = b.get_state()
-    with _Inject("error:kalman_smooth"):
-        with pytest.raises(_capi.LLPFError) as ei:
-            b.smooth(None, Y)
-    assert ei.value.code == _capi.ERR_INTERNAL
-    x0, R0 = b.get_state()
-    assert kc.bits_equal(x0, xi) and kc.bits_equal(R0, Ri)
-    again = b.smooth(None, Y)
-    _same(again, ref, SOUTS + ("ll",), "after a throw")
     # 2^40 steps: the stored posterior alone is beyond the device; refused by its allocation before any launch, the state untouched
-    b.reset()
-    b.run(None, Y[:10])
-    x1, R1 = b.get_state()
-    L = _capi.lib()
-    out = S.KalmanSmoothOutputs()
-    out.struct_size = C.sizeof(S.KalmanSmoothOutputs)
-    xT = np.zeros(4)
-    out.xT = _capi.dptr(xT)
-    ll = np.zeros(64)
-    rc = L.llpf_kalman_bank_smooth(b.h, None, _capi.dptr(Y), C.c_int64(1 << 40), 0, _capi.dptr(ll), None, C.byref(out))
-    assert rc == _capi.ERR_ALLOC, rc
-    x2, R2 = b.get_state()
-    assert kc.bits_equal(x1, x2) and kc.bits_equal(R1, R2) and np.all(xT == 0.0)
-    b.reset()
-    _same(b.smooth(None, Y), ref, SOUTS + ("ll",), "after a refused allocation")
+    kg.check_throw_and_refused_allocation(_family(lambda k: True), seed=45, F=64, T=50, nx=2, ny=1, nu=0, short=10, huge=1 << 40)

@@ -6,15 +6,16 @@ import numpy as np
 import pytest
 
 import llpf_amd
-from llpf_amd import _capi, _structs as S
+from llpf_amd import _capi
 import kalman_common as kc
-from kalman_common import _data, _same
+from kalman_common import _same
+import kf_gpu_frame as kg
+from kf_gpu_frame import OUTS, lg_models, quadtank_models, with_id
 import models as M
 import ukf_common as uc
 import user_models as UM
 
 pytestmark = pytest.mark.gpu
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
 W1 = uc.merwe(2, 1.0, 0.0, 1.0)
 
 
@@ -27,14 +28,10 @@ def _bank(models, w):
     return _capi.UkfBankHandle(0, list(models), w)
 
 
-def _with_id(m, model_id):
-    c = S.Model.from_buffer_copy(bytes(m))
-    c.model_id = model_id
-    return c
-
-
-def _lg_models(rng, F, nx, ny, nu):
-    return [kc.random_system(rng, nx, ny, nu, k % 3, D=False)[0] for k in range(F)]
+def _family(w):
+    """the unscented bank with the weights w"""
+    return kg.Family("ukf", lambda models: _bank(models, w), lambda host, models, U, Y, T, **kw: uc.host_run(host, models, w, U, Y, T, **kw),
+                     lg_models, True)
 
 
 @pytest.mark.parametrize("nx", range(1, 5))
@@ -44,34 +41,18 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
     for ny in range(1, 5):
         rng = np.random.default_rng(10 * nx + ny)
         nu = int(rng.integers(0, 4))
-        models = _lg_models(rng, 1000, nx, ny, nu)
-        U, Y = _data(rng, 200, nu, ny, missing=(50, 51, 120))
-        w = (uc.merwe_set(nx, uc.ALPHA1_SETS[(nx + ny) % 3]), uc.merwe(nx, *uc.SMALL_ALPHA))[ny == 4]
-        b = _bank(models, w)
-        g = b.run(U, Y, outputs=OUTS)
-        h, _ = uc.host_run(host, models, w, U, Y, 200)
-        _same(g, h, what=(nx, ny))
+        fam = _family((uc.merwe_set(nx, uc.ALPHA1_SETS[(nx + ny) % 3]), uc.merwe(nx, *uc.SMALL_ALPHA))[ny == 4])
+        b, g, _, _, U, Y = kg.check_shape(fam, host, rng, F=1000, T=200, nx=nx, ny=ny, nu=nu, missing=(50, 51, 120), what=(nx, ny))
         assert np.isfinite(g["ll"]).all()
-        b.reset()
-        gp = b.run(np.broadcast_to(U, (1000,) + U.shape), np.broadcast_to(Y, (1000,) + Y.shape), u_per_filter=nu > 0, y_per_filter=True, outputs=OUTS)
-        _same(gp, g, what=(nx, ny, "per-filter"))
+        kg.check_broadcast_inputs(fam, b, g, U, Y, F=1000, nu=nu, what=(nx, ny, "per-filter"))
         b.close()
-
-
-def _quadtank_models(F):
-    base = M.quadtank_model()
-    out = []
-    for k in range(F):
-        out.append(S.make_quadtank_model(base.dynamics_density, base.measurement_density, base.initial_density, 1.0, 2,
-                                         gamma1=0.2 + 0.001 * (k % 50), a1=0.03 + 0.0001 * (k % 7)))
-    return out
 
 
 def test_quadtank_across_the_switch_time(host):
     """the built-in quad-tank with per-filter parameters over T = 700 from t_index0 = 1 (tau crosses TSWITCH = 500; three chunks), three
     missing rows: the device's RK4 in the oracle's order"""
     F, T = 65, 700
-    models = _quadtank_models(F)
+    models = quadtank_models(F)
     U, Y = M.quadtank_data(T)
     Y = Y.copy()
     Y[[5, 256, 600], 0] = np.nan
@@ -87,46 +68,36 @@ def test_runtime_compiled_shapes(host):
     quad-tank's bits), the pendulum, the x0^2 model as a snippet and as a traced Python callable"""
     rng = np.random.default_rng(21)
     for nx, ny, nu in ((6, 3, 2), (8, 4, 1), (5, 1, 0)):
-        models = _lg_models(rng, 130, nx, ny, nu)
-        U, Y = _data(rng, 60, nu, ny, missing=(7,))
-        w = uc.merwe(nx, 1.0, 0.0, 1.0)
-        g = _bank(models, w).run(U, Y, outputs=OUTS)
-        h, _ = uc.host_run(host, models, w, U, Y, 60)
-        _same(g, h, what=("LG", nx, ny))
+        kg.check_shape(_family(uc.merwe(nx, 1.0, 0.0, 1.0)), host, rng, F=130, T=60, nx=nx, ny=ny, nu=nu, missing=(7,),
+                       what=("LG", nx, ny))
     # the quad-tank as a snippet
     qid = _capi.model_compile(UM.QUADTANK_SRC, 4, 2)
-    models = _quadtank_models(70)
+    models = quadtank_models(70)
     U, Y = M.quadtank_data(520)
     w = uc.merwe(4, 1.0, 0.0, 1.0)
-    g = _bank([_with_id(m, qid) for m in models], w).run(U, Y, outputs=OUTS, t_index0=1.0)
+    g = _bank([with_id(m, qid) for m in models], w).run(U, Y, outputs=OUTS, t_index0=1.0)
     gb = _bank(models, w).run(U, Y, outputs=OUTS, t_index0=1.0)
     _same(g, gb, what="quad-tank snippet vs built-in")
     h, _ = uc.host_run(host, models, w, U, Y, 520, t_index0=1.0)
     _same(g, h, what="quad-tank snippet vs host")
     # the pendulum: per-filter parameters, every weight set of the CPU test
     pid = _capi.model_compile(UM.PENDULUM_SRC, 2, 1)
-    pend = []
-    for k in range(100):
-        m = uc.pendulum_model()
-        m.qt[0], m.qt[1] = 9.81 * (1 + 0.002 * k), 0.05 + 0.001 * (k % 10)
-        pend.append(m)
+    pend = kg.pendulum_models(100)
     U, Y = uc.pendulum_data(300)
     Y = Y.copy()
     Y[[3, 256], 0] = np.nan
     for w in (uc.merwe(2, 1.0, 0.0, 1.0), uc.merwe(2, 1.0, 0.0, 0.0), uc.merwe(2, *uc.SMALL_ALPHA)):
-        g = _bank([_with_id(m, pid) for m in pend], w).run(U, Y, outputs=OUTS)
+        g = _bank([with_id(m, pid) for m in pend], w).run(U, Y, outputs=OUTS)
         h, _ = uc.host_run(host, pend, w, U, Y, 300, twin=uc.TWIN_PENDULUM)
         _same(g, h, what=("pendulum", w))
         assert np.isfinite(g["ll"]).all()
     # f(x) = x, g(x) = x0^2: as a snippet and as a traced Python callable
-    g_ = S.make_gaussian
-    sq = [S.make_lg_model(np.eye(1), np.zeros((1, 0)), np.eye(1), g_(np.zeros(1), 0.1), g_(np.zeros(1), 0.25), g_(np.array([1.0 + 0.01 * k]), 0.36))
-          for k in range(64)]
+    sq = kg.square_models(64)
     Y = 3.0 + 0.5 * rng.standard_normal((80, 1))
     w = uc.merwe(1, 1.0, 0.0, 1.0)
     h, _ = uc.host_run(host, sq, w, None, Y, 80, twin=uc.TWIN_SQUARE)
     sid = _capi.model_compile(uc.SQUARE_SRC, 1, 1)
-    g = _bank([_with_id(m, sid) for m in sq], w).run(None, Y, outputs=OUTS)
+    g = _bank([with_id(m, sid) for m in sq], w).run(None, Y, outputs=OUTS)
     _same(g, h, what="square snippet")
     ukf = llpf_amd.UnscentedKalmanFilter(lambda x, u, p, t: [x[0]], lambda x, u, p, t: [x[0] * x[0]], 0.1, 0.25,
                                          llpf_amd.MvNormal(np.array([1.0]), 0.36), nu=0, ny=1, weight_params=w)
@@ -139,45 +110,15 @@ def test_runtime_compiled_shapes(host):
 @pytest.mark.parametrize("F", [1, 63, 64, 65, 1000])
 def test_bank_sizes_and_chunk_edges(host, F):
     """per-filter parameters at every bank size around the wave, T around the 256-step chunk of the staging pipe"""
-    rng = np.random.default_rng(100 + F)
-    models = _lg_models(rng, F, 2, 1, 1)
-    U, Y = _data(rng, 700, 1, 1, missing=(0, 255, 256, 699))
-    b = _bank(models, W1)
-    for T in (1, 255, 256, 257, 700):
-        b.reset()
-        g = b.run(U[:T], Y[:T], outputs=OUTS)
-        h, st = uc.host_run(host, models, W1, U[:T], Y[:T], T)
-        _same(g, h, what=(F, T))
-        x, R = b.get_state()
-        assert kc.bits_equal(x, st[0]) and kc.bits_equal(R, st[1]), (F, T, "final state")
+    kg.check_bank_sizes_and_chunk_edges(_family(W1), host, seed=100 + F, F=F, nx=2, ny=1, nu=1, missing=(0, 255, 256, 699),
+                                        Ts=(1, 255, 256, 257, 700))
 
 
 def test_continuation_set_models_set_weights_and_state(host):
-    rng = np.random.default_rng(5)
-    models = _lg_models(rng, 300, 3, 2, 2)
-    U, Y = _data(rng, 600, 2, 2, missing=(255, 256, 500))
-    W3 = uc.merwe(3, 1.0, 0.0, 0.0)
-    b = _bank(models, W3)
-    whole = b.run(U, Y, outputs=OUTS)
-    b.reset()
-    first = b.run(U[:300], Y[:300], outputs=OUTS)
-    x, R = b.get_state()
-    second = b.run(U[300:], Y[300:], outputs=OUTS, t_index0=300.0)
-    for k in OUTS:
-        assert kc.bits_equal(np.concatenate([first[k], second[k]]), whole[k]), k
-    h2, _ = uc.host_run(host, models, W3, U[300:], Y[300:], 300, state=(x, R), t_index0=300.0)
-    _same(second, h2, what="second half")
-    fresh = _bank(models, W3)
-    fresh.set_state(x, R)
-    xs, Rs = fresh.get_state()
-    assert kc.bits_equal(xs, x) and kc.bits_equal(np.tril(Rs), np.tril(R))
-    again = fresh.run(U[300:], Y[300:], outputs=OUTS, t_index0=300.0)
-    _same(again, second, what="set_state")
-    b.reset()
-    bare = b.run(U, Y)                                  # ll only: nothing is staged per step
-    assert kc.bits_equal(bare["ll"], whole["ll"])
+    rng, b, U, Y = kg.check_continuation(_family(uc.merwe(3, 1.0, 0.0, 0.0)), host, seed=5, F=300, T=600, nx=3, ny=2, nu=2,
+                                        missing=(255, 256, 500), cut=300)
     # set_models / set_weights = a fresh bank
-    other = _lg_models(rng, 300, 3, 2, 2)
+    other = lg_models(rng, 300, 3, 2, 2)
     W2 = uc.merwe(3, 1.0, 0.0, 1.0)
     b.set_models(other)
     b.set_weights(W2)
@@ -188,47 +129,18 @@ def test_continuation_set_models_set_weights_and_state(host):
     h, _ = uc.host_run(host, other, W2, U, Y, 600)
     _same(g, h, what="set_models + set_weights vs host")
     with pytest.raises(_capi.LLPFError):
-        b.set_models(_lg_models(rng, 300, 2, 2, 2))
+        b.set_models(lg_models(rng, 300, 2, 2, 2))
     with pytest.raises(_capi.LLPFError):
         b.set_weights((1.0, 0.0, 0.0, -1.0))
 
 
 def test_per_filter_inputs_missing_rows_and_a_nan_filter_beside_healthy_ones(host):
-    rng = np.random.default_rng(6)
-    models = _lg_models(rng, 130, 2, 1, 1)
-    U = rng.standard_normal((130, 40, 1))
-    Y = 2.0 * rng.standard_normal((130, 40, 1))
-    Y[:, [5, 6, 30], 0] = np.nan
-    Y[::7, 11, 0] = np.nan
-    b = _bank(models, W1)
-    x, R = b.get_state()
-    ok = b.run(U, Y, True, True, outputs=OUTS)
-    assert np.all(ok["ll_steps"][[5, 6, 30]] == 0.0) and np.all(np.isnan(ok["e"][[5, 6, 30]]))
-    h, _ = uc.host_run(host, models, W1, U, Y, 40, per_filter=3)
-    _same(ok, h, what="per-filter inputs")
-    R[77] = -100.0 * np.eye(2)
-    b.set_state(x, R)
-    bad = b.run(U, Y, True, True, outputs=OUTS)
-    assert np.isnan(bad["ll"][77]) and np.all(np.isnan(bad["xt"][:, 77])) and np.all(np.isnan(bad["R"][1:, 77]))
-    assert np.all(bad["ll_steps"][[5, 6, 30], 77] == 0.0)
-    keep = [f for f in range(130) if f != 77]
-    for k in OUTS:
-        assert kc.bits_equal(bad[k][:, keep], ok[k][:, keep]), k
-    hb, _ = uc.host_run(host, models, W1, U, Y, 40, per_filter=3, state=(x, R))
-    _same(bad, hb, what="NaN filter")
-
-
-def _quadtank_specs(n):
-    specs = []
-    for k in range(n):
-        specs.append((llpf_amd.QuadTankDynamics(supersample=2, gamma1=0.2 + 0.01 * k), llpf_amd.QuadTankMeasurement(),
-                      llpf_amd.MvNormal(np.zeros(4), np.full(4, 0.1)), llpf_amd.MvNormal(np.zeros(2), np.full(2, 1e-4)),
-                      llpf_amd.MvNormal(np.array([2.0, 2.0, 3.0, 3.0]), np.full(4, 0.1))))
-    return specs
+    kg.check_per_filter_inputs_and_a_nan_filter(_family(W1), host, seed=6, F=130, T=40, nx=2, ny=1, nu=1, missing=(5, 6, 30), stride=7, row=11,
+                                                nan_filter=77)
 
 
 def test_python_api_from_filter_bank_equals_a_loop_of_single_filters(host):
-    specs = _quadtank_specs(6)
+    specs = kg.quadtank_specs(6)
     U, Y = M.quadtank_data(300)
     pf = llpf_amd.FilterBank(1000, specs, rng=3)
     ub = llpf_amd.UnscentedKalmanFilterBank.from_filter_bank(pf)
@@ -268,14 +180,8 @@ def test_python_api_from_filter_bank_equals_a_loop_of_single_filters(host):
 def test_ukf_bank_on_the_linear_c1_model_is_the_kalman_bank():
     """the statistical tie to the rest of the project: on the linear-Gaussian C1 model the UKF bank's log-likelihood equals
     KalmanFilterBank's to 1e-10 relative, on the device"""
-    specs = []
-    for k in range(16):
-        model = M.lg_c1_model(seed=k)
-        mt = kc.matrices(model, np.zeros((2, 2)))
-        specs.append((llpf_amd.LinearDynamics(mt["A"], mt["B"]), llpf_amd.LinearMeasurement(mt["C"]), llpf_amd.MvNormal(np.zeros(2), mt["R1"]),
-                      llpf_amd.MvNormal(np.zeros(2), mt["R2"]), llpf_amd.MvNormal(mt["x0"], mt["P0"])))
     _, U, Y = M.simulate_lg(M.lg_c1_model(0), 200)
-    pf = llpf_amd.FilterBank(1000, specs, rng=1)
+    pf = llpf_amd.FilterBank(1000, kg.c1_specs(16), rng=1)
     kb = llpf_amd.KalmanFilterBank.from_filter_bank(pf).loglik(U, Y)
     for wp in (None, llpf_amd.MerweParams(1.0, 0.0, 1.0), llpf_amd.WikiParams(1.0, 0.0, 1.0)):
         ub = llpf_amd.UnscentedKalmanFilterBank.from_filter_bank(pf, weight_params=wp).loglik(U, Y)

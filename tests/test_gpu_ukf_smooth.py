@@ -3,24 +3,22 @@ the GPU reproduces the host build of csrc/shared/llpf_ukf.h (tests/ukf_host.c ar
 functions) bit for bit in every output — smoothed and forward, precompiled and run-time compiled models, whatever the bank, the chunking
 of T or the split of a run — the state after a smooth is the state after a run, and the Python API is the smoother the CPU tests pin
 down."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import llpf_amd
-from llpf_amd import _capi, _structs as S
-from gpu_common import _Inject
+from llpf_amd import _capi
 import kalman_common as kc
 import models as M
 import ukf_common as uc
 import ukf_smooth_common as us
 import user_models as UM
 from kalman_common import _data, _same
-from test_gpu_ukf import OUTS, W1, _bank, _lg_models, _quadtank_models, _quadtank_specs, _with_id
+import kf_gpu_frame as kg
+from kf_gpu_frame import OUTS, SOUTS, lg_models, quadtank_models, with_id
+from test_gpu_ukf import W1, _bank, _family as _ukf_family
 
 pytestmark = pytest.mark.gpu
-SOUTS = ("xT", "RT")
 ALL = OUTS + SOUTS + ("ll",)
 
 
@@ -34,11 +32,16 @@ def hsmooth(tmp_path_factory):
     return us.build_host_smooth(tmp_path_factory.mktemp("ukf_smooth_host"))
 
 
-def _host(host, hsmooth, models, w, U, Y, T, per_filter=0, t_index0=0.0, state=None, twin=0):
+def _family(w):
+    """the unscented bank with the weights w, and its smoother"""
+    def host_smooth(L, models, U, fw, T, per_filter=0, t_index0=0.0, state=None, twin=0):
+        return us.host_smooth(L, models, w, U, fw, T, per_filter=per_filter & 1, t_index0=t_index0, twin=twin)
+    return _ukf_family(w)._replace(host_smooth=host_smooth)
+
+
+def _host(host, hsmooth, models, w, U, Y, T, **kw):
     """the host build of the forward pass and of the smoother over its outputs: every output of a smooth, and the final state"""
-    h, st = uc.host_run(host, models, w, U, Y, T, per_filter=per_filter, t_index0=t_index0, state=state, twin=twin)
-    h.update(us.host_smooth(hsmooth, models, w, U, h, T, per_filter=per_filter & 1, t_index0=t_index0, twin=twin))
-    return h, st
+    return kg.twin(_family(w), (host, hsmooth), models, U, Y, T, **kw)
 
 
 @pytest.mark.parametrize("nx", range(1, 5))
@@ -48,18 +51,10 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
     for ny in range(1, 5):
         rng = np.random.default_rng(10 * nx + ny)
         nu = int(rng.integers(0, 4))
-        models = _lg_models(rng, 1000, nx, ny, nu)
-        U, Y = _data(rng, 200, nu, ny, missing=(50, 51, 120, 199))
-        w = (uc.merwe_set(nx, uc.ALPHA1_SETS[(nx + ny) % 3]), uc.merwe(nx, *uc.SMALL_ALPHA))[ny == 4]
-        b = _bank(models, w)
-        g = b.smooth(U, Y, forward=OUTS)
-        h, _ = _host(host, hsmooth, models, w, U, Y, 200)
-        _same(g, h, ALL, what=(nx, ny))
+        fam = _family((uc.merwe_set(nx, uc.ALPHA1_SETS[(nx + ny) % 3]), uc.merwe(nx, *uc.SMALL_ALPHA))[ny == 4])
+        b, g, _, _, U, Y = kg.check_shape(fam, (host, hsmooth), rng, F=1000, T=200, nx=nx, ny=ny, nu=nu, missing=(50, 51, 120, 199), what=(nx, ny))
         assert not np.isnan(g["xT"]).any() and not np.isnan(g["RT"]).any()
-        b.reset()
-        gp = b.smooth(np.broadcast_to(U, (1000,) + U.shape), np.broadcast_to(Y, (1000,) + Y.shape), u_per_filter=nu > 0, y_per_filter=True,
-                      forward=OUTS)
-        _same(gp, g, ALL, what=(nx, ny, "per-filter"))
+        kg.check_broadcast_inputs(fam, b, g, U, Y, F=1000, nu=nu, what=(nx, ny, "per-filter"))
         b.close()
 
 
@@ -67,7 +62,7 @@ def test_quadtank_across_the_switch_time(host, hsmooth):
     """the 17th precompiled shape: the built-in quad-tank with per-filter parameters, F = 1000, T = 200 with missing rows; and T = 700 from
     t_index0 = 1 (tau crosses TSWITCH = 500; three chunks): the device's RK4 in the oracle's order, forward and backward"""
     w = uc.merwe(4, 1.0, 0.0, 1.0)
-    models = _quadtank_models(1000)
+    models = quadtank_models(1000)
     U, Y = M.quadtank_data(200)
     Y = Y.copy()
     Y[[5, 77, 199], 0] = np.nan
@@ -75,7 +70,7 @@ def test_quadtank_across_the_switch_time(host, hsmooth):
     h, _ = _host(host, hsmooth, models, w, U, Y, 200, t_index0=1.0)
     _same(g, h, ALL, what="quad-tank F = 1000")
     F, T = 65, 700
-    models = _quadtank_models(F)
+    models = quadtank_models(F)
     U, Y = M.quadtank_data(T)
     Y = Y.copy()
     Y[[5, 256, 600], 0] = np.nan
@@ -91,46 +86,36 @@ def test_runtime_compiled_shapes(host, hsmooth):
     built-in quad-tank's bits), the pendulum, the x0^2 model as a snippet and as a traced Python callable"""
     rng = np.random.default_rng(21)
     for nx, ny, nu in ((5, 1, 0), (6, 3, 2), (8, 4, 1)):
-        models = _lg_models(rng, 130, nx, ny, nu)
-        U, Y = _data(rng, 60, nu, ny, missing=(7,))
-        w = uc.merwe(nx, 1.0, 0.0, 1.0)
-        g = _bank(models, w).smooth(U, Y, forward=OUTS)
-        h, _ = _host(host, hsmooth, models, w, U, Y, 60)
-        _same(g, h, ALL, what=("LG", nx, ny))
+        kg.check_shape(_family(uc.merwe(nx, 1.0, 0.0, 1.0)), (host, hsmooth), rng, F=130, T=60, nx=nx, ny=ny, nu=nu, missing=(7,),
+                       what=("LG", nx, ny))
     # the quad-tank as a snippet
     qid = _capi.model_compile(UM.QUADTANK_SRC, 4, 2)
-    models = _quadtank_models(70)
+    models = quadtank_models(70)
     U, Y = M.quadtank_data(520)
     w = uc.merwe(4, 1.0, 0.0, 1.0)
-    g = _bank([_with_id(m, qid) for m in models], w).smooth(U, Y, forward=OUTS, t_index0=1.0)
+    g = _bank([with_id(m, qid) for m in models], w).smooth(U, Y, forward=OUTS, t_index0=1.0)
     gb = _bank(models, w).smooth(U, Y, forward=OUTS, t_index0=1.0)
     _same(g, gb, ALL, what="quad-tank snippet vs built-in")
     h, _ = _host(host, hsmooth, models, w, U, Y, 520, t_index0=1.0)
     _same(g, h, ALL, what="quad-tank snippet vs host")
     # the pendulum: per-filter parameters, every weight set of the CPU test
     pid = _capi.model_compile(UM.PENDULUM_SRC, 2, 1)
-    pend = []
-    for k in range(100):
-        m = uc.pendulum_model()
-        m.qt[0], m.qt[1] = 9.81 * (1 + 0.002 * k), 0.05 + 0.001 * (k % 10)
-        pend.append(m)
+    pend = kg.pendulum_models(100)
     U, Y = uc.pendulum_data(300)
     Y = Y.copy()
     Y[[3, 256], 0] = np.nan
     for w in (uc.merwe(2, 1.0, 0.0, 1.0), uc.merwe(2, 1.0, 0.0, 0.0), uc.merwe(2, *uc.SMALL_ALPHA)):
-        g = _bank([_with_id(m, pid) for m in pend], w).smooth(U, Y, forward=OUTS)
+        g = _bank([with_id(m, pid) for m in pend], w).smooth(U, Y, forward=OUTS)
         h, _ = _host(host, hsmooth, pend, w, U, Y, 300, twin=uc.TWIN_PENDULUM)
         _same(g, h, ALL, what=("pendulum", w))
         assert not np.isnan(g["xT"]).any()
     # f(x) = x, g(x) = x0^2: as a snippet and as a traced Python callable
-    g_ = S.make_gaussian
-    sq = [S.make_lg_model(np.eye(1), np.zeros((1, 0)), np.eye(1), g_(np.zeros(1), 0.1), g_(np.zeros(1), 0.25), g_(np.array([1.0 + 0.01 * k]), 0.36))
-          for k in range(64)]
+    sq = kg.square_models(64)
     Y = 3.0 + 0.5 * rng.standard_normal((80, 1))
     w = uc.merwe(1, 1.0, 0.0, 1.0)
     h, _ = _host(host, hsmooth, sq, w, None, Y, 80, twin=uc.TWIN_SQUARE)
     sid = _capi.model_compile(uc.SQUARE_SRC, 1, 1)
-    g = _bank([_with_id(m, sid) for m in sq], w).smooth(None, Y, forward=OUTS)
+    g = _bank([with_id(m, sid) for m in sq], w).smooth(None, Y, forward=OUTS)
     _same(g, h, ALL, what="square snippet")
     ukf = llpf_amd.UnscentedKalmanFilter(lambda x, u, p, t: [x[0]], lambda x, u, p, t: [x[0] * x[0]], 0.1, 0.25,
                                          llpf_amd.MvNormal(np.array([1.0]), 0.36), nu=0, ny=1, weight_params=w)
@@ -144,24 +129,15 @@ def test_runtime_compiled_shapes(host, hsmooth):
 def test_bank_sizes_and_chunk_edges(host, hsmooth, F):
     """per-filter parameters at every bank size around the wave, T around the 256-step chunk of the staging pipe; the state after a smooth
     is the state after a run"""
-    rng = np.random.default_rng(100 + F)
-    models = _lg_models(rng, F, 2, 1, 1)
-    U, Y = _data(rng, 700, 1, 1, missing=(0, 255, 256, 699))
-    b = _bank(models, W1)
-    for T in (1, 255, 256, 257, 700):
-        b.reset()
-        g = b.smooth(U[:T], Y[:T], forward=OUTS)
-        h, st = _host(host, hsmooth, models, W1, U[:T], Y[:T], T)
-        _same(g, h, ALL, what=(F, T))
-        x, R = b.get_state()
-        assert kc.bits_equal(x, st[0]) and kc.bits_equal(R, st[1]), (F, T, "final state")
+    kg.check_bank_sizes_and_chunk_edges(_family(W1), (host, hsmooth), seed=100 + F, F=F, nx=2, ny=1, nu=1, missing=(0, 255, 256, 699),
+                                        Ts=(1, 255, 256, 257, 700))
 
 
 def test_chunks_are_invisible(host, hsmooth):
     """T = 1000 with shared inputs (four chunks); 4000 filters with per-filter U, where the backward pipe — which stages U and the smoothed
     outputs only — cuts T into other chunks than the forward one; a prefix smoothed on its own equals the host smoother of that prefix"""
     rng = np.random.default_rng(7)
-    models = _lg_models(rng, 200, 3, 2, 2)
+    models = lg_models(rng, 200, 3, 2, 2)
     U, Y = _data(rng, 1000, 2, 2, missing=(255, 256, 511, 999))
     W3 = uc.merwe(3, 1.0, 0.0, 1.0)
     b = _bank(models, W3)
@@ -179,7 +155,7 @@ def test_chunks_are_invisible(host, hsmooth):
     only = b.smooth(U, Y, outputs=("xT",))
     assert kc.bits_equal(only["xT"], g["xT"]) and kc.bits_equal(only["ll"], g["ll"])
     F = 4000
-    models = _lg_models(rng, F, 2, 1, 1)
+    models = lg_models(rng, F, 2, 1, 1)
     T = 600
     Up = rng.standard_normal((F, T, 1))
     _, Y = _data(rng, T, 1, 1, missing=(100, 599))
@@ -192,7 +168,7 @@ def test_chunks_are_invisible(host, hsmooth):
 def test_state_after_smooth_continuation_set_models_and_set_weights(host, hsmooth):
     """the state after smooth is the state after run; a smooth that continues a run with the matching t_index0 smooths the steps it was
     given; set_weights / set_models between calls = a fresh bank"""
-    models = _quadtank_models(100)
+    models = quadtank_models(100)
     U, Y = M.quadtank_data(620)
     W4 = uc.merwe(4, 1.0, 0.0, 1.0)
     b = _bank(models, W4)
@@ -217,7 +193,7 @@ def test_state_after_smooth_continuation_set_models_and_set_weights(host, hsmoot
     x2, R2 = b.get_state()
     assert kc.bits_equal(x2, xs) and kc.bits_equal(R2, Rs) and kc.bits_equal(x2, st[0])
     # set_models / set_weights = a fresh bank
-    other = _quadtank_models(150)[50:]
+    other = quadtank_models(150)[50:]
     W2 = uc.merwe(4, 1.0, 0.0, 0.0)
     b.set_models(other)
     b.set_weights(W2)
@@ -231,7 +207,7 @@ def test_state_after_smooth_continuation_set_models_and_set_weights(host, hsmoot
 
 def test_a_filters_bits_do_not_depend_on_the_bank_and_nan_stays_home(host, hsmooth):
     rng = np.random.default_rng(6)
-    models = _lg_models(rng, 130, 2, 1, 1)
+    models = lg_models(rng, 130, 2, 1, 1)
     U = rng.standard_normal((130, 40, 1))
     Y = 2.0 * rng.standard_normal((130, 40, 1))
     Y[:, [5, 6, 30], 0] = np.nan
@@ -257,54 +233,15 @@ def test_a_filters_bits_do_not_depend_on_the_bank_and_nan_stays_home(host, hsmoo
 
 
 def test_a_throw_and_a_refused_allocation_leave_a_usable_handle():
-    rng = np.random.default_rng(45)
-    models = _lg_models(rng, 64, 2, 1, 0)
-    U, Y = _data(rng, 50, 0, 1)
-    b = _bank(models, W1)
-    ref = b.smooth(None, Y)
-    b.reset()
-    xi, Ri = b.get_state()
-    with _Inject("error:ukf_smooth"):
-        with pytest.raises(_capi.LLPFError) as ei:
-            b.smooth(None, Y)
-    assert ei.value.code == _capi.ERR_INTERNAL
-    x0, R0 = b.get_state()
-    assert kc.bits_equal(x0, xi) and kc.bits_equal(R0, Ri)
-    again = b.smooth(None, Y)
-    _same(again, ref, SOUTS + ("ll",), "after a throw")
     # 2^40 steps: the stored posterior alone is beyond the device; refused by its allocation before any launch, the state untouched
-    b.reset()
-    b.run(None, Y[:10])
-    x1, R1 = b.get_state()
-    L = _capi.lib()
-    out = S.KalmanSmoothOutputs()
-    out.struct_size = C.sizeof(S.KalmanSmoothOutputs)
-    xT = np.zeros(4)
-    out.xT = _capi.dptr(xT)
-    ll = np.zeros(64)
-    rc = L.llpf_ukf_bank_smooth(b.h, None, _capi.dptr(Y), C.c_int64(1 << 40), 0, 0.0, _capi.dptr(ll), None, C.byref(out))
-    assert rc == _capi.ERR_ALLOC, rc
-    x2, R2 = b.get_state()
-    assert kc.bits_equal(x1, x2) and kc.bits_equal(R1, R2) and np.all(xT == 0.0)
-    b.reset()
-    _same(b.smooth(None, Y), ref, SOUTS + ("ll",), "after a refused allocation")
-
-
-def _c1_specs(n):
-    specs = []
-    for k in range(n):
-        model = M.lg_c1_model(seed=k)
-        mt = kc.matrices(model, np.zeros((2, 2)))
-        specs.append((llpf_amd.LinearDynamics(mt["A"], mt["B"]), llpf_amd.LinearMeasurement(mt["C"]), llpf_amd.MvNormal(np.zeros(2), mt["R1"]),
-                      llpf_amd.MvNormal(np.zeros(2), mt["R2"]), llpf_amd.MvNormal(mt["x0"], mt["P0"])))
-    return specs
+    kg.check_throw_and_refused_allocation(_family(W1), seed=45, F=64, T=50, nx=2, ny=1, nu=0, short=10, huge=1 << 40)
 
 
 def test_ukf_bank_smooth_on_the_linear_c1_model_is_the_kalman_banks():
     """the statistical tie to the rest of the project: on the linear-Gaussian C1 model the unscented bank's smoothed estimates equal
     KalmanFilterBank.smooth's to 1e-10 relative, on the device"""
     _, U, Y = M.simulate_lg(M.lg_c1_model(0), 200)
-    pf = llpf_amd.FilterBank(1000, _c1_specs(16), rng=1)
+    pf = llpf_amd.FilterBank(1000, kg.c1_specs(16), rng=1)
     kb = llpf_amd.KalmanFilterBank.from_filter_bank(pf).smooth(U, Y)
     for wp in (None, llpf_amd.MerweParams(1.0, 0.0, 1.0), llpf_amd.WikiParams(1.0, 0.0, 1.0)):
         ub = llpf_amd.UnscentedKalmanFilterBank.from_filter_bank(pf, weight_params=wp).smooth(U, Y)
@@ -318,7 +255,7 @@ def test_ukf_bank_smooth_on_the_linear_c1_model_is_the_kalman_banks():
 def test_python_api(host, hsmooth):
     """smooth(ukf, u, y) against the bank column; its forward fields bit-equal to forward_trajectory; from_filter_bank(...).smooth against
     a loop of single filters"""
-    specs = _quadtank_specs(6)
+    specs = kg.quadtank_specs(6)
     U, Y = M.quadtank_data(300)
     pf = llpf_amd.FilterBank(1000, specs, rng=3)
     ub = llpf_amd.UnscentedKalmanFilterBank.from_filter_bank(pf)
@@ -357,7 +294,7 @@ def test_smoothing_lowers_the_error_on_pendulum_data():
     pid = _capi.model_compile(UM.PENDULUM_SRC, 2, 1)
     for abk in uc.ALPHA1_SETS + (uc.SMALL_ALPHA,):
         w = uc.merwe_set(2, abk)
-        r = _bank([_with_id(m, pid)], w).smooth(U, Y, forward=("xt",))
+        r = _bank([with_id(m, pid)], w).smooth(U, Y, forward=("xt",))
         mse_f = float(np.mean((r["xt"][:, 0] - X) ** 2))
         mse_s = float(np.mean((r["xT"][:, 0] - X) ** 2))
         print("pendulum", abk, "filtered mse %.3e smoothed mse %.3e" % (mse_f, mse_s))

@@ -17,7 +17,7 @@ import models as M
 import ukf_common as uc
 from test_ukf import linear_systems, T_LIN
 
-OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTPUTS = _capi.KALMAN_OUTPUTS
 
 
 @pytest.fixture(scope="module")

@@ -129,7 +129,7 @@ def test_host_header_is_the_references_kalman_filter(host, nx):
             U, Y = kc.simulate(rng, mats, 40, missing=(3, 17, 18))
             h, _ = kc.host_run(host, [(m, D)], U, Y, 40)
             ref = kc.numpy_reference(mats, U, Y)
-            for k in ("ll_steps", "x", "xt", "R", "Rt", "e"):
+            for k in _capi.KALMAN_OUTPUTS:
                 assert kc.close(h[k][:, 0], ref[k]), (nx, ny, kind, k)
             assert abs(h["ll"][0] - ref["ll"]) <= 1e-10 * abs(ref["ll"]), (nx, ny, kind)
             assert np.all(h["ll_steps"][[3, 17, 18], 0] == 0.0) and np.all(np.isnan(h["e"][[3, 17, 18], 0]))
@@ -158,7 +158,7 @@ def test_host_header_per_filter_inputs_and_continuation(host):
         assert kc.bits_equal(shared[k], per[k]), k
     a, st = kc.host_run(host, systems, U[:12], Y[:12], 12)
     b, _ = kc.host_run(host, systems, U[12:], Y[12:], 18, state=st)
-    for k in ("ll_steps", "x", "xt", "R", "Rt", "e"):
+    for k in _capi.KALMAN_OUTPUTS:
         assert kc.bits_equal(np.concatenate([a[k], b[k]]), shared[k]), k
 
 

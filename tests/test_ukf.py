@@ -13,7 +13,7 @@ import models as M
 import ukf_common as uc
 import user_models as UM
 
-OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTPUTS = _capi.KALMAN_OUTPUTS
 T_LIN = 200
 MISSING = (17, 120)
 

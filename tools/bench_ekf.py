@@ -30,7 +30,7 @@ import kalman_common as kc  # noqa: E402
 import models as M  # noqa: E402
 import ukf_common as uc  # noqa: E402
 
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTS = _capi.KALMAN_OUTPUTS
 
 
 def quadtank_models(n):

@@ -21,7 +21,7 @@ from llpf_amd import _capi, _structs as S  # noqa: E402
 import models as M  # noqa: E402
 import ukf_common as uc  # noqa: E402
 
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTS = _capi.KALMAN_OUTPUTS
 
 
 def quadtank_models(n):

@@ -23,7 +23,7 @@ from llpf_amd import _capi  # noqa: E402
 import kalman_common as kc  # noqa: E402
 import kalman_smooth_common as ks  # noqa: E402
 
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTS = _capi.KALMAN_OUTPUTS
 
 
 def main():

@@ -27,7 +27,7 @@ import models as M  # noqa: E402
 import ukf_common as uc  # noqa: E402
 import ukf_smooth_common as us  # noqa: E402
 
-OUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")
+OUTS = _capi.KALMAN_OUTPUTS
 
 
 def quadtank_models(n):
