@@ -422,6 +422,45 @@ int  llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double*
 int  llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R);
 int  llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R);
 
+/* ---- banks of interacting-multiple-model (IMM) filters over Kalman filters (the reference's IMM(models, P, mu), src/imm.jl) ---------------
+ * n_filters independent IMM filters of n_modes modes each (1 <= n_modes <= 4), one GPU lane per (filter, mode), in the operation order of
+ * csrc/shared/llpf_imm.h (that header is the definition: a host build of it gives the same bits).  The recursion is the textbook one
+ * (Blom & Bar-Shalom); it was not checked against the reference's source.  There is no smoother, and no nonlinear modes: every mode is a
+ * Kalman filter with constant matrices as llpf_kalman_bank_create takes it (LLPF_MODEL_LINEAR_GAUSSIAN, nx <= 8, ny <= 4, nu <= 8, the
+ * same for every mode of every filter).  models [F][M]; D [F][M][ny][nu] or NULL (zero); P [F][M][M] row-stochastic, P_ij from mode i to
+ * mode j; mu0 [F][M] the initial mode probabilities; flags bit 0 (LLPF_IMM_INTERACT): the modes mix after every step.  LLPF_ERR_ARG, the
+ * message naming filter and mode: n_modes outside 1..4, dimensions that differ between modes, a negative entry of P or mu0, a row of P
+ * or a mu0 whose sum differs from 1 by more than 1e-12, and whatever llpf_kalman_bank_create refuses.
+ * Step t of a run: the combined prior x[t], R[t] (x = sum_j mu_j x_j, R = sum_j mu_j (R_j + (x_j - x)(x_j - x)')); correct! of every
+ * mode, ll_j; mu_j <- (sum_i P_ij mu_i) exp(ll_j) normalised, ll[t] the log of the normaliser; the combined posterior xt[t], Rt[t]; the
+ * mixing of the modes; predict! of every mode.  A missing row (first element NaN): no correct!, ll[t] = 0, mu_j <- sum_i P_ij mu_i.  An
+ * IMM one of whose modes loses the definiteness of its S is NaN from that step on; the run returns LLPF_OK and the other filters are
+ * unaffected.  The state (every mode's x, R, and mu) carries from run to run: run(a) then run(b) is run(a + b). */
+#define LLPF_IMM_INTERACT 1
+typedef struct llpf_imm_bank llpf_imm_bank;
+typedef struct llpf_imm_outputs {        /* every output optional (NULL); time-major like llpf_kalman_outputs.  No innovation: an IMM has one per mode */
+    uint32_t struct_size;                /* sizeof(llpf_imm_outputs): guards growth */
+    uint32_t pad;
+    double *ll_steps, *x, *xt, *R, *Rt;  /* ll_steps [T][F]; x, xt [T][F][nx]; R, Rt [T][F][nx][nx]: the combined estimate */
+    double *mu, *ll_modes;               /* [T][F][M]: the posterior mode probabilities; every mode's own ll_j */
+} llpf_imm_outputs;
+int  llpf_imm_bank_create(int32_t device, const llpf_model* models, const double* D /* or NULL */, const double* P, const double* mu0,
+                          int32_t n_filters, int32_t n_modes, int32_t flags, llpf_imm_bank** out);
+int  llpf_imm_bank_destroy(llpf_imm_bank* b);
+/* reset!: every mode's x = mean(d0), R = cov(d0); mu = mu0 */
+int  llpf_imm_bank_reset(llpf_imm_bank* b);
+/* new matrices, P and mu0 for every filter (same dimensions, nothing reallocated; the state is left as it is, the next reset uses the new
+ * d0 and mu0) */
+int  llpf_imm_bank_set_models(llpf_imm_bank* b, const llpf_model* models, const double* D, const double* P, const double* mu0);
+/* T steps of every filter; U, Y, per_filter and ll_total as llpf_kalman_bank_run takes them; out NULL: nothing per step is stored (and
+ * nothing is combined) */
+int  llpf_imm_bank_run(llpf_imm_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                       const llpf_imm_outputs* out);
+/* the combined x [F][nx], R [F][nx][nx] (get only), mu [F][M], and every mode's x_modes [F][M][nx], R_modes [F][M][nx][nx]; get: each
+ * may be NULL; set: all three are needed, the lower triangles of R_modes are taken */
+int  llpf_imm_bank_get_state(llpf_imm_bank* b, double* x, double* R, double* mu, double* x_modes, double* R_modes);
+int  llpf_imm_bank_set_state(llpf_imm_bank* b, const double* mu, const double* x_modes, const double* R_modes);
+
 /* ---- banks of unscented Kalman filters (the reference's UnscentedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise) -----
  * n_filters independent unscented Kalman filters, one GPU thread each, in the operation order of csrc/shared/llpf_ukf.h (that header is
  * the definition: a host build of it around the same model functions gives the same bits):

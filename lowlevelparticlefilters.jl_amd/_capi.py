@@ -47,6 +47,13 @@ SYMBOLS = {
     "llpf_kalman_bank_smooth": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.KalmanOutputs), C.POINTER(S.KalmanSmoothOutputs)],
     "llpf_kalman_bank_get_state": [_vp, _dp, _dp],
     "llpf_kalman_bank_set_state": [_vp, _dp, _dp],
+    "llpf_imm_bank_create": [C.c_int32, C.POINTER(S.Model), _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)],
+    "llpf_imm_bank_destroy": [_vp],
+    "llpf_imm_bank_reset": [_vp],
+    "llpf_imm_bank_set_models": [_vp, C.POINTER(S.Model), _dp, _dp, _dp],
+    "llpf_imm_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.ImmOutputs)],
+    "llpf_imm_bank_get_state": [_vp, _dp, _dp, _dp, _dp, _dp],
+    "llpf_imm_bank_set_state": [_vp, _dp, _dp, _dp],
     "llpf_ukf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.POINTER(S.UkfWeights), C.POINTER(_vp)],
     "llpf_ukf_bank_destroy": [_vp],
     "llpf_ukf_bank_reset": [_vp],
@@ -590,6 +597,80 @@ class KalmanBankHandle(_KfBankHandle):
         and RT [T, F, nx, nx] for the names in `outputs` (KALMAN_SMOOTH_OUTPUTS) and the forward outputs named in `forward`
         (KALMAN_OUTPUTS); the state afterwards is the one run() leaves."""
         return self._smooth(U, Y, u_per_filter, y_per_filter, outputs, forward)
+
+
+IMM_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "mu", "ll_modes")
+IMM_INTERACT = 1
+
+
+class IMMBankHandle(_KfBankHandle):
+    """RAII wrapper of an `llpf_imm_bank*` (independent IMM filters of M Kalman-filter modes each on one device, one lane per mode).
+    `models`: [F][M] descriptors (a list of F lists of M), D [F, M, ny, nu] or None, P [F, M, M], mu0 [F, M]."""
+    _SYM = "llpf_imm_bank"
+
+    def __init__(self, device, models, D, P, mu0, interact=True):
+        self.M = len(models[0]) if len(models) else 0
+        if any(len(row) != self.M for row in models):
+            raise ValueError("every filter of an IMM bank has the same number of modes")
+        arr = self._pack(models, first=True)
+        D, P, mu0 = self._tables(D, P, mu0)
+        check(self.L.llpf_imm_bank_create(int(device), arr, dptr(D), dptr(P), dptr(mu0), self.F, self.M, IMM_INTERACT if interact else 0,
+                                          C.byref(self.h)))
+
+    def _pack(self, models, first=False):
+        flat = [m for row in models for m in row]
+        if first:
+            self._open(flat if flat else [S.Model()])
+            self.F = len(models)
+        return (S.Model * max(len(flat), 1))(*flat)
+
+    def _tables(self, D, P, mu0):
+        F, M = self.F, self.M
+        D = None if D is None else f64(D).reshape(F, M, self.ny, self.nu)
+        return D, f64(P).reshape(F, M, M), f64(mu0).reshape(F, M)
+
+    def set_models(self, models, D, P, mu0):
+        arr = self._pack(models)
+        D, P, mu0 = self._tables(D, P, mu0)
+        self._call("set_models", arr, dptr(D), dptr(P), dptr(mu0))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
+        """T steps of every filter; inputs as KalmanBankHandle.run.  Returns {"ll": [F], name: array} for every name of `outputs`
+        (IMM_OUTPUTS), time-major: ll_steps [T, F], x / xt [T, F, nx], R / Rt [T, F, nx, nx] (the combined estimate), mu / ll_modes
+        [T, F, M]."""
+        U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
+        F, nx, M = self.F, self.nx, self.M
+        shapes = {"ll_steps": (T, F), "x": (T, F, nx), "xt": (T, F, nx), "R": (T, F, nx, nx), "Rt": (T, F, nx, nx), "mu": (T, F, M),
+                  "ll_modes": (T, F, M)}
+        res = {k: np.empty(shapes[k]) for k in outputs}
+        out = None
+        if res:
+            out = S.ImmOutputs()
+            out.struct_size = C.sizeof(S.ImmOutputs)
+            for k, a in res.items():
+                setattr(out, k, dptr(a))
+        ll = np.empty(F)
+        self._call("run", dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
+                   None if out is None else C.byref(out))
+        res["ll"] = ll
+        return res
+
+    def get_state(self):
+        """the combined (x [F, nx], R [F, nx, nx])"""
+        return self.get_modes()[:2]
+
+    def get_modes(self):
+        """(x [F, nx], R [F, nx, nx], mu [F, M], x_modes [F, M, nx], R_modes [F, M, nx, nx])"""
+        F, M, nx = self.F, self.M, self.nx
+        x, R, mu = np.empty((F, nx)), np.empty((F, nx, nx)), np.empty((F, M))
+        xm, Rm = np.empty((F, M, nx)), np.empty((F, M, nx, nx))
+        self._call("get_state", dptr(x), dptr(R), dptr(mu), dptr(xm), dptr(Rm))
+        return x, R, mu, xm, Rm
+
+    def set_state(self, mu, x_modes, R_modes):
+        F, M, nx = self.F, self.M, self.nx
+        mu, xm, Rm = f64(mu).reshape(F, M), f64(x_modes).reshape(F, M, nx), f64(R_modes).reshape(F, M, nx, nx)
+        self._call("set_state", dptr(mu), dptr(xm), dptr(Rm))
 
 
 def ukf_weights(w):

@@ -65,6 +65,12 @@ class KalmanSmoothOutputs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_uint32), ("xT", C.POINTER(C.c_double)), ("RT", C.POINTER(C.c_double))]
 
 
+class ImmOutputs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_uint32), ("ll_steps", C.POINTER(C.c_double)), ("x", C.POINTER(C.c_double)),
+                ("xt", C.POINTER(C.c_double)), ("R", C.POINTER(C.c_double)), ("Rt", C.POINTER(C.c_double)), ("mu", C.POINTER(C.c_double)),
+                ("ll_modes", C.POINTER(C.c_double))]
+
+
 class UkfWeights(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_uint32), ("gamma", C.c_double), ("wm0", C.c_double), ("wc0", C.c_double),
                 ("wi", C.c_double)]

@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "IMM", "IMMBank", "IMMFilteringSolution", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -444,6 +444,68 @@ class KalmanSmoothingSolution(KalmanFilteringSolution):
         self.xT, self.RT = xT, RT
 
 
+class IMM:
+    """IMM(models, P, mu; interact, device) — the reference's interacting-multiple-model filter (src/imm.jl) over a list of KalmanFilter
+    of the same dimensions: P [M, M] the row-stochastic transition matrix (P[i, j]: from mode i to mode j), mu [M] the initial mode
+    probabilities, M <= 4.  Runs on the device as a bank of one IMM (llpf_imm_bank_*), created on first use, in the operation order of
+    csrc/shared/llpf_imm.h: the textbook recursion of Blom & Bar-Shalom, not checked against the reference's source.  interact = False:
+    the modes never mix (M independent Kalman filters with a shared mode probability).  There is no smoother."""
+
+    def __init__(self, models, P, mu, *, interact=True, device=0):
+        self.models = list(models)
+        if not self.models or not all(isinstance(m, KalmanFilter) for m in self.models):
+            raise TypeError("IMM: models is a non-empty list of KalmanFilter")
+        self.P, self.mu0 = np.atleast_2d(np.asarray(P, float)), np.atleast_1d(np.asarray(mu, float))
+        self.interact, self.device = bool(interact), int(device)
+        self.Ts = self.models[0].Ts
+        self._handle = None
+
+    def _spec(self):
+        """(models [M], D [M, ny, nu], P, mu0) of this filter"""
+        md = [kf._model() for kf in self.models]
+        return [m for m, _ in md], np.stack([D for _, D in md]), self.P, self.mu0
+
+    @property
+    def _h(self):
+        if self._handle is None:
+            models, D, P, mu0 = self._spec()
+            self._handle = _capi.IMMBankHandle(self.device, [models], D[None], P[None], mu0[None], self.interact)
+        return self._handle
+
+    @property
+    def nx(self):
+        return self.models[0].nx
+
+    @property
+    def x(self):
+        """state(imm): the combined estimate sum_j mu_j x_j"""
+        return self._h.get_state()[0][0]
+
+    @property
+    def R(self):
+        """covariance(imm): the combined covariance sum_j mu_j (R_j + (x_j - x)(x_j - x)')"""
+        return self._h.get_state()[1][0]
+
+    @property
+    def mu(self):
+        """the current mode probabilities [M]"""
+        return self._h.get_modes()[2][0]
+
+    def _run(self, u, y, outputs=()):
+        y = np.asarray(y, dtype=np.float64)
+        y = y.reshape(y.shape[0], -1) if y.ndim else y.reshape(1, 1)
+        return self._h.run(None if self._h.nu == 0 else np.asarray(u, dtype=np.float64).reshape(y.shape[0], -1), y, outputs=outputs)
+
+
+class IMMFilteringSolution(KalmanFilteringSolution):
+    """forward_trajectory(imm, u, y): the fields of a KalmanFilteringSolution for the combined estimate (e is None: an IMM has one
+    innovation per mode), plus mu [T, M], the posterior mode probabilities, and ll_modes [T, M], every mode's own log-likelihood."""
+
+    def __init__(self, f, u, y, x, xt, R, Rt, ll, mu, ll_modes):
+        super().__init__(f, u, y, x, xt, R, Rt, ll, None)
+        self.mu, self.ll_modes = mu, ll_modes
+
+
 def covariance(kf):
     """covariance(kf) — the covariance R of the current estimate of a KalmanFilter, an UnscentedKalmanFilter, an ExtendedKalmanFilter or an
     EnsembleKalmanFilter (its sample covariance)"""
@@ -528,6 +590,42 @@ class KalmanFilterBank(_KfBank):
         """new matrices for every filter (same dimensions, nothing reallocated: llpf_kalman_bank_set_models)"""
         models, Ds = self._models(filters_spec)
         self._h.set_models(models, Ds)
+
+
+class IMMBank(_KfBank):
+    """n independent IMM filters of the same number of modes and the same dimensions on one device, one GPU lane per (filter, mode)
+    (llpf_imm_bank_*): the exact log-likelihood of a switching linear-Gaussian model for every parameter set of a sweep.  `specs` is a
+    list of IMM or of (models, P, mu) tuples (all with the same `interact`, the first one's)."""
+
+    def __init__(self, specs, device=0):
+        models, D, P, mu0, interact = self._pack(specs)
+        self.device = int(device)
+        self._h = _capi.IMMBankHandle(self.device, models, D, P, mu0, interact)
+        self.n_filters = len(models)
+        self.Ts = float(models[0][0].Ts)
+
+    @staticmethod
+    def _pack(specs):
+        imms = [f if isinstance(f, IMM) else IMM(*f) for f in specs]
+        sp = [f._spec() for f in imms]
+        return [s[0] for s in sp], np.stack([s[1] for s in sp]), np.stack([s[2] for s in sp]), np.stack([s[3] for s in sp]), imms[0].interact
+
+    def state(self):
+        """(x [F, nx], R [F, nx, nx], mu [F, M]): the combined estimate and the mode probabilities of every filter"""
+        return self._h.get_modes()[:3]
+
+    def forward(self, u, y, outputs=_capi.IMM_OUTPUTS):
+        """forward_trajectory of every filter: {"ll": [F], "ll_steps": [T, F], "x", "xt": [T, F, nx], "R", "Rt": [T, F, nx, nx], "mu",
+        "ll_modes": [T, F, M]} for the names in `outputs`"""
+        return super().forward(u, y, outputs)
+
+    def smooth(self, u=None, y=None, outputs=None, forward=()):
+        raise TypeError("the IMM filter has no smoother")
+
+    def set_parameters(self, specs):
+        """new matrices, P and mu for every filter (same shapes, nothing reallocated: llpf_imm_bank_set_models)"""
+        models, D, P, mu0, _ = self._pack(specs)
+        self._h.set_models(models, D, P, mu0)
 
 
 class MerweParams:
@@ -1111,6 +1209,9 @@ def update(pf, u, y, *args, **kw):
     if isinstance(pf, KalmanFilter):
         r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], ("e",))
         return float(r["ll"][0]), r["e"][0, 0]
+    if isinstance(pf, IMM):                         # the step of csrc/shared/llpf_imm.h; an IMM has no single innovation
+        r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None])
+        return float(r["ll"][0]), None
     if isinstance(pf, _NonlinearKalmanFilter):
         r = pf._step(u, y, _pt(args, kw, 0)[1], ("e",))
         return float(r["ll"][0]), r["e"][0, 0]
@@ -1131,6 +1232,11 @@ def forward_trajectory(pf, u, y, p=None, quantiles=None):
         reset(pf)
         r = pf._run(u, y, _capi.KALMAN_OUTPUTS)
         return KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
+    if isinstance(pf, IMM):
+        reset(pf)
+        r = pf._run(u, y, _capi.IMM_OUTPUTS)
+        return IMMFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["mu"][:, 0],
+                                    r["ll_modes"][:, 0])
     if isinstance(pf, _NonlinearKalmanFilter):
         reset(pf)
         r = pf._run(u, y, _capi.KALMAN_OUTPUTS, 0.0)
@@ -1150,7 +1256,7 @@ def loglik(pf, u, y, p=None):
     t = index(pf)*Ts, i.e. the first step is at t = 1*Ts); :232-236 for the auxiliary filter (t = (k-1)*Ts, the
     last step is an update! of the wrapped filter).  For a KalmanFilter: reset!, then the sum of T update! steps (exact)."""
     reset(pf)
-    if isinstance(pf, KalmanFilter):
+    if isinstance(pf, (KalmanFilter, IMM)):
         return float(pf._run(u, y)["ll"][0])
     if isinstance(pf, _NonlinearKalmanFilter):      # the first step at t = 1 * Ts, as the particle filters' loglik
         return float(pf._run(u, y, (), 1.0)["ll"][0])
@@ -1386,6 +1492,8 @@ def smooth(pf, *args):
         pf._index += yy.shape[0]
         sol = KalmanFilteringSolution(pf, u, y, r["x"][:, 0], r["xt"][:, 0], r["R"][:, 0], r["Rt"][:, 0], float(r["ll"][0]), r["e"][:, 0])
         return KalmanSmoothingSolution(sol, r["xT"][:, 0], r["RT"][:, 0])
+    if isinstance(pf, IMM):
+        raise TypeError("the IMM filter has no smoother")
     if isinstance(pf, EnsembleKalmanFilter):
         raise TypeError("the ensemble Kalman filter has no smoother")
     if isinstance(pf, ExtendedKalmanFilter):
@@ -1454,7 +1562,7 @@ def expweights(pf):
 
 
 def state(pf):
-    if isinstance(pf, (KalmanFilter, _NonlinearKalmanFilter)):
+    if isinstance(pf, (KalmanFilter, _NonlinearKalmanFilter, IMM)):
         return pf.x
     return pf.state
 

@@ -17,6 +17,7 @@
 #include "engine.hpp"
 #include "shared/llpf_rbkf.h"
 #include "shared/llpf_kalman.h"
+#include "shared/llpf_imm.h"
 #include "shared/llpf_ukf.h"
 #include "shared/llpf_ekf.h"
 #include "shared/llpf_enkf.h"
@@ -102,6 +103,7 @@ static void test_throw(const char* site) {
 #include "host/simulate.hpp"
 #include "host/kfbank.hpp"
 #include "host/kalman.hpp"
+#include "host/imm.hpp"
 #include "host/ukf.hpp"
 #include "host/ekf.hpp"
 #include "host/enkf.hpp"
@@ -231,6 +233,31 @@ int llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double* 
 } LLPF_GUARD(llpf_kalman_bank_smooth)
 int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
 int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
+
+// ---- banks of IMM filters over Kalman filters (host/kfbank.hpp, host/imm.hpp) ----
+int llpf_imm_bank_create(int32_t device, const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t n_filters,
+                         int32_t n_modes, int32_t flags, llpf_imm_bank** out) LLPF_TRY {
+    return make_handle(out, [&](llpf_imm_bank& b) { return imm_create(device, models, D, P, mu0, n_filters, n_modes, flags, b); });
+} LLPF_GUARD(llpf_imm_bank_create)
+int llpf_imm_bank_destroy(llpf_imm_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_imm_bank_destroy)
+int llpf_imm_bank_reset(llpf_imm_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_imm_bank_reset)
+int llpf_imm_bank_set_models(llpf_imm_bank* b, const llpf_model* models, const double* D, const double* P, const double* mu0) LLPF_TRY {
+    NEEDF(b);
+    return imm_set_models(*b, models, D, P, mu0);
+} LLPF_GUARD(llpf_imm_bank_set_models)
+int llpf_imm_bank_run(llpf_imm_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                      const llpf_imm_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return imm_run(*b, U, Y, T, per_filter, ll_total, out);
+} LLPF_GUARD(llpf_imm_bank_run)
+int llpf_imm_bank_get_state(llpf_imm_bank* b, double* x, double* R, double* mu, double* x_modes, double* R_modes) LLPF_TRY {
+    NEEDF(b);
+    return imm_get_state(*b, x, R, mu, x_modes, R_modes);
+} LLPF_GUARD(llpf_imm_bank_get_state)
+int llpf_imm_bank_set_state(llpf_imm_bank* b, const double* mu, const double* x_modes, const double* R_modes) LLPF_TRY {
+    NEEDF(b);
+    return imm_set_state(*b, mu, x_modes, R_modes);
+} LLPF_GUARD(llpf_imm_bank_set_state)
 
 // ---- banks of unscented Kalman filters (host/kfbank.hpp, host/ukf.hpp) ----
 int llpf_ukf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, const llpf_ukf_weights* w, llpf_ukf_bank** out) LLPF_TRY {

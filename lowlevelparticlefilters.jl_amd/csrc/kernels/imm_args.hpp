@@ -1,0 +1,23 @@
+// kernels/imm_args.hpp — arguments of k_imm (kernels/imm.hpp) and its launcher.  Included inside namespace llpf by the two units that
+// know the IMM bank: k_imm.hip (the kernel) and, through host/imm.hpp, capi.hip (the host side); no other unit sees it.
+// One launch is one chunk of steps [t0, t0 + Tc) of F IMM filters of M modes, one lane per (filter, mode): G = 1, 2 or 4 lanes per filter
+// (the smallest G >= M), thread f * G + j is mode j of filter f, the lanes j >= M idle.  L = F * G is the number of columns of the SoA
+// arrays: a lane's column is its thread index.
+struct ImmArgs {
+    const double* par;       // [npar + LLPF_IMM_MAXM][L]: the mode's constant matrices (shared/llpf_kalman.h: LLPF_KF_OFF_*), then column j of
+                             // the filter's transition matrix, P_ij at row npar + i
+    double* state;           // [nx + np + 2][L] the mode's x, packed R and mu_j, the run's running ll_total: in at t0, out at t0 + Tc
+    const double* u;         // inputs of the chunk: [Tc][nu] shared, or [Tc][F][nu] (u_per = 1); unused when nu = 0
+    const double* y;         // measurements of the chunk: [Tc][ny] shared, or [Tc][F][ny] (y_per = 1)
+    double *ll, *x, *xt, *R, *Rt;   // per-step outputs of the chunk, each optional: [Tc][F], [Tc][F][nx], [Tc][F][nx][nx] (the combined estimate)
+    double *mu, *ll_modes;   // ... and [Tc][F][M]: the posterior mode probabilities, every mode's own ll
+    int64_t F;
+    int32_t Tc, nu, M;
+    int32_t u_per, y_per;
+    int32_t first;           // 1: the first chunk of a run (ll_total starts at 0)
+    int32_t interact;        // 1: the modes mix after every step
+    int32_t pad;
+    int64_t par_tstride;     // always 0 (kernels/kalman.hpp: KF_RELOAD)
+};
+// one chunk of steps (k_imm.hip): nx in 1..8, ny in 1..4, g = 1, 2 or 4 lanes per filter (the smallest g >= ImmArgs::M)
+hipError_t launch_imm(int nx, int ny, int g, const ImmArgs& a, hipStream_t s);

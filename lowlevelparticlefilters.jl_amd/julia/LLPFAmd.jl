@@ -38,7 +38,8 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
        GPUKalmanFilter, GPUKalmanFilterBank, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
        ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank, set_iterations!,
-       GPUEnsembleKalmanFilter, GPUEnsembleKalmanFilterBank, set_inflation!, members, set_members!
+       GPUEnsembleKalmanFilter, GPUEnsembleKalmanFilterBank, set_inflation!, members, set_members!,
+       GPUIMM, GPUIMMBank, mode_probabilities, mode_states, set_mode_states!
 
 const LIB = get(ENV, "LLPF_HIP_LIB", joinpath(@__DIR__, "..", "libllpf_hip.so"))
 const MAXD = 16          # LLPF_MAX_DIM: states / outputs
@@ -1099,6 +1100,145 @@ function LowLevelParticleFilters.smooth(kf::GPUKalmanFilter, u, y, p = NullParam
                                   [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
     KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
 end
+
+# ---- banks of IMM filters over Kalman filters (the reference's IMM(models, P, mu), src/imm.jl; csrc/shared/llpf_imm.h is the definition): llpf_imm_bank_* ----
+struct CImmOutputs                    # llpf_imm_outputs
+    struct_size::UInt32
+    pad::UInt32
+    ll_steps::Ptr{Float64}
+    x::Ptr{Float64}
+    xt::Ptr{Float64}
+    R::Ptr{Float64}
+    Rt::Ptr{Float64}
+    mu::Ptr{Float64}
+    ll_modes::Ptr{Float64}
+end
+mutable struct GPUIMMBank
+    h::Ptr{Cvoid}
+    F::Int
+    M::Int
+    nx::Int
+    nu::Int
+    ny::Int
+end
+# (models, P, mu) of every filter -> the descriptors [F][M], D [F][M][ny][nu], P [F][M][M] and mu0 [F][M], row-major
+function imm_tables(filters::Vector, Ts)
+    M = length(filters[1][1])
+    all(length(f[1]) == M for f in filters) || throw(ArgumentError("every filter of an IMM bank has the same number of modes"))
+    cms = [kalman_model(m[1], m[2], m[3], m[5], m[6], m[7], Ts) for f in filters for m in f[1]]
+    Dv = kalman_D([m[4] for f in filters for m in f[1]], cms[1].ny, cms[1].nu)
+    Pv = Float64[f[2][i, j] for f in filters for i in 1:M for j in 1:M]
+    mv = Float64[f[3][j] for f in filters for j in 1:M]
+    M, cms, Dv, Pv, mv
+end
+"""
+    GPUIMMBank(filters; interact = true, Ts = 1.0, device = 0)
+
+Independent interacting-multiple-model filters on the device, one GPU lane per (filter, mode); `filters` is a vector of (models, P, mu)
+tuples: `models` a vector of M <= 4 (A, B, C, D, R1, R2, d0) tuples of the same dimensions, `P` the M x M row-stochastic transition
+matrix (P[i, j]: from mode i to mode j), `mu` the initial mode probabilities.  The recursion is the textbook one (Blom & Bar-Shalom), in
+the operation order of csrc/shared/llpf_imm.h; it was not checked against the reference's `IMM`.  `loglik(bank, u, y)` is the vector of
+every filter's log-likelihood.  There is no smoother.
+"""
+function GPUIMMBank(filters::Vector; interact = true, Ts = 1.0, device = 0)
+    M, cms, Dv, Pv, mv = imm_tables(filters, Ts)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_imm_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
+                device, cms, Dv, Pv, mv, length(filters), M, interact ? 1 : 0, h))
+    b = GPUIMMBank(h[], length(filters), M, cms[1].nx, cms[1].nu, cms[1].ny)
+    finalizer(x -> ccall((:llpf_imm_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    b
+end
+function set_parameters!(b::GPUIMMBank, filters::Vector; Ts = 1.0)
+    M, cms, Dv, Pv, mv = imm_tables(filters, Ts)
+    (length(filters) == b.F && M == b.M) || throw(ArgumentError("set_parameters!: $(length(filters)) filters of $M modes for a bank of $(b.F) of $(b.M)"))
+    check(ccall((:llpf_imm_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, cms, Dv, Pv, mv))
+    b
+end
+reset!(b::GPUIMMBank) = check(ccall((:llpf_imm_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+# u, y: vectors of T vectors shared by every filter (a missing y is `missing` / a NaN first element); returns ll_total and the outputs asked for
+function imm_run(b::GPUIMMBank, u, y; outputs = false)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), mu = zeros(b.M, b.F, T), ll_modes = zeros(b.M, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CImmOutputs(UInt32(sizeof(CImmOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                        pointer(o.R), pointer(o.Rt), pointer(o.mu), pointer(o.ll_modes)))
+        check(ccall((:llpf_imm_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{CImmOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+"loglik(bank, u, y): every filter's log-likelihood of the switching model (reset! first, then T update! steps)"
+loglik(b::GPUIMMBank, u, y) = (reset!(b); imm_run(b, u, y)[1])
+"the combined x (nx x F), R (nx x nx x F) of every filter"
+function state(b::GPUIMMBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_imm_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.h, x, R, C_NULL, C_NULL, C_NULL))
+    x, R
+end
+covariance(b::GPUIMMBank) = state(b)[2]
+"mode_probabilities(bank): mu (M x F)"
+function mode_probabilities(b::GPUIMMBank)
+    mu = zeros(b.M, b.F)
+    check(ccall((:llpf_imm_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.h, C_NULL, C_NULL, mu, C_NULL, C_NULL))
+    mu
+end
+"mode_states(bank): every mode's x (nx x M x F) and R (nx x nx x M x F; symmetric)"
+function mode_states(b::GPUIMMBank)
+    xm = zeros(b.nx, b.M, b.F); Rm = zeros(b.nx, b.nx, b.M, b.F)
+    check(ccall((:llpf_imm_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.h, C_NULL, C_NULL, C_NULL, xm, Rm))
+    xm, Rm
+end
+"set_mode_states!(bank, mu, x, R): mu (M x F), every mode's x (nx x M x F) and R (nx x nx x M x F; its lower triangle is read)"
+function set_mode_states!(b::GPUIMMBank, mu, x, R)
+    mm = Matrix{Float64}(reshape(mu, b.M, b.F)); xm = Array{Float64}(reshape(x, b.nx, b.M, b.F))
+    Rr = permutedims(Array{Float64}(reshape(R, b.nx, b.nx, b.M, b.F)), (2, 1, 3, 4))      # column-major nx x nx = the row-major [nx][nx] of its transpose
+    check(ccall((:llpf_imm_bank_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, mm, xm, Rr))
+    b
+end
+
+"""
+    GPUIMM(models, P, mu; interact = true, Ts = 1.0, device = 0)
+
+The interacting-multiple-model filter over M <= 4 Kalman filters `models` (a vector of (A, B, C, D, R1, R2, d0) tuples), run on the device
+(a bank of one filter, llpf_imm_bank_*): `forward_trajectory` returns a named tuple (x, xt, R, Rt, ll, mu, ll_modes) of the combined
+estimate, the mode probabilities and every mode's own log-likelihood per step; `loglik`, `reset!`, `update!`, `state`, `covariance`,
+`mode_probabilities`.  Unverified against the reference's `IMM` (its source was not available when this was written); no smoother.
+"""
+mutable struct GPUIMM
+    bank::GPUIMMBank
+    Ts::Float64
+end
+GPUIMM(models::Vector, P, mu; interact = true, Ts = 1.0, device = 0) =
+    GPUIMM(GPUIMMBank([(models, P, mu)]; interact = interact, Ts = Ts, device = device), Float64(Ts))
+reset!(f::GPUIMM) = reset!(f.bank)
+loglik(f::GPUIMM, u, y, p = NullParameters()) = loglik(f.bank, u, y)[1]
+"update!(imm, u, y): correct! of every mode, the mode probabilities, the mixing, predict!; returns ll"
+function update!(f::GPUIMM, u, y, p = NullParameters(), t = 0)
+    ll, _ = imm_run(f.bank, [u], [y])
+    ll[1]
+end
+state(f::GPUIMM) = state(f.bank)[1][:, 1]
+covariance(f::GPUIMM) = state(f.bank)[2][:, :, 1]
+mode_probabilities(f::GPUIMM) = mode_probabilities(f.bank)[:, 1]
+function forward_trajectory(f::GPUIMM, u, y, p = NullParameters())
+    reset!(f.bank)
+    ll, o = imm_run(f.bank, u, y; outputs = true)
+    T = length(y)
+    (x = [o.x[:, 1, t] for t in 1:T], xt = [o.xt[:, 1, t] for t in 1:T], R = [o.R[:, :, 1, t] for t in 1:T], Rt = [o.Rt[:, :, 1, t] for t in 1:T],
+     ll = ll[1], mu = [o.mu[:, 1, t] for t in 1:T], ll_modes = [o.ll_modes[:, 1, t] for t in 1:T])
+end
+LowLevelParticleFilters.smooth(f::GPUIMM, args...) = throw(ArgumentError("the IMM filter has no smoother"))
 
 # ---- banks of unscented Kalman filters (the reference's UnscentedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise): llpf_ukf_bank_* ----
 struct CUkfWeights                    # llpf_ukf_weights

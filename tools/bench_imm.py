@@ -1,0 +1,95 @@
+"""The price of the interaction: a bank of F IMM filters of M modes (llpf_imm_bank_run) beside a bank of F * M Kalman filters
+(llpf_kalman_bank_run) — the same correct! / predict! work without the exchange between the lanes of a filter — in one process,
+alternating, for F = 10^4, M in {2, 3, 4}, (nx, ny) in {(2, 1), (4, 2)}, T = 1000, ll_total only, shared U / Y.
+
+Without arguments: the end-to-end wall time of the two calls (median of --reps after one warm-up each), one JSON line per configuration.
+The kernels' own time comes from a run of this script under `rocprofv3 --kernel-trace --output-format csv`, in a run of its own:
+`--trace <kernel_trace.csv>` reads that file, assigns its launches to the runs in the order this script makes them (the k_imm of M = 3 and
+of M = 4 is the same kernel, G = 4: only the order tells them apart; give the --shapes, --modes, --T and --reps of the traced run) and
+prints per configuration the median kernel time of an IMM run, of the Kalman run and their ratio."""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+CHUNK = 256      # host/pipe.hpp: CHUNK_STEPS (shared inputs, no per-step output: a chunk is 256 steps)
+
+
+def configs(a):
+    for shape in a.shapes.split(","):
+        nx, ny = (int(v) for v in shape.split("x"))
+        for M in (int(v) for v in a.modes.split(",")):
+            yield nx, ny, M
+
+
+def measure(a):
+    from llpf_amd import _capi
+    import imm_common as ic
+    rng = np.random.default_rng(0)
+    T, F = a.T, a.F
+    for nx, ny, M in configs(a):
+        base = [ic.random_imm(rng, M, nx, ny, a.nu, k % 3) for k in range(64)]
+        imms = [base[k % len(base)] for k in range(F)]
+        U = rng.standard_normal((T, a.nu))
+        Y = rng.standard_normal((T, ny))
+        bi = ic.bank(imms)
+        flat = [s for imm in imms for s in imm["systems"]]
+        bk = _capi.KalmanBankHandle(0, [m for m, _ in flat], np.stack([D for _, D in flat]))
+        ti, tk = [], []
+        for r in range(a.reps + 1):
+            for b, ts in ((bi, ti), (bk, tk)):
+                b.reset()
+                t1 = time.perf_counter()
+                res = b.run(U, Y)
+                ts.append(time.perf_counter() - t1)
+                assert np.all(np.isfinite(res["ll"]))
+        wi, wk = float(np.median(ti[1:])), float(np.median(tk[1:]))
+        print(json.dumps(dict(bench="imm", nx=nx, ny=ny, nu=a.nu, M=M, F=F, T=T, imm_wall_s=wi, kalman_wall_s=wk, kalman_filters=F * M,
+                              wall_ratio=wi / wk, imm_steps_per_s=F * T / wi)), flush=True)
+        bi.close()
+        bk.close()
+
+
+def from_trace(a):
+    rows = list(csv.DictReader(open(a.trace, newline="")))
+    key = {k.lower(): k for k in rows[0]}
+    name, t0, t1 = key["kernel_name"], key["start_timestamp"], key["end_timestamp"]
+    rows = sorted((r for r in rows if "k_imm" in r[name] or "k_kalman" in r[name]), key=lambda r: int(r[t0]))
+    n = (a.T + CHUNK - 1) // CHUNK
+    it = iter(rows)
+    for nx, ny, M in configs(a):
+        sums = {"k_imm": [], "k_kalman": []}
+        for r in range(a.reps + 1):
+            for kern in ("k_imm", "k_kalman"):
+                launches = [next(it) for _ in range(n)]
+                assert all(kern + "<" in l[name] or kern + "I" in l[name] for l in launches), (nx, ny, M, r, kern, launches[0][name])
+                sums[kern].append(sum(int(l[t1]) - int(l[t0]) for l in launches) * 1e-6)
+        ki, kk = float(np.median(sums["k_imm"][1:])), float(np.median(sums["k_kalman"][1:]))
+        print(json.dumps(dict(bench="imm_kernels", nx=nx, ny=ny, M=M, F=a.F, T=a.T, k_imm_ms=ki, k_kalman_ms=kk, kalman_filters=a.F * M,
+                              ratio=ki / kk, k_imm_spread_ms=[min(sums["k_imm"][1:]), max(sums["k_imm"][1:])],
+                              k_kalman_spread_ms=[min(sums["k_kalman"][1:]), max(sums["k_kalman"][1:])])), flush=True)
+    assert next(it, None) is None, "launches left over: the trace is not of a run with these arguments"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--F", type=int, default=10000)
+    ap.add_argument("--shapes", default="2x1,4x2")
+    ap.add_argument("--modes", default="2,3,4")
+    ap.add_argument("--T", type=int, default=1000)
+    ap.add_argument("--nu", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--trace", help="the kernel trace (csv) of a run of this script under rocprofv3 with the same arguments")
+    a = ap.parse_args()
+    return from_trace(a) if a.trace else measure(a)
+
+
+if __name__ == "__main__":
+    main()
