@@ -422,10 +422,10 @@ int  llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double*
 int  llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R);
 int  llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R);
 
-/* ---- banks of interacting-multiple-model (IMM) filters over Kalman filters (the reference's IMM(models, P, mu), src/imm.jl) ---------------
+/* ---- banks of interacting-multiple-model (IMM) filters over Kalman or extended Kalman filters (the reference's IMM(models, P, mu), src/imm.jl) ----
  * n_filters independent IMM filters of n_modes modes each (1 <= n_modes <= 4), one GPU lane per (filter, mode), in the operation order of
  * csrc/shared/llpf_imm.h (that header is the definition: a host build of it gives the same bits).  The recursion is the textbook one
- * (Blom & Bar-Shalom); it was not checked against the reference's source.  There is no smoother, and no nonlinear modes: every mode is a
+ * (Blom & Bar-Shalom); it was not checked against the reference's source.  There is no smoother.  Without LLPF_IMM_EXTENDED every mode is a
  * Kalman filter with constant matrices as llpf_kalman_bank_create takes it (LLPF_MODEL_LINEAR_GAUSSIAN, nx <= 8, ny <= 4, nu <= 8, the
  * same for every mode of every filter).  models [F][M]; D [F][M][ny][nu] or NULL (zero); P [F][M][M] row-stochastic, P_ij from mode i to
  * mode j; mu0 [F][M] the initial mode probabilities; flags bit 0 (LLPF_IMM_INTERACT): the modes mix after every step.  LLPF_ERR_ARG, the
@@ -435,8 +435,17 @@ int  llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const doub
  * mode, ll_j; mu_j <- (sum_i P_ij mu_i) exp(ll_j) normalised, ll[t] the log of the normaliser; the combined posterior xt[t], Rt[t]; the
  * mixing of the modes; predict! of every mode.  A missing row (first element NaN): no correct!, ll[t] = 0, mu_j <- sum_i P_ij mu_i.  An
  * IMM one of whose modes loses the definiteness of its S is NaN from that step on; the run returns LLPF_OK and the other filters are
- * unaffected.  The state (every mode's x, R, and mu) carries from run to run: run(a) then run(b) is run(a + b). */
+ * unaffected.  The state (every mode's x, R, and mu) carries from run to run: run(a) then run(b) is run(a + b).
+ * Extended modes.  flags bit 1 (LLPF_IMM_EXTENDED), implied by a model_id other than LLPF_MODEL_LINEAR_GAUSSIAN: every mode is a
+ * first-order extended Kalman filter as llpf_ekf_bank_create takes it (csrc/shared/llpf_ekf.h; correct! linearises the measurement at the
+ * mode's prior, predict! the dynamics at the mode's state after the mixing), all modes of all filters ONE model type — one model_id, one
+ * (nx, ny, nu) — each with its own descriptor: its own parameters, R1, R2, d0.  With LLPF_MODEL_LINEAR_GAUSSIAN and the flag the modes
+ * run that path through the model's A and C as Jacobians.  LLPF_ERR_ARG as well: whatever llpf_ekf_bank_create refuses (a compiled model
+ * without dynamics_jac or measurement_jac, or with a noise, initial or loglik member; the Rao-Blackwellized ids), a mode whose model_id
+ * or dimensions differ (the message names filter and mode), and D not NULL.  The kernel of a run-time compiled model is compiled on the
+ * first such bank (LLPF_ERR_HIP with the log).  Step t runs at tau = (t_index0 + t) * Ts of llpf_imm_bank_run_at. */
 #define LLPF_IMM_INTERACT 1
+#define LLPF_IMM_EXTENDED 2
 typedef struct llpf_imm_bank llpf_imm_bank;
 typedef struct llpf_imm_outputs {        /* every output optional (NULL); time-major like llpf_kalman_outputs.  No innovation: an IMM has one per mode */
     uint32_t struct_size;                /* sizeof(llpf_imm_outputs): guards growth */
@@ -456,6 +465,10 @@ int  llpf_imm_bank_set_models(llpf_imm_bank* b, const llpf_model* models, const 
  * nothing is combined) */
 int  llpf_imm_bank_run(llpf_imm_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
                        const llpf_imm_outputs* out);
+/* the same run with the time of its first step: step t at tau = (t_index0 + t) * Ts, as llpf_ekf_bank_run takes it (finite: LLPF_ERR_ARG
+ * otherwise; a bank of Kalman modes ignores it).  llpf_imm_bank_run is this with t_index0 = 0.0 */
+int  llpf_imm_bank_run_at(llpf_imm_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                          double* ll_total, const llpf_imm_outputs* out);
 /* the combined x [F][nx], R [F][nx][nx] (get only), mu [F][M], and every mode's x_modes [F][M][nx], R_modes [F][M][nx][nx]; get: each
  * may be NULL; set: all three are needed, the lower triangles of R_modes are taken */
 int  llpf_imm_bank_get_state(llpf_imm_bank* b, double* x, double* R, double* mu, double* x_modes, double* R_modes);

@@ -52,6 +52,7 @@ SYMBOLS = {
     "llpf_imm_bank_reset": [_vp],
     "llpf_imm_bank_set_models": [_vp, C.POINTER(S.Model), _dp, _dp, _dp],
     "llpf_imm_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.ImmOutputs)],
+    "llpf_imm_bank_run_at": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.ImmOutputs)],
     "llpf_imm_bank_get_state": [_vp, _dp, _dp, _dp, _dp, _dp],
     "llpf_imm_bank_set_state": [_vp, _dp, _dp, _dp],
     "llpf_ukf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.POINTER(S.UkfWeights), C.POINTER(_vp)],
@@ -601,21 +602,23 @@ class KalmanBankHandle(_KfBankHandle):
 
 IMM_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "mu", "ll_modes")
 IMM_INTERACT = 1
+IMM_EXTENDED = 2
 
 
 class IMMBankHandle(_KfBankHandle):
-    """RAII wrapper of an `llpf_imm_bank*` (independent IMM filters of M Kalman-filter modes each on one device, one lane per mode).
-    `models`: [F][M] descriptors (a list of F lists of M), D [F, M, ny, nu] or None, P [F, M, M], mu0 [F, M]."""
+    """RAII wrapper of an `llpf_imm_bank*` (independent IMM filters of M modes each on one device, one lane per mode).
+    `models`: [F][M] descriptors (a list of F lists of M), D [F, M, ny, nu] or None, P [F, M, M], mu0 [F, M].  extended: the modes are
+    first-order extended Kalman filters of one model type (LLPF_IMM_EXTENDED; implied by a model other than the linear-Gaussian one), D None."""
     _SYM = "llpf_imm_bank"
 
-    def __init__(self, device, models, D, P, mu0, interact=True):
+    def __init__(self, device, models, D, P, mu0, interact=True, extended=False):
         self.M = len(models[0]) if len(models) else 0
         if any(len(row) != self.M for row in models):
             raise ValueError("every filter of an IMM bank has the same number of modes")
         arr = self._pack(models, first=True)
         D, P, mu0 = self._tables(D, P, mu0)
-        check(self.L.llpf_imm_bank_create(int(device), arr, dptr(D), dptr(P), dptr(mu0), self.F, self.M, IMM_INTERACT if interact else 0,
-                                          C.byref(self.h)))
+        check(self.L.llpf_imm_bank_create(int(device), arr, dptr(D), dptr(P), dptr(mu0), self.F, self.M,
+                                          (IMM_INTERACT if interact else 0) | (IMM_EXTENDED if extended else 0), C.byref(self.h)))
 
     def _pack(self, models, first=False):
         flat = [m for row in models for m in row]
@@ -634,10 +637,10 @@ class IMMBankHandle(_KfBankHandle):
         D, P, mu0 = self._tables(D, P, mu0)
         self._call("set_models", arr, dptr(D), dptr(P), dptr(mu0))
 
-    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
-        """T steps of every filter; inputs as KalmanBankHandle.run.  Returns {"ll": [F], name: array} for every name of `outputs`
-        (IMM_OUTPUTS), time-major: ll_steps [T, F], x / xt [T, F, nx], R / Rt [T, F, nx, nx] (the combined estimate), mu / ll_modes
-        [T, F, M]."""
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
+        """T steps of every filter, step t at time (t_index0 + t) Ts (a bank of Kalman modes ignores the time); inputs as
+        KalmanBankHandle.run.  Returns {"ll": [F], name: array} for every name of `outputs` (IMM_OUTPUTS), time-major: ll_steps [T, F],
+        x / xt [T, F, nx], R / Rt [T, F, nx, nx] (the combined estimate), mu / ll_modes [T, F, M]."""
         U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
         F, nx, M = self.F, self.nx, self.M
         shapes = {"ll_steps": (T, F), "x": (T, F, nx), "xt": (T, F, nx), "R": (T, F, nx, nx), "Rt": (T, F, nx, nx), "mu": (T, F, M),
@@ -650,7 +653,7 @@ class IMMBankHandle(_KfBankHandle):
             for k, a in res.items():
                 setattr(out, k, dptr(a))
         ll = np.empty(F)
-        self._call("run", dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), dptr(ll),
+        self._call("run_at", dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), float(t_index0), dptr(ll),
                    None if out is None else C.byref(out))
         res["ll"] = ll
         return res

@@ -446,22 +446,40 @@ class KalmanSmoothingSolution(KalmanFilteringSolution):
 
 class IMM:
     """IMM(models, P, mu; interact, device) — the reference's interacting-multiple-model filter (src/imm.jl) over a list of KalmanFilter
-    of the same dimensions: P [M, M] the row-stochastic transition matrix (P[i, j]: from mode i to mode j), mu [M] the initial mode
-    probabilities, M <= 4.  Runs on the device as a bank of one IMM (llpf_imm_bank_*), created on first use, in the operation order of
-    csrc/shared/llpf_imm.h: the textbook recursion of Blom & Bar-Shalom, not checked against the reference's source.  interact = False:
-    the modes never mix (M independent Kalman filters with a shared mode probability).  There is no smoother."""
+    of the same dimensions, or over a list of ExtendedKalmanFilter of ONE model (the same compiled model id and dimensions; the modes
+    differ by their parameters, R1, R2 and d0 — a snippet that needs structurally different modes branches on one of its parameters):
+    P [M, M] the row-stochastic transition matrix (P[i, j]: from mode i to mode j), mu [M] the initial mode probabilities, M <= 4.  Runs on
+    the device as a bank of one IMM (llpf_imm_bank_*), created on first use, in the operation order of csrc/shared/llpf_imm.h: the
+    textbook recursion of Blom & Bar-Shalom, not checked against the reference's source.  An extended mode linearises its measurement at
+    its own prior and its dynamics at its own state after the mixing (csrc/shared/llpf_ekf.h); iterated or unscented modes are not
+    provided.  interact = False: the modes never mix (M independent filters with a shared mode probability).  There is no smoother."""
 
     def __init__(self, models, P, mu, *, interact=True, device=0):
         self.models = list(models)
-        if not self.models or not all(isinstance(m, KalmanFilter) for m in self.models):
-            raise TypeError("IMM: models is a non-empty list of KalmanFilter")
+        if not self.models:
+            raise TypeError("IMM: models is a non-empty list of KalmanFilter or of ExtendedKalmanFilter")
+        self.extended = not isinstance(self.models[0], KalmanFilter)
+        for j, m in enumerate(self.models):
+            ok = (isinstance(m, ExtendedKalmanFilter) and not isinstance(m, IteratedExtendedKalmanFilter)) if self.extended else isinstance(m, KalmanFilter)
+            if not ok:
+                raise TypeError("IMM: models is a list of KalmanFilter or a list of ExtendedKalmanFilter; mode %d is a %s" % (j, type(m).__name__))
+        if self.extended:
+            m0 = self.models[0]._model
+            for j, f in enumerate(self.models):
+                m = f._model
+                if (m.model_id, m.nx, m.ny, m.nu) != (m0.model_id, m0.nx, m0.ny, m0.nu):
+                    raise TypeError("IMM: the modes of an extended IMM are one model (the same compiled model id and dimensions); mode %d "
+                                    "differs from mode 0" % j)
         self.P, self.mu0 = np.atleast_2d(np.asarray(P, float)), np.atleast_1d(np.asarray(mu, float))
         self.interact, self.device = bool(interact), int(device)
         self.Ts = self.models[0].Ts
         self._handle = None
+        self._index = 0         # extended: the step counter of the nonlinear filters (the time of update!'s step)
 
     def _spec(self):
-        """(models [M], D [M, ny, nu], P, mu0) of this filter"""
+        """(models [M], D [M, ny, nu] or None (extended), P, mu0) of this filter"""
+        if self.extended:
+            return [f._model for f in self.models], None, self.P, self.mu0
         md = [kf._model() for kf in self.models]
         return [m for m, _ in md], np.stack([D for _, D in md]), self.P, self.mu0
 
@@ -469,7 +487,8 @@ class IMM:
     def _h(self):
         if self._handle is None:
             models, D, P, mu0 = self._spec()
-            self._handle = _capi.IMMBankHandle(self.device, [models], D[None], P[None], mu0[None], self.interact)
+            self._handle = _capi.IMMBankHandle(self.device, [models], None if D is None else D[None], P[None], mu0[None], self.interact,
+                                               self.extended)
         return self._handle
 
     @property
@@ -491,10 +510,17 @@ class IMM:
         """the current mode probabilities [M]"""
         return self._h.get_modes()[2][0]
 
-    def _run(self, u, y, outputs=()):
+    def reset(self):
+        self._h.reset()
+        self._index = 1         # index(pf) after reset!, as the nonlinear filters count it
+
+    def _run(self, u, y, outputs=(), t_index0=0.0):
         y = np.asarray(y, dtype=np.float64)
         y = y.reshape(y.shape[0], -1) if y.ndim else y.reshape(1, 1)
-        return self._h.run(None if self._h.nu == 0 else np.asarray(u, dtype=np.float64).reshape(y.shape[0], -1), y, outputs=outputs)
+        r = self._h.run(None if self._h.nu == 0 else np.asarray(u, dtype=np.float64).reshape(y.shape[0], -1), y, outputs=outputs,
+                        t_index0=t_index0)
+        self._index += y.shape[0]
+        return r
 
 
 class IMMFilteringSolution(KalmanFilteringSolution):
@@ -594,21 +620,30 @@ class KalmanFilterBank(_KfBank):
 
 class IMMBank(_KfBank):
     """n independent IMM filters of the same number of modes and the same dimensions on one device, one GPU lane per (filter, mode)
-    (llpf_imm_bank_*): the exact log-likelihood of a switching linear-Gaussian model for every parameter set of a sweep.  `specs` is a
-    list of IMM or of (models, P, mu) tuples (all with the same `interact`, the first one's)."""
+    (llpf_imm_bank_*): the exact log-likelihood of a switching linear-Gaussian model for every parameter set of a sweep, or, over
+    ExtendedKalmanFilter modes of one model, the first-order one of a switching nonlinear model.  `specs` is a list of IMM or of
+    (models, P, mu) tuples (all with the same `interact`, the first one's, and all over the same kind of mode).  An extended bank runs
+    loglik from t = 1 * Ts and forward from t = 0, as ExtendedKalmanFilterBank does."""
 
     def __init__(self, specs, device=0):
-        models, D, P, mu0, interact = self._pack(specs)
+        models, D, P, mu0, interact, self.extended = self._pack(specs)
         self.device = int(device)
-        self._h = _capi.IMMBankHandle(self.device, models, D, P, mu0, interact)
+        self._h = _capi.IMMBankHandle(self.device, models, D, P, mu0, interact, self.extended)
         self.n_filters = len(models)
         self.Ts = float(models[0][0].Ts)
+        if self.extended:
+            self._AT_LOGLIK, self._AT_FORWARD = {"t_index0": 1.0}, {"t_index0": 0.0}
 
     @staticmethod
     def _pack(specs):
         imms = [f if isinstance(f, IMM) else IMM(*f) for f in specs]
+        extended = imms[0].extended
+        for k, f in enumerate(imms):
+            if f.extended != extended:
+                raise TypeError("IMMBank: filter %d is %s where filter 0 is not: a bank is over one kind of mode" % (k, "extended" if f.extended else "linear"))
         sp = [f._spec() for f in imms]
-        return [s[0] for s in sp], np.stack([s[1] for s in sp]), np.stack([s[2] for s in sp]), np.stack([s[3] for s in sp]), imms[0].interact
+        D = None if extended else np.stack([s[1] for s in sp])
+        return [s[0] for s in sp], D, np.stack([s[2] for s in sp]), np.stack([s[3] for s in sp]), imms[0].interact, extended
 
     def state(self):
         """(x [F, nx], R [F, nx, nx], mu [F, M]): the combined estimate and the mode probabilities of every filter"""
@@ -624,7 +659,9 @@ class IMMBank(_KfBank):
 
     def set_parameters(self, specs):
         """new matrices, P and mu for every filter (same shapes, nothing reallocated: llpf_imm_bank_set_models)"""
-        models, D, P, mu0, _ = self._pack(specs)
+        models, D, P, mu0, _, extended = self._pack(specs)
+        if extended != self.extended:
+            raise TypeError("IMMBank.set_parameters: the bank keeps its kind of mode")
         self._h.set_models(models, D, P, mu0)
 
 
@@ -1147,7 +1184,7 @@ class ParticleFilteringSolution:
 # ---------------------------------------------------------------------------------------------------
 def reset(pf):
     """reset!(pf) — reference src/filtering.jl:4-14 (src/kalman.jl:159-164 for a KalmanFilter)."""
-    if isinstance(pf, _NonlinearKalmanFilter):
+    if isinstance(pf, (_NonlinearKalmanFilter, IMM)):
         return pf.reset()
     pf._h.reset()
 
@@ -1210,7 +1247,9 @@ def update(pf, u, y, *args, **kw):
         r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], ("e",))
         return float(r["ll"][0]), r["e"][0, 0]
     if isinstance(pf, IMM):                         # the step of csrc/shared/llpf_imm.h; an IMM has no single innovation
-        r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None])
+        t = _pt(args, kw, 0)[1]                     # (extended modes: the step's time, default index * Ts as the nonlinear filters')
+        r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], (),
+                    float(pf._index) if t is None else float(t) / pf.Ts)
         return float(r["ll"][0]), None
     if isinstance(pf, _NonlinearKalmanFilter):
         r = pf._step(u, y, _pt(args, kw, 0)[1], ("e",))
@@ -1256,7 +1295,9 @@ def loglik(pf, u, y, p=None):
     t = index(pf)*Ts, i.e. the first step is at t = 1*Ts); :232-236 for the auxiliary filter (t = (k-1)*Ts, the
     last step is an update! of the wrapped filter).  For a KalmanFilter: reset!, then the sum of T update! steps (exact)."""
     reset(pf)
-    if isinstance(pf, (KalmanFilter, IMM)):
+    if isinstance(pf, IMM):                         # extended modes: the first step at t = 1 * Ts, as the extended filter's loglik
+        return float(pf._run(u, y, (), 1.0 if pf.extended else 0.0)["ll"][0])
+    if isinstance(pf, KalmanFilter):
         return float(pf._run(u, y)["ll"][0])
     if isinstance(pf, _NonlinearKalmanFilter):      # the first step at t = 1 * Ts, as the particle filters' loglik
         return float(pf._run(u, y, (), 1.0)["ll"][0])

@@ -234,7 +234,7 @@ int llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double* 
 int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
 int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
 
-// ---- banks of IMM filters over Kalman filters (host/kfbank.hpp, host/imm.hpp) ----
+// ---- banks of IMM filters over Kalman filters or over extended Kalman filters (host/kfbank.hpp, host/imm.hpp) ----
 int llpf_imm_bank_create(int32_t device, const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t n_filters,
                          int32_t n_modes, int32_t flags, llpf_imm_bank** out) LLPF_TRY {
     return make_handle(out, [&](llpf_imm_bank& b) { return imm_create(device, models, D, P, mu0, n_filters, n_modes, flags, b); });
@@ -248,8 +248,14 @@ int llpf_imm_bank_set_models(llpf_imm_bank* b, const llpf_model* models, const d
 int llpf_imm_bank_run(llpf_imm_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
                       const llpf_imm_outputs* out) LLPF_TRY {
     NEEDF(b);
-    return imm_run(*b, U, Y, T, per_filter, ll_total, out);
+    return imm_run(*b, U, Y, T, per_filter, 0.0, ll_total, out);
 } LLPF_GUARD(llpf_imm_bank_run)
+int llpf_imm_bank_run_at(llpf_imm_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                         const llpf_imm_outputs* out) LLPF_TRY {
+    CHK(imm_check_time(t_index0));
+    NEEDF(b);
+    return imm_run(*b, U, Y, T, per_filter, t_index0, ll_total, out);
+} LLPF_GUARD(llpf_imm_bank_run_at)
 int llpf_imm_bank_get_state(llpf_imm_bank* b, double* x, double* R, double* mu, double* x_modes, double* R_modes) LLPF_TRY {
     NEEDF(b);
     return imm_get_state(*b, x, R, mu, x_modes, R_modes);

@@ -1,5 +1,6 @@
-// host/imm.hpp — banks of interacting-multiple-model filters over Kalman filters with constant matrices (llpf_imm_bank_*; kernel:
-// kernels/imm.hpp, step: shared/llpf_imm.h).  Part of capi.hip (one translation unit).
+// host/imm.hpp — banks of interacting-multiple-model filters over Kalman filters with constant matrices or over first-order extended
+// Kalman filters of one model type (llpf_imm_bank_*; kernels: kernels/imm.hpp, kernels/imm_ekf.hpp, step: shared/llpf_imm.h).  Part of
+// capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
 // The bank is a KfBank (host/kfbank.hpp) whose columns are lanes: G = 1, 2 or 4 lanes per filter (the smallest G >= M), column f * G + j is
 // mode j of filter f, L = F * G columns in all (those of the idle lanes j >= M stay zero).  par is [npar + LLPF_IMM_MAXM][L]: the mode's
@@ -7,17 +8,47 @@
 // mode's x, packed R, mu_j and the run's running ll_total (the same number in every lane of a filter).  A run goes through the chunked
 // staging pipeline of host/pipe.hpp like kf_forward, with this bank's own outputs.  The combined estimate of get_state is formed on the
 // host from the downloaded state, by the functions of shared/llpf_imm.h the kernel forms it with.
+// An extended bank (LLPF_IMM_EXTENDED, implied by a model id other than LLPF_MODEL_LINEAR_GAUSSIAN) keeps the columns and the state and
+// has, in the place of the Kalman constants, the descriptors ModelD [L] that the model's own functions read and par
+// [LLPF_EKF_NPAR + LLPF_IMM_MAXM][L]: R1, R2 packed, then column j of P.  The columns of its idle lanes stay zero as well: k_imm_ekf
+// reads mode 0's column in their place.
 
 namespace llpf {
 #include "../kernels/imm_args.hpp"
+#include "../kernels/imm_ekf_args.hpp"
+// the extended bank's kernel (k_imm_ekf.hip): imm_ekf_prepare compiles the k_imm_ekf of a run-time compiled model at g lanes per filter on
+// its first use (0, or -1 with `err` set); launch_imm_ekf runs one chunk of steps
+int imm_ekf_prepare(int model_id, int nx, int ny, int g, std::string& err);
+hipError_t launch_imm_ekf(int model_id, int nx, int ny, int g, const ModelD* models, const ImmEkfArgs& a, hipStream_t s);
 }
 
 struct llpf_imm_bank : KfBank {
     int M = 0, G = 0, L = 0, interact = 1;
+    int extended = 0, model_id = 0;   // extended: the modes are extended Kalman filters of the model `model_id`
+    double Ts = 1.0;
+    DevBuf<ModelD> d_models;          // extended: [L] the descriptors the model's own functions read
+    DevBuf<double> d_zero;            // extended: MAXU zeros, the u of a model without inputs
     llpf_imm_bank() : KfBank("imm") {}
 };
 
 static int imm_group(int M) { return M <= 1 ? 1 : M == 2 ? 2 : 4; }
+
+// P [M][M] row-stochastic and mu0 [M] a distribution, of one filter (`atf`: its message prefix)
+static int imm_check_tables(const double* Pf, const double* mf, int M, const std::string& atf) {
+    double smu = 0.0;
+    for (int i = 0; i < M; ++i) {
+        double srow = 0.0;
+        for (int j = 0; j < M; ++j) {
+            if (!(Pf[i * M + j] >= 0.0)) return fail(LLPF_ERR_ARG, atf + "row " + std::to_string(i) + " of P has a negative (or NaN) entry");
+            srow += Pf[i * M + j];
+        }
+        if (!(fabs(srow - 1.0) <= 1e-12)) return fail(LLPF_ERR_ARG, atf + "row " + std::to_string(i) + " of P does not sum to 1");
+        if (!(mf[i] >= 0.0)) return fail(LLPF_ERR_ARG, atf + "mu0 of mode " + std::to_string(i) + " is negative (or NaN)");
+        smu += mf[i];
+    }
+    if (!(fabs(smu - 1.0) <= 1e-12)) return fail(LLPF_ERR_ARG, atf + "mu0 does not sum to 1");
+    return LLPF_OK;
+}
 
 // models [F][M] (+ D [F][M][ny][nu] or NULL), P [F][M][M], mu0 [F][M] -> the SoA constants and initial state; every check that needs no device
 static int imm_pack(const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t F, int32_t M, int& nx, int& ny,
@@ -37,18 +68,7 @@ static int imm_pack(const llpf_model* models, const double* D, const double* P, 
         const std::string atf = "imm: filter " + std::to_string(f) + ": ";
         const double* Pf = P + (size_t)f * M * M;
         const double* mf = mu0 + (size_t)f * M;
-        double smu = 0.0;
-        for (int i = 0; i < M; ++i) {
-            double srow = 0.0;
-            for (int j = 0; j < M; ++j) {
-                if (!(Pf[i * M + j] >= 0.0)) return fail(LLPF_ERR_ARG, atf + "row " + std::to_string(i) + " of P has a negative (or NaN) entry");
-                srow += Pf[i * M + j];
-            }
-            if (!(fabs(srow - 1.0) <= 1e-12)) return fail(LLPF_ERR_ARG, atf + "row " + std::to_string(i) + " of P does not sum to 1");
-            if (!(mf[i] >= 0.0)) return fail(LLPF_ERR_ARG, atf + "mu0 of mode " + std::to_string(i) + " is negative (or NaN)");
-            smu += mf[i];
-        }
-        if (!(fabs(smu - 1.0) <= 1e-12)) return fail(LLPF_ERR_ARG, atf + "mu0 does not sum to 1");
+        CHK(imm_check_tables(Pf, mf, M, atf));
         for (int j = 0; j < M; ++j) {
             const llpf_model& m = models[(size_t)f * M + j];
             const std::string at = "imm: filter " + std::to_string(f) + ", mode " + std::to_string(j) + ": ";
@@ -71,15 +91,75 @@ static int imm_pack(const llpf_model* models, const double* D, const double* P, 
     return LLPF_OK;
 }
 
+// the pack of an extended bank: models [F][M] of one model id -> the descriptors ModelD [L], the SoA constants and the initial state; the
+// checks of llpf_ekf_bank_create (kf_pack_models on the first model: both Jacobian members, no noise / initial / loglik member, not
+// Rao-Blackwellized) and, per mode, one model id and one set of dimensions, the densities and their definiteness
+static int imm_pack_extended(const llpf_model* models, const double* P, const double* mu0, int32_t F, int32_t M, int& model_id, int& nx,
+                             int& ny, int& nu, std::vector<ModelD>& hm, std::vector<double>& par, std::vector<double>& init) {
+    if (!models) return fail(LLPF_ERR_ARG, "imm: models is null");
+    if (!P || !mu0) return fail(LLPF_ERR_ARG, "imm: P and mu0 must both be given");
+    if (F < 1) return fail(LLPF_ERR_ARG, "imm: n_filters must be >= 1");
+    if (M < 1 || M > LLPF_IMM_MAXM) return fail(LLPF_ERR_ARG, "imm: n_modes must be in 1..4");
+    {
+        std::vector<ModelD> hm0;
+        std::vector<double> par0, init0;
+        CHK(kf_pack_models("imm", "extended Kalman filter", LLPF_TRAIT_DYNAMICS_JAC | LLPF_TRAIT_MEASUREMENT_JAC, 0, models, 1, model_id, nx, ny,
+                           nu, hm0, par0, init0));
+    }
+    const int G = imm_group(M), L = F * G;
+    const int np = LLPF_KF_NP(nx), npar = LLPF_EKF_NPAR(nx, ny), nstate = nx + np + 2;
+    hm.assign((size_t)L, ModelD{});
+    par.assign((size_t)(npar + LLPF_IMM_MAXM) * L, 0.0);
+    init.assign((size_t)nstate * L, 0.0);
+    for (int f = 0; f < F; ++f) {
+        const double* Pf = P + (size_t)f * M * M;
+        const double* mf = mu0 + (size_t)f * M;
+        CHK(imm_check_tables(Pf, mf, M, "imm: filter " + std::to_string(f) + ": "));
+        for (int j = 0; j < M; ++j) {
+            const llpf_model& m = models[(size_t)f * M + j];
+            const std::string at = "imm: filter " + std::to_string(f) + ", mode " + std::to_string(j) + ": ";
+            const int col = f * G + j;
+            if (m.model_id != model_id) return fail(LLPF_ERR_ARG, at + "model_id differs from that of filter 0, mode 0: the modes of an extended bank are one model type");
+            if (m.nx != nx || m.ny != ny || m.nu != nu) return fail(LLPF_ERR_ARG, at + "dimensions differ from those of filter 0, mode 0");
+            CHK(kf_pack_filter(m, at, col, L, nx, ny, LLPF_EKF_OFF_R1, LLPF_EKF_OFF_R2(nx), par, init));
+            const int rc = model_prepare(&m, &hm[(size_t)col]);
+            if (rc == -1) return fail(LLPF_ERR_ARG, at + "R1 (dynamics_density) is not positive definite");
+            if (rc == -2) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
+            if (rc == -3) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
+            if (rc) return fail(LLPF_ERR_ARG, at + "invalid model descriptor, code " + std::to_string(rc));
+            for (int i = 0; i < M; ++i) par[(size_t)(npar + i) * L + col] = Pf[i * M + j];
+            init[(size_t)(nx + np) * L + col] = mf[j];
+        }
+    }
+    return LLPF_OK;
+}
+
 static int imm_create(int32_t device, const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t F, int32_t M,
                       int32_t flags, llpf_imm_bank& b) {
-    if (flags & ~1) return fail(LLPF_ERR_ARG, "imm: flags has bits other than 0");
+    if (flags & ~(LLPF_IMM_INTERACT | LLPF_IMM_EXTENDED)) return fail(LLPF_ERR_ARG, "imm: flags has bits other than 0 and 1");
     std::vector<double> par;
-    CHK(imm_pack(models, D, P, mu0, F, M, b.nx, b.ny, b.nu, par, b.h_init));
-    CHK(kf_open(b, device, F, LLPF_KF_NPAR(b.nx, b.ny, b.nu), "imm_create"));
+    std::vector<ModelD> hm;
+    b.extended = ((flags & LLPF_IMM_EXTENDED) || (models && models[0].model_id != LLPF_MODEL_LINEAR_GAUSSIAN)) ? 1 : 0;
+    if (b.extended) {
+        if (D) return fail(LLPF_ERR_ARG, "imm: D must be NULL when the modes are extended Kalman filters (LLPF_IMM_EXTENDED)");
+        CHK(imm_pack_extended(models, P, mu0, F, M, b.model_id, b.nx, b.ny, b.nu, hm, par, b.h_init));
+        CHK(kf_open(b, device, F, LLPF_EKF_NPAR(b.nx, b.ny), "imm_create"));
+        b.Ts = models[0].Ts;
+    } else {
+        CHK(imm_pack(models, D, P, mu0, F, M, b.nx, b.ny, b.nu, par, b.h_init));
+        CHK(kf_open(b, device, F, LLPF_KF_NPAR(b.nx, b.ny, b.nu), "imm_create"));
+    }
     b.M = M; b.G = imm_group(M); b.L = F * b.G;
-    b.interact = flags & 1;
+    b.interact = flags & LLPF_IMM_INTERACT;
     b.nstate = b.nx + b.np + 2;
+    if (b.extended) {
+        std::string err;
+        if (imm_ekf_prepare(b.model_id, b.nx, b.ny, b.G, err) != 0) return fail(LLPF_ERR_HIP, "imm: " + err);
+        CHK(b.d_models.ensure(hm.size()));
+        CHK(b.d_zero.ensure(MAXU));
+        HIPC(hipMemsetAsync(b.d_zero, 0, sizeof(double) * MAXU, b.stream));
+        HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
+    }
     CHK(b.d_par.ensure(par.size()));
     CHK(b.d_state.ensure(b.h_init.size()));
     HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
@@ -90,19 +170,38 @@ static int imm_create(int32_t device, const llpf_model* models, const double* D,
 
 static int imm_set_models(llpf_imm_bank& b, const llpf_model* models, const double* D, const double* P, const double* mu0) {
     std::vector<double> par, init;
+    std::vector<ModelD> hm;
     int nx = 0, ny = 0, nu = 0;
-    CHK(imm_pack(models, D, P, mu0, b.F, b.M, nx, ny, nu, par, init));
-    if (nx != b.nx || ny != b.ny || nu != b.nu) return fail(LLPF_ERR_ARG, "imm: set_models must keep the dimensions of the bank");
+    if (b.extended) {
+        int id = 0;
+        if (D) return fail(LLPF_ERR_ARG, "imm: D must be NULL when the modes are extended Kalman filters (LLPF_IMM_EXTENDED)");
+        CHK(imm_pack_extended(models, P, mu0, b.F, b.M, id, nx, ny, nu, hm, par, init));
+        if (id != b.model_id || nx != b.nx || ny != b.ny || nu != b.nu)
+            return fail(LLPF_ERR_ARG, "imm: set_models must keep the model id and the dimensions of the bank");
+    } else {
+        CHK(imm_pack(models, D, P, mu0, b.F, b.M, nx, ny, nu, par, init));
+        if (nx != b.nx || ny != b.ny || nu != b.nu) return fail(LLPF_ERR_ARG, "imm: set_models must keep the dimensions of the bank");
+    }
     HIPC(hipSetDevice(b.device));
+    if (b.extended) HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
     HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
     HIPC(hipStreamSynchronize(b.stream));
     b.h_init.swap(init);
+    if (b.extended) b.Ts = models[0].Ts;
     return LLPF_OK;
 }
 
-static int imm_run(llpf_imm_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+// t_index0 (the C ABI checks it before it looks at the handle): step t of an extended bank runs at tau = (t_index0 + t) * Ts; a Kalman
+// bank ignores it
+static int imm_check_time(double t_index0) {
+    if (!std::isfinite(t_index0)) return fail(LLPF_ERR_ARG, "imm: t_index0 must be finite");
+    return LLPF_OK;
+}
+
+static int imm_run(llpf_imm_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
                    const llpf_imm_outputs* out) {
     CHK(kf_check_run(b, U, Y, T, per_filter, nullptr));
+    CHK(imm_check_time(t_index0));
     if (out && out->struct_size < sizeof(llpf_imm_outputs)) return kf_fail(b.who, "llpf_imm_outputs.struct_size too small (ABI)");
     test_throw("imm_run");
     const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu, M = b.M;
@@ -128,6 +227,22 @@ static int imm_run(llpf_imm_bank& b, const double* U, const double* Y, int64_t T
                   {{nu > 0 ? U : nullptr, upf ? (size_t)F : 0, (size_t)nu, true}, {Y, ypf ? (size_t)F : 0, (size_t)ny, true}}));
     for (int64_t c = 0; c < pipe.nchunk; ++c) {
         CHK(pipe.begin(c, c));
+        if (b.extended) {
+            ImmEkfArgs a{};
+            a.par = b.d_par; a.state = b.d_state; a.zero_u = b.d_zero;
+            a.u = pipe.in(0);
+            a.y = pipe.in(1);
+            double** slot[7] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.mu, &a.ll_modes};
+            for (int k = 0; k < 7; ++k) *slot[k] = pipe.out(k);
+            a.F = F; a.t0 = pipe.t0; a.Tc = (int32_t)pipe.tc; a.nu = nu; a.M = M;
+            a.u_per = upf ? 1 : 0; a.y_per = ypf ? 1 : 0;
+            a.first = c == 0 ? 1 : 0;
+            a.interact = b.interact;
+            a.t_index0 = t_index0; a.Ts = b.Ts;
+            HIPC(launch_imm_ekf(b.model_id, nx, ny, b.G, b.d_models, a, b.stream));
+            CHK(pipe.end());
+            continue;
+        }
         ImmArgs a{};
         a.par = b.d_par; a.state = b.d_state;
         a.u = pipe.in(0);

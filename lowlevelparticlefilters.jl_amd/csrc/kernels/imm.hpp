@@ -1,5 +1,6 @@
 // kernels/imm.hpp — k_imm: banks of interacting-multiple-model filters over Kalman filters with constant matrices (llpf_imm_bank_run; host
-// side: host/imm.hpp).  Part of k_imm.hip (namespace llpf).
+// side: host/imm.hpp).  Part of k_imm.hip (namespace llpf); its exchange (imm_fetch, imm_weighted, imm_c) is also k_imm_ekf's: the file is
+// part of k_imm_ekf.hip and of the text of that kernel's run-time programs (jit_imm_ekf.inc) as well.
 // ------------------------------------------------------------------------------------------------
 // One lane per (filter, mode): G = 1, 2 or 4 lanes per filter, aligned to G, thread f * G + j is mode j of filter f (M = 3 runs in G = 4
 // with one idle lane, which stores nothing and is never a source).  The time loop is inside the kernel; the lane's x_j and packed R_j are

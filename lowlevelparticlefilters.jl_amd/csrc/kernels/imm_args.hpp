@@ -1,5 +1,6 @@
 // kernels/imm_args.hpp — arguments of k_imm (kernels/imm.hpp) and its launcher.  Included inside namespace llpf by the two units that
-// know the IMM bank: k_imm.hip (the kernel) and, through host/imm.hpp, capi.hip (the host side); no other unit sees it.
+// know the IMM bank: k_imm.hip (the kernel) and, through host/imm.hpp, capi.hip (the host side); k_imm_ekf.hip and the run-time programs
+// of k_imm_ekf take it along with kernels/imm.hpp (tools/gen_jit_prelude.py drops the launcher's declaration from their text).
 // One launch is one chunk of steps [t0, t0 + Tc) of F IMM filters of M modes, one lane per (filter, mode): G = 1, 2 or 4 lanes per filter
 // (the smallest G >= M), thread f * G + j is mode j of filter f, the lanes j >= M idle.  L = F * G is the number of columns of the SoA
 // arrays: a lane's column is its thread index.

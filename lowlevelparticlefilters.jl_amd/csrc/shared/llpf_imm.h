@@ -1,8 +1,11 @@
-/* llpf_imm.h — the interacting-multiple-model (IMM) filter over Kalman filters with constant matrices (the reference's IMM(models, P, mu),
- * src/imm.jl), in the one operation order that the device bank (kernels/imm.hpp, one lane per (filter, mode)) and a host build of this
- * file share.  This header IS the device-order definition: the GPU reproduces a host build of it (-ffp-contract=off) bit for bit.
+/* llpf_imm.h — the interacting-multiple-model (IMM) filter over Kalman filters with constant matrices or over first-order extended Kalman
+ * filters (the reference's IMM(models, P, mu), src/imm.jl), in the one operation order that the device banks (kernels/imm.hpp and
+ * kernels/imm_ekf.hpp, one lane per (filter, mode)) and a host build of this file share.  This header IS the device-order definition: the GPU reproduces a host build of it (-ffp-contract=off) bit for bit.
  * The recursion is the textbook one (Blom & Bar-Shalom 1988); it was NOT checked against the reference's source, which was not available
- * when this was written.  No smoother, and no nonlinear modes: every mode is a Kalman filter of llpf_kalman.h.
+ * when this was written.  No smoother.  The mode's own step is either header's: a Kalman filter of llpf_kalman.h (llpf_kf_correct,
+ * llpf_kf_predict), or a first-order extended Kalman filter of llpf_ekf.h (llpf_ekf_correct, llpf_ekf_predict around the model's value
+ * and Jacobian) — every mode of an IMM the same kind, and an extended IMM's modes one model type with a descriptor each.  The
+ * arithmetic of this file is the same for both: it never looks inside a mode's step.
  *
  * Plain C for host and device, on top of llpf_kalman.h and in its style: explicit llpf_fma, every sum over the mode index in increasing
  * order, llpf_exp / llpf_log of llpf_detmath.h.
@@ -22,6 +25,10 @@
  *      R_j <- sum_i mu_ij (R_i + (x_i - x_j)(x_i - x_j)') with the new x_j — every mode from the modes as they were before the mixing;
  *   6. every mode runs llpf_kf_predict.
  * update! is this step; a run's ll_total starts at 0.0 and adds ll[t] in step order.
+ * Extended modes: stage 2 is the model's measurement_jac at the mode's prior x_j followed by llpf_ekf_correct; on a missing row
+ * (llpf_ekf_missing) the stage is skipped, e is unused and ll_j = 0 — what llpf_kf_correct gives there.  Stage 6 is the model's
+ * dynamics_jac at the mode's x_j AFTER the mixing, followed by llpf_ekf_predict.  The model is evaluated at tau = (t_index0 + t) * Ts, as
+ * the extended Kalman bank evaluates it.  Stages 1, 3, 4, 5 and every corner rule below are unchanged.
  *
  * Corner rules.
  *   - A missing row (first element NaN): no mode corrects, ll[t] = 0 exactly, mu <- c without normalisation, every ll_j of the step is 0.

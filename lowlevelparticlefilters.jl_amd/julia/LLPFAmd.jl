@@ -1101,7 +1101,8 @@ function LowLevelParticleFilters.smooth(kf::GPUKalmanFilter, u, y, p = NullParam
     KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
 end
 
-# ---- banks of IMM filters over Kalman filters (the reference's IMM(models, P, mu), src/imm.jl; csrc/shared/llpf_imm.h is the definition): llpf_imm_bank_* ----
+# ---- banks of IMM filters over Kalman filters or over extended Kalman filters of one model (the reference's IMM(models, P, mu), src/imm.jl;
+# csrc/shared/llpf_imm.h is the definition): llpf_imm_bank_* ----
 struct CImmOutputs                    # llpf_imm_outputs
     struct_size::UInt32
     pad::UInt32
@@ -1120,13 +1121,25 @@ mutable struct GPUIMMBank
     nx::Int
     nu::Int
     ny::Int
+    extended::Bool                    # the modes are extended Kalman filters (LLPF_IMM_EXTENDED)
 end
-# (models, P, mu) of every filter -> the descriptors [F][M], D [F][M][ny][nu], P [F][M][M] and mu0 [F][M], row-major
+# (models, P, mu) of every filter -> the descriptors [F][M], D [F][M][ny][nu] (nothing: extended modes), P [F][M][M] and mu0 [F][M],
+# row-major.  A mode is an (A, B, C, D, R1, R2, d0) tuple, or — extended — a (dynamics, measurement, R1, R2, d0) tuple as
+# GPUExtendedKalmanFilterBank takes it
 function imm_tables(filters::Vector, Ts)
     M = length(filters[1][1])
     all(length(f[1]) == M for f in filters) || throw(ArgumentError("every filter of an IMM bank has the same number of modes"))
-    cms = [kalman_model(m[1], m[2], m[3], m[5], m[6], m[7], Ts) for f in filters for m in f[1]]
-    Dv = kalman_D([m[4] for f in filters for m in f[1]], cms[1].ny, cms[1].nu)
+    extended = length(filters[1][1][1]) == 5
+    all(length(m) == (extended ? 5 : 7) for f in filters for m in f[1]) || throw(ArgumentError("the modes of an IMM bank are all Kalman filters or all extended Kalman filters"))
+    if extended
+        cms = [ukf_model(m, Ts) for f in filters for m in f[1]]
+        foreach(need_jacobians, cms)
+        all(c.model_id == cms[1].model_id for c in cms) || throw(ArgumentError("the modes of an extended IMM bank are one model type"))
+        Dv = nothing
+    else
+        cms = [kalman_model(m[1], m[2], m[3], m[5], m[6], m[7], Ts) for f in filters for m in f[1]]
+        Dv = kalman_D([m[4] for f in filters for m in f[1]], cms[1].ny, cms[1].nu)
+    end
     Pv = Float64[f[2][i, j] for f in filters for i in 1:M for j in 1:M]
     mv = Float64[f[3][j] for f in filters for j in 1:M]
     M, cms, Dv, Pv, mv
@@ -1139,25 +1152,31 @@ tuples: `models` a vector of M <= 4 (A, B, C, D, R1, R2, d0) tuples of the same 
 matrix (P[i, j]: from mode i to mode j), `mu` the initial mode probabilities.  The recursion is the textbook one (Blom & Bar-Shalom), in
 the operation order of csrc/shared/llpf_imm.h; it was not checked against the reference's `IMM`.  `loglik(bank, u, y)` is the vector of
 every filter's log-likelihood.  There is no smoother.
+With `models` a vector of (dynamics, measurement, R1, R2, d0) tuples of ONE model type (as `GPUExtendedKalmanFilterBank` takes them) every
+mode is a first-order extended Kalman filter (LLPF_IMM_EXTENDED); `loglik` then runs from t = 1 * Ts and `forward_trajectory` from t = 0.
 """
 function GPUIMMBank(filters::Vector; interact = true, Ts = 1.0, device = 0)
     M, cms, Dv, Pv, mv = imm_tables(filters, Ts)
+    extended = Dv === nothing
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:llpf_imm_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
-                device, cms, Dv, Pv, mv, length(filters), M, interact ? 1 : 0, h))
-    b = GPUIMMBank(h[], length(filters), M, cms[1].nx, cms[1].nu, cms[1].ny)
+                device, cms, extended ? C_NULL : Dv, Pv, mv, length(filters), M, (interact ? 1 : 0) | (extended ? 2 : 0), h))
+    b = GPUIMMBank(h[], length(filters), M, cms[1].nx, cms[1].nu, cms[1].ny, extended)
     finalizer(x -> ccall((:llpf_imm_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
     b
 end
 function set_parameters!(b::GPUIMMBank, filters::Vector; Ts = 1.0)
     M, cms, Dv, Pv, mv = imm_tables(filters, Ts)
     (length(filters) == b.F && M == b.M) || throw(ArgumentError("set_parameters!: $(length(filters)) filters of $M modes for a bank of $(b.F) of $(b.M)"))
-    check(ccall((:llpf_imm_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, cms, Dv, Pv, mv))
+    (Dv === nothing) == b.extended || throw(ArgumentError("set_parameters!: the bank keeps its kind of mode"))
+    check(ccall((:llpf_imm_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, cms,
+                Dv === nothing ? C_NULL : Dv, Pv, mv))
     b
 end
 reset!(b::GPUIMMBank) = check(ccall((:llpf_imm_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
-# u, y: vectors of T vectors shared by every filter (a missing y is `missing` / a NaN first element); returns ll_total and the outputs asked for
-function imm_run(b::GPUIMMBank, u, y; outputs = false)
+# u, y: vectors of T vectors shared by every filter (a missing y is `missing` / a NaN first element); returns ll_total and the outputs asked for.
+# t_index0: nothing (llpf_imm_bank_run), or the time index of the first step (llpf_imm_bank_run_at; an extended bank's steps run at (t_index0 + t) Ts)
+function imm_run(b::GPUIMMBank, u, y; outputs = false, t_index0 = nothing)
     T = length(y)
     Y = zeros(b.ny, T); U = zeros(b.nu, T)
     for t in 1:T
@@ -1170,13 +1189,18 @@ function imm_run(b::GPUIMMBank, u, y; outputs = false)
     GC.@preserve U Y ll o begin
         out = o === nothing ? nothing : Ref(CImmOutputs(UInt32(sizeof(CImmOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
                                                         pointer(o.R), pointer(o.Rt), pointer(o.mu), pointer(o.ll_modes)))
-        check(ccall((:llpf_imm_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{CImmOutputs}),
-                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), pointer(ll), out === nothing ? C_NULL : out))
+        if t_index0 === nothing
+            check(ccall((:llpf_imm_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{CImmOutputs}),
+                        b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), pointer(ll), out === nothing ? C_NULL : out))
+        else
+            check(ccall((:llpf_imm_bank_run_at, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Ptr{CImmOutputs}),
+                        b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), Float64(t_index0), pointer(ll), out === nothing ? C_NULL : out))
+        end
     end
     ll, o
 end
 "loglik(bank, u, y): every filter's log-likelihood of the switching model (reset! first, then T update! steps)"
-loglik(b::GPUIMMBank, u, y) = (reset!(b); imm_run(b, u, y)[1])
+loglik(b::GPUIMMBank, u, y) = (reset!(b); imm_run(b, u, y; t_index0 = b.extended ? 1.0 : nothing)[1])
 "the combined x (nx x F), R (nx x nx x F) of every filter"
 function state(b::GPUIMMBank)
     x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F)
@@ -1210,7 +1234,8 @@ end
 """
     GPUIMM(models, P, mu; interact = true, Ts = 1.0, device = 0)
 
-The interacting-multiple-model filter over M <= 4 Kalman filters `models` (a vector of (A, B, C, D, R1, R2, d0) tuples), run on the device
+The interacting-multiple-model filter over M <= 4 Kalman filters `models` (a vector of (A, B, C, D, R1, R2, d0) tuples) or over M <= 4
+extended Kalman filters of one model type (a vector of (dynamics, measurement, R1, R2, d0) tuples), run on the device
 (a bank of one filter, llpf_imm_bank_*): `forward_trajectory` returns a named tuple (x, xt, R, Rt, ll, mu, ll_modes) of the combined
 estimate, the mode probabilities and every mode's own log-likelihood per step; `loglik`, `reset!`, `update!`, `state`, `covariance`,
 `mode_probabilities`.  Unverified against the reference's `IMM` (its source was not available when this was written); no smoother.
@@ -1218,23 +1243,26 @@ estimate, the mode probabilities and every mode's own log-likelihood per step; `
 mutable struct GPUIMM
     bank::GPUIMMBank
     Ts::Float64
+    index::Int                        # extended modes: the step counter (the time of update!'s step), 1 after reset!
 end
 GPUIMM(models::Vector, P, mu; interact = true, Ts = 1.0, device = 0) =
-    GPUIMM(GPUIMMBank([(models, P, mu)]; interact = interact, Ts = Ts, device = device), Float64(Ts))
-reset!(f::GPUIMM) = reset!(f.bank)
+    GPUIMM(GPUIMMBank([(models, P, mu)]; interact = interact, Ts = Ts, device = device), Float64(Ts), 0)
+reset!(f::GPUIMM) = (reset!(f.bank); f.index = 1; nothing)
 loglik(f::GPUIMM, u, y, p = NullParameters()) = loglik(f.bank, u, y)[1]
 "update!(imm, u, y): correct! of every mode, the mode probabilities, the mixing, predict!; returns ll"
-function update!(f::GPUIMM, u, y, p = NullParameters(), t = 0)
-    ll, _ = imm_run(f.bank, [u], [y])
+function update!(f::GPUIMM, u, y, p = NullParameters(), t = f.index * f.Ts)
+    ll, _ = imm_run(f.bank, [u], [y]; t_index0 = f.bank.extended ? t / f.Ts : nothing)
+    f.index += 1
     ll[1]
 end
 state(f::GPUIMM) = state(f.bank)[1][:, 1]
 covariance(f::GPUIMM) = state(f.bank)[2][:, :, 1]
 mode_probabilities(f::GPUIMM) = mode_probabilities(f.bank)[:, 1]
 function forward_trajectory(f::GPUIMM, u, y, p = NullParameters())
-    reset!(f.bank)
-    ll, o = imm_run(f.bank, u, y; outputs = true)
+    reset!(f)
+    ll, o = imm_run(f.bank, u, y; outputs = true, t_index0 = f.bank.extended ? 0.0 : nothing)
     T = length(y)
+    f.index += T
     (x = [o.x[:, 1, t] for t in 1:T], xt = [o.xt[:, 1, t] for t in 1:T], R = [o.R[:, :, 1, t] for t in 1:T], Rt = [o.Rt[:, :, 1, t] for t in 1:T],
      ll = ll[1], mu = [o.mu[:, 1, t] for t in 1:T], ll_modes = [o.ll_modes[:, 1, t] for t in 1:T])
 end

@@ -6,7 +6,12 @@ Without arguments: the end-to-end wall time of the two calls (median of --reps a
 The kernels' own time comes from a run of this script under `rocprofv3 --kernel-trace --output-format csv`, in a run of its own:
 `--trace <kernel_trace.csv>` reads that file, assigns its launches to the runs in the order this script makes them (the k_imm of M = 3 and
 of M = 4 is the same kernel, G = 4: only the order tells them apart; give the --shapes, --modes, --T and --reps of the traced run) and
-prints per configuration the median kernel time of an IMM run, of the Kalman run and their ratio."""
+prints per configuration the median kernel time of an IMM run, of the Kalman run and their ratio.
+
+--extended: the same question for extended modes.  F quad-tank IMMs of M modes (the built-in model, modes that differ in gamma1 and a1;
+k_imm_ekf through llpf_imm_bank_run_at) beside an ExtendedKalmanFilterBank's handle of F * M filters over the same descriptors (k_ekf), in
+the same process, alternating; (nx, ny) = (4, 2) and nu = 2 are the model's, --shapes and --nu are ignored.  --trace reads k_imm_ekf and
+k_ekf in the place of k_imm and k_kalman."""
 import argparse
 import csv
 import json
@@ -23,6 +28,10 @@ CHUNK = 256      # host/pipe.hpp: CHUNK_STEPS (shared inputs, no per-step output
 
 
 def configs(a):
+    if a.extended:
+        for M in (int(v) for v in a.modes.split(",")):
+            yield 4, 2, M
+        return
     for shape in a.shapes.split(","):
         nx, ny = (int(v) for v in shape.split("x"))
         for M in (int(v) for v in a.modes.split(",")):
@@ -57,24 +66,56 @@ def measure(a):
         bk.close()
 
 
+def measure_extended(a):
+    from llpf_amd import _capi, _structs as S
+    import imm_ekf_common as xc
+    import models as Mo
+    rng = np.random.default_rng(0)
+    T, F = a.T, a.F
+    base = Mo.quadtank_model()
+    U, Y = Mo.quadtank_data(T)
+    for nx, ny, M in configs(a):
+        modes = [S.make_quadtank_model(base.dynamics_density, base.measurement_density, base.initial_density, 1.0, 2,
+                                       gamma1=0.2 + 0.001 * (k % 50) + 0.05 * (k % M), a1=0.03 + 0.0001 * (k % 7) + 0.003 * (k % M)) for k in range(F * M)]
+        imms = xc.grouped(modes, rng, F, M)
+        bi = xc.bank(imms)
+        be = _capi.EkfBankHandle(0, modes)
+        ti, te = [], []
+        for r in range(a.reps + 1):
+            for b, ts in ((bi, ti), (be, te)):
+                b.reset()
+                t1 = time.perf_counter()
+                res = b.run(U, Y, t_index0=1.0)
+                ts.append(time.perf_counter() - t1)
+                assert np.all(np.isfinite(res["ll"]))
+        wi, we = float(np.median(ti[1:])), float(np.median(te[1:]))
+        print(json.dumps(dict(bench="imm_extended", model="quadtank", nx=nx, ny=ny, M=M, F=F, T=T, imm_wall_s=wi, ekf_wall_s=we, ekf_filters=F * M,
+                              wall_ratio=wi / we, imm_steps_per_s=F * T / wi)), flush=True)
+        bi.close()
+        be.close()
+
+
 def from_trace(a):
     rows = list(csv.DictReader(open(a.trace, newline="")))
     key = {k.lower(): k for k in rows[0]}
     name, t0, t1 = key["kernel_name"], key["start_timestamp"], key["end_timestamp"]
-    rows = sorted((r for r in rows if "k_imm" in r[name] or "k_kalman" in r[name]), key=lambda r: int(r[t0]))
+    kerns = ("k_imm_ekf", "k_ekf") if a.extended else ("k_imm", "k_kalman")
+    mine = lambda kern, r: kern + "<" in r[name] or kern + "I" in r[name]
+    rows = sorted((r for r in rows if mine(kerns[0], r) or mine(kerns[1], r)), key=lambda r: int(r[t0]))
     n = (a.T + CHUNK - 1) // CHUNK
     it = iter(rows)
     for nx, ny, M in configs(a):
-        sums = {"k_imm": [], "k_kalman": []}
+        sums = {kerns[0]: [], kerns[1]: []}
         for r in range(a.reps + 1):
-            for kern in ("k_imm", "k_kalman"):
+            for kern in kerns:
                 launches = [next(it) for _ in range(n)]
-                assert all(kern + "<" in l[name] or kern + "I" in l[name] for l in launches), (nx, ny, M, r, kern, launches[0][name])
+                assert all(mine(kern, l) for l in launches), (nx, ny, M, r, kern, launches[0][name])
                 sums[kern].append(sum(int(l[t1]) - int(l[t0]) for l in launches) * 1e-6)
-        ki, kk = float(np.median(sums["k_imm"][1:])), float(np.median(sums["k_kalman"][1:]))
-        print(json.dumps(dict(bench="imm_kernels", nx=nx, ny=ny, M=M, F=a.F, T=a.T, k_imm_ms=ki, k_kalman_ms=kk, kalman_filters=a.F * M,
-                              ratio=ki / kk, k_imm_spread_ms=[min(sums["k_imm"][1:]), max(sums["k_imm"][1:])],
-                              k_kalman_spread_ms=[min(sums["k_kalman"][1:]), max(sums["k_kalman"][1:])])), flush=True)
+        ki, kk = float(np.median(sums[kerns[0]][1:])), float(np.median(sums[kerns[1]][1:]))
+        print(json.dumps({"bench": "imm_extended_kernels" if a.extended else "imm_kernels", "nx": nx, "ny": ny, "M": M, "F": a.F, "T": a.T,
+                          kerns[0] + "_ms": ki, kerns[1] + "_ms": kk, ("ekf" if a.extended else "kalman") + "_filters": a.F * M, "ratio": ki / kk,
+                          kerns[0] + "_spread_ms": [min(sums[kerns[0]][1:]), max(sums[kerns[0]][1:])],
+                          kerns[1] + "_spread_ms": [min(sums[kerns[1]][1:]), max(sums[kerns[1]][1:])]}), flush=True)
     assert next(it, None) is None, "launches left over: the trace is not of a run with these arguments"
 
 
@@ -86,9 +127,10 @@ def main():
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--nu", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--extended", action="store_true", help="quad-tank IMMs over extended Kalman filter modes beside an extended Kalman bank")
     ap.add_argument("--trace", help="the kernel trace (csv) of a run of this script under rocprofv3 with the same arguments")
     a = ap.parse_args()
-    return from_trace(a) if a.trace else measure(a)
+    return from_trace(a) if a.trace else measure_extended(a) if a.extended else measure(a)
 
 
 if __name__ == "__main__":
