@@ -422,6 +422,29 @@ int  llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double*
 int  llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R);
 int  llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R);
 
+/* ---- banks of square-root Kalman filters (the reference's SqKalmanFilter, src/sq_kalman.jl) ----
+ * The filters of llpf_kalman_bank_* (the same models, D, inputs, outputs and carried state), each carrying a lower-triangular factor Lr
+ * of its covariance, R = Lr Lr', in the operation order of csrc/shared/llpf_sqkf.h (that header is the definition: a host build of it
+ * gives the same bits; it is the textbook array form and was not checked against the reference's source).  predict! triangularises
+ * [L1 | A Lr], correct! [[L2, C Lr], [0, Lr]] by Householder reflections: no covariance is ever subtracted from, so a filter with a
+ * diffuse prior and a near-perfect measurement, which llpf_kalman_bank_run turns NaN, stays finite here; a filter is NaN only where its
+ * inputs or its state are.  R1, R2 and cov(d0) must all be positive definite (they are factored at create and set_models): LLPF_ERR_ARG
+ * naming the filter otherwise.  The R and Rt outputs are Lr Lr' (exactly symmetric).  There is no smoother. */
+typedef struct llpf_sqkf_bank llpf_sqkf_bank;
+int  llpf_sqkf_bank_create(int32_t device, const llpf_model* models, const double* D /* [F][ny][nu] or NULL */, int32_t n_filters,
+                           llpf_sqkf_bank** out);
+int  llpf_sqkf_bank_destroy(llpf_sqkf_bank* b);
+int  llpf_sqkf_bank_reset(llpf_sqkf_bank* b);
+int  llpf_sqkf_bank_set_models(llpf_sqkf_bank* b, const llpf_model* models, const double* D);
+/* T steps of every filter; U, Y, per_filter, ll_total and out as llpf_kalman_bank_run takes them */
+int  llpf_sqkf_bank_run(llpf_sqkf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter,
+                        double* ll_total, const llpf_kalman_outputs* out);
+/* x [F][nx], R [F][nx][nx] = Lr Lr' and the dense lower factor L [F][nx][nx] (zeros above the diagonal); any may be NULL */
+int  llpf_sqkf_bank_get_state(llpf_sqkf_bank* b, double* x, double* R, double* L);
+/* x and exactly one of R and L: R's lower triangle is factored (LLPF_ERR_ARG naming the filter when it is not positive definite), L's
+ * lower triangle is taken as given, so get_state(L) -> set_state(L) keeps every bit */
+int  llpf_sqkf_bank_set_state(llpf_sqkf_bank* b, const double* x, const double* R, const double* L);
+
 /* ---- banks of interacting-multiple-model (IMM) filters over Kalman or extended Kalman filters (the reference's IMM(models, P, mu), src/imm.jl) ----
  * n_filters independent IMM filters of n_modes modes each (1 <= n_modes <= 4), one GPU lane per (filter, mode), in the operation order of
  * csrc/shared/llpf_imm.h (that header is the definition: a host build of it gives the same bits).  The recursion is the textbook one

@@ -47,6 +47,13 @@ SYMBOLS = {
     "llpf_kalman_bank_smooth": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.KalmanOutputs), C.POINTER(S.KalmanSmoothOutputs)],
     "llpf_kalman_bank_get_state": [_vp, _dp, _dp],
     "llpf_kalman_bank_set_state": [_vp, _dp, _dp],
+    "llpf_sqkf_bank_create": [C.c_int32, C.POINTER(S.Model), _dp, C.c_int32, C.POINTER(_vp)],
+    "llpf_sqkf_bank_destroy": [_vp],
+    "llpf_sqkf_bank_reset": [_vp],
+    "llpf_sqkf_bank_set_models": [_vp, C.POINTER(S.Model), _dp],
+    "llpf_sqkf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_sqkf_bank_get_state": [_vp, _dp, _dp, _dp],
+    "llpf_sqkf_bank_set_state": [_vp, _dp, _dp, _dp],
     "llpf_imm_bank_create": [C.c_int32, C.POINTER(S.Model), _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)],
     "llpf_imm_bank_destroy": [_vp],
     "llpf_imm_bank_reset": [_vp],
@@ -598,6 +605,42 @@ class KalmanBankHandle(_KfBankHandle):
         and RT [T, F, nx, nx] for the names in `outputs` (KALMAN_SMOOTH_OUTPUTS) and the forward outputs named in `forward`
         (KALMAN_OUTPUTS); the state afterwards is the one run() leaves."""
         return self._smooth(U, Y, u_per_filter, y_per_filter, outputs, forward)
+
+
+class SqkfBankHandle(_KfBankHandle):
+    """RAII wrapper of an `llpf_sqkf_bank*` (independent square-root Kalman filters with constant matrices on one device): the models,
+    D, inputs and outputs of KalmanBankHandle; the state is x and a lower-triangular factor L of the covariance, R = L L'."""
+    _SYM = "llpf_sqkf_bank"
+
+    def __init__(self, device, models, D=None):
+        arr = self._open(models)
+        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
+        check(self.L.llpf_sqkf_bank_create(int(device), arr, dptr(D), self.F, C.byref(self.h)))
+
+    def set_models(self, models, D=None):
+        arr = (S.Model * self.F)(*models)
+        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
+        self._call("set_models", arr, dptr(D))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
+        """T steps of every filter; inputs and the returned dictionary as KalmanBankHandle.run (R and Rt are L L')"""
+        return self._run(U, Y, u_per_filter, y_per_filter, outputs)
+
+    def get_state(self, factor=False):
+        """(x [F, nx], R [F, nx, nx]), R = L L'; with factor: (x, R, L), L [F, nx, nx] the lower-triangular factor itself"""
+        x = np.empty((self.F, self.nx))
+        R = np.empty((self.F, self.nx, self.nx))
+        L = np.empty((self.F, self.nx, self.nx)) if factor else None
+        self._call("get_state", dptr(x), dptr(R), dptr(L))
+        return (x, R, L) if factor else (x, R)
+
+    def set_state(self, x, R=None, L=None):
+        """x and exactly one of R (a positive definite covariance, factored) and L (a factor, whose lower triangle is taken as it is:
+        get_state(factor=True) -> set_state(x, L=L) keeps every bit)"""
+        x = f64(x).reshape(self.F, self.nx)
+        R = None if R is None else f64(R).reshape(self.F, self.nx, self.nx)
+        L = None if L is None else f64(L).reshape(self.F, self.nx, self.nx)
+        self._call("set_state", dptr(x), dptr(R), dptr(L))
 
 
 IMM_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "mu", "ll_modes")

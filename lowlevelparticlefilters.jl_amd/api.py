@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "IMM", "IMMBank", "IMMFilteringSolution", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "SqKalmanFilter", "SqKalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "IMM", "IMMBank", "IMMFilteringSolution", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -377,6 +377,7 @@ class KalmanFilter:
     x' = A x + B u + w, w ~ N(0, R1);  y = C x + D u + e, e ~ N(0, R2);  x_0 ~ d0.  Runs on the device as a bank of one filter
     (llpf_kalman_bank_*), created on first use: as the inner filter of an RBPF it is a descriptor only (D = 0 there).
     R1, R2: matrices (a 1-D array: the diagonal; a float: sigma^2 I); d0: MvNormal.  nx <= 8, ny <= 4, nu <= 8."""
+    _HANDLE = _capi.KalmanBankHandle          # the bank of one filter this class runs on
 
     def __init__(self, A, B, C, D, R1, R2, d0, *, Ts=1.0, device=0):
         self.A, self.B, self.C, self.D = np.atleast_2d(np.asarray(A, float)), B, C, D
@@ -402,7 +403,7 @@ class KalmanFilter:
     def _h(self):
         if self._handle is None:
             m, D = self._model()
-            self._handle = _capi.KalmanBankHandle(self.device, [m], D[None])
+            self._handle = self._HANDLE(self.device, [m], D[None])
         return self._handle
 
     @property
@@ -424,6 +425,15 @@ class KalmanFilter:
         y = y.reshape(y.shape[0], -1) if y.ndim else y.reshape(1, 1)
         r = self._h.run(None if self._h.nu == 0 else np.asarray(u, dtype=np.float64).reshape(y.shape[0], -1), y, outputs=outputs)
         return r
+
+
+class SqKalmanFilter(KalmanFilter):
+    """SqKalmanFilter(A, B, C, D, R1, R2, d0; Ts, device) — the reference's square-root Kalman filter (src/sq_kalman.jl): KalmanFilter's
+    model and arguments, run on the device as a bank of one filter that carries a triangular factor of the covariance
+    (llpf_sqkf_bank_*, csrc/shared/llpf_sqkf.h).  It stays finite where the covariance form loses positive definiteness (a diffuse prior
+    with a near-perfect measurement).  R1, R2 and cov(d0) must be positive definite.  Every verb of a KalmanFilter applies except smooth;
+    it is no inner filter of an RBPF and no mode of an IMM."""
+    _HANDLE = _capi.SqkfBankHandle
 
 
 class KalmanFilteringSolution:
@@ -458,6 +468,9 @@ class IMM:
         self.models = list(models)
         if not self.models:
             raise TypeError("IMM: models is a non-empty list of KalmanFilter or of ExtendedKalmanFilter")
+        for j, m in enumerate(self.models):
+            if isinstance(m, SqKalmanFilter):
+                raise TypeError("IMM: the modes are KalmanFilter or ExtendedKalmanFilter; mode %d is a SqKalmanFilter" % j)
         self.extended = not isinstance(self.models[0], KalmanFilter)
         for j, m in enumerate(self.models):
             ok = (isinstance(m, ExtendedKalmanFilter) and not isinstance(m, IteratedExtendedKalmanFilter)) if self.extended else isinstance(m, KalmanFilter)
@@ -585,11 +598,12 @@ class KalmanFilterBank(_KfBank):
     """n independent Kalman filters with constant matrices of the same dimensions on one device, one GPU thread each
     (llpf_kalman_bank_*): the exact log-likelihood of every parameter set of a linear-Gaussian sweep.  `filters_spec` is a list of
     KalmanFilter or of (A, B, C, D, R1, R2, d0) tuples."""
+    _HANDLE = _capi.KalmanBankHandle
 
     def __init__(self, filters_spec, device=0):
         models, Ds = self._models(filters_spec)
         self.device = int(device)
-        self._h = _capi.KalmanBankHandle(self.device, models, Ds)
+        self._h = self._HANDLE(self.device, models, Ds)
         self.n_filters = len(models)
         self.Ts = float(models[0].Ts)
 
@@ -607,7 +621,7 @@ class KalmanFilterBank(_KfBank):
         if any(m.model_id != S.MODEL_LINEAR_GAUSSIAN for m in models):
             raise TypeError("from_filter_bank: every filter of the bank must be linear-Gaussian")
         self.device = int(bank._h.cfg.device if device is None else device)
-        self._h = _capi.KalmanBankHandle(self.device, models, None)
+        self._h = cls._HANDLE(self.device, models, None)
         self.n_filters = len(models)
         self.Ts = float(models[0].Ts)
         return self
@@ -616,6 +630,17 @@ class KalmanFilterBank(_KfBank):
         """new matrices for every filter (same dimensions, nothing reallocated: llpf_kalman_bank_set_models)"""
         models, Ds = self._models(filters_spec)
         self._h.set_models(models, Ds)
+
+
+class SqKalmanFilterBank(KalmanFilterBank):
+    """n independent square-root Kalman filters on one device, one GPU thread each (llpf_sqkf_bank_*): KalmanFilterBank's constructor,
+    from_filter_bank, loglik, forward, state and set_parameters, for sweeps whose noise levels span so many decades that the covariance
+    form loses positive definiteness.  `filters_spec` is a list of KalmanFilter, SqKalmanFilter or (A, B, C, D, R1, R2, d0) tuples.
+    There is no smoother."""
+    _HANDLE = _capi.SqkfBankHandle
+
+    def smooth(self, *args, **kwargs):
+        raise TypeError("the square-root Kalman filter has no smoother")
 
 
 class IMMBank(_KfBank):
@@ -1082,6 +1107,8 @@ class RBPF(_AbstractParticleFilter):
 
     def __init__(self, N, kf, dynamics, nl_measurement_model, R1n, d0n, *, An=None, nu=-1, Ts=1.0, p=None, rng=None,
                  resample_threshold=0.1, names=None, device=0):
+        if isinstance(kf, SqKalmanFilter):
+            raise TypeError("RBPF: the inner filter is a KalmanFilter; a SqKalmanFilter is not supported")
         if np.any(np.asarray(0.0 if kf.D is None else kf.D) != 0):
             raise NotImplementedError("D != 0")
         as_g = lambda d: d.struct() if isinstance(d, MvNormal) else d
@@ -1514,6 +1541,8 @@ def smooth(pf, *args):
     on the device: a KalmanSmoothingSolution.
     sol = smooth(ukf::UnscentedKalmanFilter, u, y, p) — reset!, forward_trajectory and the unscented Rauch-Tung-Striebel smoother
     (csrc/shared/llpf_ukf.h: llpf_ukf_smooth_finish), on the device: a KalmanSmoothingSolution."""
+    if isinstance(pf, SqKalmanFilter):
+        raise TypeError("the square-root Kalman filter has no smoother")
     if isinstance(pf, KalmanFilter):
         u, y = args[:2]
         reset(pf)

@@ -17,6 +17,7 @@
 #include "engine.hpp"
 #include "shared/llpf_rbkf.h"
 #include "shared/llpf_kalman.h"
+#include "shared/llpf_sqkf.h"
 #include "shared/llpf_imm.h"
 #include "shared/llpf_ukf.h"
 #include "shared/llpf_ekf.h"
@@ -103,6 +104,7 @@ static void test_throw(const char* site) {
 #include "host/simulate.hpp"
 #include "host/kfbank.hpp"
 #include "host/kalman.hpp"
+#include "host/sqkf.hpp"
 #include "host/imm.hpp"
 #include "host/ukf.hpp"
 #include "host/ekf.hpp"
@@ -233,6 +235,24 @@ int llpf_kalman_bank_smooth(llpf_kalman_bank* b, const double* U, const double* 
 } LLPF_GUARD(llpf_kalman_bank_smooth)
 int llpf_kalman_bank_get_state(llpf_kalman_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_get_state)
 int llpf_kalman_bank_set_state(llpf_kalman_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_kalman_bank_set_state)
+
+// ---- banks of square-root Kalman filters (host/kfbank.hpp, host/sqkf.hpp) ----
+int llpf_sqkf_bank_create(int32_t device, const llpf_model* models, const double* D, int32_t n_filters, llpf_sqkf_bank** out) LLPF_TRY {
+    return make_handle(out, [&](llpf_sqkf_bank& b) { return sqkf_create(device, models, D, n_filters, b); });
+} LLPF_GUARD(llpf_sqkf_bank_create)
+int llpf_sqkf_bank_destroy(llpf_sqkf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_sqkf_bank_destroy)
+int llpf_sqkf_bank_reset(llpf_sqkf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_sqkf_bank_reset)
+int llpf_sqkf_bank_set_models(llpf_sqkf_bank* b, const llpf_model* models, const double* D) LLPF_TRY {
+    NEEDF(b);
+    return sqkf_set_models(*b, models, D);
+} LLPF_GUARD(llpf_sqkf_bank_set_models)
+int llpf_sqkf_bank_run(llpf_sqkf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
+                       const llpf_kalman_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return sqkf_run(*b, U, Y, T, per_filter, ll_total, out);
+} LLPF_GUARD(llpf_sqkf_bank_run)
+int llpf_sqkf_bank_get_state(llpf_sqkf_bank* b, double* x, double* R, double* L) LLPF_TRY { NEEDF(b); return sqkf_get_state(*b, x, R, L); } LLPF_GUARD(llpf_sqkf_bank_get_state)
+int llpf_sqkf_bank_set_state(llpf_sqkf_bank* b, const double* x, const double* R, const double* L) LLPF_TRY { NEEDF(b); return sqkf_set_state(*b, x, R, L); } LLPF_GUARD(llpf_sqkf_bank_set_state)
 
 // ---- banks of IMM filters over Kalman filters or over extended Kalman filters (host/kfbank.hpp, host/imm.hpp) ----
 int llpf_imm_bank_create(int32_t device, const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t n_filters,

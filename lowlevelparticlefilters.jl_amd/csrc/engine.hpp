@@ -412,6 +412,9 @@ hipError_t launch_simulate(int model_id, int nx, int ny, const ModelD* models, i
 hipError_t launch_kalman(int nx, int ny, const KalmanArgs& a, hipStream_t s);
 // the backward (RTS smoother) pass of those banks over one chunk, nx in 1..8 (ny, nu at run time)
 hipError_t launch_kalman_smooth(int nx, const KalmanSmoothArgs& a, hipStream_t s);
+// banks of square-root Kalman filters (k_sqkf.hip; kernels/sqkf.hpp): one chunk of steps, nx in 1..8, ny in 1..4; KalmanArgs with the
+// factor Lr where R is in the state, the factors L1, L2 where R1, R2 are in par, post null
+hipError_t launch_sqkf(int nx, int ny, const KalmanArgs& a, hipStream_t s);
 // banks of unscented Kalman filters (k_ukf.hip; kernels/ukf.hpp): ukf_prepare compiles the k_ukf of a run-time compiled model (a user model,
 // the linear-Gaussian model above 4 states) on its first use (0, or -1 with `err` set); launch_ukf runs one chunk of steps
 int ukf_prepare(int model_id, int nx, int ny, std::string& err);

@@ -36,7 +36,7 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMeasurement, GaussianLikelihood,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
-       GPUKalmanFilter, GPUKalmanFilterBank, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
+       GPUKalmanFilter, GPUKalmanFilterBank, GPUSqKalmanFilter, GPUSqKalmanFilterBank, sqkf_run, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
        ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank, set_iterations!,
        GPUEnsembleKalmanFilter, GPUEnsembleKalmanFilterBank, set_inflation!, members, set_members!,
        GPUIMM, GPUIMMBank, mode_probabilities, mode_states, set_mode_states!
@@ -1099,6 +1099,104 @@ function LowLevelParticleFilters.smooth(kf::GPUKalmanFilter, u, y, p = NullParam
     sol = KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
                                   [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
     KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
+end
+
+# ---- banks of square-root Kalman filters (the reference's SqKalmanFilter, src/sq_kalman.jl): llpf_sqkf_bank_* ----
+mutable struct GPUSqKalmanFilterBank
+    h::Ptr{Cvoid}
+    F::Int
+    nx::Int
+    nu::Int
+    ny::Int
+end
+"""
+    GPUSqKalmanFilterBank(filters; Ts = 1.0, device = 0)
+
+Independent square-root Kalman filters on the device, one GPU thread each: `GPUKalmanFilterBank`'s filters, each carrying a triangular
+factor of its covariance (csrc/shared/llpf_sqkf.h), so that a diffuse prior with a near-perfect measurement stays finite.  R1, R2 and
+cov(d0) must be positive definite.  There is no smoother.
+"""
+function GPUSqKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0)
+    cms = [kalman_model(f[1], f[2], f[3], f[5], f[6], f[7], Ts) for f in filters]
+    Dv = kalman_D([f[4] for f in filters], cms[1].ny, cms[1].nu)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_sqkf_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Ptr{Float64}, Int32, Ref{Ptr{Cvoid}}), device, cms, Dv, length(cms), h))
+    b = GPUSqKalmanFilterBank(h[], length(cms), cms[1].nx, cms[1].nu, cms[1].ny)
+    finalizer(x -> ccall((:llpf_sqkf_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    b
+end
+function set_parameters!(b::GPUSqKalmanFilterBank, filters::Vector; Ts = 1.0)
+    cms = [kalman_model(f[1], f[2], f[3], f[5], f[6], f[7], Ts) for f in filters]
+    length(cms) == b.F || throw(ArgumentError("set_parameters!: $(length(cms)) filters for a bank of $(b.F)"))
+    Dv = kalman_D([f[4] for f in filters], b.ny, b.nu)
+    check(ccall((:llpf_sqkf_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}, Ptr{Float64}), b.h, cms, Dv))
+    b
+end
+reset!(b::GPUSqKalmanFilterBank) = check(ccall((:llpf_sqkf_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+# u, y and the returned values as kalman_run's
+function sqkf_run(b::GPUSqKalmanFilterBank, u, y; outputs = false)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        check(ccall((:llpf_sqkf_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{CKalmanOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+loglik(b::GPUSqKalmanFilterBank, u, y) = (reset!(b); sqkf_run(b, u, y)[1])
+"x (nx x F), R = L L' (nx x nx x F) and the lower-triangular factor L (nx x nx x F) of every filter"
+function state(b::GPUSqKalmanFilterBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F); Lt = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_sqkf_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, x, R, Lt))
+    x, R, permutedims(Lt, (2, 1, 3))                 # the row-major [nx][nx] read column-major is the transpose
+end
+covariance(b::GPUSqKalmanFilterBank) = state(b)[2]
+"set the estimate of every filter: x (nx x F) and the covariance R (factored; its lower triangle is read) or, with factor = true, the lower-triangular factor itself"
+function set_state!(b::GPUSqKalmanFilterBank, x, R; factor = false)
+    xm = Matrix{Float64}(reshape(x, b.nx, b.F)); Rm = Array{Float64}(reshape(R, b.nx, b.nx, b.F))
+    Rr = permutedims(Rm, (2, 1, 3))
+    GC.@preserve Rr begin
+        check(ccall((:llpf_sqkf_bank_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, xm,
+                    factor ? C_NULL : pointer(Rr), factor ? pointer(Rr) : C_NULL))
+    end
+    b
+end
+
+"""
+    GPUSqKalmanFilter(A, B, C, D, R1, R2, d0; Ts = 1.0, device = 0)
+
+The reference's `SqKalmanFilter`, run on the device (a bank of one filter, llpf_sqkf_bank_*): `forward_trajectory` returns the reference's
+`KalmanFilteringSolution`; `loglik`, `reset!`, `update!`, `state`, `covariance`.  There is no smoother.
+"""
+mutable struct GPUSqKalmanFilter
+    bank::GPUSqKalmanFilterBank
+    Ts::Float64
+end
+GPUSqKalmanFilter(A, B, C, D, R1, R2, d0; Ts = 1.0, device = 0) =
+    GPUSqKalmanFilter(GPUSqKalmanFilterBank([(A, B, C, D, R1, R2, d0)]; Ts = Ts, device = device), Float64(Ts))
+reset!(kf::GPUSqKalmanFilter) = reset!(kf.bank)
+loglik(kf::GPUSqKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
+function update!(kf::GPUSqKalmanFilter, u, y, p = NullParameters(), t = 0)
+    _, o = sqkf_run(kf.bank, [u], [y]; outputs = true)
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+state(kf::GPUSqKalmanFilter) = state(kf.bank)[1][:, 1]
+covariance(kf::GPUSqKalmanFilter) = state(kf.bank)[2][:, :, 1]
+function forward_trajectory(kf::GPUSqKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o = sqkf_run(kf.bank, u, y; outputs = true)
+    T = length(y)
+    KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                            [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
 end
 
 # ---- banks of IMM filters over Kalman filters or over extended Kalman filters of one model (the reference's IMM(models, P, mu), src/imm.jl;
