@@ -530,14 +530,16 @@ class _KfBankHandle(_Handle):
             U, u_per_filter = None, False
         return U, Y, T, u_per_filter
 
-    def _forward_outputs(self, T, outputs):
-        F, nx, ny = self.F, self.nx, self.ny
-        shapes = {"ll_steps": (T, F), "x": (T, F, nx), "xt": (T, F, nx), "R": (T, F, nx, nx), "Rt": (T, F, nx, nx), "e": (T, F, ny)}
+    def _forward_outputs(self, T, outputs, struct=S.KalmanOutputs, more=None):
+        """`struct`: the outputs' struct of the bank's run; `more`: the shapes of its members next to ll_steps, x, xt, R and Rt"""
+        F, nx = self.F, self.nx
+        shapes = {"ll_steps": (T, F), "x": (T, F, nx), "xt": (T, F, nx), "R": (T, F, nx, nx), "Rt": (T, F, nx, nx)}
+        shapes.update({"e": (T, F, self.ny)} if more is None else more)
         res = {k: np.empty(shapes[k]) for k in outputs}
         out = None
         if res:
-            out = S.KalmanOutputs()
-            out.struct_size = C.sizeof(S.KalmanOutputs)
+            out = struct()
+            out.struct_size = C.sizeof(struct)
             for k, a in res.items():
                 setattr(out, k, dptr(a))
         return res, out
@@ -580,19 +582,23 @@ class _KfBankHandle(_Handle):
         self._call("set_state", dptr(x), dptr(R))
 
 
-class KalmanBankHandle(_KfBankHandle):
-    """RAII wrapper of an `llpf_kalman_bank*` (independent Kalman filters with constant matrices on one device)."""
-    _SYM = "llpf_kalman_bank"
+class _KfMatrixBankHandle(_KfBankHandle):
+    """What the handles of the banks with constant matrices share: the models and D [F, ny, nu] or None."""
 
     def __init__(self, device, models, D=None):
         arr = self._open(models)
         D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
-        check(self.L.llpf_kalman_bank_create(int(device), arr, dptr(D), self.F, C.byref(self.h)))
+        check(getattr(self.L, self._SYM + "_create")(int(device), arr, dptr(D), self.F, C.byref(self.h)))
 
     def set_models(self, models, D=None):
         arr = (S.Model * self.F)(*models)
         D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
         self._call("set_models", arr, dptr(D))
+
+
+class KalmanBankHandle(_KfMatrixBankHandle):
+    """RAII wrapper of an `llpf_kalman_bank*` (independent Kalman filters with constant matrices on one device)."""
+    _SYM = "llpf_kalman_bank"
 
     def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
         """T steps of every filter: U [T, nu] or [F, T, nu] (u_per_filter), Y [T, ny] or [F, T, ny] (y_per_filter).  Returns
@@ -607,20 +613,10 @@ class KalmanBankHandle(_KfBankHandle):
         return self._smooth(U, Y, u_per_filter, y_per_filter, outputs, forward)
 
 
-class SqkfBankHandle(_KfBankHandle):
+class SqkfBankHandle(_KfMatrixBankHandle):
     """RAII wrapper of an `llpf_sqkf_bank*` (independent square-root Kalman filters with constant matrices on one device): the models,
     D, inputs and outputs of KalmanBankHandle; the state is x and a lower-triangular factor L of the covariance, R = L L'."""
     _SYM = "llpf_sqkf_bank"
-
-    def __init__(self, device, models, D=None):
-        arr = self._open(models)
-        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
-        check(self.L.llpf_sqkf_bank_create(int(device), arr, dptr(D), self.F, C.byref(self.h)))
-
-    def set_models(self, models, D=None):
-        arr = (S.Model * self.F)(*models)
-        D = None if D is None else f64(D).reshape(self.F, self.ny, self.nu)
-        self._call("set_models", arr, dptr(D))
 
     def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=()):
         """T steps of every filter; inputs and the returned dictionary as KalmanBankHandle.run (R and Rt are L L')"""
@@ -685,17 +681,8 @@ class IMMBankHandle(_KfBankHandle):
         KalmanBankHandle.run.  Returns {"ll": [F], name: array} for every name of `outputs` (IMM_OUTPUTS), time-major: ll_steps [T, F],
         x / xt [T, F, nx], R / Rt [T, F, nx, nx] (the combined estimate), mu / ll_modes [T, F, M]."""
         U, Y, T, u_per_filter = self._inputs(U, Y, u_per_filter, y_per_filter)
-        F, nx, M = self.F, self.nx, self.M
-        shapes = {"ll_steps": (T, F), "x": (T, F, nx), "xt": (T, F, nx), "R": (T, F, nx, nx), "Rt": (T, F, nx, nx), "mu": (T, F, M),
-                  "ll_modes": (T, F, M)}
-        res = {k: np.empty(shapes[k]) for k in outputs}
-        out = None
-        if res:
-            out = S.ImmOutputs()
-            out.struct_size = C.sizeof(S.ImmOutputs)
-            for k, a in res.items():
-                setattr(out, k, dptr(a))
-        ll = np.empty(F)
+        res, out = self._forward_outputs(T, outputs, S.ImmOutputs, {"mu": (T, self.F, self.M), "ll_modes": (T, self.F, self.M)})
+        ll = np.empty(self.F)
         self._call("run_at", dptr(U), dptr(Y), T, (1 if u_per_filter else 0) | (2 if y_per_filter else 0), float(t_index0), dptr(ll),
                    None if out is None else C.byref(out))
         res["ll"] = ll

@@ -39,7 +39,7 @@ static int ekf_run(llpf_ekf_bank& b, const double* U, const double* Y, int64_t T
     CHK(kf_check_run(b, U, Y, T, per_filter, out));
     if (!std::isfinite(t_index0)) return fail(LLPF_ERR_ARG, "ekf: t_index0 must be finite");
     test_throw("ekf_run");
-    return kf_forward(b, U, Y, T, per_filter, ll_total, out, nullptr, [&](const KfChunk& c) -> int {
+    return kf_forward(b, U, Y, T, per_filter, kf_outputs(b, ll_total, out), nullptr, [&](const KfChunk& c) -> int {
         const EkfArgs a{kf_model_args(b, c, t_index0)};
         if (b.maxiters > 1)
             HIPC(launch_iekf(b.model_id, b.nx, b.ny, b.d_models, a, b.maxiters, b.epsilon, b.stream));

@@ -89,7 +89,7 @@ static int enkf_forward(llpf_enkf_bank& b, const double* U, const double* Y, int
     if (!std::isfinite(t_index0)) return fail(LLPF_ERR_ARG, "enkf: t_index0 must be finite");
     test_throw("enkf_run");
     const uint32_t step0 = b.step;
-    CHK(kf_forward(b, U, Y, T, per_filter, ll_total, out, nullptr, [&](const KfChunk& c) -> int {
+    CHK(kf_forward(b, U, Y, T, per_filter, kf_outputs(b, ll_total, out), nullptr, [&](const KfChunk& c) -> int {
         EnkfArgs a{};
         static_cast<KfModelArgs&>(a) = kf_model_args(b, c, t_index0);
         a.members = b.d_members; a.key0 = b.seed; a.rho = b.rho; a.N = b.N; a.step0 = step0; a.phases = phases;

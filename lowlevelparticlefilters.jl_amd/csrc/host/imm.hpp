@@ -5,9 +5,9 @@
 // The bank is a KfBank (host/kfbank.hpp) whose columns are lanes: G = 1, 2 or 4 lanes per filter (the smallest G >= M), column f * G + j is
 // mode j of filter f, L = F * G columns in all (those of the idle lanes j >= M stay zero).  par is [npar + LLPF_IMM_MAXM][L]: the mode's
 // Kalman constants as host/kalman.hpp packs them, then column j of the filter's transition matrix; the state is [nx + np + 2][L]: the
-// mode's x, packed R, mu_j and the run's running ll_total (the same number in every lane of a filter).  A run goes through the chunked
-// staging pipeline of host/pipe.hpp like kf_forward, with this bank's own outputs.  The combined estimate of get_state is formed on the
-// host from the downloaded state, by the functions of shared/llpf_imm.h the kernel forms it with.
+// mode's x, packed R, mu_j and the run's running ll_total (the same number in every lane of a filter).  A run is kf_forward with this
+// bank's own outputs.  The combined estimate of get_state is formed on the host from the downloaded state, by the functions of
+// shared/llpf_imm.h the kernel forms it with.
 // An extended bank (LLPF_IMM_EXTENDED, implied by a model id other than LLPF_MODEL_LINEAR_GAUSSIAN) keeps the columns and the state and
 // has, in the place of the Kalman constants, the descriptors ModelD [L] that the model's own functions read and par
 // [LLPF_EKF_NPAR + LLPF_IMM_MAXM][L]: R1, R2 packed, then column j of P.  The columns of its idle lanes stay zero as well: k_imm_ekf
@@ -15,7 +15,6 @@
 
 namespace llpf {
 #include "../kernels/imm_args.hpp"
-#include "../kernels/imm_ekf_args.hpp"
 // the extended bank's kernel (k_imm_ekf.hip): imm_ekf_prepare compiles the k_imm_ekf of a run-time compiled model at g lanes per filter on
 // its first use (0, or -1 with `err` set); launch_imm_ekf runs one chunk of steps
 int imm_ekf_prepare(int model_id, int nx, int ny, int g, std::string& err);
@@ -50,65 +49,44 @@ static int imm_check_tables(const double* Pf, const double* mf, int M, const std
     return LLPF_OK;
 }
 
-// models [F][M] (+ D [F][M][ny][nu] or NULL), P [F][M][M], mu0 [F][M] -> the SoA constants and initial state; every check that needs no device
-static int imm_pack(const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t F, int32_t M, int& nx, int& ny,
-                    int& nu, std::vector<double>& par, std::vector<double>& init) {
-    if (!models) return fail(LLPF_ERR_ARG, "imm: models is null");
-    if (!P || !mu0) return fail(LLPF_ERR_ARG, "imm: P and mu0 must both be given");
-    if (F < 1) return fail(LLPF_ERR_ARG, "imm: n_filters must be >= 1");
-    if (M < 1 || M > LLPF_IMM_MAXM) return fail(LLPF_ERR_ARG, "imm: n_modes must be in 1..4");
-    nx = models[0].nx; ny = models[0].ny; nu = models[0].nu;
-    if (nx < 1 || nx > LLPF_KF_MAXX || ny < 1 || ny > LLPF_KF_MAXY || nu < 0 || nu > LLPF_KF_MAXU)
-        return fail(LLPF_ERR_ARG, "imm: nx must be in 1..8, ny in 1..4 and nu in 0..8");
-    const int G = imm_group(M), L = F * G;
-    const int np = LLPF_KF_NP(nx), npar = LLPF_KF_NPAR(nx, ny, nu), nstate = nx + np + 2;
-    par.assign((size_t)(npar + LLPF_IMM_MAXM) * L, 0.0);
-    init.assign((size_t)nstate * L, 0.0);
-    for (int f = 0; f < F; ++f) {
-        const std::string atf = "imm: filter " + std::to_string(f) + ": ";
-        const double* Pf = P + (size_t)f * M * M;
-        const double* mf = mu0 + (size_t)f * M;
-        CHK(imm_check_tables(Pf, mf, M, atf));
-        for (int j = 0; j < M; ++j) {
-            const llpf_model& m = models[(size_t)f * M + j];
-            const std::string at = "imm: filter " + std::to_string(f) + ", mode " + std::to_string(j) + ": ";
-            const int col = f * G + j;
-            if (m.model_id != LLPF_MODEL_LINEAR_GAUSSIAN) return fail(LLPF_ERR_ARG, at + "model_id must be LLPF_MODEL_LINEAR_GAUSSIAN");
-            if (m.nx != nx || m.ny != ny || m.nu != nu) return fail(LLPF_ERR_ARG, at + "dimensions differ from those of filter 0, mode 0");
-            CHK(kf_pack_filter(m, at, col, L, nx, ny, LLPF_KF_OFF_R1(nx, ny), LLPF_KF_OFF_R2(nx, ny), par, init));
-            GaussD gd;                                // positive definiteness of R2 and P0, as the Kalman bank checks them
-            if (gauss_prepare(&m.measurement_density, &gd) != 0) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
-            if (gauss_prepare(&m.initial_density, &gd) != 0) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
-            auto put = [&](int e, double v) { par[(size_t)e * L + col] = v; };
-            for (int i = 0; i < nx * nx; ++i) put(LLPF_KF_OFF_A + i, m.A[i]);
-            for (int i = 0; i < ny * nx; ++i) put(LLPF_KF_OFF_C(nx) + i, m.C[i]);
-            for (int i = 0; i < nx * nu; ++i) put(LLPF_KF_OFF_B(nx, ny) + i, m.B[i]);
-            for (int i = 0; i < ny * nu; ++i) put(LLPF_KF_OFF_D(nx, ny, nu) + i, D ? D[((size_t)f * M + j) * ny * nu + i] : 0.0);
-            for (int i = 0; i < M; ++i) put(npar + i, Pf[i * M + j]);
-            init[(size_t)(nx + np) * L + col] = mf[j];
-        }
-    }
+// what a mode of a Kalman bank adds to the pack: positive definiteness of R2 and P0, as the Kalman bank checks them, and A, C, B and
+// D (Dm [ny][nu], or NULL) as host/kalman.hpp packs them
+static int imm_pack_kalman_mode(const llpf_model& m, const std::string& at, const double* Dm, int col, int L, int nx, int ny, int nu,
+                                std::vector<double>& par) {
+    GaussD gd;
+    if (gauss_prepare(&m.measurement_density, &gd) != 0) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
+    if (gauss_prepare(&m.initial_density, &gd) != 0) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
+    auto put = [&](int e, double v) { par[(size_t)e * L + col] = v; };
+    for (int i = 0; i < nx * nx; ++i) put(LLPF_KF_OFF_A + i, m.A[i]);
+    for (int i = 0; i < ny * nx; ++i) put(LLPF_KF_OFF_C(nx) + i, m.C[i]);
+    for (int i = 0; i < nx * nu; ++i) put(LLPF_KF_OFF_B(nx, ny) + i, m.B[i]);
+    for (int i = 0; i < ny * nu; ++i) put(LLPF_KF_OFF_D(nx, ny, nu) + i, Dm ? Dm[i] : 0.0);
     return LLPF_OK;
 }
 
-// the pack of an extended bank: models [F][M] of one model id -> the descriptors ModelD [L], the SoA constants and the initial state; the
-// checks of llpf_ekf_bank_create (kf_pack_models on the first model: both Jacobian members, no noise / initial / loglik member, not
-// Rao-Blackwellized) and, per mode, one model id and one set of dimensions, the densities and their definiteness
-static int imm_pack_extended(const llpf_model* models, const double* P, const double* mu0, int32_t F, int32_t M, int& model_id, int& nx,
-                             int& ny, int& nu, std::vector<ModelD>& hm, std::vector<double>& par, std::vector<double>& init) {
+// models [F][M] (+ D [F][M][ny][nu] or NULL), P [F][M][M], mu0 [F][M] -> the SoA constants and initial state and, of an extended bank,
+// the descriptors ModelD [L]; every check that needs no device.  A Kalman bank's modes are linear-Gaussian models; an extended bank's
+// are of one model id, which passes the checks of llpf_ekf_bank_create (kf_pack_models on the first model: both Jacobian members, no
+// noise / initial / loglik member, not Rao-Blackwellized); what a mode adds is imm_pack_kalman_mode or the model's descriptor
+static int imm_pack(bool extended, const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t F, int32_t M,
+                    int& model_id, int& nx, int& ny, int& nu, std::vector<ModelD>& hm, std::vector<double>& par, std::vector<double>& init) {
     if (!models) return fail(LLPF_ERR_ARG, "imm: models is null");
     if (!P || !mu0) return fail(LLPF_ERR_ARG, "imm: P and mu0 must both be given");
     if (F < 1) return fail(LLPF_ERR_ARG, "imm: n_filters must be >= 1");
     if (M < 1 || M > LLPF_IMM_MAXM) return fail(LLPF_ERR_ARG, "imm: n_modes must be in 1..4");
-    {
-        std::vector<ModelD> hm0;
+    if (extended) {
         std::vector<double> par0, init0;
         CHK(kf_pack_models("imm", "extended Kalman filter", LLPF_TRAIT_DYNAMICS_JAC | LLPF_TRAIT_MEASUREMENT_JAC, 0, models, 1, model_id, nx, ny,
-                           nu, hm0, par0, init0));
+                           nu, hm, par0, init0));
+    } else {
+        model_id = LLPF_MODEL_LINEAR_GAUSSIAN; nx = models[0].nx; ny = models[0].ny; nu = models[0].nu;
+        if (nx < 1 || nx > LLPF_KF_MAXX || ny < 1 || ny > LLPF_KF_MAXY || nu < 0 || nu > LLPF_KF_MAXU)
+            return fail(LLPF_ERR_ARG, "imm: nx must be in 1..8, ny in 1..4 and nu in 0..8");
     }
     const int G = imm_group(M), L = F * G;
-    const int np = LLPF_KF_NP(nx), npar = LLPF_EKF_NPAR(nx, ny), nstate = nx + np + 2;
-    hm.assign((size_t)L, ModelD{});
+    const int np = LLPF_KF_NP(nx), npar = extended ? LLPF_EKF_NPAR(nx, ny) : LLPF_KF_NPAR(nx, ny, nu), nstate = nx + np + 2;
+    const int off_r1 = extended ? LLPF_EKF_OFF_R1 : LLPF_KF_OFF_R1(nx, ny), off_r2 = extended ? LLPF_EKF_OFF_R2(nx) : LLPF_KF_OFF_R2(nx, ny);
+    hm.assign(extended ? (size_t)L : 0, ModelD{});
     par.assign((size_t)(npar + LLPF_IMM_MAXM) * L, 0.0);
     init.assign((size_t)nstate * L, 0.0);
     for (int f = 0; f < F; ++f) {
@@ -116,17 +94,17 @@ static int imm_pack_extended(const llpf_model* models, const double* P, const do
         const double* mf = mu0 + (size_t)f * M;
         CHK(imm_check_tables(Pf, mf, M, "imm: filter " + std::to_string(f) + ": "));
         for (int j = 0; j < M; ++j) {
-            const llpf_model& m = models[(size_t)f * M + j];
+            const size_t fj = (size_t)f * M + j;
+            const llpf_model& m = models[fj];
             const std::string at = "imm: filter " + std::to_string(f) + ", mode " + std::to_string(j) + ": ";
             const int col = f * G + j;
-            if (m.model_id != model_id) return fail(LLPF_ERR_ARG, at + "model_id differs from that of filter 0, mode 0: the modes of an extended bank are one model type");
+            if (m.model_id != model_id)
+                return fail(LLPF_ERR_ARG, at + (extended ? "model_id differs from that of filter 0, mode 0: the modes of an extended bank are one model type"
+                                                         : "model_id must be LLPF_MODEL_LINEAR_GAUSSIAN"));
             if (m.nx != nx || m.ny != ny || m.nu != nu) return fail(LLPF_ERR_ARG, at + "dimensions differ from those of filter 0, mode 0");
-            CHK(kf_pack_filter(m, at, col, L, nx, ny, LLPF_EKF_OFF_R1, LLPF_EKF_OFF_R2(nx), par, init));
-            const int rc = model_prepare(&m, &hm[(size_t)col]);
-            if (rc == -1) return fail(LLPF_ERR_ARG, at + "R1 (dynamics_density) is not positive definite");
-            if (rc == -2) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
-            if (rc == -3) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
-            if (rc) return fail(LLPF_ERR_ARG, at + "invalid model descriptor, code " + std::to_string(rc));
+            CHK(kf_pack_filter(m, at, col, L, nx, ny, off_r1, off_r2, par, init));
+            if (extended) CHK(kf_model_descriptor(m, at, &hm[(size_t)col]));
+            else CHK(imm_pack_kalman_mode(m, at, D ? D + fj * ny * nu : nullptr, col, L, nx, ny, nu, par));
             for (int i = 0; i < M; ++i) par[(size_t)(npar + i) * L + col] = Pf[i * M + j];
             init[(size_t)(nx + np) * L + col] = mf[j];
         }
@@ -134,58 +112,38 @@ static int imm_pack_extended(const llpf_model* models, const double* P, const do
     return LLPF_OK;
 }
 
+static const char* const IMM_NO_D = "imm: D must be NULL when the modes are extended Kalman filters (LLPF_IMM_EXTENDED)";
+
 static int imm_create(int32_t device, const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t F, int32_t M,
                       int32_t flags, llpf_imm_bank& b) {
     if (flags & ~(LLPF_IMM_INTERACT | LLPF_IMM_EXTENDED)) return fail(LLPF_ERR_ARG, "imm: flags has bits other than 0 and 1");
     std::vector<double> par;
     std::vector<ModelD> hm;
     b.extended = ((flags & LLPF_IMM_EXTENDED) || (models && models[0].model_id != LLPF_MODEL_LINEAR_GAUSSIAN)) ? 1 : 0;
-    if (b.extended) {
-        if (D) return fail(LLPF_ERR_ARG, "imm: D must be NULL when the modes are extended Kalman filters (LLPF_IMM_EXTENDED)");
-        CHK(imm_pack_extended(models, P, mu0, F, M, b.model_id, b.nx, b.ny, b.nu, hm, par, b.h_init));
-        CHK(kf_open(b, device, F, LLPF_EKF_NPAR(b.nx, b.ny), "imm_create"));
-        b.Ts = models[0].Ts;
-    } else {
-        CHK(imm_pack(models, D, P, mu0, F, M, b.nx, b.ny, b.nu, par, b.h_init));
-        CHK(kf_open(b, device, F, LLPF_KF_NPAR(b.nx, b.ny, b.nu), "imm_create"));
-    }
+    if (b.extended && D) return fail(LLPF_ERR_ARG, IMM_NO_D);
+    CHK(imm_pack(b.extended, models, D, P, mu0, F, M, b.model_id, b.nx, b.ny, b.nu, hm, par, b.h_init));
+    CHK(kf_open(b, device, F, b.extended ? LLPF_EKF_NPAR(b.nx, b.ny) : LLPF_KF_NPAR(b.nx, b.ny, b.nu), "imm_create"));
+    if (b.extended) b.Ts = models[0].Ts;
     b.M = M; b.G = imm_group(M); b.L = F * b.G;
     b.interact = flags & LLPF_IMM_INTERACT;
     b.nstate = b.nx + b.np + 2;
     if (b.extended) {
         std::string err;
         if (imm_ekf_prepare(b.model_id, b.nx, b.ny, b.G, err) != 0) return fail(LLPF_ERR_HIP, "imm: " + err);
-        CHK(b.d_models.ensure(hm.size()));
-        CHK(b.d_zero.ensure(MAXU));
-        HIPC(hipMemsetAsync(b.d_zero, 0, sizeof(double) * MAXU, b.stream));
-        HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
     }
-    CHK(b.d_par.ensure(par.size()));
-    CHK(b.d_state.ensure(b.h_init.size()));
-    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipStreamSynchronize(b.stream));
-    return LLPF_OK;
+    return kf_upload(b, b.d_models, b.d_zero, hm, par, true);
 }
 
 static int imm_set_models(llpf_imm_bank& b, const llpf_model* models, const double* D, const double* P, const double* mu0) {
     std::vector<double> par, init;
     std::vector<ModelD> hm;
-    int nx = 0, ny = 0, nu = 0;
-    if (b.extended) {
-        int id = 0;
-        if (D) return fail(LLPF_ERR_ARG, "imm: D must be NULL when the modes are extended Kalman filters (LLPF_IMM_EXTENDED)");
-        CHK(imm_pack_extended(models, P, mu0, b.F, b.M, id, nx, ny, nu, hm, par, init));
-        if (id != b.model_id || nx != b.nx || ny != b.ny || nu != b.nu)
-            return fail(LLPF_ERR_ARG, "imm: set_models must keep the model id and the dimensions of the bank");
-    } else {
-        CHK(imm_pack(models, D, P, mu0, b.F, b.M, nx, ny, nu, par, init));
-        if (nx != b.nx || ny != b.ny || nu != b.nu) return fail(LLPF_ERR_ARG, "imm: set_models must keep the dimensions of the bank");
-    }
-    HIPC(hipSetDevice(b.device));
-    if (b.extended) HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipStreamSynchronize(b.stream));
+    int id = 0, nx = 0, ny = 0, nu = 0;
+    if (b.extended && D) return fail(LLPF_ERR_ARG, IMM_NO_D);
+    CHK(imm_pack(b.extended, models, D, P, mu0, b.F, b.M, id, nx, ny, nu, hm, par, init));
+    if (id != b.model_id || nx != b.nx || ny != b.ny || nu != b.nu)
+        return fail(LLPF_ERR_ARG, b.extended ? "imm: set_models must keep the model id and the dimensions of the bank"
+                                             : "imm: set_models must keep the dimensions of the bank");
+    CHK(kf_upload(b, b.d_models, b.d_zero, hm, par, false));
     b.h_init.swap(init);
     if (b.extended) b.Ts = models[0].Ts;
     return LLPF_OK;
@@ -198,73 +156,33 @@ static int imm_check_time(double t_index0) {
     return LLPF_OK;
 }
 
+// T steps of every filter from the current state: kf_forward with this bank's seven outputs and k_imm or k_imm_ekf.  ll_total is row
+// nx + np + 1 of the state, the same number in every lane of a filter
 static int imm_run(llpf_imm_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
                    const llpf_imm_outputs* out) {
-    CHK(kf_check_run(b, U, Y, T, per_filter, nullptr));
+    CHK(kf_check_run(b, U, Y, T, per_filter, out, "llpf_imm_outputs"));
     CHK(imm_check_time(t_index0));
-    if (out && out->struct_size < sizeof(llpf_imm_outputs)) return kf_fail(b.who, "llpf_imm_outputs.struct_size too small (ABI)");
     test_throw("imm_run");
-    const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu, M = b.M;
-    const bool upf = nu > 0 && (per_filter & 1), ypf = (per_filter & 2) != 0;
-    // the outputs of one step, in staging order: ll, x, xt, R, Rt, mu, ll_modes
-    double* dst[7] = {out ? out->ll_steps : nullptr, out ? out->x : nullptr, out ? out->xt : nullptr, out ? out->R : nullptr,
-                      out ? out->Rt : nullptr, out ? out->mu : nullptr, out ? out->ll_modes : nullptr};
-    const uint64_t width[7] = {1, (uint64_t)nx, (uint64_t)nx, (uint64_t)nx * nx, (uint64_t)nx * nx, (uint64_t)M, (uint64_t)M};
-    uint64_t w = 0;
-    std::vector<ChunkOut> outs;
-    for (int k = 0; k < 7; ++k) {
-        if (dst[k]) w += width[k];
-        outs.push_back({dst[k], 1, (size_t)F * width[k]});
-    }
-    const uint64_t in_w = (upf ? (uint64_t)nu : 0) + (ypf ? (uint64_t)ny : 0);
-    uint64_t total = 0, in_total = 0;
-    if (!doubles_fit({(uint64_t)F, w, (uint64_t)T}, total) || !doubles_fit({(uint64_t)F, in_w, (uint64_t)T}, in_total))
-        return kf_fail(b.who, "the size of the outputs or of the inputs overflows");
-    std::vector<double> h_ll(ll_total ? (size_t)b.L : 0);
-    HIPC(hipSetDevice(b.device));
-    ChunkPipe pipe(b.stream);
-    CHK(pipe.open(T, (size_t)F * (w + in_w) * sizeof(double), outs,
-                  {{nu > 0 ? U : nullptr, upf ? (size_t)F : 0, (size_t)nu, true}, {Y, ypf ? (size_t)F : 0, (size_t)ny, true}}));
-    for (int64_t c = 0; c < pipe.nchunk; ++c) {
-        CHK(pipe.begin(c, c));
-        if (b.extended) {
-            ImmEkfArgs a{};
-            a.par = b.d_par; a.state = b.d_state; a.zero_u = b.d_zero;
-            a.u = pipe.in(0);
-            a.y = pipe.in(1);
-            double** slot[7] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.mu, &a.ll_modes};
-            for (int k = 0; k < 7; ++k) *slot[k] = pipe.out(k);
-            a.F = F; a.t0 = pipe.t0; a.Tc = (int32_t)pipe.tc; a.nu = nu; a.M = M;
-            a.u_per = upf ? 1 : 0; a.y_per = ypf ? 1 : 0;
-            a.first = c == 0 ? 1 : 0;
-            a.interact = b.interact;
-            a.t_index0 = t_index0; a.Ts = b.Ts;
-            HIPC(launch_imm_ekf(b.model_id, nx, ny, b.G, b.d_models, a, b.stream));
-            CHK(pipe.end());
-            continue;
-        }
-        ImmArgs a{};
+    const uint64_t nx = (uint64_t)b.nx, M = (uint64_t)b.M;
+    const llpf_imm_outputs none{};
+    if (!out) out = &none;
+    const KfOutputs o{7, {out->ll_steps, out->x, out->xt, out->R, out->Rt, out->mu, out->ll_modes}, {1, nx, nx, nx * nx, nx * nx, M, M},
+                      ll_total, b.nx + b.np + 1, b.G};
+    return kf_forward(b, U, Y, T, per_filter, o, nullptr, [&](const KfChunk& c) -> int {
+        ImmBaseArgs a{};
         a.par = b.d_par; a.state = b.d_state;
-        a.u = pipe.in(0);
-        a.y = pipe.in(1);
+        a.u = c.u;
+        a.y = c.y;
         double** slot[7] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.mu, &a.ll_modes};
-        for (int k = 0; k < 7; ++k) *slot[k] = pipe.out(k);
-        a.F = F; a.Tc = (int32_t)pipe.tc; a.nu = nu; a.M = M;
-        a.u_per = upf ? 1 : 0; a.y_per = ypf ? 1 : 0;
-        a.first = c == 0 ? 1 : 0;
+        for (int k = 0; k < 7; ++k) *slot[k] = c.out[k];
+        a.F = b.F; a.Tc = c.tc; a.nu = b.nu; a.M = b.M;
+        a.u_per = c.upf; a.y_per = c.ypf;
+        a.first = c.first;
         a.interact = b.interact;
-        a.par_tstride = 0;
-        HIPC(launch_imm(nx, ny, b.G, a, b.stream));
-        CHK(pipe.end());
-    }
-    CHK(pipe.finish());
-    if (ll_total) {    // the running sum: row nx + np + 1 of the state, the same in every lane of a filter
-        HIPC(hipMemcpyAsync(h_ll.data(), b.d_state.p + (size_t)(nx + b.np + 1) * b.L, sizeof(double) * b.L, hipMemcpyDeviceToHost, b.stream));
-        HIPC(hipStreamSynchronize(b.stream));
-        for (int f = 0; f < F; ++f) ll_total[f] = h_ll[(size_t)f * b.G];
-    }
-    HIPC(hipStreamSynchronize(b.stream));
-    return LLPF_OK;
+        if (b.extended) HIPC(launch_imm_ekf(b.model_id, b.nx, b.ny, b.G, b.d_models, ImmEkfArgs{a, b.d_zero, c.t0, t_index0, b.Ts}, b.stream));
+        else HIPC(launch_imm(b.nx, b.ny, b.G, ImmArgs{a, 0}, b.stream));
+        return LLPF_OK;
+    });
 }
 
 // the combined x [F][nx], R [F][nx][nx], and mu [F][M], the modes' xm [F][M][nx], Rm [F][M][nx][nx] of the current state (each may be NULL)

@@ -65,7 +65,7 @@ static int kalman_set_models(llpf_kalman_bank& b, const llpf_model* models, cons
 static int kalman_forward(llpf_kalman_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
                           const llpf_kalman_outputs* out, double* post) {
     const int nx = b.nx, ny = b.ny;
-    return kf_forward(b, U, Y, T, per_filter, ll_total, out, post, [&](const KfChunk& c) -> int {
+    return kf_forward(b, U, Y, T, per_filter, kf_outputs(b, ll_total, out), post, [&](const KfChunk& c) -> int {
         KalmanArgs a{};
         a.par = b.d_par; a.state = b.d_state;
         a.u = c.u;

@@ -1,14 +1,14 @@
-// host/kfbank.hpp — what the banks of Kalman filters share (host/kalman.hpp, host/ukf.hpp, host/ekf.hpp, host/enkf.hpp): the bank, its state, the
-// checks of a run's arguments and the drivers of the forward and the backward pass; for the two model-driven banks also their models
-// (KfModelBank).  Part of capi.hip (one translation unit).
+// host/kfbank.hpp — what the banks of Kalman filters share (host/kalman.hpp, host/sqkf.hpp, host/imm.hpp, host/ukf.hpp, host/ekf.hpp,
+// host/enkf.hpp): the bank, its state, the checks of a run's arguments and the drivers of the forward and the backward pass; for the
+// model-driven banks also their models (KfModelBank).  Part of capi.hip (one translation unit).
 // ------------------------------------------------------------------------------------------------
 // Device layout: the constants par [npar][F] (each bank's own rows) and the state [nx + np + 1][F] (x, packed R, the running ll_total of a
 // run), SoA so that lane f of a wave reads column f.  A run drives T through the chunked staging pipeline of host/pipe.hpp, counting a
 // step's outputs and per-filter inputs; outputs are time-major [T][F][width], per-filter inputs reach the device time-major as well.  The
 // state carries from chunk to chunk (and from run to run) in the device buffer, so the prefix of a long run is a short run and run(a)
 // followed by run(b) is run(a + b), bit for bit.  A run that asks for ll_total only stages nothing per step.
-// Nothing here knows which bank it serves: a bank gives its name (the prefix of its messages), its fault-injection sites and, per chunk,
-// a launcher that fills its kernel's own argument struct from a KfChunk / KfSmoothChunk.
+// Nothing here knows which bank it serves: a bank gives its name (the prefix of its messages), its fault-injection sites, the list of
+// its per-step outputs (KfOutputs) and, per chunk, a launcher that fills its kernel's own argument struct from a KfChunk / KfSmoothChunk.
 
 struct KfBank : BankStream {
     const char* who;                  // "kalman" / "ukf": the prefix of every message
@@ -43,6 +43,16 @@ static int kf_pack_filter(const llpf_model& m, const std::string& at, int f, int
         for (int r = 0; r < dims[k]; ++r) for (int c = 0; c <= r; ++c) row[k][(size_t)llpf_kf_idx(r, c) * F + f] = S[r * dims[k] + c];
     }
     for (int i = 0; i < nx; ++i) init[(size_t)i * F + f] = m.initial_density.mu[i];
+    return LLPF_OK;
+}
+
+// the descriptor the model's own methods read (`at`: the filter's message prefix); positive definiteness of R1, R2, cov(d0)
+static int kf_model_descriptor(const llpf_model& m, const std::string& at, ModelD* d) {
+    const int rc = model_prepare(&m, d);
+    if (rc == -1) return fail(LLPF_ERR_ARG, at + "R1 (dynamics_density) is not positive definite");
+    if (rc == -2) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
+    if (rc == -3) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
+    if (rc) return fail(LLPF_ERR_ARG, at + "invalid model descriptor, code " + std::to_string(rc));
     return LLPF_OK;
 }
 
@@ -88,11 +98,7 @@ static int kf_pack_models(const char* who, const char* filter_name, int need_tra
         const std::string at = w + "filter " + std::to_string(f) + ": ";
         if (m.model_id != model_id || m.nx != nx || m.ny != ny || m.nu != nu) return fail(LLPF_ERR_ARG, at + "model id or dimensions differ from filter 0's");
         CHK(kf_pack_filter(m, at, f, F, nx, ny, 0, np, par, init));
-        const int rc = model_prepare(&m, &hm[(size_t)f]);      // the descriptor the model's own methods read; positive definiteness of R1, R2, cov(d0)
-        if (rc == -1) return fail(LLPF_ERR_ARG, at + "R1 (dynamics_density) is not positive definite");
-        if (rc == -2) return fail(LLPF_ERR_ARG, at + "R2 (measurement_density) is not positive definite");
-        if (rc == -3) return fail(LLPF_ERR_ARG, at + "cov(d0) (initial_density) is not positive definite");
-        if (rc) return fail(LLPF_ERR_ARG, at + "invalid model descriptor, code " + std::to_string(rc));
+        CHK(kf_model_descriptor(m, at, &hm[(size_t)f]));
     }
     return LLPF_OK;
 }
@@ -122,6 +128,27 @@ struct KfModelBank : KfBank {
     KfModelBank(const char* who_, const char* filter_name_, int need_traits_) : KfBank(who_), filter_name(filter_name_), need_traits(need_traits_) {}
 };
 
+// the descriptors (hm empty: the bank has none) and the constants of a bank to the device, at its creation (`create`) also the zero input
+// that goes with the descriptors and the initial state b.h_init; synchronised
+static int kf_upload(KfBank& b, DevBuf<ModelD>& d_models, DevBuf<double>& d_zero, const std::vector<ModelD>& hm, const std::vector<double>& par,
+                     bool create) {
+    HIPC(hipSetDevice(b.device));
+    if (create) {
+        if (!hm.empty()) {
+            CHK(d_models.ensure(hm.size()));
+            CHK(d_zero.ensure(MAXU));
+            HIPC(hipMemsetAsync(d_zero, 0, sizeof(double) * MAXU, b.stream));
+        }
+        CHK(b.d_par.ensure(par.size()));
+        CHK(b.d_state.ensure(b.h_init.size()));
+        HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
+    }
+    if (!hm.empty()) HIPC(hipMemcpyAsync(d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
+    HIPC(hipStreamSynchronize(b.stream));
+    return LLPF_OK;
+}
+
 // `site`: the bank's create site of test_throw; prepare(model_id, nx, ny, err): the bank's kernel of a run-time compiled model, on the
 // first bank of that model
 static int kf_model_create(KfModelBank& b, int32_t device, const llpf_model* models, int32_t F, const char* site,
@@ -135,16 +162,7 @@ static int kf_model_create(KfModelBank& b, int32_t device, const llpf_model* mod
         std::string err;
         if (prepare(b.model_id, b.nx, b.ny, err) != 0) return fail(LLPF_ERR_HIP, std::string(b.who) + ": " + err);
     }
-    CHK(b.d_models.ensure(hm.size()));
-    CHK(b.d_par.ensure(par.size()));
-    CHK(b.d_state.ensure(b.h_init.size()));
-    CHK(b.d_zero.ensure(MAXU));
-    HIPC(hipMemsetAsync(b.d_zero, 0, sizeof(double) * MAXU, b.stream));
-    HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_state, b.h_init.data(), sizeof(double) * b.h_init.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipStreamSynchronize(b.stream));
-    return LLPF_OK;
+    return kf_upload(b, b.d_models, b.d_zero, hm, par, true);
 }
 
 static int kf_model_set_models(KfModelBank& b, const llpf_model* models) {
@@ -153,10 +171,7 @@ static int kf_model_set_models(KfModelBank& b, const llpf_model* models) {
     int id = 0, nx = 0, ny = 0, nu = 0;
     CHK(kf_pack_models(b.who, b.filter_name, b.need_traits, b.allow_traits, models, b.F, id, nx, ny, nu, hm, par, init));
     if (id != b.model_id || nx != b.nx || ny != b.ny || nu != b.nu) return kf_fail(b.who, "set_models must keep the model id and the dimensions of the bank");
-    HIPC(hipSetDevice(b.device));
-    HIPC(hipMemcpyAsync(b.d_models, hm.data(), sizeof(ModelD) * hm.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipMemcpyAsync(b.d_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, b.stream));
-    HIPC(hipStreamSynchronize(b.stream));
+    CHK(kf_upload(b, b.d_models, b.d_zero, hm, par, false));
     b.h_init.swap(init);
     b.Ts = models[0].Ts;
     return LLPF_OK;
@@ -198,20 +213,40 @@ static int kf_set_state(KfBank& b, const double* x, const double* R) {
     return LLPF_OK;
 }
 
-// the checks of a run's arguments that need no device (run and smooth of either bank)
-static int kf_check_run(const KfBank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, const llpf_kalman_outputs* out) {
+// the checks of a run's arguments that need no device (run and smooth of every bank); `out_type`: the name of the outputs' struct
+template <class Out>
+static int kf_check_run(const KfBank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, const Out* out,
+                        const char* out_type = "llpf_kalman_outputs") {
     if (T < 1) return kf_fail(b.who, "T must be >= 1");
     if (!Y) return kf_fail(b.who, "Y is null");
     if (b.nu > 0 && !U) return kf_fail(b.who, "U is null");
     if (per_filter & ~3) return kf_fail(b.who, "per_filter has bits other than 0 and 1");
-    if (out && out->struct_size < sizeof(llpf_kalman_outputs)) return kf_fail(b.who, "llpf_kalman_outputs.struct_size too small (ABI)");
+    if (out && out->struct_size < sizeof(Out)) return kf_fail(b.who, (std::string(out_type) + ".struct_size too small (ABI)").c_str());
     return LLPF_OK;
+}
+
+// what a run gives back, as its bank lists it for kf_forward: the outputs of one step in staging order (dst null: not asked for; width:
+// doubles per filter) and ll_total [F] (or null), which is row ll_row of the state at every ll_every-th column
+struct KfOutputs {
+    static constexpr int MAX = 7;
+    int n;
+    double* dst[MAX];
+    uint64_t width[MAX];
+    double* ll_total;
+    int ll_row, ll_every;
+};
+// ... of the banks of one filter per column: ll, x, xt, R, Rt, e, and the running sum behind x and the packed R
+static KfOutputs kf_outputs(const KfBank& b, double* ll_total, const llpf_kalman_outputs* out) {
+    const uint64_t nx = (uint64_t)b.nx;
+    const llpf_kalman_outputs none{};
+    if (!out) out = &none;
+    return {6, {out->ll_steps, out->x, out->xt, out->R, out->Rt, out->e}, {1, nx, nx, nx * nx, nx * nx, (uint64_t)b.ny}, ll_total, b.nx + b.np, 1};
 }
 
 // one chunk of the forward pass, as its launcher gets it: steps [t0, t0 + tc) of the run
 struct KfChunk {
     const double *u, *y;      // the chunk's inputs on the device (u null: the model has none)
-    double* out[6];           // ... and where its outputs are staged, each null when not asked for: ll, x, xt, R, Rt, e
+    double* out[KfOutputs::MAX];   // ... and where its outputs are staged, in the run's KfOutputs order, each null when not asked for
     int64_t t0;
     int32_t tc;
     int32_t first;            // 1: the first chunk of the run
@@ -235,27 +270,25 @@ static KfModelArgs kf_model_args(const KfModelBank& b, const KfChunk& c, double 
 }
 
 // the forward pass of a run (arguments checked); post: null, or the device array [T][nx + np][F] that receives the posterior of every
-// step.  launch(const KfChunk&) fills the bank's kernel arguments and launches on b.stream (a status).  Everything is allocated before
-// the first launch.
+// step.  o: the bank's outputs (kf_outputs; the columns of an IMM bank are lanes, F * o.ll_every of them).  launch(const KfChunk&) fills
+// the bank's kernel arguments and launches on b.stream (a status).  Everything is allocated before the first launch.
 template <class Launch>
-static int kf_forward(KfBank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double* ll_total,
-                      const llpf_kalman_outputs* out, double* post, Launch&& launch) {
+static int kf_forward(KfBank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, const KfOutputs& o, double* post,
+                      Launch&& launch) {
     const int F = b.F, nx = b.nx, ny = b.ny, nu = b.nu;
     const bool upf = nu > 0 && (per_filter & 1), ypf = (per_filter & 2) != 0;
-    // the outputs of one step, in staging order: ll, x, xt, R, Rt, e
-    double* dst[6] = {out ? out->ll_steps : nullptr, out ? out->x : nullptr, out ? out->xt : nullptr, out ? out->R : nullptr,
-                      out ? out->Rt : nullptr, out ? out->e : nullptr};
-    const uint64_t width[6] = {1, (uint64_t)nx, (uint64_t)nx, (uint64_t)nx * nx, (uint64_t)nx * nx, (uint64_t)ny};
     uint64_t w = 0;
     std::vector<ChunkOut> outs;
-    for (int k = 0; k < 6; ++k) {
-        if (dst[k]) w += width[k];
-        outs.push_back({dst[k], 1, (size_t)F * width[k]});
+    for (int k = 0; k < o.n; ++k) {
+        if (o.dst[k]) w += o.width[k];
+        outs.push_back({o.dst[k], 1, (size_t)F * o.width[k]});
     }
     const uint64_t in_w = (upf ? (uint64_t)nu : 0) + (ypf ? (uint64_t)ny : 0);
     uint64_t total = 0, in_total = 0;      // the per-step outputs / per-filter inputs of all filters and steps, in doubles
     if (!doubles_fit({(uint64_t)F, w, (uint64_t)T}, total) || !doubles_fit({(uint64_t)F, in_w, (uint64_t)T}, in_total))
         return kf_fail(b.who, "the size of the outputs or of the inputs overflows");
+    const size_t ncol = (size_t)F * o.ll_every;
+    std::vector<double> h_ll(o.ll_total && o.ll_every > 1 ? ncol : 0);      // (the same number in every lane of a filter)
     HIPC(hipSetDevice(b.device));
     ChunkPipe pipe(b.stream);
     // (shared inputs and no per-step outputs: nothing per step scales with F, the chunk is CHUNK_STEPS)
@@ -266,7 +299,7 @@ static int kf_forward(KfBank& b, const double* U, const double* Y, int64_t T, in
         KfChunk ch{};
         ch.u = pipe.in(0);
         ch.y = pipe.in(1);
-        for (int k = 0; k < 6; ++k) ch.out[k] = pipe.out(k);
+        for (int k = 0; k < o.n; ++k) ch.out[k] = pipe.out(k);
         ch.t0 = pipe.t0; ch.tc = (int32_t)pipe.tc;
         ch.first = c == 0 ? 1 : 0;
         ch.upf = upf ? 1 : 0; ch.ypf = ypf ? 1 : 0;
@@ -275,9 +308,11 @@ static int kf_forward(KfBank& b, const double* U, const double* Y, int64_t T, in
         CHK(pipe.end());
     }
     CHK(pipe.finish());
-    if (ll_total)     // the running sum: row nx + np of the state
-        HIPC(hipMemcpyAsync(ll_total, b.d_state.p + (size_t)(nx + b.np) * F, sizeof(double) * F, hipMemcpyDeviceToHost, b.stream));
+    if (o.ll_total)   // the running sum
+        HIPC(hipMemcpyAsync(h_ll.empty() ? o.ll_total : h_ll.data(), b.d_state.p + (size_t)o.ll_row * ncol, sizeof(double) * ncol,
+                            hipMemcpyDeviceToHost, b.stream));
     HIPC(hipStreamSynchronize(b.stream));
+    for (size_t f = 0; f < h_ll.size() / o.ll_every; ++f) o.ll_total[f] = h_ll[f * o.ll_every];
     return LLPF_OK;
 }
 

@@ -65,7 +65,7 @@ static int sqkf_run(llpf_sqkf_bank& b, const double* U, const double* Y, int64_t
     CHK(kf_check_run(b, U, Y, T, per_filter, out));
     test_throw("sqkf_run");
     const int nx = b.nx, ny = b.ny;
-    return kf_forward(b, U, Y, T, per_filter, ll_total, out, nullptr, [&](const KfChunk& c) -> int {
+    return kf_forward(b, U, Y, T, per_filter, kf_outputs(b, ll_total, out), nullptr, [&](const KfChunk& c) -> int {
         KalmanArgs a{};
         a.par = b.d_par; a.state = b.d_state;
         a.u = c.u;

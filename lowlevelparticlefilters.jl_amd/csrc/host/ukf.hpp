@@ -42,7 +42,7 @@ static int ukf_check_run(const llpf_ukf_bank& b, const double* U, const double* 
 // the forward pass of a run (arguments checked): kf_forward with k_ukf, or k_ukf<..., true> where post is given
 static int ukf_forward(llpf_ukf_bank& b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
                        const llpf_kalman_outputs* out, double* post) {
-    return kf_forward(b, U, Y, T, per_filter, ll_total, out, post, [&](const KfChunk& c) -> int {
+    return kf_forward(b, U, Y, T, per_filter, kf_outputs(b, ll_total, out), post, [&](const KfChunk& c) -> int {
         UkfArgs a{kf_model_args(b, c, t_index0)};
         a.gamma = b.w.gamma; a.wm0 = b.w.wm0; a.wc0 = b.w.wc0; a.wi = b.w.wi;
         a.post = c.post;

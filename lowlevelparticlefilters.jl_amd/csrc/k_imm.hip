@@ -1,5 +1,5 @@
-// k_imm.hip — k_imm (kernels/imm.hpp): banks of interacting-multiple-model filters over Kalman filters with constant matrices
-// (llpf_imm_bank_run).
+// k_imm.hip — k_imm (kernels/imm.hpp: the step frame imm_chunk with ImmKalmanMode): banks of interacting-multiple-model filters over
+// Kalman filters with constant matrices (llpf_imm_bank_run).  No model code is instantiated here.
 // One of the engine's device translation units: every (NX, NY, G) of 1..8 x 1..4 x {1, 2, 4} is instantiated here and nowhere else, by
 // dispatch_dim (kernels/dispatch.hpp).
 #include "engine.hpp"

@@ -1,5 +1,5 @@
-// k_imm_ekf.hip — k_imm_ekf (kernels/imm_ekf.hpp): banks of interacting-multiple-model filters over first-order extended Kalman filters
-// of one model type (llpf_imm_bank_run_at on an extended bank).
+// k_imm_ekf.hip — k_imm_ekf (kernels/imm_ekf.hpp: ImmEkfMode in the step frame imm_chunk of kernels/imm.hpp): banks of
+// interacting-multiple-model filters over first-order extended Kalman filters of one model type (llpf_imm_bank_run_at on an extended bank).
 // One of the engine's device translation units: LinGauss<NX, NY> for NX, NY in 1..4 and QuadTank<4, 2>, each at G = 1, 2 and 4, are
 // instantiated here and nowhere else, by dispatch_builtin_model (kernels/dispatch.hpp).  A run-time compiled model (a user snippet or a
 // traced callable with dynamics_jac and measurement_jac, the linear-Gaussian model above 4 states) gets its k_imm_ekf from a program of
@@ -17,7 +17,6 @@ namespace llpf {
 #include "kernels/reduce.hpp"
 #include "kernels/models.hpp"
 #include "kernels/imm_args.hpp"
-#include "kernels/imm_ekf_args.hpp"
 #include "kernels/kf_store.hpp"
 #include "kernels/imm.hpp"
 #include "kernels/imm_ekf.hpp"

@@ -1,17 +1,27 @@
-// kernels/imm.hpp — k_imm: banks of interacting-multiple-model filters over Kalman filters with constant matrices (llpf_imm_bank_run; host
-// side: host/imm.hpp).  Part of k_imm.hip (namespace llpf); its exchange (imm_fetch, imm_weighted, imm_c) is also k_imm_ekf's: the file is
-// part of k_imm_ekf.hip and of the text of that kernel's run-time programs (jit_imm_ekf.inc) as well.
+// kernels/imm.hpp — the step of a bank of interacting-multiple-model filters, one frame for every kind of mode (imm_chunk), and k_imm: the
+// bank over Kalman filters with constant matrices (llpf_imm_bank_run; host side: host/imm.hpp).  Part of k_imm.hip (namespace llpf) and,
+// for k_imm_ekf (kernels/imm_ekf.hpp: the bank over extended Kalman filters), of k_imm_ekf.hip and of the text of that kernel's run-time
+// programs (jit_imm_ekf.inc).
 // ------------------------------------------------------------------------------------------------
-// One lane per (filter, mode): G = 1, 2 or 4 lanes per filter, aligned to G, thread f * G + j is mode j of filter f (M = 3 runs in G = 4
-// with one idle lane, which stores nothing and is never a source).  The time loop is inside the kernel; the lane's x_j and packed R_j are
-// in registers and its correct! / predict! are shared/llpf_kalman.h with literal NX, NY on the lane's own parameter column, exactly as
-// k_kalman runs them.  The constants are SoA [entry][F * G]: a lane's column is its thread index and a wave reads whole lines.
+// One lane per (filter, mode): G = 1, 2 or 4 lanes per filter, aligned to G, thread f * G + j is mode j of filter f.  The time loop is
+// inside the kernel; the lane's x_j, packed R_j and mu_j are in registers, no LDS and no barrier.  The constants are SoA [entry][F * G]:
+// a lane's column is its thread index and a wave reads whole lines.  The step is the six stages of shared/llpf_imm.h; stages 2 and 6, the
+// mode's own correct! and predict!, are the Mode's (below: ImmKalmanMode; kernels/imm_ekf.hpp: ImmEkfMode), everything else is here.
 //
 // The exchange.  What the step of shared/llpf_imm.h sums over the source mode i — mu_i, a_i, w_i, x_i, R_i — a lane fetches from lane i of
 // its group, i = 0 .. M - 1 in that order, and does the header's arithmetic on it: a lane's bits are those of the host loop.  A group lies
-// inside one quad, so the fetch is a quad permute (DPP through the compiler's builtin, a double as two halves): no LDS, no barrier, and
-// the compiler keeps the DPP hazards.  Every branch that holds a fetch is uniform over the group (M, interact and the outputs asked for
-// are the launch's, a missing row is the filter's); the branches on a lost definiteness are per lane and hold none.
+// inside one quad, so the fetch is a quad permute (DPP through the compiler's builtin, a double as two halves): the compiler keeps the DPP
+// hazards.
+//
+// Fetch uniformity (the invariant of this file).  Every imm_fetch sits in control flow that is uniform over the group, with all G lanes
+// of the group active: the branches around a fetch test only the launch's M, interact and outputs and the filter's missing row, never a
+// lane's own numbers.  A mode's own branches (a lost definiteness, a model's switch time, a snippet's `if` or loop) are per lane; they
+// live inside the Mode's begin / correct / predict, which are called between the fetches and have reconverged when they return.  No
+// fetch may move into a block conditioned on per-lane data (cj == 0, a NaN ll, `on`), nor into a Mode.
+//
+// Idle lanes (M = 3 in G = 4).  Lane 3 of a group runs along on finite numbers, is never a source (every loop over the source mode stops
+// at M) and stores nothing.  Its column of P is zero, so its c_j is 0 and it is never mixed.  Which column it runs on is the Mode's
+// (IDLE_ON_MODE0): its own, which the host leaves zero, or mode 0's where a zero column is not safe to compute on.
 // ------------------------------------------------------------------------------------------------
 #ifndef KF_RELOAD
 #define KF_RELOAD(nx, ny) ((nx) >= 5)
@@ -82,8 +92,17 @@ DEV double imm_c(const int M, const double* Pc, double mu, double* mu_all) {
     return c;
 }
 
-template <int NX, int NY, int G>
-__global__ __launch_bounds__(KF_BLOCK) void k_imm(ImmArgs a) {
+// A chunk of steps of this thread's lane.  Mode: the kind of filter a mode is, constructed by the kernel from its own arguments —
+//   IDLE_ON_MODE0        an idle lane reads mode 0's column and a zero column of P (false: its own, zero, column)
+//   npar(nu)             the rows of par in front of column j of P
+//   no_u()               what stands in for u when the model has no inputs
+//   begin(P, col, u, k)  once per step, before stage 1: the constants of step k (P: the lane's column of par)
+//   missing(y)           the filter's row is missing (uniform over the group)
+//   correct(Pk, L, u, y, missing, x, R) -> ll_j   and   predict(Pk, L, u, x, R): stages 2 and 6 on the lane's own x_j, R_j
+// (a: by value.  Through a reference to the kernel's own argument the compiler leaves the tests of the launch's outputs inside the time
+// loop: k_imm measured 2 to 3.5 % slower at F = 10^4.)
+template <int NX, int NY, int G, class Mode>
+DEV void imm_chunk(const ImmBaseArgs a, Mode& mode) {
     constexpr int NP = LLPF_KF_NP(NX);
     const int64_t F = a.F, L = F * G;
     const int64_t t = (int64_t)blockIdx.x * KF_BLOCK + threadIdx.x;
@@ -91,12 +110,14 @@ __global__ __launch_bounds__(KF_BLOCK) void k_imm(ImmArgs a) {
     const int64_t f = t / G;
     const int j = (int)(t % G);
     const int nu = a.nu, M = a.M;
-    const bool on = j < M;                // (an idle lane runs along on its zero column)
-    const double* __restrict__ P0 = a.par + t;
-    double* st = a.state + t;
+    const bool on = j < M;
+    const bool own = on || !Mode::IDLE_ON_MODE0;
+    const int64_t col = own ? t : t - j;
+    const double* __restrict__ P = a.par + col;
+    double* st = a.state + col;
     double Pc[G];
 #pragma unroll
-    for (int i = 0; i < G; ++i) Pc[i] = P0[(int64_t)(LLPF_KF_NPAR(NX, NY, nu) + i) * L];
+    for (int i = 0; i < G; ++i) Pc[i] = own ? P[(int64_t)(mode.npar(nu) + i) * L] : 0.0;
     double x[NX], R[NP];
 #pragma unroll
     for (int d = 0; d < NX; ++d) x[d] = st[d * L];
@@ -107,8 +128,9 @@ __global__ __launch_bounds__(KF_BLOCK) void k_imm(ImmArgs a) {
 #pragma unroll 1
     for (int k = 0; k < a.Tc; ++k) {
         const size_t kf = (size_t)k * F + f;
-        const double* u = nu > 0 ? a.u + (a.u_per ? kf : (size_t)k) * nu : a.u;
+        const double* u = nu > 0 ? a.u + (a.u_per ? kf : (size_t)k) * nu : mode.no_u();
         const double* y = a.y + (a.y_per ? kf : (size_t)k) * NY;
+        const double* Pk = mode.begin(P, col, u, k);
         double mu_all[G], xc[NX], Rc[NP];
         // 1. the combined prior
         if (a.x || a.R) {
@@ -119,13 +141,12 @@ __global__ __launch_bounds__(KF_BLOCK) void k_imm(ImmArgs a) {
             if (j == 0 && a.R) kf_store_dense<NX>(a.R + kf * NX * NX, Rc);
         }
         // 2. correct! of the lane's mode
-        double e[NY];
-        const double* P = KF_RELOAD(NX, NY) ? P0 + (size_t)k * a.par_tstride : P0;
-        const double llj = llpf_kf_correct(NX, NY, nu, P, L, u, y, x, R, e);
+        const bool missing = mode.missing(y);
+        const double llj = mode.correct(Pk, L, u, y, missing, x, R);
         // 3. the mode probabilities
         const double c = imm_c<G>(M, Pc, mu, mu_all);
         double ll = 0.0;
-        if (!(y[0] == y[0])) {
+        if (missing) {
             mu = c;
         } else {
             const double aj = llpf_imm_loga(c, llj);
@@ -171,7 +192,7 @@ __global__ __launch_bounds__(KF_BLOCK) void k_imm(ImmArgs a) {
             }
         }
         // 6. predict! of the lane's mode
-        llpf_kf_predict(NX, NY, nu, P, L, u, x, R);
+        mode.predict(Pk, L, u, x, R);
     }
     if (!on) return;
 #pragma unroll
@@ -180,4 +201,27 @@ __global__ __launch_bounds__(KF_BLOCK) void k_imm(ImmArgs a) {
     for (int i = 0; i < NP; ++i) st[(NX + i) * L] = R[i];
     st[(NX + NP) * L] = mu;
     st[(NX + NP + 1) * L] = llt;
+}
+
+// A Kalman filter with constant matrices: shared/llpf_kalman.h with literal NX, NY on the lane's own parameter column, exactly as k_kalman
+// runs it (correct! sees a missing row itself: ll_j = 0).  An idle lane runs along on its own zero column.
+template <int NX, int NY>
+struct ImmKalmanMode {
+    static constexpr bool IDLE_ON_MODE0 = false;
+    const ImmArgs& a;
+    DEV int npar(int nu) const { return LLPF_KF_NPAR(NX, NY, nu); }
+    DEV const double* no_u() const { return a.u; }
+    DEV const double* begin(const double* P, int64_t, const double*, int k) const { return KF_RELOAD(NX, NY) ? P + (size_t)k * a.par_tstride : P; }
+    DEV bool missing(const double* y) const { return !(y[0] == y[0]); }
+    DEV double correct(const double* Pk, int64_t L, const double* u, const double* y, bool, double* x, double* R) const {
+        double e[NY];
+        return llpf_kf_correct(NX, NY, a.nu, Pk, L, u, y, x, R, e);
+    }
+    DEV void predict(const double* Pk, int64_t L, const double* u, double* x, double* R) const { llpf_kf_predict(NX, NY, a.nu, Pk, L, u, x, R); }
+};
+
+template <int NX, int NY, int G>
+__global__ __launch_bounds__(KF_BLOCK) void k_imm(ImmArgs a) {
+    ImmKalmanMode<NX, NY> mode{a};
+    imm_chunk<NX, NY, G>(a, mode);
 }

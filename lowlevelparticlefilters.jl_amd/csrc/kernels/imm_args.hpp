@@ -1,12 +1,14 @@
-// kernels/imm_args.hpp — arguments of k_imm (kernels/imm.hpp) and its launcher.  Included inside namespace llpf by the two units that
-// know the IMM bank: k_imm.hip (the kernel) and, through host/imm.hpp, capi.hip (the host side); k_imm_ekf.hip and the run-time programs
-// of k_imm_ekf take it along with kernels/imm.hpp (tools/gen_jit_prelude.py drops the launcher's declaration from their text).
+// kernels/imm_args.hpp — arguments of k_imm (kernels/imm.hpp) and of k_imm_ekf (kernels/imm_ekf.hpp), and k_imm's launcher.  Included
+// inside namespace llpf by the units that know the IMM banks: k_imm.hip, k_imm_ekf.hip and, through host/imm.hpp, capi.hip (the host
+// side); compiled into the run-time program of a model's k_imm_ekf (jit_imm_ekf.inc: tools/gen_jit_prelude.py drops the launcher's
+// declaration from that text).
 // One launch is one chunk of steps [t0, t0 + Tc) of F IMM filters of M modes, one lane per (filter, mode): G = 1, 2 or 4 lanes per filter
 // (the smallest G >= M), thread f * G + j is mode j of filter f, the lanes j >= M idle.  L = F * G is the number of columns of the SoA
 // arrays: a lane's column is its thread index.
-struct ImmArgs {
-    const double* par;       // [npar + LLPF_IMM_MAXM][L]: the mode's constant matrices (shared/llpf_kalman.h: LLPF_KF_OFF_*), then column j of
-                             // the filter's transition matrix, P_ij at row npar + i
+// What the step frame reads (kernels/imm.hpp: imm_chunk): the leading members of both kernels' arguments
+struct ImmBaseArgs {
+    const double* par;       // [npar + LLPF_IMM_MAXM][L]: the mode's own constants (npar rows), then column j of the filter's transition
+                             // matrix, P_ij at row npar + i
     double* state;           // [nx + np + 2][L] the mode's x, packed R and mu_j, the run's running ll_total: in at t0, out at t0 + Tc
     const double* u;         // inputs of the chunk: [Tc][nu] shared, or [Tc][F][nu] (u_per = 1); unused when nu = 0
     const double* y;         // measurements of the chunk: [Tc][ny] shared, or [Tc][F][ny] (y_per = 1)
@@ -18,7 +20,17 @@ struct ImmArgs {
     int32_t first;           // 1: the first chunk of a run (ll_total starts at 0)
     int32_t interact;        // 1: the modes mix after every step
     int32_t pad;
+};
+// Kalman modes: par holds the constant matrices (shared/llpf_kalman.h: LLPF_KF_OFF_*)
+struct ImmArgs : ImmBaseArgs {
     int64_t par_tstride;     // always 0 (kernels/kalman.hpp: KF_RELOAD)
 };
+// extended Kalman modes of one model type: par holds R1, R2 as packed lower triangles (shared/llpf_ekf.h: LLPF_EKF_OFF_*)
+struct ImmEkfArgs : ImmBaseArgs {
+    const double* zero_u;    // MAXU zeros: the u of a model without inputs
+    int64_t t0;              // first step of this chunk
+    double t_index0, Ts;     // tau_t = (t_index0 + t) * Ts, as k_ekf takes it
+};
+static_assert(sizeof(ImmBaseArgs) == 128 && sizeof(ImmArgs) == 136 && sizeof(ImmEkfArgs) == 160, "kernel argument layout");
 // one chunk of steps (k_imm.hip): nx in 1..8, ny in 1..4, g = 1, 2 or 4 lanes per filter (the smallest g >= ImmArgs::M)
 hipError_t launch_imm(int nx, int ny, int g, const ImmArgs& a, hipStream_t s);

@@ -13,7 +13,7 @@ from kalman_common import _data
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1, 0), (3, 2, 1), (4, 2, 2), (8, 4, 2)]
+SHAPES = [(1, 1, 0), (3, 2, 1), (4, 2, 2), (5, 1, 1), (8, 4, 2)]
 
 
 @pytest.fixture(scope="module")
