@@ -67,14 +67,7 @@ static int kalman_forward(llpf_kalman_bank& b, const double* U, const double* Y,
     const int nx = b.nx, ny = b.ny;
     return kf_forward(b, U, Y, T, per_filter, kf_outputs(b, ll_total, out), post, [&](const KfChunk& c) -> int {
         KalmanArgs a{};
-        a.par = b.d_par; a.state = b.d_state;
-        a.u = c.u;
-        a.y = c.y;
-        double** slot[6] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.e};
-        for (int k = 0; k < 6; ++k) *slot[k] = c.out[k];
-        a.F = b.F; a.Tc = c.tc; a.nu = b.nu;
-        a.u_per = c.upf; a.y_per = c.ypf;
-        a.first = c.first;
+        kf_fill_args(a, b, c);
         a.par_tstride = 0;
         a.post = c.post;
         HIPC(launch_kalman(nx, ny, a, b.stream));
@@ -99,15 +92,8 @@ static int kalman_smooth(llpf_kalman_bank& b, const double* U, const double* Y, 
         [&](double* post) { return kalman_forward(b, U, Y, T, per_filter, ll_total, fwd, post); },
         [&](const KfSmoothChunk& c) -> int {
             KalmanSmoothArgs a{};
-            a.par = b.d_par;
-            a.post = c.post;
-            a.carry = c.carry;
-            a.u = c.u;
-            a.xT = c.xT;
-            a.RT = c.RT;
-            a.F = b.F; a.Tc = c.tc; a.ny = b.ny; a.nu = b.nu;
-            a.u_per = c.upf;
-            a.init = c.init;
+            kf_fill_smooth_args(a, b, c);
+            a.ny = b.ny;
             a.par_tstride = 0;
             HIPC(launch_kalman_smooth(nx, a, b.stream));
             return LLPF_OK;

@@ -254,17 +254,26 @@ struct KfChunk {
     double* post;             // null, or where the posterior of the chunk's steps goes: [tc][nx + np][F]
 };
 
-// the arguments of one chunk that the kernels of the model-driven banks have in common (the base of UkfArgs and EkfArgs)
-static KfModelArgs kf_model_args(const KfModelBank& b, const KfChunk& c, double t_index0) {
-    KfModelArgs a{};
-    a.par = b.d_par; a.state = b.d_state; a.zero_u = b.d_zero;
+// the members that the forward argument structs name alike (KalmanArgs, and KfModelArgs through kf_model_args below), from the bank and
+// one chunk
+template <class Args>
+static void kf_fill_args(Args& a, const KfBank& b, const KfChunk& c) {
+    a.par = b.d_par; a.state = b.d_state;
     a.u = c.u;
     a.y = c.y;
     double** slot[6] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.e};
     for (int k = 0; k < 6; ++k) *slot[k] = c.out[k];
-    a.F = b.F; a.t0 = c.t0; a.Tc = c.tc; a.nu = b.nu;
+    a.F = b.F; a.Tc = c.tc; a.nu = b.nu;
     a.u_per = c.upf; a.y_per = c.ypf;
     a.first = c.first;
+}
+
+// the arguments of one chunk that the kernels of the model-driven banks have in common
+static KfModelArgs kf_model_args(const KfModelBank& b, const KfChunk& c, double t_index0) {
+    KfModelArgs a{};
+    kf_fill_args(a, b, c);
+    a.zero_u = b.d_zero;
+    a.t0 = c.t0;
     a.t_index0 = t_index0; a.Ts = b.Ts;
     return a;
 }
@@ -327,6 +336,20 @@ struct KfSmoothChunk {
     int32_t upf;              // 1: u is per filter
     int32_t init;             // 1: the chunk holds the run's last step
 };
+
+// the members that KalmanSmoothArgs and UkfSmoothArgs name alike, from the bank and one chunk
+template <class Args>
+static void kf_fill_smooth_args(Args& a, const KfBank& b, const KfSmoothChunk& c) {
+    a.par = b.d_par;
+    a.post = c.post;
+    a.carry = c.carry;
+    a.u = c.u;
+    a.xT = c.xT;
+    a.RT = c.RT;
+    a.F = b.F; a.Tc = c.tc; a.nu = b.nu;
+    a.u_per = c.upf;
+    a.init = c.init;
+}
 
 // smooth(f, u, y) of every filter (the run's arguments checked): the forward pass of a run (the same chunks, outputs and state) that also
 // stores the packed posterior of every step on the device (d_post: (nx + np) * 8 bytes per filter-step), then the backward pass over the

@@ -67,14 +67,7 @@ static int sqkf_run(llpf_sqkf_bank& b, const double* U, const double* Y, int64_t
     const int nx = b.nx, ny = b.ny;
     return kf_forward(b, U, Y, T, per_filter, kf_outputs(b, ll_total, out), nullptr, [&](const KfChunk& c) -> int {
         KalmanArgs a{};
-        a.par = b.d_par; a.state = b.d_state;
-        a.u = c.u;
-        a.y = c.y;
-        double** slot[6] = {&a.ll, &a.x, &a.xt, &a.R, &a.Rt, &a.e};
-        for (int k = 0; k < 6; ++k) *slot[k] = c.out[k];
-        a.F = b.F; a.Tc = c.tc; a.nu = b.nu;
-        a.u_per = c.upf; a.y_per = c.ypf;
-        a.first = c.first;
+        kf_fill_args(a, b, c);
         HIPC(launch_sqkf(nx, ny, a, b.stream));
         return LLPF_OK;
     });

@@ -74,16 +74,9 @@ static int ukf_smooth(llpf_ukf_bank& b, const double* U, const double* Y, int64_
         [&](double* post) { return ukf_forward(b, U, Y, T, per_filter, t_index0, ll_total, fwd, post); },
         [&](const KfSmoothChunk& c) -> int {
             UkfSmoothArgs a{};
-            a.par = b.d_par;
-            a.post = c.post;
-            a.carry = c.carry;
-            a.u = c.u;
+            kf_fill_smooth_args(a, b, c);
             a.zero_u = b.d_zero;
-            a.xT = c.xT;
-            a.RT = c.RT;
-            a.F = b.F; a.t0 = c.t0; a.Tc = c.tc; a.nu = b.nu;
-            a.u_per = c.upf;
-            a.init = c.init;
+            a.t0 = c.t0;
             a.t_index0 = t_index0; a.Ts = b.Ts;
             a.gamma = b.w.gamma; a.wm0 = b.w.wm0; a.wc0 = b.w.wc0; a.wi = b.w.wi;
             HIPC(launch_ukf_smooth(b.model_id, b.nx, b.ny, b.d_models, a, b.stream));

@@ -128,6 +128,26 @@ def check_broadcast_inputs(fam, b, g, U, Y, *, F, nu, what):
     _same(gp, g, keys(fam), what)
 
 
+def check_each_output_alone(fam, host, *, seed, F, T, nx, ny, nu):
+    """one bank, every output at once (held to the twin), then from a reset one run per output with only that output asked for: its
+    columns and ll are the bits of the run with every output.  A smoother family asks for one forward output at a time beside xT and RT,
+    then for xT alone and for RT alone."""
+    rng = np.random.default_rng(seed)
+    models = fam.models(rng, F, nx, ny, nu)
+    U, Y = _data(rng, T, nu, ny)
+    b = fam.bank(models)
+    ref = every_output(fam, b, U, Y)
+    _same(ref, twin(fam, host, models, U, Y, T)[0], keys(fam), "every output")
+    for key in OUTS:
+        b.reset()
+        one = b.run(U, Y, outputs=(key,)) if fam.host_smooth is None else b.smooth(U, Y, forward=(key,))
+        _same(one, ref, (key, "ll"), "%s alone" % key)
+    for key in () if fam.host_smooth is None else SOUTS:
+        b.reset()
+        _same(b.smooth(U, Y, outputs=(key,)), ref, (key, "ll"), "%s alone" % key)
+    b.close()
+
+
 def check_bank_sizes_and_chunk_edges(fam, host, *, seed, F, nx, ny, nu, missing, Ts):
     """one bank of F filters over the first T of max(Ts) steps for every T of Ts, from a reset: the outputs and the final state"""
     rng = np.random.default_rng(seed)

@@ -65,6 +65,11 @@ def test_quadtank_precompiled_shape_and_the_switch_time(host):
     b.close()
 
 
+def test_each_output_alone(host):
+    """every optional output asked for on its own is the column of the run with all of them: F = 65 (a full workgroup and a ragged one)"""
+    kg.check_each_output_alone(EKF, host, seed=77, F=65, T=3, nx=2, ny=1, nu=1)
+
+
 @pytest.mark.parametrize("F", [1, 63, 64, 65, 1000])
 def test_bank_sizes_and_chunk_edges(host, F):
     """3. per-filter parameters at every bank size around the wave, T around the 256-step chunk of the staging pipe"""

@@ -61,6 +61,11 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
         b.close()
 
 
+def test_each_output_alone(host):
+    """every optional output asked for on its own is the column of the run with all of them: F = 65 (a full workgroup and a ragged one)"""
+    kg.check_each_output_alone(IEKF, host, seed=77, F=65, T=3, nx=2, ny=1, nu=1)
+
+
 def test_quadtank_precompiled_shape_across_the_switch_time(host):
     """6. the 17th shape: the built-in quad-tank, F = 200 with per-filter parameters, T = 60 across tau = TSWITCH = 500 with missing rows"""
     models = quadtank_models(200)

@@ -46,6 +46,11 @@ def test_bit_identical_to_the_host_header_for_every_shape(host, nx):
         b.close()
 
 
+def test_each_output_alone(host):
+    """every optional output asked for on its own is the column of the run with all of them: F = 65 (a full workgroup and a ragged one)"""
+    kg.check_each_output_alone(_family(lambda k: k % 5 != 0), host, seed=77, F=65, T=3, nx=2, ny=1, nu=1)
+
+
 def test_per_filter_inputs_of_their_own(host):
     rng = np.random.default_rng(3)
     systems = [kc.random_system(rng, 4, 2, 2, k % 3) for k in range(300)]

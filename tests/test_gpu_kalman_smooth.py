@@ -47,6 +47,11 @@ def test_bit_identical_to_the_host_header_for_every_shape(host, hsmooth, nx):
         b.close()
 
 
+def test_each_output_alone(host, hsmooth):
+    """every optional output asked for on its own is the column of the run with all of them: F = 65 (a full workgroup and a ragged one)"""
+    kg.check_each_output_alone(_family(lambda k: k % 5 != 0), (host, hsmooth), seed=77, F=65, T=3, nx=2, ny=1, nu=1)
+
+
 def test_chunks_are_invisible(host, hsmooth):
     rng = np.random.default_rng(41)
     base = [kc.random_system(rng, 4, 2, 2, k % 3) for k in range(300)]

@@ -47,6 +47,11 @@ def test_bit_identical_to_the_host_header_for_every_shape(host, nx):
         b.close()
 
 
+def test_each_output_alone(host):
+    """every optional output asked for on its own is the column of the run with all of them: F = 65 (a full workgroup and a ragged one)"""
+    kg.check_each_output_alone(FAM, host, seed=77, F=65, T=3, nx=2, ny=1, nu=1)
+
+
 @pytest.mark.parametrize("F", [1, 63, 64, 65])
 def test_bank_sizes_and_chunk_edges(host, F):
     """nx = 2, ny = 1, nu = 1 around the wave of 64 and the pipe's chunk of 256 steps; the final get_state x and R against the twin"""

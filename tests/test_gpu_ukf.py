@@ -48,6 +48,11 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
         b.close()
 
 
+def test_each_output_alone(host):
+    """every optional output asked for on its own is the column of the run with all of them: F = 65 (a full workgroup and a ragged one)"""
+    kg.check_each_output_alone(_family(W1), host, seed=77, F=65, T=3, nx=2, ny=1, nu=1)
+
+
 def test_quadtank_across_the_switch_time(host):
     """the built-in quad-tank with per-filter parameters over T = 700 from t_index0 = 1 (tau crosses TSWITCH = 500; three chunks), three
     missing rows: the device's RK4 in the oracle's order"""

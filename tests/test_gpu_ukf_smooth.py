@@ -58,6 +58,11 @@ def test_lingauss_bit_identical_to_the_host_header_for_every_precompiled_shape(h
         b.close()
 
 
+def test_each_output_alone(host, hsmooth):
+    """every optional output asked for on its own is the column of the run with all of them: F = 65 (a full workgroup and a ragged one)"""
+    kg.check_each_output_alone(_family(W1), (host, hsmooth), seed=77, F=65, T=3, nx=2, ny=1, nu=1)
+
+
 def test_quadtank_across_the_switch_time(host, hsmooth):
     """the 17th precompiled shape: the built-in quad-tank with per-filter parameters, F = 1000, T = 200 with missing rows; and T = 700 from
     t_index0 = 1 (tau crosses TSWITCH = 500; three chunks): the device's RK4 in the oracle's order, forward and backward"""
