@@ -1,32 +1,26 @@
 """Banks of IMM filters on the device (llpf_imm_bank_*; kernels/imm.hpp, host/imm.hpp): the GPU reproduces the host build of
 csrc/shared/llpf_imm.h (tests/imm_host.c) bit for bit, whatever the number of modes, the shape, the bank, the chunking of T or the split
-of a run; and the Python API (IMM, IMMBank) is that bank."""
+of a run; and the Python API (IMM, IMMBank) is that bank.  The bodies this file shares with test_gpu_imm_ekf.py are in imm_gpu_frame.py."""
 import numpy as np
 import pytest
 
 import llpf_amd
-from llpf_amd import _capi
 import imm_common as ic
 from imm_common import OUTS
+import imm_gpu_frame as ig
 import kalman_common as kc
 from kalman_common import _data
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 0), (3, 2, 1), (4, 2, 2), (5, 1, 1), (8, 4, 2)]
+# the D != 0 systems: four IMMs of five have a feedthrough
+FAM = ig.ImmFamily(lambda rng, F, M, nx, ny, nu: [ic.random_imm(rng, M, nx, ny, nu, k % 3, D=k % 5 != 0) for k in range(F)], None)
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
     return ic.build_host(tmp_path_factory.mktemp("imm_host"))
-
-
-def _imms(rng, F, M, nx, ny, nu):
-    return [ic.random_imm(rng, M, nx, ny, nu, k % 3, D=k % 5 != 0) for k in range(F)]
-
-
-def _final(b):
-    return b.get_modes()[2:]
 
 
 @pytest.mark.parametrize("M", [1, 2, 3, 4])
@@ -35,39 +29,14 @@ def test_bit_identical_to_the_host_header(host, M, shape):
     """F = 70 (a ragged last wave at every G, two workgroups at G = 4), T = 40 with missing rows, every output; shared inputs, the same
     as per-filter inputs, per-filter inputs of their own whose missing rows differ between the filters of a wave; interact on and off"""
     nx, ny, nu = shape
-    F, T = 70, 40
-    rng = np.random.default_rng(1000 * M + 10 * nx + ny)
-    imms = _imms(rng, F, M, nx, ny, nu)
-    U, Y = _data(rng, T, nu, ny, missing=(5, 6, 30))
-    Uf = rng.standard_normal((F, T, nu))
-    Yf = 2.0 * rng.standard_normal((F, T, ny))
-    Yf[::3, 11, 0] = Yf[1::4, 12, 0] = Yf[:, 20, 0] = np.nan
-    for interact in (True, False):
-        b = ic.bank(imms, interact)
-        g = b.run(U, Y, outputs=OUTS)
-        h, st = ic.host_run(host, imms, U, Y, T, interact=interact)
-        ic.same(g, h, what=(M, shape, interact))
-        for a, s in zip(_final(b), st):
-            assert kc.bits_equal(a, s), (M, shape, interact, "final state")
-        x, R = b.get_state()
-        xc, Rc = ic.host_combine(host, *st)
-        assert kc.bits_equal(x, xc) and kc.bits_equal(R, Rc)
-        assert np.all(g["ll_steps"][[5, 6, 30]] == 0.0) and np.all(g["ll_modes"][[5, 6, 30]] == 0.0)
-        assert np.all(np.isfinite(g["ll"])) and np.all(g["mu"] >= 0.0) and np.all(np.abs(g["mu"].sum(axis=2) - 1.0) <= 1e-12)
-        b.reset()
-        gp = b.run(np.broadcast_to(U, (F,) + U.shape), np.broadcast_to(Y, (F,) + Y.shape), nu > 0, True, outputs=OUTS)
-        ic.same(gp, g, what=(M, shape, interact, "shared inputs given per filter"))
-        b.reset()
-        gf = b.run(Uf, Yf, nu > 0, True, outputs=OUTS)
-        hf, _ = ic.host_run(host, imms, Uf, Yf, T, per_filter=3, interact=interact)
-        ic.same(gf, hf, what=(M, shape, interact, "per-filter inputs"))
-        b.close()
+    ig.check_shape(FAM, host, np.random.default_rng(1000 * M + 10 * nx + ny), F=70, T=40, M=M, nx=nx, ny=ny, nu=nu, missing=(5, 6, 30),
+                   what=(M, shape))
 
 
 @pytest.mark.parametrize("M", [2, 3])
 def test_a_filters_bits_do_not_depend_on_the_bank(M):
     rng = np.random.default_rng(4 + M)
-    imms = _imms(rng, 70, M, 3, 2, 1)
+    imms = FAM.imms(rng, 70, M, 3, 2, 1)
     U, Y = _data(rng, 30, 1, 2, missing=(7,))
     g = ic.bank(imms).run(U, Y, outputs=OUTS)
     pick = [69, 0, 37, 16, 15, 17, 32, 31]
@@ -82,8 +51,7 @@ def test_a_filters_bits_do_not_depend_on_the_bank(M):
 
 def test_chunks_and_continuation(host):
     rng = np.random.default_rng(5)
-    F, M = 70, 3
-    imms = _imms(rng, F, M, 4, 2, 2)
+    imms = FAM.imms(rng, 70, 3, 4, 2, 2)
     U, Y = _data(rng, 300, 2, 2, missing=(255, 256, 280))
     b = ic.bank(imms)
     long = b.run(U, Y, outputs=OUTS)                   # two chunks: 256 steps and 44
@@ -92,81 +60,33 @@ def test_chunks_and_continuation(host):
     b.reset()
     bare = b.run(U, Y)                                 # no per-step output: nothing is staged out, nothing is combined
     assert kc.bits_equal(bare["ll"], long["ll"])
-    end = _final(b)
+    end = ig.final(b)
     b.reset()
     b.run(U, Y, outputs=OUTS)
-    for a, s in zip(_final(b), end):
-        assert kc.bits_equal(a, s), "final state with and without per-step outputs"
-    b.reset()
-    whole = b.run(U[:50], Y[:50], outputs=OUTS)
-    b.reset()
-    first = b.run(U[:25], Y[:25], outputs=OUTS)
-    st = _final(b)
-    second = b.run(U[25:50], Y[25:50], outputs=OUTS)
-    for k in OUTS:
-        assert kc.bits_equal(np.concatenate([first[k], second[k]]), whole[k]), k
-    h2, _ = ic.host_run(host, imms, U[25:50], Y[25:50], 25, state=st)
-    ic.same(second, h2, what="second half")
-    fresh = ic.bank(imms)
-    fresh.set_state(*st)
-    for a, s in zip(_final(fresh), st):
-        assert kc.bits_equal(np.tril(a) if a.ndim == 4 else a, np.tril(s) if s.ndim == 4 else s)
-    again = fresh.run(U[25:50], Y[25:50], outputs=OUTS)
-    ic.same(again, second, what="set_state")
+    ig.same_final(b, end, "with and without per-step outputs")
+    ig.check_continuation(FAM, host, imms, U[:50], Y[:50], cut=25)
 
 
 def test_a_nan_imm_leaves_its_neighbours_in_the_wave_alone(host):
     rng = np.random.default_rng(6)
-    F, M, T = 70, 3, 30
-    imms = _imms(rng, F, M, 2, 1, 0)
-    U, Y = _data(rng, T, 0, 1, missing=(5, 6, 20))
+    imms = FAM.imms(rng, 70, 3, 2, 1, 0)
+    _, Y = _data(rng, 30, 0, 1, missing=(5, 6, 20))
     for interact in (True, False):
-        b = ic.bank(imms, interact)
-        ok = b.run(None, Y, outputs=OUTS)
-        mu, xm, Rm = ic.initial_state(imms)
-        Rm[13, 1] = -100.0 * np.eye(2)
-        b.set_state(mu, xm, Rm)
-        bad = b.run(None, Y, outputs=OUTS)
-        steps = np.delete(np.arange(T), [5, 6, 20])
-        assert np.all(np.isnan(bad["ll_steps"][steps, 13])) and np.all(bad["ll_steps"][[5, 6, 20], 13] == 0.0) and np.isnan(bad["ll"][13])
-        assert np.all(np.isnan(bad["mu"][:, 13])) and np.all(np.isnan(bad["xt"][:, 13])) and np.all(np.isnan(bad["x"][1:, 13]))
-        assert all(np.all(np.isnan(a[13])) for a in _final(b))
-        keep = [f for f in range(F) if f != 13]
-        for k in OUTS:
-            assert kc.bits_equal(bad[k][:, keep], ok[k][:, keep]), (interact, k)
-        assert kc.bits_equal(bad["ll"][keep], ok["ll"][keep])
-        hb, _ = ic.host_run(host, imms, None, Y, T, state=(mu, xm, Rm), interact=interact)
-        ic.same(bad, hb, what=("NaN IMM", interact))
+        ig.check_a_nan_imm(FAM, host, imms, None, Y, interact=interact, missing=(5, 6, 20), nan_filter=13, nan_mode=1)
 
 
 def test_a_mode_without_mass_on_the_device(host):
     rng = np.random.default_rng(8)
-    F, M, T = 70, 4, 30
-    imms = _imms(rng, F, M, 3, 2, 1)
-    for k, imm in enumerate(imms):
-        if k % 2:
-            imm["P"], imm["mu0"] = np.eye(M), np.array([0.5, 0.0, 0.25, 0.25])
-    U, Y = _data(rng, T, 1, 2, missing=(9,))
-    b = ic.bank(imms)
-    g = b.run(U, Y, outputs=OUTS)
-    h, st = ic.host_run(host, imms, U, Y, T)
-    ic.same(g, h, what="a mode without mass")
-    assert np.all(g["mu"][:, 1::2, 1] == 0.0) and np.all(np.isfinite(g["ll"]))
-    for a, s in zip(_final(b), st):
-        assert kc.bits_equal(a, s)
+    imms = FAM.imms(rng, 70, 4, 3, 2, 1)
+    U, Y = _data(rng, 30, 1, 2, missing=(9,))
+    ig.check_a_mode_without_mass(FAM, host, imms, U, Y, mu0=[0.5, 0.0, 0.25, 0.25])
 
 
 def test_set_parameters_is_a_fresh_bank():
     rng = np.random.default_rng(9)
-    F, M = 70, 2
-    old, new = _imms(rng, F, M, 3, 2, 1), _imms(rng, F, M, 3, 2, 1)
+    old, new = FAM.imms(rng, 70, 2, 3, 2, 1), FAM.imms(rng, 70, 2, 3, 2, 1)
     U, Y = _data(rng, 20, 1, 2, missing=(3,))
-    b = ic.bank(old)
-    b.run(U, Y)
-    b.set_models(*ic.bank_args(new))
-    b.reset()
-    g = b.run(U, Y, outputs=OUTS)
-    ic.same(g, ic.bank(new).run(U, Y, outputs=OUTS), what="set_models")
+    ig.check_set_models(FAM, old, new, U, Y)
 
 
 def test_python_api():
@@ -181,7 +101,8 @@ def test_python_api():
     sol = llpf_amd.forward_trajectory(imm, U, Y)
     assert sol.x.shape == (T, 3) and sol.Rt.shape == (T, 3, 3) and sol.mu.shape == (T, M) and sol.ll_modes.shape == (T, M)
     assert sol.e is None and np.isscalar(sol.ll) and sol.t.shape == (T,)
-    ref = ic.numpy_reference(dict(systems=[kf._model() for kf in kfs], P=P, mu0=mu0), U, Y)
+    systems = [kf._model() for kf in kfs]
+    ref = ic.numpy_reference(ic.imm([m for m, _ in systems], P=P, mu0=mu0, D=[D for _, D in systems]), U, Y)
     for k in ("x", "xt", "R", "Rt", "mu", "ll_modes"):
         assert kc.close(getattr(sol, k), ref[k]), k
     assert abs(sol.ll - ref["ll"]) <= 1e-10 * abs(ref["ll"])

@@ -1,7 +1,8 @@
 """Banks of IMM filters over extended Kalman filter modes on the device (llpf_imm_bank_* with LLPF_IMM_EXTENDED; kernels/imm_ekf.hpp,
 host/imm.hpp): the GPU reproduces the host build of csrc/shared/llpf_imm.h over csrc/shared/llpf_ekf.h (tests/imm_ekf_host.c) bit for bit
 — precompiled and run-time compiled models, whatever the number of modes, the bank, the chunking of T or the split of a run — it is the
-extended Kalman bank where it must be, and the Python API (IMM, IMMBank over ExtendedKalmanFilter) is that bank."""
+extended Kalman bank where it must be, and the Python API (IMM, IMMBank over ExtendedKalmanFilter) is that bank.  The bodies this file shares
+with test_gpu_imm.py are in imm_gpu_frame.py."""
 import ctypes as C
 
 import numpy as np
@@ -11,8 +12,8 @@ import llpf_amd
 from llpf_amd import _capi, _structs as S
 import ekf_common as ec
 import imm_common as ic
-import imm_ekf_common as xc
-from imm_ekf_common import OUTS
+from imm_common import OUTS
+import imm_gpu_frame as ig
 import kalman_common as kc
 from kalman_common import _data
 from gpu_common import _Inject
@@ -25,26 +26,29 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    return xc.build_host(tmp_path_factory.mktemp("imm_ekf_host"))
-
-
-def _final(b):
-    return b.get_modes()[2:]
+    return ic.build_host(tmp_path_factory.mktemp("imm_ekf_host"))
 
 
 def _check(b, g, h, st, what):
     """every output and ll of a run `g` of bank `b` against the twin's `h`, and the bank's final (mu, x_modes, R_modes) against `st`"""
-    xc.same(g, h, what=what)
-    for a, s in zip(_final(b), st):
-        assert kc.bits_equal(a, s), (what, "final state")
+    ic.same(g, h, what=what)
+    ig.same_final(b, st, what)
 
 
 def _quadtank_imms(rng, F, M):
-    return xc.grouped(kg.quadtank_models(F * M), rng, F, M)
+    return ic.grouped(kg.quadtank_models(F * M), rng, F, M)
 
 
 def _pendulum_imms(rng, F, M):
-    return xc.grouped(kg.pendulum_models(F * M), rng, F, M)
+    return ic.grouped(kg.pendulum_models(F * M), rng, F, M)
+
+
+LG = ig.ImmFamily(ic.lg_imms, None)
+
+
+def _quadtank(t0):
+    """the built-in quad-tank (its own shape) in runs from t_index0 = t0"""
+    return ig.ImmFamily(lambda rng, F, M, nx=4, ny=2, nu=2: _quadtank_imms(rng, F, M), t0)
 
 
 @pytest.mark.parametrize("nx", range(1, 5))
@@ -52,35 +56,11 @@ def test_lingauss_bit_identical_to_the_host_headers_for_every_precompiled_shape(
     """1. LLPF_IMM_EXTENDED over LinGauss<nx, ny>, ny and M in 1..4: F = 70 (a ragged last wave at every G, two workgroups at G = 4),
     T = 40 with missing rows, interact on and off; shared inputs, the same handed per filter, per-filter inputs of their own whose missing
     rows differ inside a wave; get_state's combined estimate; mu a distribution"""
-    F, T = 70, 40
     for ny in range(1, 5):
         for Mo in range(1, 5):
             rng = np.random.default_rng(1000 * Mo + 10 * nx + ny)
             nu = int(rng.integers(0, 3))
-            imms = xc.lg_imms(rng, F, Mo, nx, ny, nu)
-            U, Y = _data(rng, T, nu, ny, missing=(5, 6, 30))
-            Uf = rng.standard_normal((F, T, nu))
-            Yf = 2.0 * rng.standard_normal((F, T, ny))
-            Yf[::3, 11, 0] = Yf[1::4, 12, 0] = Yf[:, 20, 0] = np.nan
-            for interact in (True, False):
-                what = (nx, ny, Mo, interact)
-                b = xc.bank(imms, interact)
-                g = b.run(U, Y, outputs=OUTS)
-                h, st = xc.host_run(host, imms, U, Y, T, interact=interact)
-                _check(b, g, h, st, what)
-                x, R = b.get_state()
-                xh, Rh = xc.host_combine(host, *st)
-                assert kc.bits_equal(x, xh) and kc.bits_equal(R, Rh), what
-                assert np.all(g["ll_steps"][[5, 6, 30]] == 0.0) and np.all(g["ll_modes"][[5, 6, 30]] == 0.0), what
-                assert np.all(np.isfinite(g["ll"])) and np.all(g["mu"] >= 0.0) and np.all(np.abs(g["mu"].sum(axis=2) - 1.0) <= 1e-12), what
-                b.reset()
-                gp = b.run(np.broadcast_to(U, (F,) + U.shape), np.broadcast_to(Y, (F,) + Y.shape), nu > 0, True, outputs=OUTS)
-                xc.same(gp, g, what=what + ("shared inputs given per filter",))
-                b.reset()
-                gf = b.run(Uf, Yf, nu > 0, True, outputs=OUTS)
-                hf, _ = xc.host_run(host, imms, Uf, Yf, T, per_filter=3, interact=interact)
-                xc.same(gf, hf, what=what + ("per-filter inputs",))
-                b.close()
+            ig.check_shape(LG, host, rng, F=70, T=40, M=Mo, nx=nx, ny=ny, nu=nu, missing=(5, 6, 30), what=(nx, ny, Mo))
 
 
 def _run_c(b, U, Y, outputs):
@@ -108,15 +88,15 @@ def test_quadtank_modes_across_the_switch_time(host, Mo):
     Y = Y.copy()
     Y[[5, 31, 32], 0] = np.nan
     for interact in (True, False):
-        b = xc.bank(imms, interact)
+        b = ic.bank(imms, interact)
         g = b.run(U, Y, outputs=OUTS, t_index0=470.0)
-        h, st = xc.host_run(host, imms, U, Y, 60, t_index0=470.0, interact=interact)
+        h, st = ic.host_run(host, imms, U, Y, 60, t_index0=470.0, interact=interact)
         _check(b, g, h, st, ("quad-tank", Mo, interact))
         assert np.isfinite(g["ll"]).all() and len(set(g["ll"].tolist())) > 40
         b.reset()
         at0 = b.run(U, Y, outputs=OUTS, t_index0=0.0)
         b.reset()
-        xc.same(_run_c(b, U, Y, OUTS), at0, what=("run is run_at(0.0)", Mo, interact))
+        ic.same(_run_c(b, U, Y, OUTS), at0, what=("run is run_at(0.0)", Mo, interact))
         assert not kc.bits_equal(at0["ll"], g["ll"])
         b.close()
 
@@ -132,31 +112,31 @@ def test_runtime_compiled_models(host):
     U, Y = uc.pendulum_data(80)
     Y = Y.copy()
     Y[[3, 40], 0] = np.nan
-    b = xc.bank(xc.with_id(pend, pid))
+    b = ic.bank(ic.with_id(pend, pid))
     g = b.run(U, Y, outputs=OUTS)
-    h, st = xc.host_run(host, pend, U, Y, 80, kind=ec.KIND_PENDULUM)
+    h, st = ic.host_run(host, pend, U, Y, 80, kind=ec.KIND_PENDULUM)
     _check(b, g, h, st, "pendulum snippet")
     assert np.isfinite(g["ll"]).all()
     sid = _capi.model_compile(ec.SQUARE_JAC_SRC, 1, 1)
-    sq = xc.grouped(kg.square_models(2 * F), rng, F, 2)
+    sq = ic.grouped(kg.square_models(2 * F), rng, F, 2)
     Ys = 3.0 + 0.5 * rng.standard_normal((60, 1))
-    b = xc.bank(xc.with_id(sq, sid))
+    b = ic.bank(ic.with_id(sq, sid))
     g = b.run(None, Ys, outputs=OUTS)
-    h, st = xc.host_run(host, sq, None, Ys, 60, kind=ec.KIND_SQUARE)
+    h, st = ic.host_run(host, sq, None, Ys, 60, kind=ec.KIND_SQUARE)
     _check(b, g, h, st, "square snippet")
-    lg = xc.lg_imms(rng, F, 4, 6, 3, 2)
+    lg = ic.lg_imms(rng, F, 4, 6, 3, 2)
     Ul, Yl = _data(rng, 40, 2, 3, missing=(7,))
-    b = xc.bank(lg)
+    b = ic.bank(lg)
     g = b.run(Ul, Yl, outputs=OUTS)
-    h, st = xc.host_run(host, lg, Ul, Yl, 40)
+    h, st = ic.host_run(host, lg, Ul, Yl, 40)
     _check(b, g, h, st, "LG (6, 3, 2)")
     # the quad-tank as a snippet: the built-in model's bits
-    qid = _capi.model_compile(xc.QUADTANK_JAC_SRC, 4, 2)
+    qid = _capi.model_compile(ic.QUADTANK_JAC_SRC, 4, 2)
     qt = _quadtank_imms(rng, F, 3)
     Uq, Yq = M.quadtank_data(50)
-    gb = xc.bank(qt).run(Uq, Yq, outputs=OUTS, t_index0=480.0)
-    gs = xc.bank(xc.with_id(qt, qid)).run(Uq, Yq, outputs=OUTS, t_index0=480.0)
-    xc.same(gs, gb, what="quad-tank snippet against the built-in model")
+    gb = ic.bank(qt).run(Uq, Yq, outputs=OUTS, t_index0=480.0)
+    gs = ic.bank(ic.with_id(qt, qid)).run(Uq, Yq, outputs=OUTS, t_index0=480.0)
+    ic.same(gs, gb, what="quad-tank snippet against the built-in model")
     # traced callables: x0^2 against the snippet
     d = [llpf_amd.MvNormal(np.array([1.0 + 0.3 * j]), 0.36) for j in range(2)]
     P, mu = [[0.9, 0.1], [0.2, 0.8]], [0.6, 0.4]
@@ -178,13 +158,13 @@ def test_bank_sizes_and_chunk_edges(host, F):
     outputs and the final state"""
     for Mo in (2, 4):
         rng = np.random.default_rng(400 + 10 * F + Mo)
-        imms = xc.lg_imms(rng, F, Mo, 2, 1, 1)
+        imms = ic.lg_imms(rng, F, Mo, 2, 1, 1)
         U, Y = _data(rng, 600, 1, 1, missing=(0, 255, 256, 599))
-        b = xc.bank(imms)
+        b = ic.bank(imms)
         for T in (1, 255, 256, 257, 600):
             b.reset()
             g = b.run(U[:T], Y[:T], outputs=OUTS)
-            h, st = xc.host_run(host, imms, U[:T], Y[:T], T)
+            h, st = ic.host_run(host, imms, U[:T], Y[:T], T)
             _check(b, g, h, st, (F, Mo, T))
         b.close()
 
@@ -192,77 +172,29 @@ def test_bank_sizes_and_chunk_edges(host, F):
 def test_continuation_and_set_state(host):
     """5. on the quad-tank: run_at(a, t0) then run_at(b, t0 + len(a)) is run_at(a + b, t0), cut at 37 of 90; set_state on a fresh bank;
     ll alone"""
-    rng = np.random.default_rng(5)
-    imms = _quadtank_imms(rng, 70, 3)
+    fam = _quadtank(450.0)
+    imms = fam.imms(np.random.default_rng(5), 70, 3)
     U, Y = M.quadtank_data(90)
     Y = Y.copy()
     Y[[10, 37, 60], 0] = np.nan
-    t0, cut = 450.0, 37
-    b = xc.bank(imms)
-    whole = b.run(U, Y, outputs=OUTS, t_index0=t0)
-    end = _final(b)
-    b.reset()
-    first = b.run(U[:cut], Y[:cut], outputs=OUTS, t_index0=t0)
-    st = _final(b)
-    second = b.run(U[cut:], Y[cut:], outputs=OUTS, t_index0=t0 + cut)
-    for k in OUTS:
-        assert kc.bits_equal(np.concatenate([first[k], second[k]]), whole[k]), k
-    for a, s in zip(_final(b), end):
-        assert kc.bits_equal(a, s)
-    h2, _ = xc.host_run(host, imms, U[cut:], Y[cut:], 90 - cut, t_index0=t0 + cut, state=st)
-    xc.same(second, h2, what="second half")
-    fresh = xc.bank(imms)
-    fresh.set_state(*st)
-    for a, s in zip(_final(fresh), st):
-        assert kc.bits_equal(np.tril(a) if a.ndim == 4 else a, np.tril(s) if s.ndim == 4 else s)
-    again = fresh.run(U[cut:], Y[cut:], outputs=OUTS, t_index0=t0 + cut)
-    xc.same(again, second, what="set_state")
-    b.reset()
-    bare = b.run(U, Y, t_index0=t0)                       # ll only: nothing is staged per step, nothing is combined
-    assert kc.bits_equal(bare["ll"], whole["ll"])
-    for a, s in zip(_final(b), end):
-        assert kc.bits_equal(a, s)
+    ig.check_continuation(fam, host, imms, U, Y, cut=37)
 
 
 def test_a_filters_bits_do_not_depend_on_the_bank(host):
     """6. filters 0, 15, 16, 69 alone in a bank of one; an IMM started from an indefinite mode covariance is NaN in its own outputs from
     that step on and the other filters' bits are unmoved; a zero column of P (a mode without mass) against the twin"""
-    rng = np.random.default_rng(6)
-    F, Mo, T = 70, 3, 30
-    imms = _quadtank_imms(rng, F, Mo)
-    U, Y = M.quadtank_data(T)
+    fam = _quadtank(1.0)
+    imms = fam.imms(np.random.default_rng(6), 70, 3)
+    U, Y = M.quadtank_data(30)
     Y = Y.copy()
     Y[[5, 6, 20], 0] = np.nan
-    b = xc.bank(imms)
-    ok = b.run(U, Y, outputs=OUTS, t_index0=1.0)
+    _, ok = ig.check_a_nan_imm(fam, host, imms, U, Y, interact=True, missing=(5, 6, 20), nan_filter=13, nan_mode=1)
     for f in (0, 15, 16, 69):
-        one = xc.bank([imms[f]]).run(U, Y, outputs=OUTS, t_index0=1.0)
+        one = ic.bank([imms[f]]).run(U, Y, outputs=OUTS, t_index0=1.0)
         for k in OUTS:
             assert kc.bits_equal(one[k][:, 0], ok[k][:, f]), (f, k)
         assert one["ll"][0] == ok["ll"][f]
-    mu, xm, Rm = xc.initial_state(imms)
-    Rm[13, 1] = -100.0 * np.eye(4)
-    b.set_state(mu, xm, Rm)
-    bad = b.run(U, Y, outputs=OUTS, t_index0=1.0)
-    steps = np.delete(np.arange(T), [5, 6, 20])
-    assert np.all(np.isnan(bad["ll_steps"][steps, 13])) and np.all(bad["ll_steps"][[5, 6, 20], 13] == 0.0) and np.isnan(bad["ll"][13])
-    assert np.all(np.isnan(bad["mu"][:, 13])) and np.all(np.isnan(bad["xt"][:, 13])) and np.all(np.isnan(bad["x"][1:, 13]))
-    assert all(np.all(np.isnan(a[13])) for a in _final(b))
-    keep = [f for f in range(F) if f != 13]
-    for k in OUTS:
-        assert kc.bits_equal(bad[k][:, keep], ok[k][:, keep]), k
-    assert kc.bits_equal(bad["ll"][keep], ok["ll"][keep])
-    hb, _ = xc.host_run(host, imms, U, Y, T, t_index0=1.0, state=(mu, xm, Rm))
-    xc.same(bad, hb, what="NaN IMM")
-    # a mode without mass
-    for k, s in enumerate(imms):
-        if k % 2:
-            s["P"], s["mu0"] = np.eye(Mo), np.array([0.5, 0.0, 0.5])
-    b = xc.bank(imms)
-    g = b.run(U, Y, outputs=OUTS, t_index0=1.0)
-    h, st = xc.host_run(host, imms, U, Y, T, t_index0=1.0)
-    _check(b, g, h, st, "a mode without mass")
-    assert np.all(g["mu"][:, 1::2, 1] == 0.0) and np.all(np.isfinite(g["ll"]))
+    ig.check_a_mode_without_mass(fam, host, imms, U, Y, mu0=[0.5, 0.0, 0.5])
 
 
 def test_ties_to_the_extended_kalman_bank():
@@ -276,14 +208,14 @@ def test_ties_to_the_extended_kalman_bank():
     for what, models, U, Y, t0 in (("quad-tank", kg.quadtank_models(F), Uq, Yq, 470.0), ("pendulum", [kg.with_id(m, pid) for m in kg.pendulum_models(F)], Up, Yp, 0.0)):
         Y = Y.copy()
         Y[[4, 30], 0] = np.nan
-        g = xc.bank([xc.imm([m], P=[[1.0]], mu0=[1.0]) for m in models]).run(U, Y, outputs=OUTS, t_index0=t0)
+        g = ic.bank([ic.imm([m], P=[[1.0]], mu0=[1.0]) for m in models]).run(U, Y, outputs=OUTS, t_index0=t0)
         e = _capi.EkfBankHandle(0, list(models)).run(U, Y, outputs=kg.OUTS, t_index0=t0)
         for k in ("x", "xt", "R", "Rt", "ll_steps", "ll"):
             assert kc.bits_equal(g[k], e[k]), (what, k)
         assert np.all(g["mu"] == 1.0)
     Mo = 3
     imms = _quadtank_imms(rng, F, Mo)
-    g = xc.bank(imms, interact=False).run(Uq, Yq, outputs=("ll_modes",), t_index0=470.0)
+    g = ic.bank(imms, interact=False).run(Uq, Yq, outputs=("ll_modes",), t_index0=470.0)
     for j in range(Mo):
         e = _capi.EkfBankHandle(0, [s["models"][j] for s in imms]).run(Uq, Yq, outputs=("ll_steps",), t_index0=470.0)
         assert kc.bits_equal(g["ll_modes"][:, :, j], e["ll_steps"]), j
@@ -301,37 +233,32 @@ def test_parameters_a_throw_and_the_python_api(host):
     step counter, bank rows equal the single filters; a Kalman IMMBank beside it gives the bits of its own twin"""
     rng = np.random.default_rng(8)
     F, Mo = 70, 2
-    old, new = _quadtank_imms(rng, F, Mo), xc.grouped(kg.quadtank_models(F * Mo)[::-1], rng, F, Mo)
+    old, new = _quadtank_imms(rng, F, Mo), ic.grouped(kg.quadtank_models(F * Mo)[::-1], rng, F, Mo)
     U, Y = M.quadtank_data(40)
-    b = xc.bank(old)
-    b.run(U, Y)
-    b.set_models(*xc.bank_args(new))
-    b.reset()
-    g = b.run(U, Y, outputs=OUTS, t_index0=1.0)
-    xc.same(g, xc.bank(new).run(U, Y, outputs=OUTS, t_index0=1.0), what="set_models")
+    b, g = ig.check_set_models(_quadtank(1.0), old, new, U, Y)
     with pytest.raises(_capi.LLPFError):
-        b.set_models(*xc.bank_args(xc.lg_imms(rng, F, Mo, 4, 2, 2)))
+        b.set_models(*ic.bank_args(ic.lg_imms(rng, F, Mo, 4, 2, 2)))
     b.reset()
-    before = _final(b)
+    before = ig.final(b)
     with _Inject("error:imm_run"):
         with pytest.raises(_capi.LLPFError) as ei:
             b.run(U, Y, t_index0=1.0)
     assert ei.value.code == _capi.ERR_INTERNAL and "imm_run" in str(ei.value)
-    for a, s in zip(_final(b), before):
+    for a, s in zip(ig.final(b), before):
         assert kc.bits_equal(a, s)
-    xc.same(b.run(U, Y, outputs=OUTS, t_index0=1.0), g, what="after the throw")
+    ic.same(b.run(U, Y, outputs=OUTS, t_index0=1.0), g, what="after the throw")
     # the Python API
     modes = [_ekf_qt(0.2, 0.03), _ekf_qt(0.3, 0.036), _ekf_qt(0.25, 0.03)]
-    P, mu0 = xc.random_P(rng, 3), xc.random_mu(rng, 3)
+    P, mu0 = ic.random_P(rng, 3), ic.random_mu(rng, 3)
     imm = llpf_amd.IMM(modes, P, mu0)
     assert imm._handle is None and imm.extended
     T = 40
     sol = llpf_amd.forward_trajectory(imm, U, Y)
     assert isinstance(sol, llpf_amd.IMMFilteringSolution) and sol.x.shape == (T, 4) and sol.Rt.shape == (T, 4, 4) and sol.mu.shape == (T, 3)
     assert sol.ll_modes.shape == (T, 3) and sol.e is None and np.isscalar(sol.ll)
-    spec = [xc.imm([f._model for f in modes], P=P, mu0=mu0)]
-    h0, _ = xc.host_run(host, spec, U, Y, T, t_index0=0.0)
-    h1, _ = xc.host_run(host, spec, U, Y, T, t_index0=1.0)
+    spec = [ic.imm([f._model for f in modes], P=P, mu0=mu0)]
+    h0, _ = ic.host_run(host, spec, U, Y, T, t_index0=0.0)
+    h1, _ = ic.host_run(host, spec, U, Y, T, t_index0=1.0)
     for k in ("x", "xt", "R", "Rt", "mu", "ll_modes"):
         assert kc.bits_equal(getattr(sol, k), h0[k][:, 0]), k
     assert sol.ll == h0["ll"][0] and llpf_amd.loglik(imm, U, Y) == h1["ll"][0] and h0["ll"][0] != h1["ll"][0]

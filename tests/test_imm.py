@@ -1,5 +1,5 @@
-"""The IMM filter of csrc/shared/llpf_imm.h on the host (tests/imm_host.c, the build the device is held to in test_gpu_imm.py): it is the
-textbook recursion (a numpy restatement in literal formulas), it degenerates to the Kalman filter of tests/kalman_host.c bit for bit
+"""The IMM filter of csrc/shared/llpf_imm.h on the host (tests/imm_host.c: the six stages of tests/kf_host_frame.h over the Kalman family,
+the build the device is held to in test_gpu_imm.py): it is the textbook recursion (a numpy restatement in literal formulas), it degenerates to the Kalman filter of tests/kalman_host.c bit for bit
 where it must (one mode, no interaction, P = I), it keeps its corner rules, and the C ABI refuses what it cannot run.  No GPU needed."""
 import ctypes as C
 from fractions import Fraction
@@ -31,7 +31,7 @@ def khost(tmp_path_factory):
 def _case(seed, M, nx, ny, nu, T, F=1, missing=()):
     rng = np.random.default_rng(seed)
     imms = [ic.random_imm(rng, M, nx, ny, nu, k) for k in range(F)]
-    U, Y = kc.simulate(rng, kc.matrices(*imms[0]["systems"][0]), T, missing=missing)
+    U, Y = kc.simulate(rng, kc.matrices(*ic.systems(imms[0])[0]), T, missing=missing)
     return imms, U, Y
 
 
@@ -61,7 +61,7 @@ def test_one_mode_is_the_kalman_filter_bit_for_bit(host, khost, shape):
     for imm in imms:
         imm["P"], imm["mu0"] = np.ones((1, 1)), np.ones(1)
     h, (mu, xm, Rm) = ic.host_run(host, imms, U, Y, T)
-    k, (xk, Rk) = kc.host_run(khost, [s["systems"][0] for s in imms], U, Y, T)
+    k, (xk, Rk) = kc.host_run(khost, [ic.systems(s)[0] for s in imms], U, Y, T)
     for key in ("ll", "ll_steps", "x", "xt", "R", "Rt"):
         assert kc.bits_equal(h[key], k[key]), key
     assert kc.bits_equal(h["ll_modes"][:, :, 0], k["ll_steps"]) and np.all(h["mu"] == 1.0)
@@ -70,10 +70,10 @@ def test_one_mode_is_the_kalman_filter_bit_for_bit(host, khost, shape):
 
 def _modes_are_the_kalman_filters(khost, imms, h, final, U, Y, T):
     """every mode's ll and final state are those of the Kalman twin of that mode alone; returns the twins' totals LL [F, M]"""
-    M = len(imms[0]["systems"])
+    M = len(imms[0]["models"])
     LL = np.empty((len(imms), M))
     for j in range(M):
-        k, (xk, Rk) = kc.host_run(khost, [s["systems"][j] for s in imms], U, Y, T)
+        k, (xk, Rk) = kc.host_run(khost, [ic.systems(s)[j] for s in imms], U, Y, T)
         assert kc.bits_equal(h["ll_modes"][:, :, j], k["ll_steps"]), j
         assert kc.bits_equal(final[1][:, j], xk) and kc.bits_equal(final[2][:, j], Rk), j
         LL[:, j] = k["ll"]
@@ -137,7 +137,7 @@ def test_a_mode_without_mass_enters_no_sum_and_is_not_mixed(host, khost):
     # mode 1 keeps its own state: the Kalman filter of that mode alone
     _modes_are_the_kalman_filters(khost, imms, h, final, U, Y, T)
     # ... and everything else is the IMM of the two modes that have mass, bit for bit
-    two = [dict(systems=[s["systems"][0], s["systems"][2]], P=np.eye(2), mu0=np.array([0.25, 0.75])) for s in imms]
+    two = [ic.imm([s["models"][0], s["models"][2]], P=np.eye(2), mu0=np.array([0.25, 0.75]), D=[s["D"][0], s["D"][2]]) for s in imms]
     h2, _ = ic.host_run(host, two, U, Y, T)
     for k in ("ll", "ll_steps", "x", "xt", "R", "Rt"):
         assert kc.bits_equal(h[k], h2[k]), k
@@ -212,13 +212,13 @@ def test_arguments_that_cannot_run_are_refused():
     rc, msg = _create(imms, mu0=mu)
     assert rc == _capi.ERR_ARG and "filter 1" in msg and "mu0" in msg, msg
     other = [ic.random_imm(rng, 3, 2, 1, 1), ic.random_imm(rng, 3, 2, 1, 1)]
-    other[1]["systems"][2] = kc.random_system(rng, 3, 1, 1)
+    other[1]["models"][2], other[1]["D"][2] = kc.random_system(rng, 3, 1, 1)
     rc, msg = _create(other)
     assert rc == _capi.ERR_ARG and "filter 1, mode 2" in msg and "dimensions" in msg, msg
     # what the Kalman bank refuses, per mode: a noise density with a mean
-    m = other[0]["systems"][1][0]
+    m = other[0]["models"][1]
     m.dynamics_density.mu[0] = 0.5
-    other[1]["systems"][2] = kc.random_system(rng, 2, 1, 1)
+    other[1]["models"][2], other[1]["D"][2] = kc.random_system(rng, 2, 1, 1)
     rc, msg = _create(other)
     assert rc == _capi.ERR_ARG and "filter 0, mode 1" in msg and "zero mean" in msg, msg
     # the arguments themselves are fine: without a device the create gets as far as asking for one

@@ -1,5 +1,6 @@
 """The IMM filter over first-order extended Kalman filter modes on the host (tests/imm_ekf_host.c, the build of csrc/shared/llpf_imm.h over
-csrc/shared/llpf_ekf.h that the device is held to in test_gpu_imm_ekf.py): with one mode it is the extended Kalman filter of
+csrc/shared/llpf_ekf.h — the six stages of tests/kf_host_frame.h over the extended family — that the device is held to in
+test_gpu_imm_ekf.py): with one mode it is the extended Kalman filter of
 tests/ekf_host.c bit for bit, on linear modes it is the Kalman IMM of tests/imm_host.c, it is the textbook recursion (a numpy
 restatement in literal formulas, float64 and long double), it has the known answer of the linearisation, it finds the mode of switching
 data, and the C ABI and the Python classes refuse what they cannot run.  No GPU needed."""
@@ -15,7 +16,6 @@ import llpf_amd
 from llpf_amd import _capi, _structs as S
 import ekf_common as ec
 import imm_common as ic
-import imm_ekf_common as xc
 import kalman_common as kc
 import models as M
 import ukf_common as uc
@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    return xc.build_host(tmp_path_factory.mktemp("imm_ekf_host"))
+    return ic.build_host(tmp_path_factory.mktemp("imm_ekf_host"))
 
 
 def _pendulum_modes(n, r1=False):
@@ -63,8 +63,8 @@ def test_one_mode_is_the_extended_kalman_filter_bit_for_bit(host):
     Up, Yp = uc.pendulum_data(80)
     for what, models, kind, U, Y, t0 in (("LG", lg, ec.KIND_LG, Ul, Yl, 0.0), ("quad-tank", _quadtank_modes(3), ec.KIND_QUADTANK, Uq, _missing(Yq, (3, 50, 51)), 460.0),
                                          ("pendulum", _pendulum_modes(3), ec.KIND_PENDULUM, Up, _missing(Yp, (0, 33)), 1.0)):
-        imms = [xc.imm([m], P=[[1.0]], mu0=[1.0]) for m in models]
-        h, (mu, xm, Rm) = xc.host_run(host, imms, U, Y, 80, t_index0=t0, kind=kind)
+        imms = [ic.imm([m], P=[[1.0]], mu0=[1.0]) for m in models]
+        h, (mu, xm, Rm) = ic.host_run(host, imms, U, Y, 80, t_index0=t0, kind=kind)
         e, (x, R) = ec.host_run(host, models, U, Y, 80, t_index0=t0, kind=kind)
         for k in ("x", "xt", "R", "Rt", "ll_steps", "ll"):
             assert kc.bits_equal(h[k], e[k]), (what, k)
@@ -77,12 +77,12 @@ def test_linear_modes_agree_with_the_kalman_imm(host):
     """2. LG modes, M = 3, (3, 2, 1), T = 100: every output of the twin against imm_host_run (the Kalman IMM, D = 0) at the bar
     tests/test_ekf.py test 1 holds the EKF to against the Kalman header (1e-10 relative, kalman_common.close)"""
     rng = np.random.default_rng(2)
-    imms = xc.lg_imms(rng, 2, 3, 3, 2, 1)
+    imms = ic.lg_imms(rng, 2, 3, 3, 2, 1)
     U, Y = kc.simulate(rng, kc.matrices(imms[0]["models"][0], np.zeros((2, 1))), 100, missing=(7, 8, 60))
     for interact in (True, False):
-        h, st = xc.host_run(host, imms, U, Y, 100, interact=interact)
-        k_, stk = ic.host_run(host, xc.as_kalman(imms), U, Y, 100, interact=interact)
-        for k in xc.OUTS:
+        h, st = ic.host_run(host, imms, U, Y, 100, interact=interact)
+        k_, stk = ic.host_run(host, ic.as_kalman(imms), U, Y, 100, interact=interact)
+        for k in ic.OUTS:
             assert kc.close(h[k], k_[k]), (interact, k)
         assert np.all(np.abs(h["ll"] - k_["ll"]) <= 1e-10 * np.abs(k_["ll"])), interact
         for a, b in zip(st, stk):
@@ -95,12 +95,12 @@ def _measured(host, imm, kind, mode_of, U, Y, t0, what):
     """the twin against the restatement with the bar of test_ekf.py::_measured: the restatement's own float64-against-long-double error
     is measured in the same run; the bar per output is 1e-10 where ten times that error is below it, otherwise ten times that error"""
     Ts = imm["models"][0].Ts
-    a = xc.numpy_imm_ekf([mode_of(m) for m in imm["models"]], imm["P"], imm["mu0"], U, Y, Ts, t0)
-    b = xc.numpy_imm_ekf([mode_of(m, np.longdouble) for m in imm["models"]], imm["P"], imm["mu0"], U, Y, Ts, t0, lin=uc.LinLong)
-    own = {k: uc.rel_err(a[k], b[k]) for k in xc.OUTS + ("ll",)}
-    got, _ = xc.host_run(host, [imm], U, Y, Y.shape[0], t_index0=t0, kind=kind)
+    a = ic.numpy_imm([mode_of(m) for m in imm["models"]], imm["P"], imm["mu0"], U, Y, Ts, t0)
+    b = ic.numpy_imm([mode_of(m, np.longdouble) for m in imm["models"]], imm["P"], imm["mu0"], U, Y, Ts, t0, lin=uc.LinLong)
+    own = {k: uc.rel_err(a[k], b[k]) for k in ic.OUTS + ("ll",)}
+    got, _ = ic.host_run(host, [imm], U, Y, Y.shape[0], t_index0=t0, kind=kind)
     assert not np.isnan(got["ll"]).any() and not np.isnan(got["Rt"]).any(), what
-    err = {k: uc.rel_err(got[k][:, 0], a[k]) for k in xc.OUTS}
+    err = {k: uc.rel_err(got[k][:, 0], a[k]) for k in ic.OUTS}
     err["ll"] = uc.rel_err(got["ll"][0], a["ll"])
     print(what, "ll %.6f" % got["ll"][0], "restatement float64 vs long double:", {k: "%.2e" % v for k, v in own.items()})
     print(what, "twin vs restatement:", {k: "%.2e" % v for k, v in err.items()})
@@ -118,8 +118,8 @@ def test_twin_equals_the_formulas_on_pendulum_modes(host):
     at hand, never from these."""
     rng = np.random.default_rng(3)
     U, Y = uc.pendulum_data(300)
-    imm = xc.imm(_pendulum_modes(3, r1=True), rng=rng)
-    got = _measured(host, imm, ec.KIND_PENDULUM, xc.pendulum_mode, U, _missing(Y, (3, 150, 298)), 0.0, "pendulum modes")
+    imm = ic.imm(_pendulum_modes(3, r1=True), rng=rng)
+    got = _measured(host, imm, ec.KIND_PENDULUM, ic.pendulum_mode, U, _missing(Y, (3, 150, 298)), 0.0, "pendulum modes")
     assert np.all(np.abs(got["mu"].sum(axis=2) - 1.0) <= 1e-12)
 
 
@@ -130,8 +130,8 @@ def test_twin_equals_the_formulas_on_quadtank_modes(host):
     mu 6.7e-16, ll_modes 2.9e-15, ll 3.3e-16: the bar is 1e-10 for every output, derived from the run at hand."""
     rng = np.random.default_rng(4)
     U, Y = M.quadtank_data(200)
-    imm = xc.imm(_quadtank_modes(2), rng=rng)
-    _measured(host, imm, ec.KIND_QUADTANK, xc.quadtank_mode, U, _missing(Y, (5, 99, 100)), 400.0, "quad-tank modes")
+    imm = ic.imm(_quadtank_modes(2), rng=rng)
+    _measured(host, imm, ec.KIND_QUADTANK, ic.quadtank_mode, U, _missing(Y, (5, 99, 100)), 400.0, "quad-tank modes")
 
 
 def test_known_answer_of_two_linearised_modes(host):
@@ -139,8 +139,8 @@ def test_known_answer_of_two_linearised_modes(host):
     ll the log of the normaliser, by hand, to 1e-13 relative"""
     ms, Ps, r2, y = (1.7, 1.2), (0.36, 0.5), 0.25, 3.0
     Pt, mu0 = np.array([[0.9, 0.1], [0.3, 0.7]]), np.array([0.6, 0.4])
-    imm = xc.imm([ec.square_model(ms[j], Ps[j], r2) for j in range(2)], P=Pt, mu0=mu0)
-    got, _ = xc.host_run(host, [imm], None, np.array([[y]]), 1, kind=ec.KIND_SQUARE)
+    imm = ic.imm([ec.square_model(ms[j], Ps[j], r2) for j in range(2)], P=Pt, mu0=mu0)
+    got, _ = ic.host_run(host, [imm], None, np.array([[y]]), 1, kind=ec.KIND_SQUARE)
     c = [Pt[0, j] * mu0[0] + Pt[1, j] * mu0[1] for j in range(2)]
     Sj = [4 * ms[j] * ms[j] * Ps[j] + r2 for j in range(2)]
     Nj = [math.exp(-0.5 * (y - ms[j] ** 2) ** 2 / Sj[j]) / math.sqrt(2 * math.pi * Sj[j]) for j in range(2)]
@@ -184,8 +184,8 @@ def test_switching_data_prefers_the_imm_and_the_true_mode(host):
     posterior probability of the true mode exceeds 1/2.  Measured on the twin: ll IMM 763.2, EKF(9.81) -3531.9, EKF(2.5) -24.1; mean
     posterior probability of the true mode 0.839."""
     ms, U, Y, mode = _switching_pendulum(600)
-    imm = xc.imm(ms, P=[[0.98, 0.02], [0.02, 0.98]], mu0=[0.5, 0.5])
-    got, _ = xc.host_run(host, [imm], U, Y, 600, kind=ec.KIND_PENDULUM)
+    imm = ic.imm(ms, P=[[0.98, 0.02], [0.02, 0.98]], mu0=[0.5, 0.5])
+    got, _ = ic.host_run(host, [imm], U, Y, 600, kind=ec.KIND_PENDULUM)
     single = [ec.host_run(host, [m], U, Y, 600, kind=ec.KIND_PENDULUM)[0]["ll"][0] for m in ms]
     p_true = float(np.mean(got["mu"][np.arange(600), 0, mode]))
     print("switching pendulum: ll IMM %.3f, EKF(g/l = %.2f) %.3f, EKF(g/l = %.2f) %.3f; mean posterior probability of the true mode %.4f"
@@ -211,7 +211,7 @@ def test_header_binding_and_julia_wrapper_name_the_new_export():
 
 
 def _create(imms, flags=3, D=None):
-    models, _, P, mu0 = xc.bank_args(imms)
+    models, _, P, mu0 = ic.bank_args(imms)
     flat = [m for row in models for m in row]
     arr = (S.Model * len(flat))(*flat)
     P, mu0 = _capi.f64(P), _capi.f64(mu0)
@@ -230,39 +230,39 @@ def test_what_cannot_run_is_refused_before_a_device_is_looked_for(monkeypatch):
     monkeypatch.setenv("LLPF_JIT_COMPILE_ONLY", "1")
     rng = np.random.default_rng(7)
     # mixed model ids among the modes
-    imms = xc.grouped(_pendulum_modes(4), rng, 2, 2)
+    imms = ic.grouped(_pendulum_modes(4), rng, 2, 2)
     pid = _capi.model_compile(ec.PENDULUM_JAC_SRC + "\n// test_imm_ekf\n", 2, 1)
-    mixed = xc.with_id(imms, pid)
+    mixed = ic.with_id(imms, pid)
     mixed[1]["models"][1] = imms[1]["models"][1]              # (the linear-Gaussian id)
     rc, msg = _create(mixed)
     assert rc == _capi.ERR_ARG and "filter 1, mode 1" in msg and "model_id" in msg, (rc, msg)
     # ... and a Kalman bank (no flag) still refuses a mode that is not linear-Gaussian, by filter and mode
-    back = xc.with_id(imms, pid)
+    back = ic.with_id(imms, pid)
     back[0]["models"][0] = imms[0]["models"][0]
     rc, msg = _create(back, flags=1)
     assert rc == _capi.ERR_ARG and "filter 0, mode 1" in msg, (rc, msg)
     # dimensions
-    odd = xc.lg_imms(rng, 2, 2, 3, 2, 1)
+    odd = ic.lg_imms(rng, 2, 2, 3, 2, 1)
     odd[1]["models"][0] = kc.random_system(rng, 3, 1, 1, D=False)[0]
     rc, msg = _create(odd)
     assert rc == _capi.ERR_ARG and "filter 1, mode 0" in msg and "dimensions" in msg, (rc, msg)
     # the checks of llpf_ekf_bank_create: one Jacobian member only; a member `initial`
     for src, word in ((ec.SQUARE_DYN_JAC_ONLY_SRC, "measurement_jac"), (ec.SQUARE_JAC_INITIAL_SRC, "initial")):
         mid = _capi.model_compile(src + "\n// test_imm_ekf\n", 1, 1)
-        sq = xc.with_id(xc.grouped([ec.square_model(1.0 + 0.1 * k, 0.3) for k in range(4)], rng, 2, 2), mid)
+        sq = ic.with_id(ic.grouped([ec.square_model(1.0 + 0.1 * k, 0.3) for k in range(4)], rng, 2, 2), mid)
         for flags in (1, 3):                                     # the flag is implied by the model id
             rc, msg = _create(sq, flags=flags)
             assert rc == _capi.ERR_ARG and word in msg and msg.startswith("imm"), (word, flags, rc, msg)
-    rb = xc.with_id(xc.lg_imms(rng, 1, 2, 2, 1, 1), S.MODEL_RB_LINEAR)
+    rb = ic.with_id(ic.lg_imms(rng, 1, 2, 2, 1, 1), S.MODEL_RB_LINEAR)
     rc, msg = _create(rb)
     assert rc == _capi.ERR_ARG and "Rao-Blackwellized" in msg, (rc, msg)
     # per mode: a density that is not positive definite
-    bad = xc.lg_imms(rng, 2, 2, 2, 1, 1)
+    bad = ic.lg_imms(rng, 2, 2, 2, 1, 1)
     bad[1]["models"][1].measurement_density = S.make_gaussian(np.zeros(1), -1.0)
     rc, msg = _create(bad)
     assert rc == _capi.ERR_ARG and "filter 1, mode 1" in msg and "R2" in msg, (rc, msg)
     # D with the flag; flags with bit 2; P that is not stochastic
-    lg = xc.lg_imms(rng, 2, 3, 2, 1, 1)
+    lg = ic.lg_imms(rng, 2, 3, 2, 1, 1)
     rc, msg = _create(lg, D=np.zeros((2, 3, 1, 1)))
     assert rc == _capi.ERR_ARG and "D must be NULL" in msg, (rc, msg)
     rc, msg = _create(lg, flags=4 | 3)
@@ -281,8 +281,8 @@ def test_what_cannot_run_is_refused_before_a_device_is_looked_for(monkeypatch):
     assert L.llpf_imm_bank_run_at(None, None, None, 1, 0, 0.0, None, None) == _capi.ERR_ARG and "handle" in L.llpf_last_error().decode()
     # valid: linear-Gaussian with the flag, the quad-tank with and without it, a snippet with both members
     ok = _capi.OK if _capi.device_count() > 0 else _capi.ERR_NO_DEVICE
-    for spec, flags in ((lg, 3), (lg, 2), (xc.grouped(_quadtank_modes(6), rng, 2, 3), 1), (xc.grouped(_quadtank_modes(6), rng, 2, 3), 3),
-                        (xc.with_id(imms, pid), 1)):
+    for spec, flags in ((lg, 3), (lg, 2), (ic.grouped(_quadtank_modes(6), rng, 2, 3), 1), (ic.grouped(_quadtank_modes(6), rng, 2, 3), 3),
+                        (ic.with_id(imms, pid), 1)):
         rc, msg = _create(spec, flags=flags)
         assert rc == ok, (flags, rc, msg)
 

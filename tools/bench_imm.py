@@ -49,8 +49,7 @@ def measure(a):
         U = rng.standard_normal((T, a.nu))
         Y = rng.standard_normal((T, ny))
         bi = ic.bank(imms)
-        flat = [s for imm in imms for s in imm["systems"]]
-        bk = _capi.KalmanBankHandle(0, [m for m, _ in flat], np.stack([D for _, D in flat]))
+        bk = _capi.KalmanBankHandle(0, [m for imm in imms for m in imm["models"]], np.stack([D for imm in imms for D in imm["D"]]))
         ti, tk = [], []
         for r in range(a.reps + 1):
             for b, ts in ((bi, ti), (bk, tk)):
@@ -68,7 +67,7 @@ def measure(a):
 
 def measure_extended(a):
     from llpf_amd import _capi, _structs as S
-    import imm_ekf_common as xc
+    import imm_common as ic
     import models as Mo
     rng = np.random.default_rng(0)
     T, F = a.T, a.F
@@ -77,8 +76,8 @@ def measure_extended(a):
     for nx, ny, M in configs(a):
         modes = [S.make_quadtank_model(base.dynamics_density, base.measurement_density, base.initial_density, 1.0, 2,
                                        gamma1=0.2 + 0.001 * (k % 50) + 0.05 * (k % M), a1=0.03 + 0.0001 * (k % 7) + 0.003 * (k % M)) for k in range(F * M)]
-        imms = xc.grouped(modes, rng, F, M)
-        bi = xc.bank(imms)
+        imms = ic.grouped(modes, rng, F, M)
+        bi = ic.bank(imms)
         be = _capi.EkfBankHandle(0, modes)
         ti, te = [], []
         for r in range(a.reps + 1):
