@@ -195,6 +195,10 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
 static inline int launch_level(const RunForm& p, bool fast, bool weight) {
     return !fast ? RUN_STORES : !weight ? std::min<int>(p.level, RUN_SKIP_W) : p.level;
 }
+// The step of the systematic thresholds, 1 / M, as a level-3 launch gets it from the host (ResArgs::inv_M) instead of dividing in every
+// wave.  IEEE division is correctly rounded on the host and on the device, so this is the double the kernel's own 1.0 / (double)M is:
+// the same bits (tests/test_lean_inv_m.py holds it against the oracle's expression).
+static inline double lean_inv_M(int32_t M) { return 1.0 / (double)M; }
 
 // ---- the host-side state of a run's timesteps (the device may have to be re-driven from a step whose bound test failed) ----
 struct RunEntry { int cur, qcur, parity; uint32_t n_predict; int64_t t_index; int nslot; };      // Bank's state when the run began; nslot = ACC_NSLOT

@@ -50,7 +50,19 @@ static hipError_t launch_resprop_t(const BankDev& b, const ResArgs& a, const Ste
             case RUN_STORES: hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); break;
             case RUN_SKIP_W: if constexpr (skips) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_SKIP_W>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
             case RUN_SKIP_ANC: if constexpr (skips) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_SKIP_ANC>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
-            case RUN_LEAN: if constexpr (lean) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_LEAN>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
+            case RUN_LEAN:
+                if constexpr (lean) {
+                    ResArgs al = a;
+#if LLPF_LEAN_HEAD
+                    // what the level-3 head and scan hold as constants (kernels/resprop.hpp: LEAN, res_head / res_counts<..., LEAN>): the plan
+                    // and the run loop guarantee all of it (host/run_plan.hpp: lean; host/run.hpp: res_args, step_args), any other caller is refused
+                    if (a.Uexp || !a.u_from_scal || a.bins_out || a.only_bins || a.xmean || a.want_xmean || st.want_xmean || a.keep_norm || a.force ||
+                        !a.accumulate || b.strategy != LLPF_RESAMPLE_SYSTEMATIC || a.M < 1) return hipErrorInvalidValue;
+                    al.inv_M = lean_inv_M(a.M);      // (shares its eight bytes with Uexp, null here)
+#endif
+                    hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_LEAN>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, al), b, b.models, al, st);
+                } else return hipErrorInvalidValue;
+                break;
             default: return hipErrorInvalidValue;
         }
     }

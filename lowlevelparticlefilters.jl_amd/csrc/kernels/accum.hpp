@@ -83,7 +83,8 @@ struct WeightAcc {
         }
     }
     // block-wide totals into the sharded accumulators of `slot`; sm: [BLOCK/64][5] u64 of LDS
-    DEV void flush(uint64_t* acc, int slot, bool need_e2, uint64_t (*sm)[5]) {
+    // (`no_atomics`: LLPF_ABLATE bit 5 of a DEVTOOLS build — the reductions without the atomics, results invalid)
+    DEV void flush(uint64_t* acc, int slot, bool need_e2, uint64_t (*sm)[5], bool no_atomics = false) {
         llpf_u128 s = wave_sum_u128(S), e2 = {0, 0};
         if (need_e2) e2 = wave_sum_u128(E2);
         const uint64_t bd = (uint64_t)__builtin_popcountll(__ballot(bad != 0));     // only its being non-zero is ever used
@@ -91,7 +92,7 @@ struct WeightAcc {
         __syncthreads();
         if (lane == 0) { sm[wv][0] = s.lo; sm[wv][1] = s.hi; sm[wv][2] = e2.lo; sm[wv][3] = e2.hi; sm[wv][4] = bd; }
         __syncthreads();
-        if (threadIdx.x == 0) {
+        if (threadIdx.x == 0 && !no_atomics) {
             llpf_u128 ts = {sm[0][0], sm[0][1]}, te = {sm[0][2], sm[0][3]};
             uint64_t tb = sm[0][4];
             for (int k = 1; k < BLOCK / 64; ++k) {
@@ -109,8 +110,10 @@ struct WeightAcc {
 
 // The end of a weighting block in ONE barrier: the block's maximum / NaN flag and (accumulate) the exp-sums of its weights go to the
 // sharded accumulators of `slot`.  Same values as block_max + __syncthreads_or + acc_max + WeightAcc::flush (nine barriers): in the
-// kernels whose blocks all reach their tails together (k_step<..., MARKS>) those were 4.5 k cycles per block with nothing to hide under.
-DEV void block_flush(uint64_t* acc, int slot, double bmax, bool bad, const WeightAcc& wa, bool accumulate, bool need_e2, uint64_t (*sm)[8]) {
+// kernels whose blocks all reach their tails together (k_step<..., MARKS>, k_resprop<..., LEVEL >= 3>) those were 4.5 k cycles per block with
+// nothing to hide under.  A block without weights (bmax -Inf, no NaN, zero sums) contributes the maximum -Inf and no sum atomic, as there.
+// The caller may hang work of its own on the one barrier: what it wrote to LDS in front of the call is visible behind it.
+DEV void block_flush(uint64_t* acc, int slot, double bmax, bool bad, const WeightAcc& wa, bool accumulate, bool need_e2, uint64_t (*sm)[8], bool no_atomics = false) {
     const double wm = wave_max(bmax);
     const uint64_t nb = __ballot(bad) ? 1u : 0u;
     llpf_u128 s = {0, 0}, e2 = {0, 0};
@@ -123,7 +126,7 @@ DEV void block_flush(uint64_t* acc, int slot, double bmax, bool bad, const Weigh
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) { sm[wv][0] = llpf_d2u(wm); sm[wv][1] = nb; sm[wv][2] = s.lo; sm[wv][3] = s.hi; sm[wv][4] = e2.lo; sm[wv][5] = e2.hi; sm[wv][6] = bd; }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && !no_atomics) {
         double r = llpf_u2d(sm[0][0]);
         uint64_t anybad = sm[0][1], tb = sm[0][6];
         llpf_u128 ts = {sm[0][2], sm[0][3]}, te = {sm[0][4], sm[0][5]};

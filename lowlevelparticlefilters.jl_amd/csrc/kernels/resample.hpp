@@ -143,7 +143,10 @@ struct NoOverlap { DEV void operator()() const {} };
 // own scalar loads); it runs after the head's vector loads are issued and before the first of them is consumed
 // `NO_TOT0`: a fast head whose quanta sum to zero asks for the exact redo as well (k_resprop<..., SKIPW>: such a head would otherwise
 // not resample and read weights that the launch in front of it did not store)
-template <int SRC, bool COH = false, class Overlap = NoOverlap, bool NO_TOT0 = false>
+// `LEAN`: the head of a level-3 launch (k_resprop<..., LEVEL >= 3>) with what host/run_plan.hpp and host/run.hpp fix for it compiled in —
+// no weighted means, keep_norm = 0, force = 0, accumulate = 1; launch_resprop_t refuses such a launch with any other value.  What tile 0
+// publishes is what the general head publishes for these values.
+template <int SRC, bool COH = false, class Overlap = NoOverlap, bool NO_TOT0 = false, bool LEAN = false>
 DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResShared& sh,
                      bool defer_skip = false, uint32_t stop_flag = 0, int fb_flag = 0, Overlap&& overlap = NoOverlap()) {
     FilterScal* sc = b.scal + f;
@@ -245,7 +248,11 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
         const bool bad = sh.accw[7] != 0;
         if (h.fast) {
             h.a = off_pre;                                        // published by the weighting kernel that filled this slot
-            if (bad || s128.hi < ((uint64_t)1 << 22) || (NO_TOT0 && h.tot == 0)) {           // sum exp(w - bound) < 2^-10, or NaN weights
+            bool fails = bad || s128.hi < ((uint64_t)1 << 22) || (NO_TOT0 && h.tot == 0);      // sum exp(w - bound) < 2^-10, or NaN weights
+#ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 5: the tail in front of this head left the accumulator atomics out; the run goes on (results invalid) */
+            if (a.ablate & 32) fails = false;
+#endif
+            if (fails) {
                 h.status = RES_STATUS_FALLBACK;
                 h.stot = 0.0;
             } else {
@@ -285,13 +292,13 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
                 sc->wmax = (h.mtrue - h.a) - l;                   // normalised weight of the best particle
                 sc->K = a.K;
                 sc->uniform = 0;
-                sc->norm_pending = a.keep_norm ? 0 : 1;
-                if (a.keep_norm) sc->wmax = h.mtrue;              // set_weights: w stays as installed
+                sc->norm_pending = (!LEAN && a.keep_norm) ? 0 : 1;
+                if (!LEAN && a.keep_norm) sc->wmax = h.mtrue;     // set_weights: w stays as installed
                 if (h.status) sc->status = h.status;
-                sc->do_resample = (h.dr || a.force) ? 1 : 0;      // `force`: the auxiliary filter resamples whatever the ESS (filtering.jl:206, 225)
-                if (a.accumulate) sc->ll_total = sc->ll_total + ll;
+                sc->do_resample = (h.dr || (!LEAN && a.force)) ? 1 : 0;      // `force`: the auxiliary filter resamples whatever the ESS (filtering.jl:206, 225)
+                if (LEAN || a.accumulate) sc->ll_total = sc->ll_total + ll;
                 if (a.ll_steps) a.ll_steps[(size_t)a.row * b.F + f] = ll;
-                sh.dval[0] = inv;
+                if (!LEAN) sh.dval[0] = inv;                      // (read by the weighted-mean output below)
             }
         }
         if (!h.status) h.status = status_pre;          // sticky until reset! (written above only when non-zero)
@@ -315,7 +322,7 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
     }
 
     // weighted_mean output (fixed-order fp64 sum of the tile partials; tile 0 only)
-    if (fin && a.xmean && tile == 0 && !h.status) {
+    if (!LEAN && fin && a.xmean && tile == 0 && !h.status) {
         __syncthreads();
         const double invb = sh.dval[0];
         const double* xp = xmpart_slot(b, a.parity, f);
@@ -339,13 +346,17 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
 
 // Scan of this tile's quanta + ancestor counts.  On return sh.cl[k] = c(bins[k]) for the tile's TILE sources
 // (after a __syncthreads), and [c_start, c_end) is the range of outputs this tile produces.
-template <int STRATEGY>
+// `LEAN`: the scan of a level-3 launch (see res_head): systematic, U from u_slot, no explicit uniforms, no bins_out / only_bins, and the
+// thresholds' step 1 / M from the host (ResArgs::inv_M: the same bits as the division here, host/run_plan.hpp: lean_inv_M).  1 / Td and
+// U * binsN / N stay divisions: they define bins and r.
+template <int STRATEGY, bool LEAN = false>
 DEV void res_counts(const BankDev& b, const ResArgs& a, int f, int tile, const ResHead& h, const ulonglong2* qv,
                     ResShared& sh, int32_t& c_start, int32_t& c_end) {
     const FilterScal* sc = b.scal + f;
     const int64_t N = b.N;
     const int lane = threadIdx.x & 63, wvid = threadIdx.x >> 6;
     const int64_t ib = (int64_t)tile * TILE + (int64_t)threadIdx.x * NORM_IPT;
+    static_assert(!LEAN || STRATEGY == LLPF_RESAMPLE_SYSTEMATIC, "level 3 resamples systematically");
     uint64_t cq[NORM_IPT];
     {
         const uint64_t Qc = h.uniform ? llpf_q64_unit(1.0 / (double)N, a.K) : 0;
@@ -376,17 +387,20 @@ DEV void res_counts(const BankDev& b, const ResArgs& a, int f, int tile, const R
     uint32_t cnt[NORM_IPT];
     if (STRATEGY == LLPF_RESAMPLE_SYSTEMATIC) {
         ThrSys th;
-        const double U = h.has_u ? h.u_sys : (a.Uexp ? a.Uexp[0] : (a.u_from_scal ? sc->u_slot[a.parity] : llpf_uniform_step(sc->step_base + a.step, LLPF_STREAM_RESAMPLE, sc->k0, sc->k1)));
-        th.M = M; th.Md = (double)M; th.step = 1.0 / (double)M;
+        double U;
+        if constexpr (LEAN) U = sc->u_slot[a.parity];
+        else U = h.has_u ? h.u_sys : (a.Uexp ? a.Uexp[0] : (a.u_from_scal ? sc->u_slot[a.parity] : llpf_uniform_step(sc->step_base + a.step, LLPF_STREAM_RESAMPLE, sc->k0, sc->k1)));
+        th.M = M; th.Md = (double)M;
+        if constexpr (LEAN) th.step = a.inv_M; else th.step = 1.0 / (double)M;
         th.delta = 1e-9 + th.Md * 1e-13;
         th.r = U * binsN / (double)N;                  // r = rand()*bins[end]/N  (resample.jl:23)
 #pragma unroll
         for (int k = 0; k < NORM_IPT; ++k) {
             const double bin = (double)(excl + cq[k]) * invTd;
-            if (a.bins_out && ib + k < N) a.bins_out[(size_t)f * N + ib + k] = bin;
-            cnt[k] = a.only_bins ? 0u : (uint32_t)th.count(bin);
+            if (!LEAN && a.bins_out && ib + k < N) a.bins_out[(size_t)f * N + ib + k] = bin;
+            cnt[k] = (!LEAN && a.only_bins) ? 0u : (uint32_t)th.count(bin);
         }
-        c_start = a.only_bins ? 0 : th.count((double)h.prefix * invTd);
+        c_start = (!LEAN && a.only_bins) ? 0 : th.count((double)h.prefix * invTd);
     } else {
         ThrStrat th;
         th.M = M; th.Md = (double)M; th.step = sc->step_base + a.step; th.k0 = sc->k0; th.k1 = sc->k1; th.Uexp = a.Uexp;
@@ -395,10 +409,10 @@ DEV void res_counts(const BankDev& b, const ResArgs& a, int f, int tile, const R
 #pragma unroll
         for (int k = 0; k < NORM_IPT; ++k) {
             const double bin = (double)(excl + cq[k]) * invTd;
-            if (a.bins_out && ib + k < N) a.bins_out[(size_t)f * N + ib + k] = bin;
-            cnt[k] = a.only_bins ? 0u : (uint32_t)th.count(bin);
+            if (!LEAN && a.bins_out && ib + k < N) a.bins_out[(size_t)f * N + ib + k] = bin;
+            cnt[k] = (!LEAN && a.only_bins) ? 0u : (uint32_t)th.count(bin);
         }
-        c_start = a.only_bins ? 0 : th.count((double)h.prefix * invTd);
+        c_start = (!LEAN && a.only_bins) ? 0 : th.count((double)h.prefix * invTd);
     }
 #pragma unroll
     for (int k = 0; k < NORM_IPT; ++k) sh.cl[threadIdx.x * NORM_IPT + k] = cnt[k];

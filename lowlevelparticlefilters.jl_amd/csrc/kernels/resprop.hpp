@@ -30,6 +30,13 @@ template <class T> DEV void st_off(T* base, uint32_t byte_off, T v) {
 #ifndef LLPF_RESPROP_PF
 #define LLPF_RESPROP_PF 2      /* rounds of the split-schedule output loop whose sources are requested together (1.6e7 particles, plain stores: 1: 240.5, 2: 236, 4: 250 us) */
 #endif
+// the fixed part of a level-3 launch (k_resprop<..., LEVEL >= 3>; EXPERIMENTS: the fixed part around the loop), each step switchable for A/B builds
+#ifndef LLPF_LEAN_TAIL
+#define LLPF_LEAN_TAIL 1       /* the tail in one barrier: block_flush instead of block_max + __syncthreads_or + acc_max + WeightAcc::flush */
+#endif
+#ifndef LLPF_LEAN_HEAD
+#define LLPF_LEAN_HEAD 1       /* head and scan with the argument values of such a launch compiled in, 1 / M from the host (res_head / res_counts<..., LEAN>) */
+#endif
 #define LLPF_RB_PLAIN_ST (Model::RB && !(model_lean<Model>::value && LLPF_RBX_WT))
 // store policy of the output loop (Mem<>::st): 1 = write-through (sc1), 0 = plain, 2 = nontemporal
 #ifndef LLPF_RESPROP_ST
@@ -197,6 +204,9 @@ static_assert(TILE == 1024, "TileSum assumes 1024-particle tiles");
 // LEAN: the run also resamples systematically and wants no weighted means — only
 // res_counts<LLPF_RESAMPLE_SYSTEMATIC> is instantiated, and there is no xm[], no block_store_xm and no test of either.  The same
 // arithmetic, counters, stores and visiting order: the form only drops tests and arms that such a run never takes.
+// Its head and scan hold the argument values of such a launch as constants (res_head / res_counts<..., LEAN>; launch_resprop_t refuses a
+// level-3 launch with others), and its tail is block_flush's one barrier: all blocks of a 10^6-particle filter are resident together and
+// pass head, scan and tail in lockstep, so nothing hides a barrier or an argument test there.
 template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, int LEVEL = 0>
 // amdgpu_waves_per_eu(4): the ~3.8 blocks per CU of a 10^6-particle filter must be resident together (<= 128 VGPRs); the
 // larger state dimensions would spill under that cap and keep the compiler's choice; the Rao-Blackwellized propagate uses
@@ -216,6 +226,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     __shared__ double sm_max[BLOCK / 64];
     __shared__ uint64_t sm_acc[BLOCK / 64][5];
     __shared__ uint64_t sh_tq[8];
+    __shared__ uint64_t sm_fl[BLOCK / 64][8];      // block_flush (level 3; the levels below use sm_max and sm_acc)
     __shared__ double sm_x[BLOCK / 64][MAXD];
     constexpr bool RBFAT = Model::RB && !(model_lean<Model>::value && LLPF_RBX_TAB);      // run-time split: no registers to spare for the tables (occupancy 3 -> 2)
     constexpr bool OWN_TABLE = !RBFAT;
@@ -277,7 +288,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     // SKIPW means that host/run_plan.hpp saw resample_threshold == 1 (RunForm::level): every step of the run resamples, none needs E2
     constexpr bool ALWAYS_RES = SKIPW;
     static_assert(!ALWAYS_RES || (WEIGHT && ACC && !AUX), "a launch that always resamples: the merged schedule's weighting form, never forced");
-    const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
+    constexpr bool LEAN_HEAD = LEAN && LLPF_LEAN_HEAD, LEAN_TAIL = LEAN && LLPF_LEAN_TAIL;
+    const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW, LEAN_HEAD>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
     if (h.status) return;
     // Values of FilterScal fetched above with the head's loads but wanted only from here on.  FilterScal is written by this
     // kernel, so they are vector loads made uniform with v_readfirstlane — which the compiler otherwise places right behind the
@@ -337,7 +349,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
                 }
             }
         }
-        if (LEAN || b.strategy == LLPF_RESAMPLE_SYSTEMATIC) res_counts<LLPF_RESAMPLE_SYSTEMATIC>(b, a, f, tile, h, qv, sh, c_start, c_end);
+        if constexpr (LEAN_HEAD) res_counts<LLPF_RESAMPLE_SYSTEMATIC, true>(b, a, f, tile, h, qv, sh, c_start, c_end);
+        else if (LEAN || b.strategy == LLPF_RESAMPLE_SYSTEMATIC) res_counts<LLPF_RESAMPLE_SYSTEMATIC>(b, a, f, tile, h, qv, sh, c_start, c_end);
         else if constexpr (!LEAN) res_counts<LLPF_RESAMPLE_STRATIFIED>(b, a, f, tile, h, qv, sh, c_start, c_end);
         first = c_start;
         last = (tile == b.P2 - 1) ? (int64_t)a.M : (int64_t)c_end;
@@ -541,10 +554,33 @@ _Pragma("unroll") \
     if (WEIGHT && ACC) ts.flush(sh_tq, tq_next, tbase);
     __builtin_amdgcn_s_setprio(3);
     LLPF_STAMP(3);
+#ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 5: the tail without its accumulator atomics (acc_max, acc_add_u128): what they cost at most; results invalid */
+#define LLPF_NO_TAIL_ATOMICS ((a.ablate & 32) != 0)
+#else
+#define LLPF_NO_TAIL_ATOMICS false
+#endif
+    if constexpr (LEAN_TAIL) {
+        // The tail in ONE barrier (block_flush, as in k_step<..., MARKS>): every wave reduces its maximum, NaN flag and exp-sums and leaves
+        // one LDS row; the threads' tile sums went to sh_tq in front of it (ts.flush above); behind the barrier thread 0 combines the rows and
+        // issues the accumulator atomics while threads 0..7 add sh_tq to the global tile sums.  A block that owns no outputs (first == last:
+        // a tile behind a very heavy one) contributes the maximum -Inf, no NaN flag and no sum, as in the levels below.
+        block_flush(b.acc + (size_t)f * ACC_WORDS, st.parity, bmax, bad, wacc, true, false, sm_fl, LLPF_NO_TAIL_ATOMICS);
+        if (threadIdx.x < 8 && sh_tq[threadIdx.x])
+            atomicAdd(reinterpret_cast<unsigned long long*>(tq_next + tbase + threadIdx.x), (unsigned long long)sh_tq[threadIdx.x]);
+        if (tile == 0 && threadIdx.x == 0) {
+            sc->xm_parts = b.P2;
+            sc->off_slot[st.parity] = pc.off;
+            sc->exact_slot[st.parity] = 0;
+            sc->e2v_slot[st.parity] = st.need_e2;
+            sc->u_slot[st.parity] = llpf_uniform_step(sb + st.next_step, LLPF_STREAM_RESAMPLE, sc->k0, sc->k1);
+        }
+        // No closing barrier: nothing behind this point reads what another thread of the block wrote — the bookkeeping below is one thread's
+        // read-modify-write of fields that no other thread of the launch touches, and LDS is not read again.
+    } else {      // every other form: the tail as it was (its lines left where they stood)
     if (WEIGHT) {
         const double r = block_max(bmax, sm_max);
         const int anybad = __syncthreads_or(bad ? 1 : 0);
-        if (threadIdx.x == 0) acc_max(b.acc + (size_t)f * ACC_WORDS, st.parity, r, anybad != 0);
+        if (threadIdx.x == 0 && !LLPF_NO_TAIL_ATOMICS) acc_max(b.acc + (size_t)f * ACC_WORDS, st.parity, r, anybad != 0);
         int exact = 0;
         if constexpr (ACC && ONE) {
             // This block is the whole filter (one tile): make the bound test of the coming head here and, if it fails,
@@ -581,7 +617,7 @@ _Pragma("unroll") \
             }
         }
         if (ACC) {
-            wacc.flush(b.acc + (size_t)f * ACC_WORDS, st.parity, LLPF_NEED_E2, sm_acc);
+            wacc.flush(b.acc + (size_t)f * ACC_WORDS, st.parity, LLPF_NEED_E2, sm_acc, LLPF_NO_TAIL_ATOMICS);
             __syncthreads();
             if (threadIdx.x < 8 && sh_tq[threadIdx.x])
                 atomicAdd(reinterpret_cast<unsigned long long*>(tq_next + tbase + threadIdx.x), (unsigned long long)sh_tq[threadIdx.x]);
@@ -601,8 +637,10 @@ _Pragma("unroll") \
         }
     }
     __syncthreads();
+    }
     LLPF_STAMP(4);
 #undef LLPF_STAMP
+#undef LLPF_NO_TAIL_ATOMICS
 #undef LLPF_NEED_E2
 #undef LLPF_WANT_XM
     if (tile == b.P2 - 1 && threadIdx.x == 0) {        // bookkeeping of this predict! (by the only block that reads anc_ident)
