@@ -16,6 +16,13 @@ numpy exp / log, Python loops over particles.  It follows the reference line by 
                                            reset_weights! src/utils.jl:73-79
                        forward_trajectory  src/filtering.jl:343-365;  loglik src/smoothing.jl:227-230
                        Gaussian logpdf     src/utils.jl:252-257;  rk4 src/utils.jl:220-237;  quad-tank examples/example_quadtank.jl:8-35
+  residual resampling  resample(ResampleResidual, ...) src/resample.jl:63-117 (resample_residual): stand-alone, as a ParticleFilter's
+                       strategy, and under the auxiliary filter; with the margins of its floor / u < bin decisions in numpy.longdouble
+                       and how far an fp64 or fixed-point implementation may be from them (residual_slack)
+  auxiliary filter     AuxiliaryParticleFilter src/PFtypes.jl:38-49: correct! src/filtering.jl:170-174, predict! :195-217 (lambda from the
+                       next measurement, expnormalize! src/utils.jl:57-63, w = lambda[i] - log N), over an AdvancedParticleFilter
+                       :219-234 (lambda only chooses the ancestors; propagated again from xprev[j]), forward_trajectory :367-384,
+                       loglik src/smoothing.jl:232-236
   RBPF, !singleR       reset! src/rbpf.jl:146-160, predict! :163-232, correct! :235-283 with
                        correct!(kf, ...) src/filtering.jl:100-128
   FFBS smoother        one backward step of smooth, src/smoothing.jl:128-141, draw_one_categorical src/resample.jl:128-152: the
@@ -218,44 +225,146 @@ def resample_stratified(we, jprev, Us, M=None):
     return j.astype(np.int64), bins
 
 
+def resample_residual(we, jprev, U, M=None):
+    """src/resample.jl:63-117: we is normalised by its sum (:66-69); nw_i = we_i M; particle i is written floor(nw_i) times, in particle
+    order, into j[0..num-1] (:75-84); num == M returns (:86-88); otherwise the residuals nw_i - floor(nw_i) are normalised by their sum
+    (:90-98) and summed cumulatively (:100-103), and output m = num..M-1 takes the first i with U[m] < bins[i] (:105-114) — the reference
+    draws one rand() per remaining output in order, and U is indexed by OUTPUT, so U[0..num-1] are never read; an output whose uniform
+    is below no bin keeps jprev[m].
+    Returns (j, info).  Both kinds of decision are comparisons of real numbers with an edge, and an implementation in other arithmetic
+    may decide a call within rounding of its edge the other way; info says how close the calls of this resampling were, in
+    numpy.longdouble from the fp64 weights:
+      int_margin    min over the particles with nw_i >= 1/2 of |nw_i - round(nw_i)| (inf if there is none).  An nw_i below 1/2 has 0 as
+                    its nearest integer and floors to 0 whichever way it is rounded: no call.
+      edge_margin   min over the uniforms that are read of the distance to the nearest bin edge bins[0..N-1]; the last one, 1, is counted
+                    too, since a uniform at or above a computed bins[N-1] = 1 - ulp keeps jprev (inf if no uniform is read).
+      num, nw_max, R = M - num: what residual_slack scales with.
+    A single particle is no call either: nw_0 = we_0 / we_0 M = M in any arithmetic (x / x = 1 exactly; q M / q for the quanta)."""
+    we = np.asarray(we, dtype=np.float64)
+    N = we.size
+    M = N if M is None else M
+    nw = we / np.sum(we) * M
+    cnt = np.floor(nw).astype(np.int64)
+    j = np.array(jprev[:M], dtype=np.int64)
+    copies = np.repeat(np.arange(N), cnt)[:M]
+    num = copies.size
+    j[:num] = copies
+    nwl = np.asarray(we, dtype=LD) / np.sum(np.asarray(we, dtype=LD)) * M
+    big = nwl >= 0.5
+    info = dict(num=num, R=M - num, nw_max=float(np.max(nw)), edge_margin=np.inf,
+                int_margin=float(np.min(np.abs(nwl[big] - np.rint(nwl[big])))) if N > 1 and np.any(big) else np.inf)
+    if num == M:
+        return j, info
+    res = nw - cnt
+    bins = np.cumsum(res / np.sum(res))
+    u = np.asarray(U, dtype=np.float64)[num:M]
+    i = np.searchsorted(bins, u, side="right")
+    met = i < N
+    j[num:M][met] = i[met]
+    resl = nwl - cnt
+    binsl = np.cumsum(resl) / np.sum(resl)
+    k = np.clip(np.searchsorted(binsl, u.astype(LD), side="left"), 1, N - 1) if N > 1 else np.zeros(u.size, dtype=np.int64)
+    info["edge_margin"] = float(np.min(np.minimum(np.abs(binsl[k] - u), np.abs(binsl[k - 1] - u))))
+    return j, info
+
+
+def residual_slack(N, M, total, nw_max, R):
+    """(slack_int, slack_edge): how far the numbers an fp64 or a fixed-point implementation of resample_residual decides on can lie from
+    the long-double nw_i and bins_i that resample_residual's margins are measured with.  Derived, not fitted:
+
+      quanta.  The engine replaces e_i (the exp-weights before normalisation, 0 <= e_i <= 1, sum E = `total`) by q_i = floor(e_i 2^K),
+      K = qbits(N): q_i = e_i 2^K - d_i, 0 <= d_i < 1, Q = sum q_i = E 2^K - D, 0 <= D < N.  Its nw'_i = M q_i / Q is exact in integers, and
+          nw'_i - nw_i = (nw_i D - M d_i) / Q   lies in (-M / Q, N nw_i / Q):   |dnw_i| <= max(M, N nw_max) / Q,  Q > E 2^K - N.
+      The cumulative sums C_i of the residuals (equal copy counts: that is what int_margin > slack_int secures) then move by less than
+      N M / Q (sum_i nw_i = M), and the engine keeps only K bits of each residual (rem >> ceil(log2 N), less than 2 N / Q each in units
+      of nw): |dC_i| <= (N M + 2 N^2) / Q =: c for every partial sum and for their total, which is R = M - num exactly (sum nw_i = M,
+      sum floor(nw_i) = num): bins_i = C_i / R <= 1 moves by at most (c + c bins_i) / (R - c) <= 2 c / (R - c).
+      `total`: the engine normalises against an analytic bound of the log-weights and accepts any E >= 2^-10 (below that it repeats the
+      step with the exact maximum, E >= 1); stand-alone calls are handed normalised weights, E = 1.
+      fp64 (the reference order).  we_i / sum * M: the serial sum of N terms carries (N - 1) roundings, the division and the product
+      one each: |dnw_i| <= (N + 2) 2^-53 nw_i.  The residuals inherit that absolutely, sum (N + 2) 2^-53 M over all particles, relative to
+      their total R; the normalisation, the serial cumulative sum (N roundings on numbers <= 1) and the reciprocal add 2 N + 8 roundings.
+    Terms of second order are dropped."""
+    Q = total * 2.0 ** qbits(N) - N
+    c = (N * M + 2.0 * N * N) / Q
+    slack_int = max(M, N * nw_max) / Q + (N + 2) * U53 * nw_max
+    slack_edge = (2 * c / (R - c) + (2 * (N + 2) * M / R + 2 * N + 8) * U53) if R > 0 else 0.0
+    return slack_int, slack_edge
+
+
+def _peak(d):
+    """the largest value a measurement density takes (all densities here are unimodal about their mean, or about 0)"""
+    return float(d.logpdf(d.mu if hasattr(d, "mu") else np.zeros((1, 1)))[0])
+
+
+def engine_total(s1, m, off):
+    """the sum E of the exp-weights the engine cuts into quanta (residual_slack's `total`) when the restatement's own normalisation found
+    s1 = sum exp(w - m), m = max w: the engine subtracts the bound `off` >= m in place of m unless that leaves E < 2^-10, and then uses m.
+    The bound's own rounding is covered by taking the smaller of the two near the switch."""
+    Eb = s1 * math.exp(m - off) * (1.0 - 1e-9)
+    return Eb if Eb >= 2.0 ** -10 * (1.0 - 1e-8) else s1
+
+
 # ---- the particle filter ----------------------------------------------------------------------------------------------------
 class ParticleFilter:
-    def __init__(self, N, model, df, dg, d0, resample_threshold=0.1, stratified=False, Ts=1.0):
+    def __init__(self, N, model, df, dg, d0, resample_threshold=0.1, stratified=False, Ts=1.0, residual=False):
         self.N, self.model, self.df, self.dg, self.d0 = N, model, df, dg, d0
-        self.thr, self.stratified, self.Ts = resample_threshold, stratified, Ts
+        self.thr, self.stratified, self.residual, self.Ts = resample_threshold, stratified, residual, Ts
         self.j = np.arange(N)
+        self.calls = []                     # residual resampling: info of every call, with the slack that goes with it
 
     def reset(self, xi, uu=None):
         self.x = self.d0.sample_u(xi, uu) if hasattr(self.d0, "sample_u") else self.d0.sample(xi)      # x_i ~ d0
         self.w = np.full(self.N, -math.log(self.N))
         self.we = np.full(self.N, 1.0 / self.N)
+        self.wbound = -math.log(self.N)     # what the engine knows the log-weights to lie below (engine_total)
         self.t = 1
 
     def correct(self, u, y, t):
-        if y is not None and not np.any(np.isnan(y)):            # any(ismissing, y) && return, src/PFtypes.jl:109
+        has_y = y is not None and not np.any(np.isnan(y))        # any(ismissing, y) && return, src/PFtypes.jl:109
+        if has_y:
             self.w = self.w + self.dg.logpdf(np.asarray(y, dtype=np.float64) - self.model.g(self.x, u, t))
+        m = float(np.max(self.w))
         self.w, self.we, ll = logsumexp_inplace(self.w)
+        if self.residual:
+            self.total = engine_total(math.exp(ll - m), m, self.wbound + (_peak(self.dg) if has_y else 0.0))
+            self.wbound = float(np.max(self.w))
         return ll
+
+    def resample(self, we, U):
+        """j = resample(strategy, we, j, bins), src/resample.jl:12"""
+        if self.residual:
+            self.j, info = resample_residual(we, self.j, U)
+            s = residual_slack(self.N, self.N, self.total, info["nw_max"], info["R"])
+            self.calls.append(dict(info, slack_int=s[0], slack_edge=s[1], total=self.total))
+        elif self.stratified:
+            self.j, self.bins = resample_stratified(we, self.j, U)
+        else:
+            self.j, self.bins = resample_systematic(we, self.j, float(U[0]))
+
+    def propagate(self, xprev, u, t, xi, uu):
+        if hasattr(self.df, "propagate"):                        # the model adds its own noise (PFtypes.jl:254 / any dynamics_density, :135)
+            return self.df.propagate(xprev, self.model.f(xprev, u, t), xi, uu)
+        return self.model.f(xprev, u, t) + self.df.sample(xi)
+
+    def reset_weights(self):
+        """src/utils.jl:73-79"""
+        self.w = np.full(self.N, math.log(1.0 / self.N))
+        self.we = np.full(self.N, 1.0 / self.N)
+        self.wbound = math.log(1.0 / self.N)
 
     def predict(self, u, t, xi, U, uu=None):
         N = self.N
         ess = 1.0 / float(np.sum(self.we * self.we))
         self.resampled = self.thr == 1.0 or ess < N * self.thr
         if self.resampled:
-            if self.stratified:
-                self.j, self.bins = resample_stratified(self.we, self.j, U)
-            else:
-                self.j, self.bins = resample_systematic(self.we, self.j, float(U[0]))
+            self.resample(self.we, U)
             xprev = self.x[self.j]
-            self.w = np.full(N, math.log(1.0 / N))
-            self.we = np.full(N, 1.0 / N)
+            self.reset_weights()
         else:
             self.j = np.arange(N)
             xprev = self.x
-        if hasattr(self.df, "propagate"):                        # the model adds its own noise (PFtypes.jl:254 / any dynamics_density, :135)
-            self.x = self.df.propagate(xprev, self.model.f(xprev, u, t), xi, uu)
-        else:
-            self.x = self.model.f(xprev, u, t) + self.df.sample(xi)
+        self.x = self.propagate(xprev, u, t, xi, uu)
         self.t += 1
 
     def run(self, U, Y, t_index0, normals, uniforms, step0=0, user_uniforms=None):
@@ -271,6 +380,96 @@ class ParticleFilter:
             uu = user_uniforms(step0 + k, self.N, self.x.shape[1]) if user_uniforms is not None else None
             self.predict(u, t, normals(step0 + k, self.N, self.x.shape[1]), uniforms(step0 + k, self.N), uu)
             nres += int(self.resampled)
+        return ll_steps, nres
+
+
+# ---- the auxiliary particle filter ------------------------------------------------------------------------------------------
+def expnormalize(w):
+    """expnormalize!(w), src/utils.jl:57-63: exp(w - maximum) scaled by 1 / (1 + sum of all but the maximum's exp(0) = 1)"""
+    imax = int(np.argmax(w))
+    we = np.exp(w - w[imax])
+    we_wo = we.copy()
+    we_wo[imax] -= 1.0
+    s = float(np.sum(we_wo))
+    return we * (1.0 / (s + 1.0)), s + 1.0
+
+
+class AuxiliaryParticleFilter:
+    """AuxiliaryParticleFilter(pf), src/PFtypes.jl:38-49, over a ParticleFilter above; `advanced`: that filter's noise is the model's own
+    (the AdvancedParticleFilter contract), which selects predict! of src/filtering.jl:219-234 in place of :195-217"""
+
+    def __init__(self, pf, advanced=False):
+        self.pf, self.advanced = pf, advanced
+
+    def reset(self, xi, uu=None):
+        self.pf.reset(xi, uu)
+
+    def correct(self, u, y, t):
+        """src/filtering.jl:170-174: the measurement was weighed in by the predict! before, what is left is ll = logsumexp!(w, we) —
+        so u, y and t are not used, and the y of the very first call never is"""
+        pf = self.pf
+        pf.w, pf.we, ll = logsumexp_inplace(pf.w)
+        pf.wbound = float(np.max(pf.w))
+        return ll
+
+    def new_weights(self, lam, j):
+        """src/filtering.jl:209-213: "note unresampled lambda[i] instead of lambda[j[i]]" """
+        return lam - math.log(self.pf.N)
+
+    def source(self, xprev, xpred):
+        """what the advanced variant propagates again, src/filtering.jl:228: propagate_particles!(pf.pf, u, j, p, t) reads xprev[j]"""
+        return xprev
+
+    def predict(self, u, y1, t, xi, U, uu=None):
+        """src/filtering.jl:195-217 (over an AdvancedParticleFilter :219-234); y1: the NEXT measurement"""
+        pf = self.pf
+        xprev = pf.x
+        xpred = pf.model.f(xprev, u, t)                          # propagate_particles!(pf.pf, u, p, t, nothing): no noise, PFtypes.jl:261-274
+        has_y = y1 is not None and not np.any(np.isnan(y1))
+        lam = np.zeros(pf.N)                                     # lambda .= 0; measurement_equation!(pf.pf, u, y1, p, t, lambda), :201-203
+        if has_y:
+            lam = lam + pf.dg.logpdf(np.asarray(y1, dtype=np.float64) - pf.model.g(xpred, u, t))
+        w = pf.w + lam                                           # s.w .+= lambda, :204
+        we, s1 = expnormalize(w)                                 # :205
+        if pf.residual:
+            m = float(np.max(w))
+            pf.total = engine_total(s1, m, pf.wbound + (_peak(pf.dg) if has_y else 0.0))
+        pf.resample(we, U)                                       # :206, with whatever strategy the wrapped filter has
+        pf.resampled = True
+        if self.advanced:                                        # lambda has chosen the ancestors and is dropped
+            pf.reset_weights()                                   # :226
+            pf.x = pf.propagate(self.source(xprev, xpred)[pf.j], u, t, xi, uu)      # :228, with noise and permutation
+        else:
+            pf.x = xpred[pf.j] + pf.df.sample(xi)                # permute_with_buffer!, src/utils.jl:81-86; add_noise!, src/PFtypes.jl:143-155
+            pf.w = self.new_weights(lam, pf.j)
+            pf.we = lam                                          # the reference's `we` is the buffer lambda lives in
+            if pf.residual:                                      # lambda <= the density's peak: what the engine bounds these weights by
+                pf.wbound = (_peak(pf.dg) if has_y else 0.0) - math.log(pf.N)
+        pf.t += 1
+
+    def run(self, U, Y, mode, normals, uniforms, t_index0=0.0, step0=0, user_uniforms=None):
+        """mode 0: forward_trajectory(pf::AuxiliaryParticleFilter, u, y), src/filtering.jl:367-384: correct! at every step, predict! with
+        y[k + 1] between them.  mode 1: loglik, src/smoothing.jl:232-236: T - 1 updates pf(u[k], y[k], y[k + 1]), then the WRAPPED filter's
+        update! (correct! and predict!) on the last pair.  Every predict! takes one draw number, step0 + k."""
+        pf = self.pf
+        T = len(Y)
+        ll_steps = np.zeros(T)
+        nres = 0
+        for k in range(T):
+            t = (t_index0 + k) * pf.Ts
+            u = U[k] if U is not None and len(U) else None
+            nd = pf.x.shape[1]
+            last = mode == 1 and k == T - 1
+            ll_steps[k] = pf.correct(u, Y[k], t) if last else self.correct(u, Y[k], t)
+            if not last and k == T - 1:
+                break
+            uu = user_uniforms(step0 + k, pf.N, nd) if user_uniforms is not None else None
+            xi, Us = normals(step0 + k, pf.N, nd), uniforms(step0 + k, pf.N)
+            if last:
+                pf.predict(u, t, xi, Us, uu)
+            else:
+                self.predict(u, Y[k + 1], t, xi, Us, uu)
+            nres += int(pf.resampled)
         return ll_steps, nres
 
 

@@ -18,16 +18,28 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 import independent_cases as IC
 import oracle_binding as ob
 
-for name, case in IC.cases().items():
+only = sys.argv[1:]                 # case names; none: every case
+for name, case in {**IC.cases(), **IC.aux_cases()}.items():
+    if only and name not in only:
+        continue
     r = IC.run_independent(ob, case)
     np.savez_compressed(os.path.join(HERE, "indep_%s.npz" % name), U=case["U"], Y=case["Y"], **r)
-    line = "%-22s resamples %2d" % (name, int(r["resamples"]))
+    line = "%-26s resamples %2d" % (name, int(r["resamples"]))
     for tag, order in (("reference order", ob.ORDER_REFERENCE), ("device order", ob.ORDER_DEVICE)):
         o = IC.oracle_of(ob, case, order)
         o.reset()
-        ro = o.run(case["U"], case["Y"], case["t0"], ll_steps=True)
-        line += " | %s: max|dll| %.1e max|dx| %.1e anc %s" % (tag, np.max(np.abs(ro["ll_steps"] - r["ll_steps"])),
+        ll, _ = IC.run_handle(o, case)
+        line += " | %s: max|dll| %.1e max|dx| %.1e anc %s" % (tag, np.max(np.abs(ll - r["ll_steps"])),
                                                             np.max(np.abs(o.particles() - r["x_final"])), np.array_equal(o.ancestors(), r["anc_final"]))
         if case.get("rb"):
             line += " max|dR| %.1e" % np.max(np.abs(o.rb_linear_state()[1] - r["R_final"]))
+        if "w_final" in r:
+            line += " max|dw| %.1e" % np.max(np.abs(o.weights() - r["w_final"]))
+    c = r.get("residual_calls")
+    if c is not None and len(c):    # the two closest calls of the run's residual resamplings, each next to its slack
+        ki, ke = int(np.argmin(c[:, 0])), int(np.argmin(c[:, 2]))
+        with np.errstate(invalid="ignore"):
+            ratio = min(np.nanmin(c[:, 0] / c[:, 1]), np.nanmin(c[:, 2] / c[:, 3]))
+        line += " | residual: %d calls, integer margin %.1e (slack %.1e), edge margin %.1e (slack %.1e), margin / slack >= %.1e" % (
+            len(c), c[ki, 0], c[ki, 1], c[ke, 2], c[ke, 3], ratio)
     print(line)

@@ -37,17 +37,89 @@ def _qt_object(m):
                         a1factor=q[14], eps=q[15], Ts=m.Ts, supersample=m.supersample)
 
 
+def _lg_data(lg, T=60):
+    """U, Y and Y with a missing measurement"""
+    _, U, Yfull = M.simulate_lg(lg, T, seed=3)
+    Y = Yfull.copy()
+    Y[17] = np.nan
+    return U, Yfull, Y
+
+
+def _lg_filter(lg, N, thr, strat):
+    return ind.ParticleFilter(N, _lg_objects(lg), _gauss(lg.dynamics_density), _gauss(lg.measurement_density), _gauss(lg.initial_density),
+                              thr, strat == S.RESAMPLE_STRATIFIED, lg.Ts, residual=strat == S.RESAMPLE_RESIDUAL)
+
+
+STRATEGIES = {"systematic": S.RESAMPLE_SYSTEMATIC, "stratified": S.RESAMPLE_STRATIFIED, "residual": S.RESAMPLE_RESIDUAL}
+MODES = {"forward": 0, "loglik": 1}
+
+
+def aux_cases():
+    """The AuxiliaryParticleFilter cases (frozen as the others): name -> the dict of cases() with `aux` = the loop (0 forward_trajectory,
+    1 loglik) and `wrap` (the plain filter -> the auxiliary one; the tests wrap it in misread variants).  Every case has a missing
+    look-ahead measurement and an outlier that sends the engine's normalisations to their exact-maximum form."""
+    out = {}
+    lg = M.lg_test_model()
+    U, _, Y = _lg_data(lg)                              # Y[17] is missing: the look-ahead of step 16
+    Y = Y.copy()
+    Y[31] += 11.0
+    qt = M.quadtank_model()
+    Uq, Yq = M.quadtank_data(40, seed=2)
+    Yq = Yq.copy()
+    Yq[9] = np.nan
+    Yq[22] += 11.0
+    for mname, mode in MODES.items():
+        for sname, strat in STRATEGIES.items():
+            out["aux_lg_%s_%s" % (sname, mname)] = dict(
+                model=lg, kind=S.PARTICLE_FILTER, N=400, T=60, thr=0.1, strategy=strat, t0=0.0, U=U, Y=Y, aux=mode,
+                make=lambda strat=strat: _lg_filter(lg, 400, 0.1, strat), wrap=ind.AuxiliaryParticleFilter)
+        # over an AdvancedParticleFilter, from t = 485: the run crosses the quadruple tank's switch time (500)
+        out["aux_quadtank_%s" % mname] = dict(
+            model=qt, kind=S.ADVANCED_PARTICLE_FILTER, N=300, T=40, thr=0.5, strategy=S.RESAMPLE_SYSTEMATIC, t0=485.0, U=Uq, Y=Yq, aux=mode,
+            make=lambda: ind.ParticleFilter(300, _qt_object(qt), _gauss(qt.dynamics_density), _gauss(qt.measurement_density),
+                                            _gauss(qt.initial_density), 0.5, False, qt.Ts),
+            wrap=lambda pf: ind.AuxiliaryParticleFilter(pf, advanced=True), advanced=True)
+    return out
+
+
+SIZES = (1, 2, 63, 64, 65, 1024, 1025, 2049)          # a tile of the kernels is 1024 particles: 1025 and 2049 leave one particle in the last
+SIZE_STEPS = 6
+
+
+def size_case(N, strategy, aux):
+    """a short run at N particles, computed live: the residual filter at threshold 1.0 (aux None), or the auxiliary filter in loop `aux`"""
+    lg = M.lg_test_model()
+    _, U, Y = M.simulate_lg(lg, SIZE_STEPS + 1, seed=3)
+    T = SIZE_STEPS if aux != 0 else SIZE_STEPS + 1      # forward_trajectory predicts T - 1 times
+    case = dict(model=lg, kind=S.PARTICLE_FILTER, N=N, T=T, thr=1.0, strategy=strategy, t0=0.0, U=U[:T], Y=Y[:T],
+                make=lambda: _lg_filter(lg, N, 1.0, strategy))
+    if aux is not None:
+        case.update(aux=aux, wrap=ind.AuxiliaryParticleFilter)
+    return case
+
+
+STANDALONE = ((10, 10), (9, 9), (1025, 1025), (4097, 300), (300, 4097))
+
+
+def standalone_residual(n, m):
+    """weights, uniforms and previous ancestors of one stand-alone residual resampling of n particles into m outputs"""
+    rng = np.random.default_rng(n + m)
+    we = rng.exponential(size=n) ** 3
+    we /= we.sum()
+    return we, rng.uniform(size=m), np.full(m, 5, dtype=np.int64)
+
+
 def cases():
     """name -> dict(model (llpf_model), kind, N, T, thr, strategy, t0, U, Y, make (-> independent filter))"""
     out = {}
     lg = M.lg_test_model()
-    _, U, Y = M.simulate_lg(lg, 60, seed=3)
-    Y = Y.copy()
-    Y[17] = np.nan                                      # a missing measurement
-    for name, thr, strat in (("pf_lg_systematic", 0.5, S.RESAMPLE_SYSTEMATIC), ("pf_lg_stratified", 1.0, S.RESAMPLE_STRATIFIED)):
-        out[name] = dict(model=lg, kind=S.PARTICLE_FILTER, N=400, T=60, thr=thr, strategy=strat, t0=0.0, U=U, Y=Y,
-                         make=lambda thr=thr, strat=strat: ind.ParticleFilter(400, _lg_objects(lg), _gauss(lg.dynamics_density), _gauss(lg.measurement_density),
-                                                                              _gauss(lg.initial_density), thr, strat == S.RESAMPLE_STRATIFIED, lg.Ts))
+    U, Yfull, Y = _lg_data(lg)
+    # residual resampling at threshold 1.0 without the missing row: there the weights are uniform, every nw_i is 1 +- 1 ulp and floor()
+    # is decided by rounding alone (tests/test_gpu_residual.py keeps the exact test of that corner)
+    for name, thr, strat, Yc in (("pf_lg_systematic", 0.5, S.RESAMPLE_SYSTEMATIC, Y), ("pf_lg_stratified", 1.0, S.RESAMPLE_STRATIFIED, Y),
+                                 ("pf_lg_residual", 0.5, S.RESAMPLE_RESIDUAL, Y), ("pf_lg_residual_thr1", 1.0, S.RESAMPLE_RESIDUAL, Yfull)):
+        out[name] = dict(model=lg, kind=S.PARTICLE_FILTER, N=400, T=60, thr=thr, strategy=strat, t0=0.0, U=U, Y=Yc,
+                         make=lambda thr=thr, strat=strat: _lg_filter(lg, 400, thr, strat))
     # measurement likelihoods of the user's own (run-time compiled on the engine side, tests/user_models.py): Laplace and Student-t
     # noise on the same linear system; `user` = (oracle kind, oracle parameters, device snippet, qt parameter block of the snippet)
     import user_models as UM
@@ -104,10 +176,27 @@ def draws(ob, case):
     return ob.normals(SEED, 1, STREAM_INIT, nd, case["N"]), normals, uniforms
 
 
-def run_independent(ob, case):
+def _residual_calls(pf):
+    """the margins of every residual resampling of a run next to their slacks, [calls, 4]: int_margin, slack_int, edge_margin, slack_edge"""
+    return np.array([[c["int_margin"], c["slack_int"], c["edge_margin"], c["slack_edge"]] for c in pf.calls]).reshape(-1, 4)
+
+
+def run_independent(ob, case, wrap=None):
+    """wrap: used in place of the case's own for an auxiliary case (a misread variant of the restatement)"""
     f = case["make"]()
     xi0, normals, uniforms = draws(ob, case)
     nd = case["model"].nx
+    if case.get("aux") is not None:
+        a = (wrap or case["wrap"])(f)
+        a.reset(xi0)
+        ll_steps, nres = a.run(case["U"], case["Y"], case["aux"], normals, uniforms, t_index0=case["t0"])
+        return dict(ll_steps=ll_steps, resamples=np.int64(nres), anc_final=np.asarray(f.j, dtype=np.int64), x_final=f.x, w_final=f.w,
+                    residual_calls=_residual_calls(f))
+    if case["strategy"] == S.RESAMPLE_RESIDUAL:
+        f.reset(xi0)
+        ll_steps, nres = f.run(case["U"], case["Y"], case["t0"], normals, uniforms)
+        return dict(ll_steps=ll_steps, resamples=np.int64(nres), anc_final=np.asarray(f.j, dtype=np.int64), x_final=f.x, w_final=f.w,
+                    residual_calls=_residual_calls(f))
     if case.get("initial"):
         f.reset(xi0, ob.uniforms_nd(SEED, 1, STREAM_USER_INIT, nd, case["N"]))
     else:
@@ -123,6 +212,30 @@ def run_independent(ob, case):
     else:
         res.update(x_final=f.x)
     return res
+
+
+def run_handle(h, case):
+    """(the per-step log-likelihoods, the number of predict! calls that resampled) of a case on the C oracle or the engine (one set of
+    verbs), after reset.  The run loops of the auxiliary filter count time from 0; a case that starts elsewhere is driven step by step, as
+    AuxiliaryParticleFilter.run is, and its resamplings are counted step by step too (the engine's counter is that of its last run)."""
+    U, Y, T, Ts = case["U"], case["Y"], case["T"], case["model"].Ts
+    if case.get("aux") is None:
+        return h.run(U, Y, case["t0"], ll_steps=True)["ll_steps"], h.resample_count()
+    if case["t0"] == 0.0:
+        return h.run_aux(U, Y, case["aux"], ll_steps=True)["ll_steps"], h.resample_count()
+    ll = np.zeros(T)
+    nres = 0
+    for k in range(T):
+        t = (case["t0"] + k) * Ts
+        if case["aux"] == 1 and k == T - 1:
+            ll[k] = h.update(U[k], Y[k], t)
+        else:
+            ll[k] = h.aux_correct()
+            if k == T - 1:
+                break
+            h.aux_predict(U[k], None if np.any(np.isnan(Y[k + 1])) else Y[k + 1], t)
+        nres += int(h.last_resampled())
+    return ll, nres
 
 
 def config_of(case):
