@@ -445,7 +445,7 @@ int  llpf_sqkf_bank_get_state(llpf_sqkf_bank* b, double* x, double* R, double* L
  * lower triangle is taken as given, so get_state(L) -> set_state(L) keeps every bit */
 int  llpf_sqkf_bank_set_state(llpf_sqkf_bank* b, const double* x, const double* R, const double* L);
 
-/* ---- banks of interacting-multiple-model (IMM) filters over Kalman or extended Kalman filters (the reference's IMM(models, P, mu), src/imm.jl) ----
+/* ---- banks of interacting-multiple-model (IMM) filters over Kalman, extended or unscented Kalman filters (the reference's IMM(models, P, mu), src/imm.jl) ----
  * n_filters independent IMM filters of n_modes modes each (1 <= n_modes <= 4), one GPU lane per (filter, mode), in the operation order of
  * csrc/shared/llpf_imm.h (that header is the definition: a host build of it gives the same bits).  The recursion is the textbook one
  * (Blom & Bar-Shalom); it was not checked against the reference's source.  There is no smoother.  Without LLPF_IMM_EXTENDED every mode is a
@@ -466,7 +466,18 @@ int  llpf_sqkf_bank_set_state(llpf_sqkf_bank* b, const double* x, const double* 
  * run that path through the model's A and C as Jacobians.  LLPF_ERR_ARG as well: whatever llpf_ekf_bank_create refuses (a compiled model
  * without dynamics_jac or measurement_jac, or with a noise, initial or loglik member; the Rao-Blackwellized ids), a mode whose model_id
  * or dimensions differ (the message names filter and mode), and D not NULL.  The kernel of a run-time compiled model is compiled on the
- * first such bank (LLPF_ERR_HIP with the log).  Step t runs at tau = (t_index0 + t) * Ts of llpf_imm_bank_run_at. */
+ * first such bank (LLPF_ERR_HIP with the log).  Step t runs at tau = (t_index0 + t) * Ts of llpf_imm_bank_run_at.
+ * Unscented modes.  llpf_imm_bank_create_unscented: every mode is an unscented Kalman filter with additive noise as llpf_ukf_bank_create
+ * takes it (csrc/shared/llpf_ukf.h defines its step: correct! maps the 2 nx + 1 sigma points of the mode's prior through the measurement,
+ * predict! those of the mode's x, R after the mixing through the dynamics), all modes of all filters ONE model type, each with its own
+ * descriptor; the model needs no Jacobian members.  One weight set (llpf_ukf_weights, below) for the whole bank, given at creation and
+ * replaced by llpf_imm_bank_set_weights.  flags: LLPF_IMM_INTERACT only.  LLPF_ERR_ARG as well: whatever llpf_ukf_bank_create refuses
+ * (a compiled model with a noise, initial or loglik member; the Rao-Blackwellized ids; dimensions that are not the model id's; weights
+ * that are not finite or gamma, wi <= 0), a mode whose model_id or dimensions differ (the message names filter and mode), and D not NULL
+ * in set_models.  A mode whose R (at either factorisation) or S loses definiteness makes its IMM NaN from that step on (ll 0 at missing
+ * rows); the run returns LLPF_OK and the other filters are unaffected.  The kernel of a run-time compiled model is compiled on the first
+ * such bank of that model and n_modes group (LLPF_ERR_HIP with the log).  Every other verb is shared: the handle is an llpf_imm_bank.
+ * No iterated modes, no mixed kinds of mode in one bank. */
 #define LLPF_IMM_INTERACT 1
 #define LLPF_IMM_EXTENDED 2
 typedef struct llpf_imm_bank llpf_imm_bank;
@@ -478,6 +489,12 @@ typedef struct llpf_imm_outputs {        /* every output optional (NULL); time-m
 } llpf_imm_outputs;
 int  llpf_imm_bank_create(int32_t device, const llpf_model* models, const double* D /* or NULL */, const double* P, const double* mu0,
                           int32_t n_filters, int32_t n_modes, int32_t flags, llpf_imm_bank** out);
+/* every mode an unscented Kalman filter as llpf_ukf_bank_create takes it, all modes of all filters ONE model type; flags: LLPF_IMM_INTERACT only */
+struct llpf_ukf_weights;                 /* (defined with the banks of unscented Kalman filters, below) */
+int  llpf_imm_bank_create_unscented(int32_t device, const llpf_model* models, const double* P, const double* mu0, int32_t n_filters,
+                                    int32_t n_modes, int32_t flags, const struct llpf_ukf_weights* w, llpf_imm_bank** out);
+/* new weights for an unscented bank (they ride in launch arguments); LLPF_ERR_ARG on a bank of Kalman or extended modes */
+int  llpf_imm_bank_set_weights(llpf_imm_bank* b, const struct llpf_ukf_weights* w);
 int  llpf_imm_bank_destroy(llpf_imm_bank* b);
 /* reset!: every mode's x = mean(d0), R = cov(d0); mu = mu0 */
 int  llpf_imm_bank_reset(llpf_imm_bank* b);

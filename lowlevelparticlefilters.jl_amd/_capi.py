@@ -55,6 +55,8 @@ SYMBOLS = {
     "llpf_sqkf_bank_get_state": [_vp, _dp, _dp, _dp],
     "llpf_sqkf_bank_set_state": [_vp, _dp, _dp, _dp],
     "llpf_imm_bank_create": [C.c_int32, C.POINTER(S.Model), _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp)],
+    "llpf_imm_bank_create_unscented": [C.c_int32, C.POINTER(S.Model), _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(S.UkfWeights), C.POINTER(_vp)],
+    "llpf_imm_bank_set_weights": [_vp, C.POINTER(S.UkfWeights)],
     "llpf_imm_bank_destroy": [_vp],
     "llpf_imm_bank_reset": [_vp],
     "llpf_imm_bank_set_models": [_vp, C.POINTER(S.Model), _dp, _dp, _dp],
@@ -647,15 +649,26 @@ IMM_EXTENDED = 2
 class IMMBankHandle(_KfBankHandle):
     """RAII wrapper of an `llpf_imm_bank*` (independent IMM filters of M modes each on one device, one lane per mode).
     `models`: [F][M] descriptors (a list of F lists of M), D [F, M, ny, nu] or None, P [F, M, M], mu0 [F, M].  extended: the modes are
-    first-order extended Kalman filters of one model type (LLPF_IMM_EXTENDED; implied by a model other than the linear-Gaussian one), D None."""
+    first-order extended Kalman filters of one model type (LLPF_IMM_EXTENDED; implied by a model other than the linear-Gaussian one), D None.
+    unscented: the modes are unscented Kalman filters of one model type (llpf_imm_bank_create_unscented), D None, `weights` =
+    (gamma, wm0, wc0, wi) the one set of the bank."""
     _SYM = "llpf_imm_bank"
 
-    def __init__(self, device, models, D, P, mu0, interact=True, extended=False):
+    def __init__(self, device, models, D, P, mu0, interact=True, extended=False, unscented=False, weights=None):
         self.M = len(models[0]) if len(models) else 0
         if any(len(row) != self.M for row in models):
             raise ValueError("every filter of an IMM bank has the same number of modes")
+        if unscented and (extended or D is not None or weights is None):
+            raise ValueError("an unscented IMM bank is not extended, has no D and needs weights")
+        if weights is not None and not unscented:
+            raise ValueError("only an unscented IMM bank has weights")
         arr = self._pack(models, first=True)
         D, P, mu0 = self._tables(D, P, mu0)
+        if unscented:
+            w = ukf_weights(weights)
+            check(self.L.llpf_imm_bank_create_unscented(int(device), arr, dptr(P), dptr(mu0), self.F, self.M, IMM_INTERACT if interact else 0,
+                                                        C.byref(w), C.byref(self.h)))
+            return
         check(self.L.llpf_imm_bank_create(int(device), arr, dptr(D), dptr(P), dptr(mu0), self.F, self.M,
                                           (IMM_INTERACT if interact else 0) | (IMM_EXTENDED if extended else 0), C.byref(self.h)))
 
@@ -675,6 +688,11 @@ class IMMBankHandle(_KfBankHandle):
         arr = self._pack(models)
         D, P, mu0 = self._tables(D, P, mu0)
         self._call("set_models", arr, dptr(D), dptr(P), dptr(mu0))
+
+    def set_weights(self, weights):
+        """new (gamma, wm0, wc0, wi) for a bank of unscented modes"""
+        w = ukf_weights(weights)
+        self._call("set_weights", C.byref(w))
 
     def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
         """T steps of every filter, step t at time (t_index0 + t) Ts (a bank of Kalman modes ignores the time); inputs as

@@ -456,42 +456,75 @@ class KalmanSmoothingSolution(KalmanFilteringSolution):
 
 class IMM:
     """IMM(models, P, mu; interact, device) — the reference's interacting-multiple-model filter (src/imm.jl) over a list of KalmanFilter
-    of the same dimensions, or over a list of ExtendedKalmanFilter of ONE model (the same compiled model id and dimensions; the modes
-    differ by their parameters, R1, R2 and d0 — a snippet that needs structurally different modes branches on one of its parameters):
+    of the same dimensions, or over a list of ExtendedKalmanFilter or a list of UnscentedKalmanFilter of ONE model (the same compiled model
+    id and dimensions; the modes differ by their parameters, R1, R2 and d0 — a snippet that needs structurally different modes branches on
+    one of its parameters):
     P [M, M] the row-stochastic transition matrix (P[i, j]: from mode i to mode j), mu [M] the initial mode probabilities, M <= 4.  Runs on
     the device as a bank of one IMM (llpf_imm_bank_*), created on first use, in the operation order of csrc/shared/llpf_imm.h: the
     textbook recursion of Blom & Bar-Shalom, not checked against the reference's source.  An extended mode linearises its measurement at
-    its own prior and its dynamics at its own state after the mixing (csrc/shared/llpf_ekf.h); iterated or unscented modes are not
-    provided.  interact = False: the modes never mix (M independent filters with a shared mode probability).  There is no smoother."""
+    its own prior and its dynamics at its own state after the mixing (csrc/shared/llpf_ekf.h).  An unscented mode is the additive-noise
+    unscented Kalman filter (csrc/shared/llpf_ukf.h): it maps the 2 nx + 1 sigma points of its own prior through the measurement and those
+    of its own state after the mixing through the dynamics, so its model needs no Jacobians (a snippet without dynamics_jac /
+    measurement_jac, a callable traced without them); all modes carry the same `weights`, the one set of the bank.  `unscented`: the
+    modes are unscented Kalman filters; `extended`: they are extended Kalman filters.  Iterated modes, and modes of different kinds in
+    one IMM, are not provided.  interact = False: the modes never mix (M independent filters with a shared mode probability).  There is no smoother."""
 
     def __init__(self, models, P, mu, *, interact=True, device=0):
         self.models = list(models)
         if not self.models:
-            raise TypeError("IMM: models is a non-empty list of KalmanFilter or of ExtendedKalmanFilter")
+            raise TypeError("IMM: models is a non-empty list of KalmanFilter, of ExtendedKalmanFilter or of UnscentedKalmanFilter")
+        kinds = []
         for j, m in enumerate(self.models):
             if isinstance(m, SqKalmanFilter):
-                raise TypeError("IMM: the modes are KalmanFilter or ExtendedKalmanFilter; mode %d is a SqKalmanFilter" % j)
-        self.extended = not isinstance(self.models[0], KalmanFilter)
-        for j, m in enumerate(self.models):
-            ok = (isinstance(m, ExtendedKalmanFilter) and not isinstance(m, IteratedExtendedKalmanFilter)) if self.extended else isinstance(m, KalmanFilter)
-            if not ok:
-                raise TypeError("IMM: models is a list of KalmanFilter or a list of ExtendedKalmanFilter; mode %d is a %s" % (j, type(m).__name__))
-        if self.extended:
+                raise TypeError("IMM: the modes are KalmanFilter, ExtendedKalmanFilter or UnscentedKalmanFilter; mode %d is a SqKalmanFilter" % j)
+            kind = ("linear" if isinstance(m, KalmanFilter) else "unscented" if isinstance(m, UnscentedKalmanFilter)
+                    else "extended" if isinstance(m, ExtendedKalmanFilter) and not isinstance(m, IteratedExtendedKalmanFilter) else None)
+            if kind is None:
+                raise TypeError("IMM: models is a list of KalmanFilter, of ExtendedKalmanFilter or of UnscentedKalmanFilter; mode %d is a %s"
+                                % (j, type(m).__name__))
+            kinds.append(kind)
+        for j, kind in enumerate(kinds):
+            if kind != kinds[0]:
+                raise TypeError("IMM: the modes of one IMM are one kind of filter; mode 0 is a %s and mode %d a %s"
+                                % (type(self.models[0]).__name__, j, type(self.models[j]).__name__))
+        self.kind = kinds[0]      # "linear", "extended" or "unscented"
+        self.weights = None
+        if self._timed:
             m0 = self.models[0]._model
             for j, f in enumerate(self.models):
                 m = f._model
                 if (m.model_id, m.nx, m.ny, m.nu) != (m0.model_id, m0.nx, m0.ny, m0.nu):
-                    raise TypeError("IMM: the modes of an extended IMM are one model (the same compiled model id and dimensions); mode %d "
-                                    "differs from mode 0" % j)
+                    raise TypeError("IMM: the modes of an %s IMM are one model (the same compiled model id and dimensions); mode %d "
+                                    "differs from mode 0" % (kinds[0], j))
+        if self.unscented:
+            self.weights = self.models[0].weights
+            for j, f in enumerate(self.models):
+                if f.weights != self.weights:
+                    raise TypeError("IMM: mode %d has other weights (gamma, wm0, wc0, wi) than mode 0; an unscented IMM has one set" % j)
         self.P, self.mu0 = np.atleast_2d(np.asarray(P, float)), np.atleast_1d(np.asarray(mu, float))
         self.interact, self.device = bool(interact), int(device)
         self.Ts = self.models[0].Ts
         self._handle = None
-        self._index = 0         # extended: the step counter of the nonlinear filters (the time of update!'s step)
+        self._index = 0         # extended, unscented: the step counter of the nonlinear filters (the time of update!'s step)
+
+    @property
+    def extended(self):
+        """the modes are extended Kalman filters"""
+        return self.kind == "extended"
+
+    @property
+    def unscented(self):
+        """the modes are unscented Kalman filters"""
+        return self.kind == "unscented"
+
+    @property
+    def _timed(self):
+        """the modes are driven by a model's own functions and take a time: extended or unscented"""
+        return self.kind != "linear"
 
     def _spec(self):
-        """(models [M], D [M, ny, nu] or None (extended), P, mu0) of this filter"""
-        if self.extended:
+        """(models [M], D [M, ny, nu] or None (extended, unscented), P, mu0) of this filter"""
+        if self._timed:
             return [f._model for f in self.models], None, self.P, self.mu0
         md = [kf._model() for kf in self.models]
         return [m for m, _ in md], np.stack([D for _, D in md]), self.P, self.mu0
@@ -501,7 +534,7 @@ class IMM:
         if self._handle is None:
             models, D, P, mu0 = self._spec()
             self._handle = _capi.IMMBankHandle(self.device, [models], None if D is None else D[None], P[None], mu0[None], self.interact,
-                                               self.extended)
+                                               self.extended, self.unscented, self.weights)
         return self._handle
 
     @property
@@ -646,29 +679,43 @@ class SqKalmanFilterBank(KalmanFilterBank):
 class IMMBank(_KfBank):
     """n independent IMM filters of the same number of modes and the same dimensions on one device, one GPU lane per (filter, mode)
     (llpf_imm_bank_*): the exact log-likelihood of a switching linear-Gaussian model for every parameter set of a sweep, or, over
-    ExtendedKalmanFilter modes of one model, the first-order one of a switching nonlinear model.  `specs` is a list of IMM or of
-    (models, P, mu) tuples (all with the same `interact`, the first one's, and all over the same kind of mode).  An extended bank runs
-    loglik from t = 1 * Ts and forward from t = 0, as ExtendedKalmanFilterBank does."""
+    ExtendedKalmanFilter modes of one model, the first-order one of a switching nonlinear model, or, over UnscentedKalmanFilter modes of
+    one model and one set of weights (a model without Jacobians), the unscented one.  `specs` is a list of IMM or of
+    (models, P, mu) tuples (all with the same `interact`, the first one's, and all over the same kind of mode).  An extended or unscented
+    bank runs loglik from t = 1 * Ts and forward from t = 0, as ExtendedKalmanFilterBank does.  Iterated modes are not provided."""
 
     def __init__(self, specs, device=0):
-        models, D, P, mu0, interact, self.extended = self._pack(specs)
+        models, D, P, mu0, interact, self.kind, self.weights = self._tables(specs)
         self.device = int(device)
-        self._h = _capi.IMMBankHandle(self.device, models, D, P, mu0, interact, self.extended)
+        self._h = _capi.IMMBankHandle(self.device, models, D, P, mu0, interact, self.extended, self.unscented, self.weights)
         self.n_filters = len(models)
         self.Ts = float(models[0][0].Ts)
-        if self.extended:
+        if self.kind != "linear":
             self._AT_LOGLIK, self._AT_FORWARD = {"t_index0": 1.0}, {"t_index0": 0.0}
+
+    extended = property(lambda self: self.kind == "extended", doc="the modes are extended Kalman filters")
+    unscented = property(lambda self: self.kind == "unscented", doc="the modes are unscented Kalman filters")
+
+    @staticmethod
+    def _tables(specs):
+        """(models, D, P, mu0, interact, kind, weights) of the specs, every IMM built once: one kind of mode (IMM.kind; D None unless it is
+        "linear") and, of an unscented bank, one set of weights (None otherwise)"""
+        imms = [f if isinstance(f, IMM) else IMM(*f) for f in specs]
+        kind, weights = imms[0].kind, imms[0].weights
+        for k, f in enumerate(imms):
+            if f.kind != kind:
+                raise TypeError("IMMBank: filter %d is %s where filter 0 is %s: a bank is over one kind of mode" % (k, f.kind, kind))
+            if f.weights != weights:
+                raise TypeError("IMMBank: filter %d has other weights than filter 0: an unscented bank has one set" % k)
+        sp = [f._spec() for f in imms]
+        D = np.stack([s[1] for s in sp]) if kind == "linear" else None
+        return [s[0] for s in sp], D, np.stack([s[2] for s in sp]), np.stack([s[3] for s in sp]), imms[0].interact, kind, weights
 
     @staticmethod
     def _pack(specs):
-        imms = [f if isinstance(f, IMM) else IMM(*f) for f in specs]
-        extended = imms[0].extended
-        for k, f in enumerate(imms):
-            if f.extended != extended:
-                raise TypeError("IMMBank: filter %d is %s where filter 0 is not: a bank is over one kind of mode" % (k, "extended" if f.extended else "linear"))
-        sp = [f._spec() for f in imms]
-        D = None if extended else np.stack([s[1] for s in sp])
-        return [s[0] for s in sp], D, np.stack([s[2] for s in sp]), np.stack([s[3] for s in sp]), imms[0].interact, extended
+        """(models, D, P, mu0, interact, extended) of the specs"""
+        t = IMMBank._tables(specs)
+        return t[:5] + (t[5] == "extended",)
 
     def state(self):
         """(x [F, nx], R [F, nx, nx], mu [F, M]): the combined estimate and the mode probabilities of every filter"""
@@ -684,10 +731,13 @@ class IMMBank(_KfBank):
 
     def set_parameters(self, specs):
         """new matrices, P and mu for every filter (same shapes, nothing reallocated: llpf_imm_bank_set_models)"""
-        models, D, P, mu0, _, extended = self._pack(specs)
-        if extended != self.extended:
+        models, D, P, mu0, _, kind, weights = self._tables(specs)
+        if kind != self.kind:
             raise TypeError("IMMBank.set_parameters: the bank keeps its kind of mode")
         self._h.set_models(models, D, P, mu0)
+        if weights != self.weights:
+            self._h.set_weights(weights)
+            self.weights = weights
 
 
 class MerweParams:
@@ -1274,7 +1324,7 @@ def update(pf, u, y, *args, **kw):
         r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], ("e",))
         return float(r["ll"][0]), r["e"][0, 0]
     if isinstance(pf, IMM):                         # the step of csrc/shared/llpf_imm.h; an IMM has no single innovation
-        t = _pt(args, kw, 0)[1]                     # (extended modes: the step's time, default index * Ts as the nonlinear filters')
+        t = _pt(args, kw, 0)[1]                     # (extended, unscented modes: the step's time, default index * Ts as the nonlinear filters')
         r = pf._run(np.atleast_1d(np.asarray(0.0 if u is None else u, float))[None], np.atleast_1d(np.asarray(y, float))[None], (),
                     float(pf._index) if t is None else float(t) / pf.Ts)
         return float(r["ll"][0]), None
@@ -1322,8 +1372,8 @@ def loglik(pf, u, y, p=None):
     t = index(pf)*Ts, i.e. the first step is at t = 1*Ts); :232-236 for the auxiliary filter (t = (k-1)*Ts, the
     last step is an update! of the wrapped filter).  For a KalmanFilter: reset!, then the sum of T update! steps (exact)."""
     reset(pf)
-    if isinstance(pf, IMM):                         # extended modes: the first step at t = 1 * Ts, as the extended filter's loglik
-        return float(pf._run(u, y, (), 1.0 if pf.extended else 0.0)["ll"][0])
+    if isinstance(pf, IMM):                         # extended, unscented modes: the first step at t = 1 * Ts, as those filters' loglik
+        return float(pf._run(u, y, (), 1.0 if pf._timed else 0.0)["ll"][0])
     if isinstance(pf, KalmanFilter):
         return float(pf._run(u, y)["ll"][0])
     if isinstance(pf, _NonlinearKalmanFilter):      # the first step at t = 1 * Ts, as the particle filters' loglik

@@ -254,11 +254,16 @@ int llpf_sqkf_bank_run(llpf_sqkf_bank* b, const double* U, const double* Y, int6
 int llpf_sqkf_bank_get_state(llpf_sqkf_bank* b, double* x, double* R, double* L) LLPF_TRY { NEEDF(b); return sqkf_get_state(*b, x, R, L); } LLPF_GUARD(llpf_sqkf_bank_get_state)
 int llpf_sqkf_bank_set_state(llpf_sqkf_bank* b, const double* x, const double* R, const double* L) LLPF_TRY { NEEDF(b); return sqkf_set_state(*b, x, R, L); } LLPF_GUARD(llpf_sqkf_bank_set_state)
 
-// ---- banks of IMM filters over Kalman filters or over extended Kalman filters (host/kfbank.hpp, host/imm.hpp) ----
+// ---- banks of IMM filters over Kalman, extended Kalman or unscented Kalman filters (host/kfbank.hpp, host/imm.hpp) ----
 int llpf_imm_bank_create(int32_t device, const llpf_model* models, const double* D, const double* P, const double* mu0, int32_t n_filters,
                          int32_t n_modes, int32_t flags, llpf_imm_bank** out) LLPF_TRY {
     return make_handle(out, [&](llpf_imm_bank& b) { return imm_create(device, models, D, P, mu0, n_filters, n_modes, flags, b); });
 } LLPF_GUARD(llpf_imm_bank_create)
+int llpf_imm_bank_create_unscented(int32_t device, const llpf_model* models, const double* P, const double* mu0, int32_t n_filters,
+                                   int32_t n_modes, int32_t flags, const llpf_ukf_weights* w, llpf_imm_bank** out) LLPF_TRY {
+    return make_handle(out, [&](llpf_imm_bank& b) { return imm_create_unscented(device, models, P, mu0, n_filters, n_modes, flags, w, b); });
+} LLPF_GUARD(llpf_imm_bank_create_unscented)
+int llpf_imm_bank_set_weights(llpf_imm_bank* b, const llpf_ukf_weights* w) LLPF_TRY { NEEDF(b); return imm_set_weights(*b, w); } LLPF_GUARD(llpf_imm_bank_set_weights)
 int llpf_imm_bank_destroy(llpf_imm_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_imm_bank_destroy)
 int llpf_imm_bank_reset(llpf_imm_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_imm_bank_reset)
 int llpf_imm_bank_set_models(llpf_imm_bank* b, const llpf_model* models, const double* D, const double* P, const double* mu0) LLPF_TRY {

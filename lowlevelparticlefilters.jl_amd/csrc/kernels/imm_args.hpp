@@ -1,7 +1,7 @@
-// kernels/imm_args.hpp — arguments of k_imm (kernels/imm.hpp) and of k_imm_ekf (kernels/imm_ekf.hpp), and k_imm's launcher.  Included
-// inside namespace llpf by the units that know the IMM banks: k_imm.hip, k_imm_ekf.hip and, through host/imm.hpp, capi.hip (the host
-// side); compiled into the run-time program of a model's k_imm_ekf (jit_imm_ekf.inc: tools/gen_jit_prelude.py drops the launcher's
-// declaration from that text).
+// kernels/imm_args.hpp — arguments of k_imm (kernels/imm.hpp), of k_imm_ekf (kernels/imm_ekf.hpp) and of k_imm_ukf (kernels/imm_ukf.hpp),
+// and k_imm's launcher.  Included inside namespace llpf by the units that know the IMM banks: k_imm.hip, k_imm_ekf.hip, k_imm_ukf.hip
+// and, through host/imm.hpp, capi.hip (the host side); compiled into the run-time programs of a model's k_imm_ekf and k_imm_ukf
+// (jit_imm_ekf.inc, jit_imm_ukf.inc: tools/gen_jit_prelude.py drops the launcher's declaration from that text).
 // One launch is one chunk of steps [t0, t0 + Tc) of F IMM filters of M modes, one lane per (filter, mode): G = 1, 2 or 4 lanes per filter
 // (the smallest G >= M), thread f * G + j is mode j of filter f, the lanes j >= M idle.  L = F * G is the number of columns of the SoA
 // arrays: a lane's column is its thread index.
@@ -31,6 +31,11 @@ struct ImmEkfArgs : ImmBaseArgs {
     int64_t t0;              // first step of this chunk
     double t_index0, Ts;     // tau_t = (t_index0 + t) * Ts, as k_ekf takes it
 };
-static_assert(sizeof(ImmBaseArgs) == 128 && sizeof(ImmArgs) == 136 && sizeof(ImmEkfArgs) == 160, "kernel argument layout");
+// unscented Kalman modes of one model type: par and the time as for the extended modes (R1, R2 packed: shared/llpf_ukf.h: LLPF_UKF_OFF_*)
+struct ImmUkfArgs : ImmEkfArgs {
+    double gamma, wm0, wc0, wi;   // the sigma-point spread and weights of the bank (llpf_ukf_weights), as in UkfArgs
+};
+static_assert(sizeof(ImmBaseArgs) == 128 && sizeof(ImmArgs) == 136 && sizeof(ImmEkfArgs) == 160 && sizeof(ImmUkfArgs) == 192,
+              "kernel argument layout");
 // one chunk of steps (k_imm.hip): nx in 1..8, ny in 1..4, g = 1, 2 or 4 lanes per filter (the smallest g >= ImmArgs::M)
 hipError_t launch_imm(int nx, int ny, int g, const ImmArgs& a, hipStream_t s);

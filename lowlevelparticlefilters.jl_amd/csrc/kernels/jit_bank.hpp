@@ -1,5 +1,5 @@
 // kernels/jit_bank.hpp — what the launchers of the one-thread-per-filter banks share (host side; part of k_kalman.hip, k_ukf.hip,
-// k_ekf.hip and — one lane per (filter, mode) — k_imm_ekf.hip, namespace llpf, after kernels/kf_store.hpp): the grid of a bank and, for the model-driven banks, which models have precompiled
+// k_ekf.hip and — one lane per (filter, mode) — k_imm_ekf.hip and k_imm_ukf.hip, namespace llpf, after kernels/kf_store.hpp): the grid of a bank and, for the model-driven banks, which models have precompiled
 // kernels, the key of a cache entry, the source of one program around a model's snippet, and the launch of a kernel of such a program.
 // ------------------------------------------------------------------------------------------------
 // one thread per filter, KF_BLOCK of them per workgroup
@@ -10,7 +10,7 @@ static dim3 kf_grid(int64_t F) { return dim3((unsigned)((F + KF_BLOCK - 1) / KF_
 static bool jit_bank_builtin(int model_id, int nx, int ny) {
     return (model_id == LLPF_MODEL_LINEAR_GAUSSIAN && nx <= 4 && ny <= 4) || model_id == LLPF_MODEL_QUADTANK_RK4;
 }
-// `variant`: "" or the suffix of a second entry of the same model (":smooth", ":iterated", k_imm_ekf's ":g<lanes per filter>")
+// `variant`: "" or the suffix of a second entry of the same model (":smooth", ":iterated", k_imm_ekf's and k_imm_ukf's ":g<lanes per filter>")
 static std::string jit_bank_key(int model_id, int nx, int ny, const char* variant) {
     return std::to_string(model_id) + ":" + std::to_string(nx) + ":" + std::to_string(ny) + variant;
 }

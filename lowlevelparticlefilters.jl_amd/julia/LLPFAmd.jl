@@ -1199,7 +1199,7 @@ function forward_trajectory(kf::GPUSqKalmanFilter, u, y, p = NullParameters())
                             [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
 end
 
-# ---- banks of IMM filters over Kalman filters or over extended Kalman filters of one model (the reference's IMM(models, P, mu), src/imm.jl;
+# ---- banks of IMM filters over Kalman filters or over extended or unscented Kalman filters of one model (the reference's IMM(models, P, mu), src/imm.jl;
 # csrc/shared/llpf_imm.h is the definition): llpf_imm_bank_* ----
 struct CImmOutputs                    # llpf_imm_outputs
     struct_size::UInt32
@@ -1219,20 +1219,22 @@ mutable struct GPUIMMBank
     nx::Int
     nu::Int
     ny::Int
-    extended::Bool                    # the modes are extended Kalman filters (LLPF_IMM_EXTENDED)
+    extended::Bool                    # the modes are driven by a model's own functions and take a time: extended Kalman filters (LLPF_IMM_EXTENDED) or
+                                      # unscented ones — true for both, unlike the Python IMM's `extended`, which means extended Kalman filters only
+    unscented::Bool                   # of those: unscented Kalman filters (llpf_imm_bank_create_unscented), which need no Jacobians
 end
 # (models, P, mu) of every filter -> the descriptors [F][M], D [F][M][ny][nu] (nothing: extended modes), P [F][M][M] and mu0 [F][M],
 # row-major.  A mode is an (A, B, C, D, R1, R2, d0) tuple, or — extended — a (dynamics, measurement, R1, R2, d0) tuple as
-# GPUExtendedKalmanFilterBank takes it
-function imm_tables(filters::Vector, Ts)
+# GPUExtendedKalmanFilterBank takes it (unscented: as GPUUnscentedKalmanFilterBank takes it, no Jacobians needed)
+function imm_tables(filters::Vector, Ts; unscented = false)
     M = length(filters[1][1])
     all(length(f[1]) == M for f in filters) || throw(ArgumentError("every filter of an IMM bank has the same number of modes"))
     extended = length(filters[1][1][1]) == 5
     all(length(m) == (extended ? 5 : 7) for f in filters for m in f[1]) || throw(ArgumentError("the modes of an IMM bank are all Kalman filters or all extended Kalman filters"))
     if extended
         cms = [ukf_model(m, Ts) for f in filters for m in f[1]]
-        foreach(need_jacobians, cms)
-        all(c.model_id == cms[1].model_id for c in cms) || throw(ArgumentError("the modes of an extended IMM bank are one model type"))
+        unscented || foreach(need_jacobians, cms)
+        all(c.model_id == cms[1].model_id for c in cms) || throw(ArgumentError("the modes of an $(unscented ? "unscented" : "extended") IMM bank are one model type"))
         Dv = nothing
     else
         cms = [kalman_model(m[1], m[2], m[3], m[5], m[6], m[7], Ts) for f in filters for m in f[1]]
@@ -1252,23 +1254,40 @@ the operation order of csrc/shared/llpf_imm.h; it was not checked against the re
 every filter's log-likelihood.  There is no smoother.
 With `models` a vector of (dynamics, measurement, R1, R2, d0) tuples of ONE model type (as `GPUExtendedKalmanFilterBank` takes them) every
 mode is a first-order extended Kalman filter (LLPF_IMM_EXTENDED); `loglik` then runs from t = 1 * Ts and `forward_trajectory` from t = 0.
+With `weight_params` given (MerweParams, WikiParams, TrivialParams or the four numbers, one set for the bank) the modes of such tuples are
+unscented Kalman filters instead (csrc/shared/llpf_ukf.h), whose model needs no Jacobian members; `set_weights!` replaces the set.
+Iterated modes are not provided.
 """
-function GPUIMMBank(filters::Vector; interact = true, Ts = 1.0, device = 0)
-    M, cms, Dv, Pv, mv = imm_tables(filters, Ts)
+function GPUIMMBank(filters::Vector; interact = true, Ts = 1.0, device = 0, weight_params = nothing)
+    unscented = weight_params !== nothing
+    M, cms, Dv, Pv, mv = imm_tables(filters, Ts; unscented = unscented)
     extended = Dv === nothing
+    (unscented && !extended) && throw(ArgumentError("weight_params: the modes of an unscented IMM bank are (dynamics, measurement, R1, R2, d0) tuples"))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:llpf_imm_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
-                device, cms, extended ? C_NULL : Dv, Pv, mv, length(filters), M, (interact ? 1 : 0) | (extended ? 2 : 0), h))
-    b = GPUIMMBank(h[], length(filters), M, cms[1].nx, cms[1].nu, cms[1].ny, extended)
+    if unscented
+        w = Ref(cukfweights(ukf_weights(weight_params, cms[1].nx)))
+        check(ccall((:llpf_imm_bank_create_unscented, LIB), Cint, (Int32, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ptr{CUkfWeights}, Ref{Ptr{Cvoid}}),
+                    device, cms, Pv, mv, length(filters), M, interact ? 1 : 0, w, h))
+    else
+        check(ccall((:llpf_imm_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
+                    device, cms, extended ? C_NULL : Dv, Pv, mv, length(filters), M, (interact ? 1 : 0) | (extended ? 2 : 0), h))
+    end
+    b = GPUIMMBank(h[], length(filters), M, cms[1].nx, cms[1].nu, cms[1].ny, extended, unscented)
     finalizer(x -> ccall((:llpf_imm_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
     b
 end
 function set_parameters!(b::GPUIMMBank, filters::Vector; Ts = 1.0)
-    M, cms, Dv, Pv, mv = imm_tables(filters, Ts)
+    M, cms, Dv, Pv, mv = imm_tables(filters, Ts; unscented = b.unscented)
     (length(filters) == b.F && M == b.M) || throw(ArgumentError("set_parameters!: $(length(filters)) filters of $M modes for a bank of $(b.F) of $(b.M)"))
     (Dv === nothing) == b.extended || throw(ArgumentError("set_parameters!: the bank keeps its kind of mode"))
     check(ccall((:llpf_imm_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, cms,
                 Dv === nothing ? C_NULL : Dv, Pv, mv))
+    b
+end
+# new weights for a bank of unscented modes (they ride in launch arguments)
+function set_weights!(b::GPUIMMBank, weight_params)
+    w = Ref(cukfweights(ukf_weights(weight_params, b.nx)))
+    check(ccall((:llpf_imm_bank_set_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{CUkfWeights}), b.h, w))
     b
 end
 reset!(b::GPUIMMBank) = check(ccall((:llpf_imm_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
@@ -1330,10 +1349,11 @@ function set_mode_states!(b::GPUIMMBank, mu, x, R)
 end
 
 """
-    GPUIMM(models, P, mu; interact = true, Ts = 1.0, device = 0)
+    GPUIMM(models, P, mu; interact = true, Ts = 1.0, device = 0, weight_params = nothing)
 
 The interacting-multiple-model filter over M <= 4 Kalman filters `models` (a vector of (A, B, C, D, R1, R2, d0) tuples) or over M <= 4
-extended Kalman filters of one model type (a vector of (dynamics, measurement, R1, R2, d0) tuples), run on the device
+extended Kalman filters of one model type (a vector of (dynamics, measurement, R1, R2, d0) tuples; with `weight_params` given they are
+unscented Kalman filters of that model, which needs no Jacobians), run on the device
 (a bank of one filter, llpf_imm_bank_*): `forward_trajectory` returns a named tuple (x, xt, R, Rt, ll, mu, ll_modes) of the combined
 estimate, the mode probabilities and every mode's own log-likelihood per step; `loglik`, `reset!`, `update!`, `state`, `covariance`,
 `mode_probabilities`.  Unverified against the reference's `IMM` (its source was not available when this was written); no smoother.
@@ -1343,8 +1363,8 @@ mutable struct GPUIMM
     Ts::Float64
     index::Int                        # extended modes: the step counter (the time of update!'s step), 1 after reset!
 end
-GPUIMM(models::Vector, P, mu; interact = true, Ts = 1.0, device = 0) =
-    GPUIMM(GPUIMMBank([(models, P, mu)]; interact = interact, Ts = Ts, device = device), Float64(Ts), 0)
+GPUIMM(models::Vector, P, mu; interact = true, Ts = 1.0, device = 0, weight_params = nothing) =
+    GPUIMM(GPUIMMBank([(models, P, mu)]; interact = interact, Ts = Ts, device = device, weight_params = weight_params), Float64(Ts), 0)
 reset!(f::GPUIMM) = (reset!(f.bank); f.index = 1; nothing)
 loglik(f::GPUIMM, u, y, p = NullParameters()) = loglik(f.bank, u, y)[1]
 "update!(imm, u, y): correct! of every mode, the mode probabilities, the mixing, predict!; returns ll"
