@@ -592,6 +592,33 @@ int  llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64
 int  llpf_ekf_bank_get_state(llpf_ekf_bank* b, double* x, double* R);
 int  llpf_ekf_bank_set_state(llpf_ekf_bank* b, const double* x, const double* R);
 
+/* ---- banks of square-root extended Kalman filters ----
+ * The filters of llpf_ekf_bank_* (the same models, traits, inputs, outputs, time convention and refusals), each carrying a
+ * lower-triangular factor Lr of its covariance, R = Lr Lr', as llpf_sqkf_bank_* does, in the operation order of
+ * csrc/shared/llpf_sqekf.h (that header is the definition: a host build of it gives the same bits; it is the textbook array form around
+ * the model linearised at the current mean and was not checked against the reference's source).  predict! triangularises [L1 | A Lr]
+ * with A = df/dx at the posterior, correct! [[L2, C Lr], [0, Lr]] with C = dg/dx at the prior, by Householder reflections: no
+ * covariance is ever subtracted from, so a filter with a diffuse prior and a near-exact sensor, which llpf_ekf_bank_run turns NaN,
+ * stays finite here; a filter is NaN only where its inputs, its model's values or its state are.  On a linear model R and Rt are
+ * llpf_sqkf_bank_run's bits.  R1, R2 and cov(d0) must all be positive definite (they are factored at create and set_models):
+ * LLPF_ERR_ARG naming the filter otherwise.  The R and Rt outputs are Lr Lr' (exactly symmetric).
+ * There is no smoother and no iterated form (llpf_ekf_bank_set_iterations has no counterpart), and the filter is not a mode of an IMM
+ * bank. */
+typedef struct llpf_sqekf_bank llpf_sqekf_bank;
+int  llpf_sqekf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, llpf_sqekf_bank** out);
+int  llpf_sqekf_bank_destroy(llpf_sqekf_bank* b);
+/* reset!: x = mean(d0), Lr = the factor of cov(d0) */
+int  llpf_sqekf_bank_reset(llpf_sqekf_bank* b);
+/* new parameters for every filter (same model id and dimensions; the state is left as it is, the next reset uses the new d0) */
+int  llpf_sqekf_bank_set_models(llpf_sqekf_bank* b, const llpf_model* models);
+/* T steps of every filter; U, Y, per_filter, t_index0, ll_total and out as llpf_ekf_bank_run takes them */
+int  llpf_sqekf_bank_run(llpf_sqekf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                         double* ll_total, const llpf_kalman_outputs* out);
+/* x [F][nx], R [F][nx][nx] = Lr Lr' and the dense lower factor L [F][nx][nx] (zeros above the diagonal); any may be NULL */
+int  llpf_sqekf_bank_get_state(llpf_sqekf_bank* b, double* x, double* R, double* L);
+/* x and exactly one of R and L, as llpf_sqkf_bank_set_state takes them: get_state(L) -> set_state(L) keeps every bit */
+int  llpf_sqekf_bank_set_state(llpf_sqekf_bank* b, const double* x, const double* R, const double* L);
+
 /* ---- banks of ensemble Kalman filters -----------------------------------------------------------------------------------------------
  * n_filters independent stochastic (perturbed-observation) ensemble Kalman filters of n_members members each, one GPU workgroup per
  * filter, in the operation order of csrc/shared/llpf_enkf.h (that header is the definition, the order of every sum over the ensemble

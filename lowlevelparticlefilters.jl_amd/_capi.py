@@ -81,6 +81,13 @@ SYMBOLS = {
     "llpf_ekf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
     "llpf_ekf_bank_get_state": [_vp, _dp, _dp],
     "llpf_ekf_bank_set_state": [_vp, _dp, _dp],
+    "llpf_sqekf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.POINTER(_vp)],
+    "llpf_sqekf_bank_destroy": [_vp],
+    "llpf_sqekf_bank_reset": [_vp],
+    "llpf_sqekf_bank_set_models": [_vp, C.POINTER(S.Model)],
+    "llpf_sqekf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_sqekf_bank_get_state": [_vp, _dp, _dp, _dp],
+    "llpf_sqekf_bank_set_state": [_vp, _dp, _dp, _dp],
     "llpf_enkf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(_vp)],
     "llpf_enkf_bank_destroy": [_vp],
     "llpf_enkf_bank_reset": [_vp],
@@ -775,6 +782,27 @@ class EkfBankHandle(_KfBankHandle):
     def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
         """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""
         return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
+
+
+class SqekfBankHandle(_KfBankHandle):
+    """RAII wrapper of an `llpf_sqekf_bank*` (independent square-root extended Kalman filters on one device): the models, inputs and
+    outputs of EkfBankHandle; the state is x and a lower-triangular factor L of the covariance, R = L L', as SqkfBankHandle's."""
+    _SYM = "llpf_sqekf_bank"
+
+    def __init__(self, device, models):
+        arr = self._open(models)
+        check(self.L.llpf_sqekf_bank_create(int(device), arr, self.F, C.byref(self.h)))
+
+    def set_models(self, models):
+        self._call("set_models", (S.Model * self.F)(*models))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
+        """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run (R and
+        Rt are L L')"""
+        return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
+
+    get_state = SqkfBankHandle.get_state
+    set_state = SqkfBankHandle.set_state
 
 
 class EnkfBankHandle(_KfBankHandle):

@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "SqKalmanFilter", "SqKalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "IMM", "IMMBank", "IMMFilteringSolution", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "SqKalmanFilter", "SqKalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "SqExtendedKalmanFilter", "SqExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "IMM", "IMMBank", "IMMFilteringSolution", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -911,6 +911,25 @@ class IteratedExtendedKalmanFilter(ExtendedKalmanFilter):
         return h
 
 
+class SqExtendedKalmanFilter(_NonlinearKalmanFilter):
+    """SqExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts, nu, ny, p, device) — the square-root extended Kalman filter:
+    ExtendedKalmanFilter's arguments, model, verbs and time conventions, carrying a lower-triangular factor L of the covariance, R = L L'
+    (csrc/shared/llpf_sqekf.h is the definition: predict! triangularises [L1 | A L], correct! [[L2, C L], [0, L]] by Householder
+    reflections, with the Jacobians A and C of the model at the current mean).  No covariance is ever subtracted from, so a diffuse prior
+    with a near-exact sensor, which turns an ExtendedKalmanFilter NaN, stays finite.  R1, R2 and cov(d0) must be positive definite.
+    Runs on the device as a bank of one filter (llpf_sqekf_bank_*), created on first use.  correct! alone puts the posterior back through
+    its covariance (factored again); update! and forward_trajectory carry the factor itself.  There is no smoother and no iterated
+    form, and the filter is not a mode of an IMM."""
+    _JACOBIANS = True
+
+    def __init__(self, dynamics, measurement, R1, R2, d0, *, Ts=1.0, nu=-1, ny=-1, p=None, device=0):
+        self._setup(dynamics, measurement, R1, R2, d0, Ts, nu, ny, p, device)
+        _need_jacobians(self._model)
+
+    def _open(self):
+        return _capi.SqekfBankHandle(self.device, [self._model])
+
+
 def _need_jacobians(model):
     """a compiled model under an extended Kalman filter must define both Jacobian members"""
     if model.model_id < S.MODEL_USER_BASE:
@@ -966,6 +985,7 @@ class ExtendedKalmanFilterBank(_KfBank):
     (llpf_ekf_bank_*): the deterministic log-likelihood of every parameter set of a nonlinear sweep at one evaluation of the model and
     its Jacobian per stage.  `filters_spec` is a list of ExtendedKalmanFilter or of (dynamics, measurement, R1, R2, d0) tuples."""
     _AT_LOGLIK, _AT_FORWARD = {"t_index0": 1.0}, {"t_index0": 0.0}
+    _HANDLE = _capi.EkfBankHandle
 
     def __init__(self, filters_spec, device=0, Ts=1.0):
         self._init(self._models(filters_spec, Ts), device)
@@ -974,7 +994,7 @@ class ExtendedKalmanFilterBank(_KfBank):
         self.device = int(device)
         for m in models:
             _need_jacobians(m)
-        self._h = _capi.EkfBankHandle(self.device, models)
+        self._h = self._HANDLE(self.device, models)
         self.n_filters = len(models)
         self.Ts = float(models[0].Ts)
 
@@ -996,6 +1016,21 @@ class ExtendedKalmanFilterBank(_KfBank):
 
     def smooth(self, u, y, outputs=None, forward=()):
         raise TypeError("the extended Kalman filter has no smoother yet: use UnscentedKalmanFilterBank.smooth")
+
+
+class SqExtendedKalmanFilterBank(ExtendedKalmanFilterBank):
+    """n independent square-root extended Kalman filters on one device, one GPU thread each (llpf_sqekf_bank_*):
+    ExtendedKalmanFilterBank's constructor, from_filter_bank, loglik, forward, state, set_parameters and time conventions, for nonlinear
+    sweeps whose noise levels span so many decades that the covariance form loses positive definiteness.  `filters_spec` is a list of
+    SqExtendedKalmanFilter, ExtendedKalmanFilter or (dynamics, measurement, R1, R2, d0) tuples.  There is no smoother."""
+    _HANDLE = _capi.SqekfBankHandle
+
+    @staticmethod
+    def _models(filters_spec, Ts):
+        return [(f if isinstance(f, (SqExtendedKalmanFilter, ExtendedKalmanFilter)) else SqExtendedKalmanFilter(*f, Ts=Ts))._model for f in filters_spec]
+
+    def smooth(self, *args, **kwargs):
+        raise TypeError("the square-root extended Kalman filter has no smoother")
 
 
 class IteratedExtendedKalmanFilterBank(ExtendedKalmanFilterBank):
@@ -1593,6 +1628,8 @@ def smooth(pf, *args):
     (csrc/shared/llpf_ukf.h: llpf_ukf_smooth_finish), on the device: a KalmanSmoothingSolution."""
     if isinstance(pf, SqKalmanFilter):
         raise TypeError("the square-root Kalman filter has no smoother")
+    if isinstance(pf, SqExtendedKalmanFilter):
+        raise TypeError("the square-root extended Kalman filter has no smoother")
     if isinstance(pf, KalmanFilter):
         u, y = args[:2]
         reset(pf)

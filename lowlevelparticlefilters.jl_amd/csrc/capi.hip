@@ -21,6 +21,7 @@
 #include "shared/llpf_imm.h"
 #include "shared/llpf_ukf.h"
 #include "shared/llpf_ekf.h"
+#include "shared/llpf_sqekf.h"
 #include "shared/llpf_enkf.h"
 
 using namespace llpf;
@@ -108,6 +109,7 @@ static void test_throw(const char* site) {
 #include "host/imm.hpp"
 #include "host/ukf.hpp"
 #include "host/ekf.hpp"
+#include "host/sqekf.hpp"
 #include "host/enkf.hpp"
 
 // A new handle: `build` fills it, a status other than LLPF_OK frees it again.  No handler here: what build throws is caught by the
@@ -330,6 +332,21 @@ int llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64_
 } LLPF_GUARD(llpf_ekf_bank_run)
 int llpf_ekf_bank_get_state(llpf_ekf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_get_state)
 int llpf_ekf_bank_set_state(llpf_ekf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_set_state)
+
+// ---- banks of square-root extended Kalman filters (host/kfbank.hpp, host/sqekf.hpp) ----
+int llpf_sqekf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, llpf_sqekf_bank** out) LLPF_TRY {
+    return make_handle(out, [&](llpf_sqekf_bank& b) { return sqekf_create(b, device, models, n_filters); });
+} LLPF_GUARD(llpf_sqekf_bank_create)
+int llpf_sqekf_bank_destroy(llpf_sqekf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_sqekf_bank_destroy)
+int llpf_sqekf_bank_reset(llpf_sqekf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_sqekf_bank_reset)
+int llpf_sqekf_bank_set_models(llpf_sqekf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return sqekf_set_models(*b, models); } LLPF_GUARD(llpf_sqekf_bank_set_models)
+int llpf_sqekf_bank_run(llpf_sqekf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                        const llpf_kalman_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return sqekf_run(*b, U, Y, T, per_filter, t_index0, ll_total, out);
+} LLPF_GUARD(llpf_sqekf_bank_run)
+int llpf_sqekf_bank_get_state(llpf_sqekf_bank* b, double* x, double* R, double* L) LLPF_TRY { NEEDF(b); return sqkf_get_state(*b, x, R, L); } LLPF_GUARD(llpf_sqekf_bank_get_state)
+int llpf_sqekf_bank_set_state(llpf_sqekf_bank* b, const double* x, const double* R, const double* L) LLPF_TRY { NEEDF(b); return sqkf_set_state(*b, x, R, L); } LLPF_GUARD(llpf_sqekf_bank_set_state)
 
 // ---- banks of ensemble Kalman filters (host/kfbank.hpp, host/enkf.hpp) ----
 int llpf_enkf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, int32_t n_members, uint64_t seed, llpf_enkf_bank** out) LLPF_TRY {

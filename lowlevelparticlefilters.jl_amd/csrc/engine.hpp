@@ -436,6 +436,11 @@ hipError_t launch_ekf(int model_id, int nx, int ny, const ModelD* models, const 
 // run-time compiled model on the first iterated use of the model, into a cache entry of its own; launch_iekf runs one chunk of steps
 int iekf_prepare(int model_id, int nx, int ny, std::string& err);
 hipError_t launch_iekf(int model_id, int nx, int ny, const ModelD* models, const EkfArgs& a, int32_t maxiters, double epsilon, hipStream_t s);
+// banks of square-root extended Kalman filters (k_sqekf.hip; kernels/sqekf.hpp): sqekf_prepare compiles the k_sqekf of a run-time compiled
+// model on its first such bank (0, or -1 with `err` set); launch_sqekf runs one chunk of steps.  KfModelArgs with the factor Lr where R
+// is in the state and the factors L1, L2 where R1, R2 are in par
+int sqekf_prepare(int model_id, int nx, int ny, std::string& err);
+hipError_t launch_sqekf(int model_id, int nx, int ny, const ModelD* models, const KfModelArgs& a, hipStream_t s);
 // banks of ensemble Kalman filters (k_enkf.hip; kernels/enkf.hpp), one workgroup per filter: enkf_prepare compiles k_enkf and k_enkf_init of
 // a run-time compiled model on its first bank (0, or -1 with `err` set); launch_enkf runs one chunk of steps, launch_enkf_init draws the
 // ensembles of a reset!, launch_enkf_moments puts mean and packed sample covariance of every ensemble into the state (nx in 1..8)

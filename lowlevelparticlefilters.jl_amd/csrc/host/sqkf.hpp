@@ -74,7 +74,8 @@ static int sqkf_run(llpf_sqkf_bank& b, const double* U, const double* Y, int64_t
 }
 
 // x [F][nx], R [F][nx][nx] = llpf_sq_cov of the factor, L [F][nx][nx] the dense lower factor (zeros above the diagonal); any may be NULL
-static int sqkf_get_state(llpf_sqkf_bank& b, double* x, double* R, double* L) {
+// (of any bank whose state rows hold a factor: host/sqekf.hpp's as well)
+static int sqkf_get_state(KfBank& b, double* x, double* R, double* L) {
     std::vector<double> h((size_t)b.nstate * b.F);
     HIPC(hipSetDevice(b.device));
     HIPC(hipMemcpyAsync(h.data(), b.d_state, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b.stream));
@@ -96,7 +97,7 @@ static int sqkf_get_state(llpf_sqkf_bank& b, double* x, double* R, double* L) {
 }
 
 // exactly one of R (its lower triangle, factored with llpf_kf_chol) and L (its lower triangle, as given); the running ll becomes 0
-static int sqkf_set_state(llpf_sqkf_bank& b, const double* x, const double* R, const double* L) {
+static int sqkf_set_state(KfBank& b, const double* x, const double* R, const double* L) {
     if (!x) return kf_fail(b.who, "x must be given");
     if ((R != nullptr) == (L != nullptr)) return kf_fail(b.who, "exactly one of R and L must be given");
     const double* src = R ? R : L;
@@ -107,7 +108,7 @@ static int sqkf_set_state(llpf_sqkf_bank& b, const double* x, const double* R, c
         for (int i = 0; i < nx; ++i) h[i * F + f] = x[f * nx + i];
         for (int r = 0; r < nx; ++r) for (int c = 0; c <= r; ++c) h[(nx + llpf_kf_idx(r, c)) * F + f] = src[(f * nx + r) * nx + c];
         if (R && !sqkf_factor(h, nx, nx, (int)f, b.F))
-            return fail(LLPF_ERR_ARG, "sqkf: filter " + std::to_string(f) + ": R is not positive definite");
+            return fail(LLPF_ERR_ARG, std::string(b.who) + ": filter " + std::to_string(f) + ": R is not positive definite");
     }
     HIPC(hipSetDevice(b.device));
     HIPC(hipMemcpyAsync(b.d_state, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, b.stream));

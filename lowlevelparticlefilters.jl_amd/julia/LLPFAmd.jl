@@ -36,7 +36,7 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMeasurement, GaussianLikelihood,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
-       GPUKalmanFilter, GPUKalmanFilterBank, GPUSqKalmanFilter, GPUSqKalmanFilterBank, sqkf_run, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
+       GPUKalmanFilter, GPUKalmanFilterBank, GPUSqKalmanFilter, GPUSqKalmanFilterBank, sqkf_run, GPUSqExtendedKalmanFilter, GPUSqExtendedKalmanFilterBank, sqekf_run, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
        ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank, set_iterations!,
        GPUEnsembleKalmanFilter, GPUEnsembleKalmanFilterBank, set_inflation!, members, set_members!,
        GPUIMM, GPUIMMBank, mode_probabilities, mode_states, set_mode_states!
@@ -1731,6 +1731,125 @@ covariance(kf::GPUExtendedKalmanFilter) = state(kf.bank)[2][:, :, 1]
 function forward_trajectory(kf::GPUExtendedKalmanFilter, u, y, p = NullParameters())
     reset!(kf.bank)
     ll, o = ekf_run(kf.bank, u, y; outputs = true)
+    T = length(y)
+    kf.index = T
+    KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                            [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+end
+
+# ---- banks of square-root extended Kalman filters (csrc/shared/llpf_sqekf.h is the definition): llpf_sqekf_bank_* ----
+mutable struct GPUSqExtendedKalmanFilterBank
+    h::Ptr{Cvoid}
+    F::Int
+    nx::Int
+    nu::Int
+    ny::Int
+    Ts::Float64
+end
+"""
+    GPUSqExtendedKalmanFilterBank(filters; Ts = 1.0, device = 0)
+
+Independent square-root extended Kalman filters on the device, one GPU thread each: the filters, models and time conventions of
+`GPUExtendedKalmanFilterBank`, each carrying a lower-triangular factor of its covariance as `GPUSqKalmanFilterBank` does, so that a
+diffuse prior with a near-exact sensor stays finite.  R1, R2 and cov(d0) must be positive definite.  There is no smoother and no
+iterated form, and the filter is not a mode of an IMM.
+"""
+function GPUSqExtendedKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0)
+    cms = [ukf_model(f, Ts) for f in filters]
+    foreach(need_jacobians, cms)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_sqekf_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Int32, Ref{Ptr{Cvoid}}), device, cms, length(cms), h))
+    b = GPUSqExtendedKalmanFilterBank(h[], length(cms), cms[1].nx, cms[1].nu, cms[1].ny, Float64(Ts))
+    finalizer(x -> ccall((:llpf_sqekf_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    b
+end
+function set_parameters!(b::GPUSqExtendedKalmanFilterBank, filters::Vector)
+    cms = [ukf_model(f, b.Ts) for f in filters]
+    foreach(need_jacobians, cms)
+    length(cms) == b.F || throw(ArgumentError("set_parameters!: $(length(cms)) filters for a bank of $(b.F)"))
+    check(ccall((:llpf_sqekf_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}), b.h, cms))
+    b
+end
+reset!(b::GPUSqExtendedKalmanFilterBank) = check(ccall((:llpf_sqekf_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+# u, y, outputs and t_index0 as ekf_run takes them
+function sqekf_run(b::GPUSqExtendedKalmanFilterBank, u, y; outputs = false, t_index0 = 0.0)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        check(ccall((:llpf_sqekf_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Ptr{CKalmanOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), Float64(t_index0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+"loglik(bank, u, y): every filter's log-likelihood (reset! first, then T update! steps, the first at t = 1 Ts as the extended bank's)"
+loglik(b::GPUSqExtendedKalmanFilterBank, u, y) = (reset!(b); sqekf_run(b, u, y; t_index0 = 1.0)[1])
+"x (nx x F), R = L L' (nx x nx x F) and the lower-triangular factor L (nx x nx x F) of every filter"
+function state(b::GPUSqExtendedKalmanFilterBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F); Lt = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_sqekf_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, x, R, Lt))
+    x, R, permutedims(Lt, (2, 1, 3))                 # the row-major [nx][nx] read column-major is the transpose
+end
+covariance(b::GPUSqExtendedKalmanFilterBank) = state(b)[2]
+"set the estimate of every filter: x (nx x F) and the covariance R (factored; its lower triangle is read) or, with factor = true, the lower-triangular factor itself"
+function set_state!(b::GPUSqExtendedKalmanFilterBank, x, R; factor = false)
+    xm = Matrix{Float64}(reshape(x, b.nx, b.F)); Rm = Array{Float64}(reshape(R, b.nx, b.nx, b.F))
+    Rr = permutedims(Rm, (2, 1, 3))
+    GC.@preserve Rr begin
+        check(ccall((:llpf_sqekf_bank_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.h, xm,
+                    factor ? C_NULL : pointer(Rr), factor ? pointer(Rr) : C_NULL))
+    end
+    b
+end
+
+"""
+    GPUSqExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0)
+
+The square-root extended Kalman filter, run on the device (a bank of one filter, llpf_sqekf_bank_*): `GPUExtendedKalmanFilter`'s
+arguments and verbs — `forward_trajectory`, `loglik`, `reset!`, `update!`, `correct!`, `predict!`, `state`, `covariance`.  `correct!`
+alone puts the posterior back through its covariance (factored again).  There is no smoother.  The textbook array form, unverified
+against the reference's source.
+"""
+mutable struct GPUSqExtendedKalmanFilter
+    bank::GPUSqExtendedKalmanFilterBank
+    Ts::Float64
+    index::Int
+end
+GPUSqExtendedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0) =
+    GPUSqExtendedKalmanFilter(GPUSqExtendedKalmanFilterBank([(dynamics, measurement, R1, R2, d0)]; Ts = Ts, device = device), Float64(Ts), 0)
+reset!(kf::GPUSqExtendedKalmanFilter) = (reset!(kf.bank); kf.index = 1; nothing)
+loglik(kf::GPUSqExtendedKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
+"update!(sqekf, u, y): correct! then predict! at time t; returns (ll, e)"
+function update!(kf::GPUSqExtendedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = sqekf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    kf.index += 1
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"correct!(sqekf, u, y): the posterior of a one-step run put back as the state through its covariance; returns (ll, e)"
+function correct!(kf::GPUSqExtendedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = sqekf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    set_state!(kf.bank, o.xt[:, :, 1], o.Rt[:, :, :, 1])
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"predict!(sqekf, u): a step whose measurement is missing (correct! is skipped)"
+function predict!(kf::GPUSqExtendedKalmanFilter, u, p = NullParameters(), t = kf.index * kf.Ts)
+    sqekf_run(kf.bank, [u], [missing]; t_index0 = t / kf.Ts)
+    kf.index += 1
+    nothing
+end
+state(kf::GPUSqExtendedKalmanFilter) = state(kf.bank)[1][:, 1]
+covariance(kf::GPUSqExtendedKalmanFilter) = state(kf.bank)[2][:, :, 1]
+function forward_trajectory(kf::GPUSqExtendedKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o = sqekf_run(kf.bank, u, y; outputs = true)
     T = length(y)
     kf.index = T
     KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
