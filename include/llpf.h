@@ -294,7 +294,8 @@ int  llpf_model_compile(const char* device_src, int32_t nx, int32_t ny, int32_t*
  * llpf_model_traits reports which optional members a compiled model has (bit set of LLPF_TRAIT_*), so that a binding can refuse a
  * UserLikelihood paired with a snippet without `loglik`, or a Gaussian likelihood paired with a snippet that defines one. */
 enum { LLPF_TRAIT_LOGLIK = 1, LLPF_TRAIT_LOGLIK_BOUND = 2, LLPF_TRAIT_NOISE = 4, LLPF_TRAIT_INITIAL = 8,
-       LLPF_TRAIT_DYNAMICS_JAC = 16, LLPF_TRAIT_MEASUREMENT_JAC = 32 };
+       LLPF_TRAIT_DYNAMICS_JAC = 16, LLPF_TRAIT_MEASUREMENT_JAC = 32,
+       LLPF_TRAIT_DYNAMICS_W = 64 /* dynamics_w(x, w, out): non-additive process noise, llpf_aukf_bank_* */ };
 int  llpf_model_traits(int32_t model_id, int32_t* traits);
 
 /* ---- accessors (reference src/PFtypes.jl:296-334) --------------------------------------- */
@@ -558,6 +559,33 @@ int  llpf_ukf_bank_smooth(llpf_ukf_bank* b, const double* U, const double* Y, in
 /* state, covariance of every filter: x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
 int  llpf_ukf_bank_get_state(llpf_ukf_bank* b, double* x, double* R);
 int  llpf_ukf_bank_set_state(llpf_ukf_bank* b, const double* x, const double* R);
+
+/* ---- banks of unscented Kalman filters with augmented (non-additive) process noise -------------------------------------------------
+ * The reference's UnscentedKalmanFilter with dynamics(x, u, p, t, w): x' = f(x, u, p, tau, w), w in R^nx, w ~ N(0, R1); the measurement
+ * noise stays additive.  The filters of llpf_ukf_bank_* (the same descriptors, dimensions, inputs, outputs, time convention, missing
+ * rows and refusals), in the operation order of csrc/shared/llpf_aukf.h (that header is the definition: a host build of it around the
+ * same model functions gives the same bits; it is the textbook augmented form and was not checked against the reference's source).
+ * correct! is llpf_ukf_bank_run's with the measurement set of weights (L = nx): on the same prior the same bits.  predict! draws
+ * 4 nx + 1 points of (x; 0) with the factor blkdiag(chol(R), chol(R1)) and the dynamics set of weights (L = 2 nx), maps them through the
+ * model's dynamics_w(x, w, out) (LLPF_TRAIT_DYNAMICS_W) and takes mean and covariance of the mapped points; nothing is added.  A model
+ * without that member (every built-in one) is taken as additive, f(x) + w: the 2 nx noise points reuse the centre's value.  A filter
+ * whose R loses definiteness, or whose R1 has no factor, is NaN from that step on.  There is no smoother, and the filter is not a mode
+ * of an IMM bank. */
+typedef struct llpf_aukf_bank llpf_aukf_bank;
+int  llpf_aukf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, const llpf_ukf_weights* w_measurement,
+                           const llpf_ukf_weights* w_dynamics, llpf_aukf_bank** out);
+int  llpf_aukf_bank_destroy(llpf_aukf_bank* b);
+/* reset!: x = mean(d0), R = cov(d0) */
+int  llpf_aukf_bank_reset(llpf_aukf_bank* b);
+/* new parameters for every filter (same model id and dimensions; the state is left as it is) / both weight sets for the bank */
+int  llpf_aukf_bank_set_models(llpf_aukf_bank* b, const llpf_model* models);
+int  llpf_aukf_bank_set_weights(llpf_aukf_bank* b, const llpf_ukf_weights* w_measurement, const llpf_ukf_weights* w_dynamics);
+/* T steps of every filter; the arguments of llpf_ukf_bank_run */
+int  llpf_aukf_bank_run(llpf_aukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0,
+                        double* ll_total, const llpf_kalman_outputs* out);
+/* x [F][nx], R [F][nx][nx] (either NULL); set_state takes R's lower triangle */
+int  llpf_aukf_bank_get_state(llpf_aukf_bank* b, double* x, double* R);
+int  llpf_aukf_bank_set_state(llpf_aukf_bank* b, const double* x, const double* R);
 
 /* ---- banks of extended Kalman filters (the reference's ExtendedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise) -------
  * n_filters independent first-order extended Kalman filters, one GPU thread each, in the operation order of csrc/shared/llpf_ekf.h (that

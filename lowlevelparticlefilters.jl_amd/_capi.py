@@ -73,6 +73,14 @@ SYMBOLS = {
     "llpf_ukf_bank_smooth": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs), C.POINTER(S.KalmanSmoothOutputs)],
     "llpf_ukf_bank_get_state": [_vp, _dp, _dp],
     "llpf_ukf_bank_set_state": [_vp, _dp, _dp],
+    "llpf_aukf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.POINTER(S.UkfWeights), C.POINTER(S.UkfWeights), C.POINTER(_vp)],
+    "llpf_aukf_bank_destroy": [_vp],
+    "llpf_aukf_bank_reset": [_vp],
+    "llpf_aukf_bank_set_models": [_vp, C.POINTER(S.Model)],
+    "llpf_aukf_bank_set_weights": [_vp, C.POINTER(S.UkfWeights), C.POINTER(S.UkfWeights)],
+    "llpf_aukf_bank_run": [_vp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, C.POINTER(S.KalmanOutputs)],
+    "llpf_aukf_bank_get_state": [_vp, _dp, _dp],
+    "llpf_aukf_bank_set_state": [_vp, _dp, _dp],
     "llpf_ekf_bank_create": [C.c_int32, C.POINTER(S.Model), C.c_int32, C.POINTER(_vp)],
     "llpf_ekf_bank_destroy": [_vp],
     "llpf_ekf_bank_reset": [_vp],
@@ -763,6 +771,28 @@ class UkfBankHandle(_KfBankHandle):
         return self._smooth(U, Y, u_per_filter, y_per_filter, outputs, forward, float(t_index0))
 
 
+class AukfBankHandle(_KfBankHandle):
+    """RAII wrapper of an `llpf_aukf_bank*` (independent unscented Kalman filters with augmented process noise on one device);
+    `weights` = the pair (measurement set, dynamics set), each (gamma, wm0, wc0, wi): the first for L = nx, the second for L = 2 nx."""
+    _SYM = "llpf_aukf_bank"
+
+    def __init__(self, device, models, weights):
+        arr = self._open(models)
+        wm, wd = (ukf_weights(w) for w in weights)
+        check(self.L.llpf_aukf_bank_create(int(device), arr, self.F, C.byref(wm), C.byref(wd), C.byref(self.h)))
+
+    def set_models(self, models):
+        self._call("set_models", (S.Model * self.F)(*models))
+
+    def set_weights(self, weights):
+        wm, wd = (ukf_weights(w) for w in weights)
+        self._call("set_weights", C.byref(wm), C.byref(wd))
+
+    def run(self, U, Y, u_per_filter=False, y_per_filter=False, outputs=(), t_index0=0.0):
+        """T steps of every filter, step t at time (t_index0 + t) Ts; inputs and the returned dictionary as KalmanBankHandle.run"""
+        return self._run(U, Y, u_per_filter, y_per_filter, outputs, float(t_index0))
+
+
 class EkfBankHandle(_KfBankHandle):
     """RAII wrapper of an `llpf_ekf_bank*` (independent extended Kalman filters on one device)."""
     _SYM = "llpf_ekf_bank"
@@ -1017,6 +1047,7 @@ def model_compile(device_src, nx, ny):
 
 TRAIT_LOGLIK, TRAIT_LOGLIK_BOUND, TRAIT_NOISE, TRAIT_INITIAL = 1, 2, 4, 8
 TRAIT_DYNAMICS_JAC, TRAIT_MEASUREMENT_JAC = 16, 32
+TRAIT_DYNAMICS_W = 64
 
 
 def model_traits(model_id):

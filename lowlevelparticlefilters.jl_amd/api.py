@@ -29,7 +29,7 @@ __all__ = [
     "StateAffineCoupling",
     "MvNormal", "ResampleSystematic", "ResampleStratified",
     "LinearDynamics", "LinearMeasurement", "QuadTankDynamics", "QuadTankMeasurement", "GaussianLikelihood",
-    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "SqKalmanFilter", "SqKalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "SqExtendedKalmanFilter", "SqExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "IMM", "IMMBank", "IMMFilteringSolution", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
+    "ResampleResidual", "weighted_cov", "weighted_quantile", "log_likelihood_fun", "metropolis", "metropolis_bank", "naive_sampler", "mode_trajectory", "KalmanFilter", "KalmanFilterBank", "SqKalmanFilter", "SqKalmanFilterBank", "KalmanFilteringSolution", "KalmanSmoothingSolution", "covariance", "UnscentedKalmanFilter", "UnscentedKalmanFilterBank", "AugmentedUnscentedKalmanFilter", "AugmentedUnscentedKalmanFilterBank", "ExtendedKalmanFilter", "ExtendedKalmanFilterBank", "IteratedExtendedKalmanFilter", "IteratedExtendedKalmanFilterBank", "SqExtendedKalmanFilter", "SqExtendedKalmanFilterBank", "EnsembleKalmanFilter", "EnsembleKalmanFilterBank", "IMM", "IMMBank", "IMMFilteringSolution", "MerweParams", "WikiParams", "TrivialParams", "RBMeasurementModel", "RBPF", "smooth", "smoothed_mean", "smoothed_cov", "smoothed_trajs", "ParticleFilter", "AdvancedParticleFilter", "AuxiliaryParticleFilter", "FilterBank", "ParticleFilteringSolution",
     "reset", "predict", "correct", "update", "forward_trajectory", "mean_trajectory", "loglik",
     "particles", "weights", "expweights", "state", "num_particles", "index", "effective_particles",
     "shouldresample", "resample", "weighted_mean", "logsumexp", "simulate", "simulate_batch", "parameters",
@@ -220,7 +220,7 @@ def _is_plain_callable(f):
     return callable(f) and not isinstance(f, _DESCRIPTORS)
 
 
-def _trace_callables(dyn, meas, mlik, nx, nu, ny, p, likelihood_bound=None, jacobians=False):
+def _trace_callables(dyn, meas, mlik, nx, nu, ny, p, likelihood_bound=None, jacobians=False, noise_input=False):
     """The reference's constructors take closures (src/PFtypes.jl:59-63, 189-193).  Plain Python callables with the reference's signatures
     — dynamics(x, u, p, t), measurement(x, u, p, t), measurement_likelihood(x, u, y, p, t) — are traced once (tracing.py) and emitted
     as the device snippet; returns the (UserDynamics, UserMeasurement, UserLikelihood | None) descriptors that stand for them."""
@@ -230,7 +230,7 @@ def _trace_callables(dyn, meas, mlik, nx, nu, ny, p, likelihood_bound=None, jaco
     if nu < 0:
         raise ValueError("pass nu= (the number of inputs) with callable dynamics: it cannot be read off a closure")
     d = tracing.traced_dynamics(dyn, nx, nu, p=p, measurement=meas, ny=ny, measurement_likelihood=mlik if _is_plain_callable(mlik) else None,
-                                loglik_bound=likelihood_bound, jacobians=jacobians)
+                                loglik_bound=likelihood_bound, jacobians=jacobians, noise_input=noise_input)
     return d, d.measurement_model, d.likelihood_model
 
 
@@ -795,6 +795,7 @@ class _NonlinearKalmanFilter:
     """What UnscentedKalmanFilter and ExtendedKalmanFilter share: the model descriptor of (dynamics, measurement, R1, R2, d0) and a bank of
     one filter on the device, created on first use by `_open()`.  `_JACOBIANS`: plain callables are traced with their Jacobians."""
     _JACOBIANS = False
+    _NOISE_INPUT = False      # a plain callable dynamics of five parameters (x, u, p, t, w) is traced into dynamics_w as well
 
     def _setup(self, dynamics, measurement, R1, R2, d0, Ts, nu, ny, p, device):
         nx = len(d0)
@@ -803,7 +804,9 @@ class _NonlinearKalmanFilter:
         if _is_plain_callable(dynamics):
             if ny < 0:
                 raise ValueError("pass ny= with callable dynamics and a scalar R2")
-            dynamics, measurement, _ = _trace_callables(dynamics, measurement, None, nx, nu, ny, p, jacobians=self._JACOBIANS)
+            from . import tracing
+            dynamics, measurement, _ = _trace_callables(dynamics, measurement, None, nx, nu, ny, p, jacobians=self._JACOBIANS,
+                                                        noise_input=self._NOISE_INPUT and tracing.n_parameters(dynamics) == 5)
         if isinstance(dynamics, UserDynamics):
             ny = dynamics.ny
         elif isinstance(measurement, LinearMeasurement):
@@ -874,6 +877,41 @@ class UnscentedKalmanFilter(_NonlinearKalmanFilter):
 
     def _open(self):
         return _capi.UkfBankHandle(self.device, [self._model], self.weights)
+
+
+def _aukf_weights(weight_params, nx):
+    """the pair (measurement set for L = nx, dynamics set for L = 2 nx), each (gamma, wm0, wc0, wi): from a preset (an object with
+    weights(L)), None (TrivialParams), or a pair of 4-tuples; one 4-tuple cannot say both"""
+    if weight_params is None:
+        weight_params = TrivialParams()
+    if hasattr(weight_params, "weights"):
+        return _ukf_weights(weight_params, nx), _ukf_weights(weight_params, 2 * nx)
+    pair = tuple(weight_params)
+    if len(pair) != 2 or any(np.ndim(w) != 1 or len(w) != 4 for w in pair):
+        raise ValueError("weight_params: a preset (MerweParams, WikiParams, TrivialParams) or a pair of four numbers (gamma, wm0, wc0, wi), "
+                         "the measurement set (L = nx) and the dynamics set (L = 2 nx)")
+    return tuple(_ukf_weights(w, nx) for w in pair)
+
+
+class AugmentedUnscentedKalmanFilter(_NonlinearKalmanFilter):
+    """AugmentedUnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts, nu, ny, p, weight_params, device) — the unscented Kalman
+    filter with augmented (non-additive) process noise, the reference's UnscentedKalmanFilter with dynamics(x, u, p, t, w):
+    x' = f(x, u, p, t, w), w in R^nx, w ~ N(0, R1);  y = g(x, u, p, t) + e, e ~ N(0, R2);  x_0 ~ d0 (csrc/shared/llpf_aukf.h is the
+    definition: predict! maps 4 nx + 1 points of (x; w), correct! is the UnscentedKalmanFilter's).  The arguments are
+    UnscentedKalmanFilter's.  A plain callable dynamics with five parameters (x, u, p, t, w) is traced into the model's `dynamics_w`
+    member (and, at w = 0, into `dynamics`); a UserDynamics snippet defines the member itself; a model without it (every built-in
+    descriptor, a callable of four parameters) is taken as additive, f(x) + w.  weight_params: a preset, used at L = nx for the measurement
+    and at L = 2 nx for the dynamics, or a pair of (gamma, wm0, wc0, wi).  Runs on the device as a bank of one filter (llpf_aukf_bank_*),
+    created on first use.  There is no smoother, and the filter is not a mode of an IMM."""
+    _NOISE_INPUT = True
+
+    def __init__(self, dynamics, measurement, R1, R2, d0, *, Ts=1.0, nu=-1, ny=-1, p=None, weight_params=None, device=0):
+        self._setup(dynamics, measurement, R1, R2, d0, Ts, nu, ny, p, device)
+        self.weight_params = weight_params
+        self.weights = _aukf_weights(weight_params, self.nx)
+
+    def _open(self):
+        return _capi.AukfBankHandle(self.device, [self._model], self.weights)
 
 
 class ExtendedKalmanFilter(_NonlinearKalmanFilter):
@@ -978,6 +1016,47 @@ class UnscentedKalmanFilterBank(_KfBank):
     def set_weights(self, weight_params):
         self.weights = _ukf_weights(weight_params, self._h.nx)
         self._h.set_weights(self.weights)
+
+
+class AugmentedUnscentedKalmanFilterBank(_KfBank):
+    """n independent unscented Kalman filters with augmented process noise of the same model family and dimensions on one device, one GPU
+    thread each (llpf_aukf_bank_*): the log-likelihood, free of Monte-Carlo noise, of every parameter set of a sweep over a model whose
+    process noise is not additive.  `filters_spec` is a list of AugmentedUnscentedKalmanFilter or of (dynamics, measurement, R1, R2, d0)
+    tuples; `weight_params` as AugmentedUnscentedKalmanFilter takes them, one pair of sets for the bank.  There is no smoother."""
+    _AT_LOGLIK, _AT_FORWARD = {"t_index0": 1.0}, {"t_index0": 0.0}
+
+    def __init__(self, filters_spec, device=0, weight_params=None, Ts=1.0):
+        self._init(self._models(filters_spec, Ts), device, weight_params)
+
+    def _init(self, models, device, weight_params):
+        self.device = int(device)
+        self.weights = _aukf_weights(weight_params, models[0].nx)
+        self._h = _capi.AukfBankHandle(self.device, models, self.weights)
+        self.n_filters = len(models)
+        self.Ts = float(models[0].Ts)
+
+    @staticmethod
+    def _models(filters_spec, Ts):
+        return [(f if isinstance(f, AugmentedUnscentedKalmanFilter) else AugmentedUnscentedKalmanFilter(*f, Ts=Ts))._model for f in filters_spec]
+
+    @classmethod
+    def from_filter_bank(cls, bank, device=None, weight_params=None):
+        """the augmented unscented twin of a FilterBank: the same descriptors (any model that is not Rao-Blackwellized and keeps the
+        Gaussian densities), loglik and forward at the times FilterBank.loglik and FilterBank.forward use"""
+        self = cls.__new__(cls)
+        self._init(list(bank._models), bank._h.cfg.device if device is None else device, weight_params)
+        return self
+
+    def set_parameters(self, filters_spec):
+        """new parameters for every filter (same model and dimensions, nothing reallocated: llpf_aukf_bank_set_models)"""
+        self._h.set_models(self._models(filters_spec, self.Ts))
+
+    def set_weights(self, weight_params):
+        self.weights = _aukf_weights(weight_params, self._h.nx)
+        self._h.set_weights(self.weights)
+
+    def smooth(self, *args, **kwargs):
+        raise TypeError("the augmented unscented Kalman filter has no smoother")
 
 
 class ExtendedKalmanFilterBank(_KfBank):
@@ -1630,6 +1709,8 @@ def smooth(pf, *args):
         raise TypeError("the square-root Kalman filter has no smoother")
     if isinstance(pf, SqExtendedKalmanFilter):
         raise TypeError("the square-root extended Kalman filter has no smoother")
+    if isinstance(pf, AugmentedUnscentedKalmanFilter):
+        raise TypeError("the augmented unscented Kalman filter has no smoother")
     if isinstance(pf, KalmanFilter):
         u, y = args[:2]
         reset(pf)

@@ -20,6 +20,7 @@
 #include "shared/llpf_sqkf.h"
 #include "shared/llpf_imm.h"
 #include "shared/llpf_ukf.h"
+#include "shared/llpf_aukf.h"
 #include "shared/llpf_ekf.h"
 #include "shared/llpf_sqekf.h"
 #include "shared/llpf_enkf.h"
@@ -108,6 +109,7 @@ static void test_throw(const char* site) {
 #include "host/sqkf.hpp"
 #include "host/imm.hpp"
 #include "host/ukf.hpp"
+#include "host/aukf.hpp"
 #include "host/ekf.hpp"
 #include "host/sqekf.hpp"
 #include "host/enkf.hpp"
@@ -332,6 +334,26 @@ int llpf_ekf_bank_run(llpf_ekf_bank* b, const double* U, const double* Y, int64_
 } LLPF_GUARD(llpf_ekf_bank_run)
 int llpf_ekf_bank_get_state(llpf_ekf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_get_state)
 int llpf_ekf_bank_set_state(llpf_ekf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_ekf_bank_set_state)
+
+// ---- banks of unscented Kalman filters with augmented process noise (host/kfbank.hpp, host/aukf.hpp) ----
+int llpf_aukf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, const llpf_ukf_weights* w_measurement,
+                          const llpf_ukf_weights* w_dynamics, llpf_aukf_bank** out) LLPF_TRY {
+    return make_handle(out, [&](llpf_aukf_bank& b) { return aukf_create(device, models, n_filters, w_measurement, w_dynamics, b); });
+} LLPF_GUARD(llpf_aukf_bank_create)
+int llpf_aukf_bank_destroy(llpf_aukf_bank* b) LLPF_TRY { delete b; return LLPF_OK; } LLPF_GUARD(llpf_aukf_bank_destroy)
+int llpf_aukf_bank_reset(llpf_aukf_bank* b) LLPF_TRY { NEEDF(b); return kf_reset(*b); } LLPF_GUARD(llpf_aukf_bank_reset)
+int llpf_aukf_bank_set_models(llpf_aukf_bank* b, const llpf_model* models) LLPF_TRY { NEEDF(b); return kf_model_set_models(*b, models); } LLPF_GUARD(llpf_aukf_bank_set_models)
+int llpf_aukf_bank_set_weights(llpf_aukf_bank* b, const llpf_ukf_weights* w_measurement, const llpf_ukf_weights* w_dynamics) LLPF_TRY {
+    NEEDF(b);
+    return aukf_set_weights(*b, w_measurement, w_dynamics);
+} LLPF_GUARD(llpf_aukf_bank_set_weights)
+int llpf_aukf_bank_run(llpf_aukf_bank* b, const double* U, const double* Y, int64_t T, int32_t per_filter, double t_index0, double* ll_total,
+                       const llpf_kalman_outputs* out) LLPF_TRY {
+    NEEDF(b);
+    return aukf_run(*b, U, Y, T, per_filter, t_index0, ll_total, out);
+} LLPF_GUARD(llpf_aukf_bank_run)
+int llpf_aukf_bank_get_state(llpf_aukf_bank* b, double* x, double* R) LLPF_TRY { NEEDF(b); return kf_get_state(*b, x, R); } LLPF_GUARD(llpf_aukf_bank_get_state)
+int llpf_aukf_bank_set_state(llpf_aukf_bank* b, const double* x, const double* R) LLPF_TRY { NEEDF(b); return kf_set_state(*b, x, R); } LLPF_GUARD(llpf_aukf_bank_set_state)
 
 // ---- banks of square-root extended Kalman filters (host/kfbank.hpp, host/sqekf.hpp) ----
 int llpf_sqekf_bank_create(int32_t device, const llpf_model* models, int32_t n_filters, llpf_sqekf_bank** out) LLPF_TRY {

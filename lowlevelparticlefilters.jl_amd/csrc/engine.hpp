@@ -321,6 +321,7 @@ struct JitCache {
 #include "kernels/sim_args.hpp"
 #include "kernels/kf_model_args.hpp"
 #include "kernels/ukf_args.hpp"
+#include "kernels/aukf_args.hpp"
 #include "kernels/ekf_args.hpp"
 #include "kernels/enkf_args.hpp"
 // arguments of k_kalman (kernels/kalman.hpp): one launch is one chunk of steps [t0, t0 + Tc) of F Kalman filters, one thread per filter.
@@ -436,6 +437,10 @@ hipError_t launch_ekf(int model_id, int nx, int ny, const ModelD* models, const 
 // run-time compiled model on the first iterated use of the model, into a cache entry of its own; launch_iekf runs one chunk of steps
 int iekf_prepare(int model_id, int nx, int ny, std::string& err);
 hipError_t launch_iekf(int model_id, int nx, int ny, const ModelD* models, const EkfArgs& a, int32_t maxiters, double epsilon, hipStream_t s);
+// banks of unscented Kalman filters with augmented process noise (k_aukf.hip; kernels/aukf.hpp): aukf_prepare compiles the k_aukf of a
+// run-time compiled model on its first such bank (0, or -1 with `err` set); launch_aukf runs one chunk of steps
+int aukf_prepare(int model_id, int nx, int ny, std::string& err);
+hipError_t launch_aukf(int model_id, int nx, int ny, const ModelD* models, const AukfArgs& a, hipStream_t s);
 // banks of square-root extended Kalman filters (k_sqekf.hip; kernels/sqekf.hpp): sqekf_prepare compiles the k_sqekf of a run-time compiled
 // model on its first such bank (0, or -1 with `err` set); launch_sqekf runs one chunk of steps.  KfModelArgs with the factor Lr where R
 // is in the state and the factors L1, L2 where R1, R2 are in par

@@ -478,6 +478,14 @@ template <class M> struct has_dynamics_jac<M, decltype((void)&M::dynamics_jac)> 
 template <class M, class = void> struct has_measurement_jac { static constexpr bool value = false; };
 template <class M> struct has_measurement_jac<M, decltype((void)&M::measurement_jac)> { static constexpr bool value = true; };
 
+// Optional member of a model whose process noise is not additive (banks of augmented unscented Kalman filters, kernels/aukf.hpp), after
+// prepare():
+//   DEV void dynamics_w(const double* x, const double* w, double* out) const   out[NX] = f(x, u, p, tau, w), w in R^NX, w ~ N(0, R1)
+// The noise dimension is NX: a model with fewer sources ignores the other components.  The model still defines dynamics, its value at
+// w = 0; every other bank keeps using that and ignores this member.
+template <class M, class = void> struct has_dynamics_w { static constexpr bool value = false; };
+template <class M> struct has_dynamics_w<M, decltype((void)&M::dynamics_w)> { static constexpr bool value = true; };
+
 // Is f(x) expensive enough to be computed once per distinct ancestor of a block and handed to the outputs that share it
 // (k_step)?  Yes unless the model says otherwise: run-time compiled user models and the quad-tank's RK4 are; a matrix-vector
 // product is not, and a model that forms its own noise needs x next to f(x) anyway.

@@ -495,7 +495,8 @@ template <int TRAITS> __global__ void k_traits_tag() {}
 template <class Model> struct model_traits {
     static constexpr int value = (has_loglik<Model>::value ? LLPF_TRAIT_LOGLIK : 0) | (has_loglik_bound<Model>::value ? LLPF_TRAIT_LOGLIK_BOUND : 0) |
                                  (has_user_noise<Model>::value ? LLPF_TRAIT_NOISE : 0) | (has_user_initial<Model>::value ? LLPF_TRAIT_INITIAL : 0) |
-                                 (has_dynamics_jac<Model>::value ? LLPF_TRAIT_DYNAMICS_JAC : 0) | (has_measurement_jac<Model>::value ? LLPF_TRAIT_MEASUREMENT_JAC : 0);
+                                 (has_dynamics_jac<Model>::value ? LLPF_TRAIT_DYNAMICS_JAC : 0) | (has_measurement_jac<Model>::value ? LLPF_TRAIT_MEASUREMENT_JAC : 0) |
+                                 (has_dynamics_w<Model>::value ? LLPF_TRAIT_DYNAMICS_W : 0);
 };
 
 // ------------------------------------------------------------------------------------------------

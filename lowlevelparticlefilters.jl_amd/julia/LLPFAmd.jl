@@ -36,7 +36,7 @@ export GPUParticleFilter, GPUAdvancedParticleFilter, GPUAuxiliaryParticleFilter,
        LinearDynamics, LinearMeasurement, QuadTankDynamics, QuadTankMeasurement, GaussianLikelihood,
        RBLinearModel, RBBilinearModel, GaussianSpec, UserDynamics, UserMeasurement, UserLikelihood, UserNoise, UserInitial, linear_state, shared_covariance, loglik_multi, mbank_unique_id,
        seed!, ancestors, last_resampled, set_parameters!, quantile_trajectory, trace_dynamics, emit_user_model, simulate_batch,
-       GPUKalmanFilter, GPUKalmanFilterBank, GPUSqKalmanFilter, GPUSqKalmanFilterBank, sqkf_run, GPUSqExtendedKalmanFilter, GPUSqExtendedKalmanFilterBank, sqekf_run, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, MerweParams, WikiParams, TrivialParams,
+       GPUKalmanFilter, GPUKalmanFilterBank, GPUSqKalmanFilter, GPUSqKalmanFilterBank, sqkf_run, GPUSqExtendedKalmanFilter, GPUSqExtendedKalmanFilterBank, sqekf_run, GPUUnscentedKalmanFilter, GPUUnscentedKalmanFilterBank, GPUAugmentedUnscentedKalmanFilter, GPUAugmentedUnscentedKalmanFilterBank, aukf_run, MerweParams, WikiParams, TrivialParams,
        ukf_weights, set_weights!, GPUExtendedKalmanFilter, GPUExtendedKalmanFilterBank, set_iterations!,
        GPUEnsembleKalmanFilter, GPUEnsembleKalmanFilterBank, set_inflation!, members, set_members!,
        GPUIMM, GPUIMMBank, mode_probabilities, mode_states, set_mode_states!
@@ -303,6 +303,7 @@ end
 UserInitial() = UserInitial(nothing)
 const TRAIT_LOGLIK, TRAIT_LOGLIK_BOUND, TRAIT_NOISE, TRAIT_INITIAL = Int32(1), Int32(2), Int32(4), Int32(8)
 const TRAIT_DYNAMICS_JAC, TRAIT_MEASUREMENT_JAC = Int32(16), Int32(32)      # the members an extended Kalman filter needs
+const TRAIT_DYNAMICS_W = Int32(64)      # dynamics_w(x, w, out): non-additive process noise (GPUAugmentedUnscentedKalmanFilter)
 function cmodel(f::UserDynamics, ::UserMeasurement, df, dg, d0, Ts; user_likelihood::Bool = false)
     id = Ref{Int32}(-1)
     check(ccall((:llpf_model_compile, LIB), Cint, (Cstring, Int32, Int32, Ref{Int32}), f.src, f.nx, f.ny, id))
@@ -1593,6 +1594,138 @@ function LowLevelParticleFilters.smooth(ukf::GPUUnscentedKalmanFilter, u, y, p =
                                   [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
     KalmanSmoothingSolution(sol, [s.xT[:, 1, t] for t in 1:T], [s.RT[:, :, 1, t] for t in 1:T])
 end
+
+# ---- banks of unscented Kalman filters with augmented (non-additive) process noise: llpf_aukf_bank_* ----
+# the pair (measurement set for L = nx, dynamics set for L = 2 nx) of a parameter set; a pair of raw 4-tuples passes through
+aukf_weights(p, nx) = (ukf_weights(p, nx), ukf_weights(p, 2nx))
+aukf_weights(w::Tuple{NTuple{4, <:Real}, NTuple{4, <:Real}}, nx) = (Float64.(w[1]), Float64.(w[2]))
+aukf_weights(w::NTuple{4, <:Real}, nx) = throw(ArgumentError("weight_params: a preset or a PAIR of (gamma, wm0, wc0, wi): the measurement set (L = nx) and the dynamics set (L = 2 nx)"))
+
+mutable struct GPUAugmentedUnscentedKalmanFilterBank
+    h::Ptr{Cvoid}
+    F::Int
+    nx::Int
+    nu::Int
+    ny::Int
+    Ts::Float64
+end
+"""
+    GPUAugmentedUnscentedKalmanFilterBank(filters; Ts = 1.0, device = 0, weight_params = TrivialParams())
+
+Independent unscented Kalman filters with augmented process noise on the device, one GPU thread each: x' = f(x, u, p, t, w),
+w ~ N(0, R1) of nx components, through the model's `dynamics_w(x, w, out)` member (a UserDynamics snippet defines it; a model without
+it is taken as additive).  `filters` as `GPUUnscentedKalmanFilterBank` takes them.  `weight_params`: MerweParams, WikiParams,
+TrivialParams — used at L = nx for the measurement and at L = 2 nx for the dynamics — or a pair of (gamma, wm0, wc0, wi).
+`loglik(bank, u, y)` is the vector of every filter's log-likelihood.  No smoother.
+"""
+function GPUAugmentedUnscentedKalmanFilterBank(filters::Vector; Ts = 1.0, device = 0, weight_params = TrivialParams())
+    cms = [ukf_model(f, Ts) for f in filters]
+    w = aukf_weights(weight_params, cms[1].nx)
+    wm = Ref(cukfweights(w[1])); wd = Ref(cukfweights(w[2]))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:llpf_aukf_bank_create, LIB), Cint, (Int32, Ptr{CModel}, Int32, Ptr{CUkfWeights}, Ptr{CUkfWeights}, Ref{Ptr{Cvoid}}),
+                device, cms, length(cms), wm, wd, h))
+    b = GPUAugmentedUnscentedKalmanFilterBank(h[], length(cms), cms[1].nx, cms[1].nu, cms[1].ny, Float64(Ts))
+    finalizer(x -> ccall((:llpf_aukf_bank_destroy, LIB), Cint, (Ptr{Cvoid},), x.h), b)
+    b
+end
+function set_parameters!(b::GPUAugmentedUnscentedKalmanFilterBank, filters::Vector)
+    cms = [ukf_model(f, b.Ts) for f in filters]
+    length(cms) == b.F || throw(ArgumentError("set_parameters!: $(length(cms)) filters for a bank of $(b.F)"))
+    check(ccall((:llpf_aukf_bank_set_models, LIB), Cint, (Ptr{Cvoid}, Ptr{CModel}), b.h, cms))
+    b
+end
+function set_weights!(b::GPUAugmentedUnscentedKalmanFilterBank, weight_params)
+    w = aukf_weights(weight_params, b.nx)
+    wm = Ref(cukfweights(w[1])); wd = Ref(cukfweights(w[2]))
+    check(ccall((:llpf_aukf_bank_set_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{CUkfWeights}, Ptr{CUkfWeights}), b.h, wm, wd))
+    b
+end
+reset!(b::GPUAugmentedUnscentedKalmanFilterBank) = check(ccall((:llpf_aukf_bank_reset, LIB), Cint, (Ptr{Cvoid},), b.h))
+# u, y as ukf_run takes them; step t runs at time (t_index0 + t - 1) Ts
+function aukf_run(b::GPUAugmentedUnscentedKalmanFilterBank, u, y; outputs = false, t_index0 = 0.0)
+    T = length(y)
+    Y = zeros(b.ny, T); U = zeros(b.nu, T)
+    for t in 1:T
+        Y[:, t] .= ismissingy(y[t]) ? fill(NaN, b.ny) : y[t]
+        b.nu > 0 && (U[:, t] .= u[t])
+    end
+    ll = zeros(b.F)
+    o = outputs ? (ll = zeros(b.F, T), x = zeros(b.nx, b.F, T), xt = zeros(b.nx, b.F, T), R = zeros(b.nx, b.nx, b.F, T),
+                   Rt = zeros(b.nx, b.nx, b.F, T), e = zeros(b.ny, b.F, T)) : nothing
+    GC.@preserve U Y ll o begin
+        out = o === nothing ? nothing : Ref(CKalmanOutputs(UInt32(sizeof(CKalmanOutputs)), 0, pointer(o.ll), pointer(o.x), pointer(o.xt),
+                                                           pointer(o.R), pointer(o.Rt), pointer(o.e)))
+        check(ccall((:llpf_aukf_bank_run, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Ptr{Float64}, Ptr{CKalmanOutputs}),
+                    b.h, b.nu > 0 ? pointer(U) : C_NULL, pointer(Y), T, Int32(0), Float64(t_index0), pointer(ll), out === nothing ? C_NULL : out))
+    end
+    ll, o
+end
+"loglik(bank, u, y): every filter's log-likelihood (reset! first, then T update! steps, the first at t = 1 Ts as the particle filters' loglik)"
+loglik(b::GPUAugmentedUnscentedKalmanFilterBank, u, y) = (reset!(b); aukf_run(b, u, y; t_index0 = 1.0)[1])
+"x (nx x F), R (nx x nx x F) of every filter"
+function state(b::GPUAugmentedUnscentedKalmanFilterBank)
+    x = zeros(b.nx, b.F); R = zeros(b.nx, b.nx, b.F)
+    check(ccall((:llpf_aukf_bank_get_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, x, R))
+    x, R
+end
+covariance(b::GPUAugmentedUnscentedKalmanFilterBank) = state(b)[2]
+"set the estimate of every filter: x (nx x F), R (nx x nx x F; its lower triangle is read)"
+function set_state!(b::GPUAugmentedUnscentedKalmanFilterBank, x, R)
+    xm = Matrix{Float64}(reshape(x, b.nx, b.F)); Rm = Array{Float64}(reshape(R, b.nx, b.nx, b.F))
+    Rr = permutedims(Rm, (2, 1, 3))                  # column-major nx x nx = the row-major [nx][nx] of its transpose
+    check(ccall((:llpf_aukf_bank_set_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.h, xm, Rr))
+    b
+end
+smooth(b::GPUAugmentedUnscentedKalmanFilterBank, args...) = throw(ArgumentError("the augmented unscented Kalman filter has no smoother"))
+
+"""
+    GPUAugmentedUnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0, weight_params = TrivialParams())
+
+The reference's `UnscentedKalmanFilter` with `dynamics(x, u, p, t, w)` — augmented, non-additive process noise — run on the device (a
+bank of one filter, llpf_aukf_bank_*): `forward_trajectory` returns the reference's `KalmanFilteringSolution`; `loglik`, `reset!`,
+`update!`, `correct!`, `predict!`, `state`, `covariance`.  The textbook augmented form, unverified against the reference's source.  No
+smoother.
+"""
+mutable struct GPUAugmentedUnscentedKalmanFilter
+    bank::GPUAugmentedUnscentedKalmanFilterBank
+    Ts::Float64
+    index::Int
+end
+GPUAugmentedUnscentedKalmanFilter(dynamics, measurement, R1, R2, d0; Ts = 1.0, device = 0, weight_params = TrivialParams()) =
+    GPUAugmentedUnscentedKalmanFilter(GPUAugmentedUnscentedKalmanFilterBank([(dynamics, measurement, R1, R2, d0)]; Ts = Ts, device = device,
+                                                                            weight_params = weight_params), Float64(Ts), 0)
+reset!(kf::GPUAugmentedUnscentedKalmanFilter) = (reset!(kf.bank); kf.index = 1; nothing)
+loglik(kf::GPUAugmentedUnscentedKalmanFilter, u, y, p = NullParameters()) = loglik(kf.bank, u, y)[1]
+"update!(aukf, u, y): correct! then predict! at time t; returns (ll, e)"
+function update!(kf::GPUAugmentedUnscentedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = aukf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    kf.index += 1
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"correct!(aukf, u, y): the posterior of a one-step run put back as the state; returns (ll, e)"
+function correct!(kf::GPUAugmentedUnscentedKalmanFilter, u, y, p = NullParameters(), t = kf.index * kf.Ts)
+    _, o = aukf_run(kf.bank, [u], [y]; outputs = true, t_index0 = t / kf.Ts)
+    set_state!(kf.bank, o.xt[:, :, 1], o.Rt[:, :, :, 1])
+    o.ll[1, 1], o.e[:, 1, 1]
+end
+"predict!(aukf, u): a step whose measurement is missing (correct! is skipped)"
+function predict!(kf::GPUAugmentedUnscentedKalmanFilter, u, p = NullParameters(), t = kf.index * kf.Ts)
+    aukf_run(kf.bank, [u], [missing]; t_index0 = t / kf.Ts)
+    kf.index += 1
+    nothing
+end
+state(kf::GPUAugmentedUnscentedKalmanFilter) = state(kf.bank)[1][:, 1]
+covariance(kf::GPUAugmentedUnscentedKalmanFilter) = state(kf.bank)[2][:, :, 1]
+function forward_trajectory(kf::GPUAugmentedUnscentedKalmanFilter, u, y, p = NullParameters())
+    reset!(kf.bank)
+    ll, o = aukf_run(kf.bank, u, y; outputs = true)
+    T = length(y)
+    kf.index = T
+    KalmanFilteringSolution(kf, u, y, [o.x[:, 1, t] for t in 1:T], [o.xt[:, 1, t] for t in 1:T], [o.R[:, :, 1, t] for t in 1:T],
+                            [o.Rt[:, :, 1, t] for t in 1:T], ll[1], [o.e[:, 1, t] for t in 1:T])
+end
+LowLevelParticleFilters.smooth(kf::GPUAugmentedUnscentedKalmanFilter, args...) = throw(ArgumentError("the augmented unscented Kalman filter has no smoother"))
 
 # ---- banks of extended Kalman filters (the reference's ExtendedKalmanFilter(dynamics, measurement, R1, R2, d0), additive noise): llpf_ekf_bank_* ----
 mutable struct GPUExtendedKalmanFilterBank

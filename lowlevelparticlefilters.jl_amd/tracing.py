@@ -222,11 +222,12 @@ def rk4(f, Ts, supersample=1):
 
 
 # ---- tracing and emission ---------------------------------------------------------------------------------------------------------
-_INPUT_OPS = ("x", "u", "t", "y")
+_INPUT_OPS = ("x", "u", "t", "y", "w")
 
 
-def trace(fn, nx, nu, p=None, ny=0, with_y=False, n_out=None, what="dynamics"):
-    """run fn on tracer numbers; returns (graph, output node ids).  fn(x, u, p, t) or fn(x, u, y, p, t) (with_y)"""
+def trace(fn, nx, nu, p=None, ny=0, with_y=False, n_out=None, what="dynamics", with_w=False):
+    """run fn on tracer numbers; returns (graph, output node ids).  fn(x, u, p, t), fn(x, u, y, p, t) (with_y) or fn(x, u, p, t, w)
+    (with_w: nx process-noise inputs, the input kind `w`)"""
     g = _Graph()
     x = [Tr(g, g.add("x", d)) for d in range(nx)]
     u = [Tr(g, g.add("u", d)) for d in range(nu)]
@@ -234,6 +235,8 @@ def trace(fn, nx, nu, p=None, ny=0, with_y=False, n_out=None, what="dynamics"):
     if with_y:
         y = [Tr(g, g.add("y", d)) for d in range(ny)]
         out = fn(x, u, y, p, t)
+    elif with_w:
+        out = fn(x, u, p, t, [Tr(g, g.add("w", d)) for d in range(nx)])
     else:
         out = fn(x, u, p, t)
     if isinstance(out, (Tr, int, float, np.floating)):
@@ -351,13 +354,13 @@ def _fdiv(a, b):
     return math.copysign(math.inf, a) * math.copysign(1.0, b)
 
 
-def evaluate(g, outs, x, u=(), t=0.0, y=None):
+def evaluate(g, outs, x, u=(), t=0.0, y=None, w=None):
     """the values of the nodes `outs` of a DAG at (x, u, t, y), in float64 on the host with math's functions (None in outs, a structurally
     zero derivative, gives 0.0).  `outs` may be nested lists, as jacobian() returns them; the result has the same shape.  Only the nodes
     the outputs depend on are evaluated, so u, t, y matter only where they are read."""
     if isinstance(outs, (list, tuple)) and any(isinstance(o, (list, tuple)) for o in outs):
         flat = [o for row in outs for o in row]
-        vals = evaluate(g, flat, x, u, t, y)
+        vals = evaluate(g, flat, x, u, t, y, w)
         it = iter(vals)
         return [[next(it) for _ in row] for row in outs]
     v = {}
@@ -374,6 +377,8 @@ def evaluate(g, outs, x, u=(), t=0.0, y=None):
             r = float(t)
         elif op == "y":
             r = float(y[node[1]])
+        elif op == "w":
+            r = float(w[node[1]])
         elif op == "const":
             r = struct.unpack("<d", struct.pack("<Q", node[1]))[0]
         elif op == "add":
@@ -454,6 +459,8 @@ def _emit_body(g, outs, out_stmt, uses, indent="        ", tname="t_"):
             name[i] = tname; uses.add("t")
         elif op == "y":
             name[i] = "y[%d]" % node[1]; uses.add("y")
+        elif op == "w":
+            name[i] = "w[%d]" % node[1]; uses.add("w")
         elif op == "const":
             name[i] = "c%d" % i
             lines.append("%sconst double c%d = %s;" % (indent, i, _const_literal(node[1])))
@@ -478,14 +485,34 @@ def _emit_jac_member(g, outs, nx, member, val, uses):
     return "    DEV void %s(const double* x, double* %s, double* J) const {\n%s%s\n    }" % (member, val, body, zeros)
 
 
-def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_bound=None, p=None, jacobians=False):
+def n_parameters(fn):
+    """the number of positional parameters of a callable (0 where it cannot be told): a dynamics of five, (x, u, p, t, w), forms its own
+    process noise"""
+    import inspect
+    try:
+        ps = inspect.signature(fn).parameters.values()
+    except (TypeError, ValueError):
+        return 0
+    return sum(1 for q in ps if q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD))
+
+
+def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_bound=None, p=None, jacobians=False, noise_input=False):
     """the `struct UserModel` snippet (include/llpf.h: llpf_model_compile) of traced callables.
     dynamics(x, u, p, t) -> nx values; measurement(x, u, p, t) -> ny values (may use neither u nor t: the engine's Model concept hands
     neither to the measurement); loglik(x, u, y, p, t) -> one value (the AdvancedParticleFilter's measurement_likelihood; may use t, not u)
     with loglik_bound: an upper bound of it (a number), or None (every step then normalises against the true maximum).
     jacobians: also emit `dynamics_jac` and `measurement_jac` (forward-mode derivatives of the same traces, jacobian()); without it the
-    text is what it always was."""
+    text is what it always was.
+    noise_input: dynamics is dynamics(x, u, p, t, w) with w the nx process-noise inputs; it is emitted as the member `dynamics_w(x, w, out)`
+    (what an AugmentedUnscentedKalmanFilter maps its points through) and, traced again at w = nx zeros, as `dynamics`."""
     uses = set()
+    dyn_w = None
+    if noise_input:
+        gw, ow = trace(dynamics, nx, nu, p, n_out=nx, what="dynamics", with_w=True)
+        dyn_w = ("    DEV void dynamics_w(const double* x, const double* w, double* out) const {\n%s\n    }"
+                 % _emit_body(gw, ow, lambda k, n: "out[%d] = %s;" % (k, n), set()))
+        with_noise = dynamics
+        dynamics = lambda x, u, pp, t: with_noise(x, u, pp, t, [0.0] * nx)
     gd, od = trace(dynamics, nx, nu, p, n_out=nx, what="dynamics")
     body_d = _emit_body(gd, od, lambda k, n: "out[%d] = %s;" % (k, n), uses)
     parts = ["    DEV void dynamics(const double* x, double* out) const {\n%s\n    }" % body_d]
@@ -517,6 +544,8 @@ def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_
         if loglik_bound is not None:
             parts.append("    DEV double loglik_bound() const { return %s; }" % _const_literal(_bits(loglik_bound)))
     parts += jac
+    if dyn_w is not None:
+        parts.append(dyn_w)
     src = ("struct UserModel {\n    static constexpr bool RB = false;\n    double u_[%d];\n    double t_;\n"
            "    DEV void prepare(const ModelD* m, const double* u, double t) {\n"
            "        for (int j = 0; j < %d; ++j) u_[j] = (u != nullptr) ? u[j] : 0.0;\n        t_ = t;\n    }\n%s\n};\n"
@@ -524,14 +553,19 @@ def emit_user_model(nx, nu, ny, dynamics, measurement=None, loglik=None, loglik_
     return src
 
 
-def traced_dynamics(f, nx, nu, p=None, measurement=None, ny=None, measurement_likelihood=None, loglik_bound=None, Ts=1.0, jacobians=False):
+def traced_dynamics(f, nx, nu, p=None, measurement=None, ny=None, measurement_likelihood=None, loglik_bound=None, Ts=1.0, jacobians=False,
+                    noise_input=False):
     """UserDynamics (+ its UserMeasurement / UserLikelihood, as attributes `measurement_model` / `likelihood_model`) from ordinary Python
     callables with the reference's signatures; the callables themselves remain the host versions (simulate).  jacobians: the snippet also
-    defines dynamics_jac / measurement_jac (what an ExtendedKalmanFilter needs)."""
+    defines dynamics_jac / measurement_jac (what an ExtendedKalmanFilter needs).  noise_input: f is f(x, u, p, t, w), emitted as dynamics_w
+    and, at w = 0, as dynamics (emit_user_model)."""
     from . import api
     if ny is None:
         raise ValueError("ny (the number of outputs) is needed")
-    src = emit_user_model(nx, nu, ny, f, measurement, measurement_likelihood, loglik_bound, p, jacobians=jacobians)
+    src = emit_user_model(nx, nu, ny, f, measurement, measurement_likelihood, loglik_bound, p, jacobians=jacobians, noise_input=noise_input)
+    if noise_input:
+        with_noise = f
+        f = lambda x, u, pp, t: with_noise(x, u, pp, t, [0.0] * nx)
     dyn = api.UserDynamics(src, nx, nu, ny, host=lambda x, u, pp, t: np.asarray(f(list(np.atleast_1d(x)), list(np.atleast_1d(u)) if u is not None else [], p, t), dtype=np.float64))
     dyn.measurement_model = api.UserMeasurement(host=None if measurement is None else
                                                 (lambda x, u, pp, t: np.asarray(measurement(list(np.atleast_1d(x)), [], p, t), dtype=np.float64)))
