@@ -107,7 +107,7 @@ static int dump_debug_timing(Bank& b, const DevBuf<uint64_t>& d_dbg) {
     FILE* fp = fopen("gpurun_out/llpf_timing.txt", "w");
     if (fp) {
         for (int t = 0; t < b.P2; ++t) {
-            for (int q = 0; q < 6; ++q) fprintf(fp, "%llu ", (unsigned long long)hd[(size_t)t * 8 + q]);
+            for (int q = 0; q < 8; ++q) fprintf(fp, "%llu ", (unsigned long long)hd[(size_t)t * 8 + q]);
             fprintf(fp, "\n");
         }
         fclose(fp);

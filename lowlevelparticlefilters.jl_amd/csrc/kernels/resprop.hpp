@@ -37,6 +37,12 @@ template <class T> DEV void st_off(T* base, uint32_t byte_off, T v) {
 #ifndef LLPF_LEAN_HEAD
 #define LLPF_LEAN_HEAD 1       /* head and scan with the argument values of such a launch compiled in, 1 / M from the host (res_head / res_counts<..., LEAN>) */
 #endif
+// wave priority by progress in the rounds of the level-3 output loop (shared/llpf_loop_prio.h has the maps; EXPERIMENTS: the output
+// loop's waves side by side)
+#ifndef LLPF_LOOP_PRIO
+#define LLPF_LOOP_PRIO 1       /* 0: one priority for the whole loop, waves served by age; 1: map A, min(2, rounds left - 1); 2: map B, min(3, rounds left - 1) */
+#endif
+#include "../shared/llpf_loop_prio.h"
 #define LLPF_RB_PLAIN_ST (Model::RB && !(model_lean<Model>::value && LLPF_RBX_WT))
 // store policy of the output loop (Mem<>::st): 1 = write-through (sc1), 0 = plain, 2 = nontemporal
 #ifndef LLPF_RESPROP_ST
@@ -235,7 +241,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     // Wave priority by phase: the head / counts / tail phases are short and latency-bound (loads, LDS, barriers, atomics), the
     // output loop is long and issue-bound.  The waves of a CU's four blocks are otherwise served oldest first, so the
     // youngest block's head is starved by the older blocks' loops and the SIMD ends the launch with that block's loop alone
-    // (in-kernel stamps, tools/dbg/timing_report.py).  Same-box A/B: C2 27.0 -> 26.4 us per timestep.
+    // (in-kernel stamps, tools/dbg/timing_report.py).  Same-box A/B: C2 27.0 -> 26.4 us per timestep.  Inside the loop the level-3
+    // kernel sets its priority by progress in the rounds, 0 to 2 (LLPF_ROUND_PRIO below); 3 stays with these phases.
     __builtin_amdgcn_s_setprio(3);
     const int f = blockIdx.y;
     const int tile = blockIdx.x;
@@ -378,6 +385,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     LLPF_STAMP(2);
 #ifdef LLPF_DEVTOOLS
     if (a.dbg && threadIdx.x == 0 && f == 0) a.dbg[(size_t)tile * 8 + 5] = (uint64_t)(last - first);
+    // where the block ran: HW_REG_HW_ID (register 4: cu_id [11:8], sh_id [12], se_id [15:13]) and HW_REG_XCC_ID (register 20: [3:0]), all 32 bits of
+    // each, so that tools/dbg/timing_report.py can give the stagger of the blocks that shared a CU
+    if (a.dbg && threadIdx.x == 0 && f == 0) {
+        a.dbg[(size_t)tile * 8 + 6] = (uint64_t)__builtin_amdgcn_s_getreg(4 | (31 << 11));
+        a.dbg[(size_t)tile * 8 + 7] = (uint64_t)__builtin_amdgcn_s_getreg(20 | (31 << 11));
+    }
 #endif
     const uint32_t tile0 = (uint32_t)tile * TILE, ulast = (uint32_t)last, ucend = (uint32_t)c_end;
     // end of the outputs that have an owner in this tile; [umain, ulast) is the last tile's [c_end, M) of a resampling step, else empty
@@ -386,6 +399,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     // the second loop they measured 1.1 % (C4 share) and 1.5 % (N = 1.6e7, threshold 1) slower (EXPERIMENTS: the output loop's rounds)
     constexpr bool PEEL = WEIGHT && ACC && !RBFAT;
     const uint32_t umain = (res && PEEL) ? (ucend < ulast ? ucend : ulast) : ulast;
+    // the map of the rounds' priority by progress: the level-3 kernel alone (the other forms keep one priority for the loop, their code untouched)
+    constexpr int LOOP_PRIO = (LEAN && PEEL) ? LLPF_LOOP_PRIO : 0;
     __builtin_amdgcn_s_setprio(0);
     // tile-local source of output o (< c_end): the owner table, the descent beyond it
     auto owner_of = [&](uint32_t o) -> uint32_t {
@@ -413,9 +428,37 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
 #else
 #define LLPF_ANC_KEPT(STALE) ((STALE) == 1 || !SKIPA)
 #endif
+    // Priority by progress (LOOP_PRIO: level 3 only; shared/llpf_loop_prio.h): inside the loop every wave used to run at priority 0, that is by
+    // age — the wave of the block dispatched first on a CU ran all its rounds first, the youngest block's wave ran its rounds last and alone
+    // on its SIMD.  Here a wave sets its priority at the top of each round with an owner from the rounds it still has to do, this one
+    // included: what is behind in rounds wins arbitration, equal progress falls back to age, and the waves of a SIMD pass the loop side by
+    // side.  The count is the wave's first lane's (the lowest output of the wave, so the most rounds of its lanes, and exactly the
+    // rounds the wave runs): scalar arithmetic on first, umain and that lane's thread index (one v_readfirstlane in front of the loop),
+    // counted down in an SGPR; s_setprio takes an immediate, so a round branches onto one of up to four.  No vector instruction and no
+    // VGPR in the round, no arithmetic, store or order changed.  Every wave's last round runs at priority 0, so the rounds of
+    // [c_end, M) behind it do too, and the tail raises it to 3 as ever.
+    // Kept: map A (C2 17.64 -> 16.71 us per timestep, map B 16.89; the last block of a launch ends at 16.5 instead of 17.9 - 18.9 us, the
+    // loop exits of a CU's four blocks are 1.9 instead of 4.7 us apart: EXPERIMENTS, profiles/loop_prio_*.txt).
+#define LLPF_ROUNDS_LEFT \
+    int rounds_left = 0; \
+    if constexpr (LOOP_PRIO != 0) { \
+        const uint32_t o0 = (uint32_t)first + (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x);      /* the first lane's output: first, umain and it are scalars */ \
+        rounds_left = o0 < umain ? (int)((umain - o0 + (uint32_t)(BLOCK - 1)) / (uint32_t)BLOCK) : 0; \
+    }
+#define LLPF_ROUND_PRIO(STALE) \
+        if constexpr (LOOP_PRIO != 0 && (STALE) == 0) { \
+            switch (llpf_loop_prio(LOOP_PRIO, rounds_left)) { \
+                case 3: __builtin_amdgcn_s_setprio(3); break; \
+                case 2: __builtin_amdgcn_s_setprio(2); break; \
+                case 1: __builtin_amdgcn_s_setprio(1); break; \
+                default: __builtin_amdgcn_s_setprio(0); break; \
+            } \
+            --rounds_left; \
+        }
 #define LLPF_OUTPUT_ROUNDS(RESX, NTLX, STALE, OEND) \
 _Pragma("unroll 1") \
     for (; o < (OEND); o += BLOCK) { \
+        LLPF_ROUND_PRIO(STALE) \
         uint32_t src = o; \
         double wprev = b.log1N; \
         if (RESX) { \
@@ -448,6 +491,7 @@ _Pragma("unroll") \
     if (umain < ulast) { LLPF_OUTPUT_ROUNDS(true, false, 1, ulast) }
 #define LLPF_OUTPUT_LOOP(RESX, NTLX) { \
     uint32_t o = (uint32_t)first + threadIdx.x; \
+    LLPF_ROUNDS_LEFT \
     LLPF_OUTPUT_ROUNDS(RESX, NTLX, PEEL ? 0 : 2, umain) \
     if (PEEL && (RESX)) { LLPF_OUTPUT_STALE } \
 }
@@ -540,6 +584,8 @@ _Pragma("unroll") \
     else { LLPF_OUTPUT_LOOP(false, (LLPF_RESPROP_LD_ID != 0)) }
 #undef LLPF_OUTPUT_LOOP
 #undef LLPF_OUTPUT_ROUNDS
+#undef LLPF_ROUNDS_LEFT
+#undef LLPF_ROUND_PRIO
 #undef LLPF_OUTPUT_STALE
 #undef LLPF_ANC_KEPT
 #undef LLPF_OUTPUT_ACC

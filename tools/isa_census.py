@@ -32,8 +32,9 @@ def main():
     marks = [i for i, l in enumerate(code) if l.strip().startswith("s_setprio")]
     regions = [("whole kernel", code)]
     if len(marks) >= 3:
-        regions = [("head + counts (to s_setprio 0)", code[:marks[1]]), ("output loop region (s_setprio 0 .. 3)", code[marks[1]:marks[2]]),
-                   ("tail", code[marks[2]:])]
+        # (the level-3 loop sets its priority in every round: the region runs from the first s_setprio behind the kernel's own to the last)
+        regions = [("head + counts (to s_setprio 0)", code[:marks[1]]), ("output loop region (s_setprio 0 .. 3)", code[marks[1]:marks[-1]]),
+                   ("tail", code[marks[-1]:])]
     for name, reg in regions:
         ops = [l.split()[0] for l in reg]
         c = collections.Counter(ops)
