@@ -254,7 +254,7 @@ struct ResArgs {
     int64_t k;             // epoch of this launch within a run (for the bank_flag stop test; recorded by a failed bound test)
     int64_t row;           // row of ll_steps / xmean this finalize writes
     int32_t count_surv;    // k_resample: add the number of distinct ancestors to BankDev::surv (models that could take the source-side form)
-    int32_t ablate;        // developer aid (LLPF_ABLATE): bit0 skip RNG, bit1 skip owner search, bit2 skip model math, bit3 skip the weight store, bit4 skip the ancestor store of the rounds with an owner, bit5 skip the accumulator atomics of the fused kernel's tail (its head then takes the sums as they are); results invalid
+    int32_t ablate;        // developer aid (LLPF_ABLATE): bit0 skip RNG, bit1 skip owner search, bit2 skip model math, bit3 skip the weight store, bit4 skip the ancestor store of the rounds with an owner, bit5 skip the accumulator atomics of the fused kernel's tail (its head then takes the sums as they are), bit6 the quantum by one shift and no NaN count of the exp-weights; results invalid
     int32_t nt_id;         // k_resprop (split schedule): the steps that do not resample read and store nontemporal — set by the host for working sets well
                            // beyond the Infinity Cache (host/run.hpp: below ~7 M particles plain accesses are up to 11 % faster, above nontemporal ones)
     int32_t lazy_q;        // k_resprop (split schedule): the k_norm in front of it stored no quanta — BankDev::quanta points at the WEIGHTS and the scan

@@ -60,6 +60,10 @@ static hipError_t launch_resprop_t(const BankDev& b, const ResArgs& a, const Ste
                         !a.accumulate || b.strategy != LLPF_RESAMPLE_SYSTEMATIC || a.M < 1) return hipErrorInvalidValue;
                     al.inv_M = lean_inv_M(a.M);      // (shares its eight bytes with Uexp, null here)
 #endif
+                    // ... and what its rounds hold (LLPF_LR_*): no output at or beyond N (the run loop passes M == N), and quanta of at least
+                    // 33 fraction bits (N <= 2^29, which the 32-bit byte offsets of the planes ask for anyway)
+                    if ((LLPF_LR_BITS & LLPF_LR_NOPAD) && (int64_t)a.M != b.N) return hipErrorInvalidValue;
+                    if ((LLPF_LR_BITS & LLPF_LR_QFIX) && (st.K < 33 || st.K > 62)) return hipErrorInvalidValue;
                     hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_LEAN>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, al), b, b.models, al, st);
                 } else return hipErrorInvalidValue;
                 break;

@@ -166,6 +166,22 @@ struct LinGauss {   // f = A x .+ B u ; g = C x   (reference examples/example_li
             out[r] = has_u ? ax + bu[r] : ax;
         }
     }
+    // The same without the per-lane select (the level-3 fused kernel): has_u is uniform, and the select is there only because adding the
+    // +0.0 that bu[] holds without an input would turn an A x of -0.0 into +0.0.  bz[] (input_term, once per launch) is B u with an input
+    // and -0.0 without: x + (-0.0) is x for every x, -0.0 and NaN included, so one add gives the bits of either arm.
+    DEV void input_term(double* bz) const {
+#pragma unroll
+        for (int r = 0; r < NX; ++r) bz[r] = has_u ? bu[r] : -0.0;
+    }
+    DEV void dynamics_bz(const double* x, const double* bz, double* out) const {
+#pragma unroll
+        for (int r = 0; r < NX; ++r) {
+            double ax = md->A[r * NX + 0] * x[0];
+#pragma unroll
+            for (int c = 1; c < NX; ++c) ax = ax + md->A[r * NX + c] * x[c];
+            out[r] = ax + bz[r];
+        }
+    }
     DEV void measurement(const double* x, double* out) const {
 #pragma unroll
         for (int r = 0; r < NY; ++r) {

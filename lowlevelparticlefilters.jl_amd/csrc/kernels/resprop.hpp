@@ -43,6 +43,21 @@ template <class T> DEV void st_off(T* base, uint32_t byte_off, T v) {
 #define LLPF_LOOP_PRIO 1       /* 0: one priority for the whole loop, waves served by age; 1: map A, min(2, rounds left - 1); 2: map B, min(3, rounds left - 1) */
 #endif
 #include "../shared/llpf_loop_prio.h"
+// a round of the level-3 output loop without its repeated work (EXPERIMENTS: a round without its repeated work): LLPF_LEAN_ROUND=0 is the loop
+// as it was; LLPF_LEAN_ROUND_ITEMS picks single items for A/B builds.  None changes a bit of any result.
+#ifndef LLPF_LEAN_ROUND
+#define LLPF_LEAN_ROUND 1
+#endif
+#define LLPF_LR_QFIX   1       /* the quantum is the fixed-point exp-weight shifted (llpf_q64_from_fix96_k33), not formed a second time from e */
+#define LLPF_LR_NANFLAG 2      /* NaN exp-weights: a lane flag instead of WeightAcc's 64-bit count (only its being non-zero is ever used); not in the default: alone it measured no gain (EXPERIMENTS) */
+#define LLPF_LR_BZ     4       /* B u by one add (LinGauss::dynamics_bz), not two adds and a select on the uniform has_u */
+#define LLPF_LR_NOPAD  8       /* no padding test: every output of such a launch is below M == N (launch_resprop_t refuses any other) */
+#define LLPF_LR_POW2   16      /* the uniforms' power-of-two scalings folded (llpf_normals_tab_s) */
+#define LLPF_LR_CARRY  32      /* the 128-bit running sum as one carry chain (unsigned __int128) */
+#ifndef LLPF_LEAN_ROUND_ITEMS
+#define LLPF_LEAN_ROUND_ITEMS (LLPF_LR_QFIX | LLPF_LR_BZ | LLPF_LR_NOPAD | LLPF_LR_POW2)
+#endif
+#define LLPF_LR_BITS (LLPF_LEAN_ROUND ? (LLPF_LEAN_ROUND_ITEMS) : 0)
 #define LLPF_RB_PLAIN_ST (Model::RB && !(model_lean<Model>::value && LLPF_RBX_WT))
 // store policy of the output loop (Mem<>::st): 1 = write-through (sc1), 0 = plain, 2 = nontemporal
 #ifndef LLPF_RESPROP_ST
@@ -61,7 +76,8 @@ template <class T> DEV void st_off(T* base, uint32_t byte_off, T v) {
 #define LLPF_STCOH ((LLPF_WT && !LLPF_RB_PLAIN_ST) ? STP : COH)
 #define LLPF_STCOH0 ((LLPF_WT && !LLPF_RB_PLAIN_ST) ? LLPF_RESPROP_ST : 0)
 // STW = false: the weights formed here are not stored (k_resprop<..., LEVEL >= 1>: nobody reads them)
-template <class Model, int NX, int NY, bool WEIGHT, bool COH = false, bool LTAB = false, bool STW = true>
+// LR: the LLPF_LR_* items of the level-3 round (0 everywhere else)
+template <class Model, int NX, int NY, bool WEIGHT, bool COH = false, bool LTAB = false, bool STW = true, int LR = 0>
 struct PropCtx {
     const BankDev& b;
     const Model& model;
@@ -79,6 +95,7 @@ struct PropCtx {
     uint64_t* qnext;       // quanta of the new weights
     const double* rng_lg = nullptr;   // the block's copy of the generator's tables in LDS , or nullptr: the
     const double* rng_sc = nullptr;   //   tables in constant memory (a global load through the GOT per lookup)
+    const double* bz = nullptr;       // LLPF_LR_BZ: the model's input term (LinGauss::input_term)
     // propagate output o from source src with previous log-weight wprev; returns the new log-weight
     // Addresses are a uniform plane base (SGPRs) + a 32-bit byte offset (one VGPR): Ns * 8 < 2^32 is checked at create.
     // the source's state (nontemporal: C2 22.8 against 20.7 us — duplicated ancestors are re-read from the L2)
@@ -122,13 +139,19 @@ struct PropCtx {
             return wr;
         }
 #ifdef LLPF_DEVTOOLS   /* ablation switches for performance experiments (results invalid); not in production builds */
-        if (!(ablate & 4)) model.dynamics(xp, fx);
+        if (!(ablate & 4)) { if constexpr ((LR & LLPF_LR_BZ) != 0) model.dynamics_bz(xp, bz, fx); else model.dynamics(xp, fx); }
         else { for (int d = 0; d < NX; ++d) fx[d] = xp[d]; }
-        if (!(ablate & 1)) { if constexpr (LTAB) llpf_normals_tab(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi, rng_lg, rng_sc); else llpf_normals(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi); }
+        if (!(ablate & 1)) {
+            if constexpr (LTAB && (LR & LLPF_LR_POW2) != 0) llpf_normals_tab_s(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi, rng_lg, rng_sc);
+            else if constexpr (LTAB) llpf_normals_tab(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi, rng_lg, rng_sc);
+            else llpf_normals(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi);
+        }
         else { for (int d = 0; d < NX; ++d) xi[d] = 0.25 * (double)(o & 7); }
 #else
-        model.dynamics(xp, fx);
-        if constexpr (LTAB) llpf_normals_tab(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi, rng_lg, rng_sc);
+        if constexpr ((LR & LLPF_LR_BZ) != 0) model.dynamics_bz(xp, bz, fx);
+        else model.dynamics(xp, fx);
+        if constexpr (LTAB && (LR & LLPF_LR_POW2) != 0) llpf_normals_tab_s(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi, rng_lg, rng_sc);
+        else if constexpr (LTAB) llpf_normals_tab(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi, rng_lg, rng_sc);
         else llpf_normals(o, pstep, LLPF_STREAM_DYNAMICS, k0, k1, NX, xi);
 #endif
         gauss_sample_c<NX>((gauss_cptr)&md->df, xi, nz);
@@ -150,7 +173,7 @@ struct PropCtx {
                 for (int k = 0; k < NY; ++k) v[k] = y[k] - g[k];
                 wv = wv + gauss_logpdf_c<NY>((gauss_cptr)&md->dg, v);
             }
-            if (o >= (uint32_t)b.N) wv = -LLPF_INF;
+            if constexpr (!(LR & LLPF_LR_NOPAD)) { if (o >= (uint32_t)b.N) wv = -LLPF_INF; }
             bad = bad || (wv != wv);
 #ifdef LLPF_DEVTOOLS
             if (!(ablate & 8))
@@ -160,6 +183,32 @@ struct PropCtx {
         return wv;
     }
 };
+
+// WeightAcc::add of the level-3 round (need_e2 false, e not wanted): the same sum S and the same quantum, by the LLPF_LR_* items of LR.
+// `nan` stands for WeightAcc::bad under LLPF_LR_NANFLAG; the kernel hands block_flush bad = nan ? 1 : 0, so the ballot it takes is the same.
+template <int LR>
+DEV uint64_t lean_acc_add(WeightAcc& wa, bool& nan, double w, double off, int K) {
+    const double e = llpf_exp_le0(w - off);
+    if constexpr ((LR & LLPF_LR_NANFLAG) != 0) nan = nan || (e != e);
+    else wa.bad += (e != e) ? 1u : 0u;
+    const llpf_u128 fx = llpf_fix96_unit(e);
+    if constexpr ((LR & LLPF_LR_CARRY) != 0) {
+        const unsigned __int128 t = (((unsigned __int128)wa.S.hi << 64) | wa.S.lo) + (((unsigned __int128)fx.hi << 64) | fx.lo);
+        wa.S.lo = (uint64_t)t; wa.S.hi = (uint64_t)(t >> 64);
+    } else wa.S = llpf_u128_add(wa.S, fx);
+    if constexpr ((LR & LLPF_LR_QFIX) != 0) return llpf_q64_from_fix96_k33(fx, K);
+    else return llpf_q64_unit(e, K);
+}
+
+#ifdef LLPF_DEVTOOLS
+// (not a constant: equal quanta would give every tile exactly 1024 outputs and no wave a fifth round — the high word of the fixed-point
+// value, one shift, keeps the ancestor counts near the real ones)
+DEV uint64_t ablated_acc_add(WeightAcc& wa, double w, double off, int K) {
+    const llpf_u128 fx = llpf_fix96_unit(llpf_exp_le0(w - off));
+    wa.S = llpf_u128_add(wa.S, fx);
+    return fx.hi << (K - 32);
+}
+#endif
 
 // per-thread running sum of quanta keyed by destination tile; flushed to LDS (first 8 tiles of the block's output
 // range) or straight to the global tile sums (heavier blocks) whenever the tile changes
@@ -312,9 +361,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
         else if (t < LLPF_RNG_SC_ENTRIES + LLPF_RNG_LG_ENTRIES) { sh_rng_lg[2 * (t - LLPF_RNG_SC_ENTRIES)] = rt0; sh_rng_lg[2 * (t - LLPF_RNG_SC_ENTRIES) + 1] = rt1; }
     }
     LLPF_STAMP(1);
-    PropCtx<Model, NX, NY, WEIGHT, false, !RBFAT, !SKIPW> pc{b, model, md, st, y, b.xcur + (size_t)f * NX * Ns, b.xnext + (size_t)f * NX * Ns,
+    // the items of the level-3 round (every other form: 0, its code untouched)
+    constexpr int LR = (LEAN && WEIGHT && ACC && !RBFAT) ? LLPF_LR_BITS : 0;
+    // lean_acc_add forms no sum of squares and hands out no e: only where neither is wanted (LEAN: always resamples, no weighted means)
+    constexpr int LR_ACC = LR & (LLPF_LR_QFIX | LLPF_LR_NANFLAG | LLPF_LR_CARRY);
+    static_assert(LR == 0 || (LEAN && SKIPW), "the items of the lean round are level 3's");
+    PropCtx<Model, NX, NY, WEIGHT, false, !RBFAT, !SKIPW, LR> pc{b, model, md, st, y, b.xcur + (size_t)f * NX * Ns, b.xnext + (size_t)f * NX * Ns,
                                       b.w + (size_t)f * Ns, b.w_next + (size_t)f * Ns, key0, key1, sb + st.step, a.ablate, 0.0, b.quanta_next + (size_t)f * Ns,
                                       RBFAT ? nullptr : sh_rng_lg, RBFAT ? nullptr : sh_rng_sc};
+    double bz[NX];
+    if constexpr ((LR & LLPF_LR_BZ) != 0) { model.input_term(bz); pc.bz = bz; }
+    bool wnan = false;       // LLPF_LR_NANFLAG: WeightAcc::bad as a flag
     int32_t* anc = b.anc + (size_t)f * Ns;
     double bmax = -LLPF_INF;
     bool bad = false;
@@ -476,10 +533,15 @@ _Pragma("unroll 1") \
         bmax = llpf_fmax(bmax, wv); \
         LLPF_OUTPUT_ACC(o, wv, xs) \
     }
+#ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 6, level 3 only (K >= 33 there: launch_resprop_t): one shift for the quantum and no NaN count (what items 1 and 2 of the lean round can save at most; results invalid) */
+#define LLPF_ACC_ADD(wv, e) ((LEAN && (a.ablate & 64)) ? ablated_acc_add(wacc, wv, pc.off, st.K) : (LR_ACC != 0 ? lean_acc_add<LR_ACC>(wacc, wnan, wv, pc.off, st.K) : wacc.add(wv, pc.off, st.K, LLPF_NEED_E2, &e)))
+#else
+#define LLPF_ACC_ADD(wv, e) (LR_ACC != 0 ? lean_acc_add<LR_ACC>(wacc, wnan, wv, pc.off, st.K) : wacc.add(wv, pc.off, st.K, LLPF_NEED_E2, &e))
+#endif
 #define LLPF_OUTPUT_ACC(o, wv, xs) \
         if (WEIGHT && ACC) { \
             double e; \
-            const uint64_t q = wacc.add(wv, pc.off, st.K, LLPF_NEED_E2, &e); \
+            const uint64_t q = LLPF_ACC_ADD(wv, e); \
             Mem<LLPF_STCOH0>::st_off(pc.qnext, (o) << 3, q); \
             ts.add(o, q, sh_tq, tq_next, tbase); \
             if (LLPF_WANT_XM) { \
@@ -589,6 +651,7 @@ _Pragma("unroll") \
 #undef LLPF_OUTPUT_STALE
 #undef LLPF_ANC_KEPT
 #undef LLPF_OUTPUT_ACC
+#undef LLPF_ACC_ADD
 #undef LLPF_OUTPUT_LOOP_PF
 #undef LLPF_OUTPUT_LOOP_ID2
     if constexpr (SKIPA) {
@@ -605,6 +668,7 @@ _Pragma("unroll") \
 #else
 #define LLPF_NO_TAIL_ATOMICS false
 #endif
+    if constexpr ((LR & LLPF_LR_NANFLAG) != 0) wacc.bad = wnan ? 1u : 0u;
     if constexpr (LEAN_TAIL) {
         // The tail in ONE barrier (block_flush, as in k_step<..., MARKS>): every wave reduces its maximum, NaN flag and exp-sums and leaves
         // one LDS row; the threads' tile sums went to sh_tq in front of it (ts.flush above); behind the barrier thread 0 combines the rows and

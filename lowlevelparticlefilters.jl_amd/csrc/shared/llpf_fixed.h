@@ -83,6 +83,20 @@ LLPF_HD uint64_t llpf_q64_unit(double e, int K) {
     return ok ? (Y >> (rs & 63)) : 0;
 }
 
+/* The quantum out of the fixed-point value: llpf_q64_unit(e, K) == llpf_fix96_unit(e) >> (96 - K) for every double e and 0 <= K <= 62 —
+ * floor(floor(e 2^96) / 2^(96 - K)) == floor(e 2^K), and both forms map what is not in [0, 2) to 0 (tests/test_lean_round_host.py).
+ * The shift is 34 .. 96 bits; fix96_unit(e) < 2^97, so the result fits 64 bits. */
+LLPF_HD uint64_t llpf_q64_from_fix96(llpf_u128 f, int K) {
+    const int s = 96 - K;
+    return s < 64 ? ((f.hi << (64 - s)) | (f.lo >> s)) : (f.hi >> ((s - 64) & 63));
+}
+/* ... for K >= 33 (N <= 2^29: every filter whose planes are addressed with 32-bit byte offsets): the first arm alone, two 64-bit shifts by
+ * uniform amounts and an or.  (Written as two 32-bit funnel shifts of neighbouring words the compiler emits no v_alignbit_b32 but one
+ * instruction more than for this form.) */
+LLPF_HD uint64_t llpf_q64_from_fix96_k33(llpf_u128 f, int K) {
+    return (f.hi << (K - 32)) | (f.lo >> (96 - K));
+}
+
 /* 64 x 64 -> 128 bit product */
 LLPF_HD llpf_u128 llpf_mul64(uint64_t a, uint64_t b) {
     llpf_u128 r;

@@ -114,6 +114,44 @@ LLPF_HD void llpf_normal_pair_tab(uint32_t idx, uint32_t step, uint32_t sub, uin
     *z0 = rad * cs;
     *z1 = rad * sn;
 }
+/* The two uniforms as the splits consume them, each with ONE power-of-two scaling or none (the level-3 fused kernel; the same bits):
+ * u_open * 2^53 is the integer itself, and 64 * u_half is the integer times 2^-47 — both scalings of (a >> 11) * 2^-53 * 64 are exact
+ * and the value stays below 64, so the one product is the same double */
+LLPF_HD double llpf_u01_open_s53(uint32_t lo, uint32_t hi) {
+    uint64_t a = ((uint64_t)hi << 32) | lo;
+    return (double)((a >> 11) + 1);
+}
+LLPF_HD double llpf_u01_half_x64(uint32_t lo, uint32_t hi) {
+    uint64_t a = ((uint64_t)hi << 32) | lo;
+    return (double)(a >> 11) * 7.1054273576010019e-15;           /* 2^-47 */
+}
+/* llpf_normal_pair_tab / llpf_normals_tab through them: identical draws */
+LLPF_HD void llpf_normal_pair_tab_s(uint32_t idx, uint32_t step, uint32_t sub, uint32_t stream, uint32_t k0, uint32_t k1,
+                                    const double* lg, const double* sc, double* z0, double* z1) {
+    llpf_philox4 r = llpf_philox4x32(idx, step, sub, stream, k0, k1);
+    double us = llpf_u01_open_s53(r.v[0], r.v[1]);
+    double t = llpf_u01_half_x64(r.v[2], r.v[3]);
+    double m, dk, f;
+    const int i = llpf_log_unit_split_s53(us, &m, &dk);
+    const int j = llpf_sincos2pi_split_x64(t, &f);
+    double rad = llpf_sqrt_rad(-2.0 * llpf_log_unit_eval(m, dk, lg[2 * i], lg[2 * i + 1]));
+    double sn, cs;
+    llpf_sincos2pi_eval(f, sc[2 * j], sc[2 * j + 1], &sn, &cs);
+    *z0 = rad * cs;
+    *z1 = rad * sn;
+}
+LLPF_HD void llpf_normals_tab_s(uint32_t idx, uint32_t step, uint32_t stream, uint32_t k0, uint32_t k1,
+                                int nd, double* xi, const double* lg, const double* sc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; 2 * b < nd; ++b) {
+        double z0, z1;
+        llpf_normal_pair_tab_s(idx, step, (uint32_t)b, stream, k0, k1, lg, sc, &z0, &z1);
+        xi[2 * b] = z0;
+        if (2 * b + 1 < nd) xi[2 * b + 1] = z1;
+    }
+}
 LLPF_HD void llpf_normals_tab(uint32_t idx, uint32_t step, uint32_t stream, uint32_t k0, uint32_t k1,
                               int nd, double* xi, const double* lg, const double* sc) {
 #if defined(__HIP_DEVICE_COMPILE__)
