@@ -72,6 +72,7 @@ static int bank_weighted_cov(Bank& b, double* cov) {
     if (!cov) return fail(LLPF_ERR_ARG, "null output");
     if (is_rbfull(b)) return fail(LLPF_ERR_ARG, "weighted_cov is not provided for LLPF_MODEL_RB_BILINEAR (take it from the particles)");
     CHK(use_device(b));
+    // d_tmp: the mean in [0, MAXD), the covariance in [MAXD, MAXD + nx * nx) — bank_carve sizes it for MAXD + MAXD * MAXD whatever N
     CHK(bank_wmean(b, b.d_tmp));
     HIPC(launch_wcov(b.dev(), b.d_tmp, b.d_tmp + MAXD, b.stream));
     return bank_to_host(b, cov, b.d_tmp + MAXD, sizeof(double) * b.nx * b.nx);

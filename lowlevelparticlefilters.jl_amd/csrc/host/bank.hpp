@@ -137,7 +137,7 @@ struct Bank : BankStream {
     DevBuf<double> d_U, d_Y;         // resident inputs of a run
     DevBuf<double> d_ll_steps, d_xmean;
     DevBuf<double> d_xcov;            // [T][nx*nx] + a mean: the xcov output of a run
-    double* d_tmp = nullptr;         // F*N*max(nx,1) doubles (also reinterpreted as int64 / double staging)
+    double* d_tmp = nullptr;         // max(F*N*max(nx,1), MAXD + MAXD*MAXD) doubles (also reinterpreted as int64 / double staging): bank_carve
     uint64_t seed = 0;
     uint64_t key_off = 0, key_stride = 1;   // filter f of this bank is filter key_off + f * key_stride of a sharded sweep (llpf_mbank): its
                                             // Philox key is seed + that global index, so results do not depend on the sharding
@@ -440,7 +440,10 @@ static size_t bank_carve(Bank& b, char* base) {
     c.take(b.d_tpre, two_level ? F * P2 : 0);
     c.take(b.d_gsum, two_level ? F * ((P2 + 4 * BLOCK - 1) / (4 * BLOCK)) : 0);
     c.take(b.d_uy, 4 * MAXD);
-    c.take(b.d_tmp, F * (size_t)b.N * (b.nxp > 1 ? b.nxp : 1) + 64 / sizeof(double));
+    // the accessors' staging: a copy of the particles or of a weight vector, [F][N][max(nxp, 1)] — or the fixed layout of the moments
+    // (host/access.hpp: bank_weighted_cov), the mean in [0, MAXD) and the covariance in [MAXD, MAXD + MAXD * MAXD), which a filter of few
+    // particles (N * nx < MAXD + nx * nx) would not hold.  d_tmp is the last carve: what does not fit lies past the pool.
+    c.take(b.d_tmp, std::max(F * (size_t)b.N * (b.nxp > 1 ? b.nxp : 1), (size_t)(MAXD + MAXD * MAXD)) + 64 / sizeof(double));
     return c.off;
 }
 
