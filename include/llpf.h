@@ -782,7 +782,9 @@ int  llpf_last_run_stats(llpf_filter* f, int64_t* fused_launches, int64_t* sourc
  * resamples at every step, so nobody reads what its launches form between the steps, and each level leaves out one thing more: bit 1 =
  * the weights were not stored (LLPF_SKIP_W=0 pins level 0); bit 2 = nor were, in every launch but the run's last, the ancestors — those
  * a run leaves are its last predict!'s either way (LLPF_SKIP_ANC=0 pins level 1); bit 4 = those launches were the kernel compiled for
- * systematic resampling without weighted means (linear-Gaussian models of one or two states, no xmean; LLPF_LEAN=0 pins level 2). */
+ * systematic resampling without weighted means (linear-Gaussian models of one or two states, no xmean; LLPF_LEAN=0 pins level 2).
+ * Bit 8 is not a level: in a level-3 run, the launches that another launch with a weighting phase follows left no running maximum of
+ * their weights either (LLPF_SKIP_MAX=0 has every launch leave one). */
 int  llpf_last_run_form(llpf_filter* f, int32_t* weights_not_stored, int64_t* exact_redos);
 int  llpf_bank_last_run_ms(llpf_bank* b, double* ms);
 

@@ -517,7 +517,7 @@ class FilterHandle(_PfHandle):
     def last_run_form(self):
         a, b = C.c_int32(0), C.c_int64(0)
         self._call("last_run_form", C.byref(a), C.byref(b))
-        return {"weights_not_stored": bool(a.value & 1), "ancestors_not_stored": bool(a.value & 2), "lean": bool(a.value & 4), "exact_redos": b.value}
+        return {"weights_not_stored": bool(a.value & 1), "ancestors_not_stored": bool(a.value & 2), "lean": bool(a.value & 4), "no_maximum": bool(a.value & 8), "exact_redos": b.value}
 
 
 KALMAN_OUTPUTS = ("ll_steps", "x", "xt", "R", "Rt", "e")

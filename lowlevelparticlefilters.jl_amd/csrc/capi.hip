@@ -466,7 +466,7 @@ int llpf_last_run_stats(llpf_filter* f, int64_t* fused_launches, int64_t* source
 } LLPF_GUARD(llpf_last_run_stats)
 int llpf_last_run_form(llpf_filter* f, int32_t* weights_not_stored, int64_t* exact_redos) LLPF_TRY {
     NEEDF(f);
-    if (weights_not_stored) *weights_not_stored = (1 << f->bank.last_run_level) - 1;
+    if (weights_not_stored) *weights_not_stored = ((1 << f->bank.last_run_level) - 1) | (f->bank.last_run_skip_max ? 8 : 0);
     if (exact_redos) *exact_redos = f->bank.last_run_redos;
     return LLPF_OK;
 } LLPF_GUARD(llpf_last_run_form)

@@ -47,6 +47,10 @@ constexpr int TILE = BLOCK * NORM_IPT;   // 1024 particles per tile: normalise a
 // Cross-block accumulators, per filter.  Every (word, shard) pair lives on its own 128-byte line: device-scope
 // atomics to one line serialise at ~11 ns each (measured: 8 shards sharing a line cost +11..15 us per launch),
 // so a launch of ~1000-2000 blocks puts only ~120-250 atomics on any line, spread over its whole duration.
+// In the fused kernel at threshold 1 the blocks reach their tails within ~4.4 us, and there the atomics are measured again (EXPERIMENTS: the
+// tail's accumulators): a launch of 977 blocks without its atomicMax — the maximum has no reader between two level-3 launches, level 4
+// leaves none — is 0.42 us shorter; its three sum atomics per block on 32 lines instead of 8 would save 0.12 us more (queueing), and
+// leaving them out altogether another 0.37 (the round trip every tail pays, which no number of shards removes).  NSHARD stays 8.
 constexpr int NSHARD = 8;
 constexpr int ACC_STRIDE = 16;                  // u64 per (word, shard) slot = 128 B
 // Every word exists three times ("slots").  A weighting kernel at timestep k accumulates its maximum into slot
@@ -254,14 +258,15 @@ struct ResArgs {
     int64_t k;             // epoch of this launch within a run (for the bank_flag stop test; recorded by a failed bound test)
     int64_t row;           // row of ll_steps / xmean this finalize writes
     int32_t count_surv;    // k_resample: add the number of distinct ancestors to BankDev::surv (models that could take the source-side form)
-    int32_t ablate;        // developer aid (LLPF_ABLATE): bit0 skip RNG, bit1 skip owner search, bit2 skip model math, bit3 skip the weight store, bit4 skip the ancestor store of the rounds with an owner, bit5 skip the accumulator atomics of the fused kernel's tail (its head then takes the sums as they are), bit6 the quantum by one shift and no NaN count of the exp-weights; results invalid
-    int32_t nt_id;         // k_resprop (split schedule): the steps that do not resample read and store nontemporal — set by the host for working sets well
+    int32_t ablate;        // developer aid (LLPF_ABLATE): bit0 skip RNG, bit1 skip owner search, bit2 skip model math, bit3 skip the weight store, bit4 skip the ancestor store of the rounds with an owner, bit5 skip the accumulator atomics of the fused kernel's tail (its head then takes the sums as they are), bit6 the quantum by one shift and no NaN count of the exp-weights, bit7 the sum atomics of a level-4 tail on 32 lines instead of 8; results invalid
+    int32_t nt_id;        // k_resprop (split schedule): the steps that do not resample read and store nontemporal — set by the host for working sets well
                            // beyond the Infinity Cache (host/run.hpp: below ~7 M particles plain accesses are up to 11 % faster, above nontemporal ones)
     int32_t lazy_q;        // k_resprop (split schedule): the k_norm in front of it stored no quanta — BankDev::quanta points at the WEIGHTS and the scan
                            // forms the tile's quanta itself, floor(exp(w - offset) 2^K): the same function of the same numbers (host/run.hpp)
     int32_t level;         // k_resprop (merged schedule, resample_threshold 1, several tiles): what this launch leaves out, a RunLevel (host/run_plan.hpp:
                            // launch_level) — from 1 the weights it forms are not stored, from 2 nor the ancestors of the outputs with an owner except
-                           // output M - 1's, 3 is the kernel for systematic resampling without weighted means (kernels/resprop.hpp)
+                           // output M - 1's, 3 is the kernel for systematic resampling without weighted means, 4 that kernel without the
+                           // running maximum of its weights, in its tail and in its head (kernels/resprop.hpp)
     uint64_t* dbg;         // optional [P2][8] phase timestamps of one launch (s_memrealtime, 100 MHz), or nullptr
 };
 static_assert(__builtin_offsetof(ResArgs, dbg) == 136 && sizeof(ResArgs) == 144, "ResArgs is a kernel argument: its layout is part of every launch");

@@ -115,6 +115,7 @@ struct Bank : BankStream {
     int64_t last_run_launches = 0, last_run_fx_steps = 0;
     double last_run_surv = -1.0;
     int last_run_level = 0;           // the RunLevel of the last run's plan (host/run_plan.hpp)
+    int last_run_skip_max = 0;        // ... and its RunKey::skip_max
     int64_t last_run_redos = 0;       // failed bound tests the last run's host loop redid in exact form
     DevBuf<double> d_xmpart;
     // Rao-Blackwellized model: host side of the shared covariance recursion (csrc/shared/llpf_rbkf.h)
@@ -146,7 +147,7 @@ struct Bank : BankStream {
     // Captured run loops (hipGraph): a chain of T dependent launches replays ~1 us per launch faster than it enqueues
     // (tools/launch_floor.hip: 1.6 vs 2.8 us per dependent empty launch).  Keyed by everything a launch argument depends on.
     struct RunGraph {
-        RunForm form;                    // every form decision of the run (host/run_plan.hpp), compared as a whole
+        RunKey form;                     // every form decision of the run (host/run_plan.hpp), compared as a whole
         int64_t T; double t_index0; int par0, cur0, qcur0, np_parity;
         const void *dU, *dY, *dll, *dxm, *dxc, *drb, *dxq, *dqp, *dw, *dws;      // every device buffer a captured launch addresses that ensure() may reallocate
         int nq;

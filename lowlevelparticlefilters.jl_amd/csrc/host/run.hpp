@@ -200,7 +200,7 @@ struct RunLoop {
             HIPC(launch_norm(d, ra.parity, p.want_xm, ne2, rel_step(b), 0, lazy_q ? 3 : 1, k, b.stream));
         }
         ra.lazy_q = lazy_q ? 1 : 0;
-        ra.level = launch_level(p, fast, weight);
+        ra.level = launch_level(p, fast, weight, k + 2 < T);
         ra.nt_id = p.nt_id;
         if (!fast) {
             ProfScope ps(b, LLPF_PROF_NORMALISE);
@@ -407,7 +407,7 @@ static int bank_run(Bank& b, const double* U, const double* Y, int64_t T, double
     const RunPlan plan = make_run_plan(facts);
     b.use_fx = plan.use_fx;
     b.last_run_launches = 0; b.last_run_fx_steps = plan.source_fx ? T : 0; b.last_run_surv = -1.0;
-    b.last_run_level = plan.level; b.last_run_redos = 0;
+    b.last_run_level = plan.level; b.last_run_skip_max = plan.skip_max; b.last_run_redos = 0;
 
     // 4. what the plan needs
     if (o.ll_steps) CHK(b.d_ll_steps.ensure((size_t)T * b.F));

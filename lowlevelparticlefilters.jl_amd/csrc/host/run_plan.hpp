@@ -19,6 +19,7 @@ struct RunSwitches {
     int lazy_q = -1, skip_w = -1, graph = -1;          // LLPF_LAZY_Q=0: the stored form; LLPF_SKIP_W=0: the storing form; LLPF_GRAPH=0: every run is enqueued
     int skip_anc = -1;                                 // LLPF_SKIP_ANC=0: a run without the weight store still stores every ancestor
     int lean = -1;                                     // LLPF_LEAN=0: such a run keeps the kernel that tests the strategy and the means at run time
+    int skip_max = -1;                                 // LLPF_SKIP_MAX=0: every level-3 launch of such a run leaves its running maximum, as the run's last one does
     int ablate = 0;                                    // LLPF_ABLATE (DEVTOOLS builds)
     bool debug_timing = false;                         // LLPF_DEBUG_TIMING=k: the fused launch of step k leaves its per-tile clock readings behind; no graphs
     int64_t debug_step = 0;
@@ -39,6 +40,7 @@ static inline RunSwitches read_run_switches() {
     s.skip_w = env_flag(getenv("LLPF_SKIP_W"));
     s.skip_anc = env_flag(getenv("LLPF_SKIP_ANC"));
     s.lean = env_flag(getenv("LLPF_LEAN"));
+    s.skip_max = env_flag(getenv("LLPF_SKIP_MAX"));
     s.graph = env_flag(graph_env);
     s.ablate = abl_env ? atoi(abl_env) : 0;
     s.debug_timing = dbg_env != nullptr;
@@ -72,7 +74,13 @@ enum RunLevel : int {
     RUN_SKIP_W = 1,           // no weights are stored
     RUN_SKIP_ANC = 2,         // ... and no ancestor but output M - 1's
     RUN_LEAN = 3,             // ... by the kernel for systematic resampling without weighted means
+    RUN_NO_MAX = 4,           // ... which leaves and reads no running maximum.  The level of single launches only (launch_level with a
+                              // plan): a plan's level is at most RUN_LEAN, and RunKey::skip_max says whether its launches may take this one
 };
+// LLPF_SKIP_MAX=0 (compile time): no launch is ever RUN_NO_MAX, and the kernel is not built (kernels/resprop.hpp)
+#ifndef LLPF_SKIP_MAX
+#define LLPF_SKIP_MAX 1
+#endif
 
 // Everything a captured launch sequence depends on besides its buffers, its length and the entry state: the key of a captured graph
 // holds one and compares it as a whole (Bank::RunGraph), so a switch added here is part of the key without further ado.  Plain ints
@@ -96,7 +104,14 @@ struct RunForm {
 };
 static_assert(std::has_unique_object_representations<RunForm>::value, "RunForm is compared bytewise: ints only, no padding");
 
-struct RunPlan : RunForm {
+// ... and what was decided since and is part of the key as well (RunForm keeps its seventeen ints).  Bank::RunGraph holds a RunKey.
+struct RunKey : RunForm {
+    int skip_max;             // the level-3 launches that another launch with a weighting phase follows are RUN_NO_MAX (launch_level)
+    using RunForm::operator==;      // (against a plain RunForm: the form alone)
+    bool operator==(const RunKey& o) const { return RunForm::operator==(o) && skip_max == o.skip_max; }
+};
+
+struct RunPlan : RunKey {
     bool use_graph;           // the asynchronous loop as a captured graph (replayed when its key is seen again)
     bool use_fx;              // Bank::use_fx after this run's look at surv_frac
 };
@@ -181,6 +196,10 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
     // shape keeps the level below.  LLPF_LEAN=0: the kernel with the run-time tests.
     const bool lean = skip_anc && f.strategy == LLPF_RESAMPLE_SYSTEMATIC && !p.want_xm && f.model_id == LLPF_MODEL_LINEAR_GAUSSIAN && f.nx <= 2 && s.lean != 0;
     p.level = lean ? RUN_LEAN : skip_anc ? RUN_SKIP_ANC : skip_w ? RUN_SKIP_W : RUN_STORES;
+    // ... and that the maximum a level-3 launch leaves is read by nobody when the launch behind it is a level-3 launch too: that head takes
+    // the bound for its offset, tests the integer sums and the NaN count, and publishes the maximum in two scalars that the head after it
+    // overwrites unread (DESIGN.md §4 goes through every reader).  Such launches are RUN_NO_MAX (launch_level below).  LLPF_SKIP_MAX=0: none is.
+    p.skip_max = (LLPF_SKIP_MAX && lean && s.skip_max != 0) ? 1 : 0;
     // The run ends in the buffer it began in (a handle's weights do not move between runs: one captured graph per shape, not two that
     // alternate): T - 1 steps have a weighting phase; when that number is odd, step 0 keeps the stored form and weights in place.
     p.k_pp0 = (p.lazy_run && ((f.T - 1) & 1)) ? 1 : 0;
@@ -194,6 +213,15 @@ static inline RunPlan make_run_plan(const RunFacts& f) {
 // storing form; the run's last launch (`weight` false: no weighting phase) forms no weights and leaves the ancestors the run ends with.
 static inline int launch_level(const RunForm& p, bool fast, bool weight) {
     return !fast ? RUN_STORES : !weight ? std::min<int>(p.level, RUN_SKIP_W) : p.level;
+}
+// ... with what the plan decided besides.  `next_weight`: the launch behind this one has a weighting phase as well (step k + 2 < T), so it
+// is a level-3 or level-4 launch whose head reads no maximum — unless that head's bound test fails, and then the exact redo forms the
+// weights again by the weighting launch (RunLoop::reweight_flagged), which leaves its own maximum in the slot.  The run's last weighting
+// launch keeps level 3: the general head of the run's last launch combines its maximum, and what that head publishes is what the run
+// leaves (k_post_predict resets it only when the step resampled).  The first launch behind an exact redo may be RUN_NO_MAX like any other.
+static inline int launch_level(const RunKey& p, bool fast, bool weight, bool next_weight) {
+    const int level = launch_level(static_cast<const RunForm&>(p), fast, weight);
+    return (level == RUN_LEAN && p.skip_max && next_weight) ? RUN_NO_MAX : level;
 }
 // The step of the systematic thresholds, 1 / M, as a level-3 launch gets it from the host (ResArgs::inv_M) instead of dividing in every
 // wave.  IEEE division is correctly rounded on the host and on the device, so this is the double the kernel's own 1.0 / (double)M is:

@@ -50,6 +50,9 @@ static hipError_t launch_resprop_t(const BankDev& b, const ResArgs& a, const Ste
             case RUN_STORES: hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); break;
             case RUN_SKIP_W: if constexpr (skips) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_SKIP_W>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
             case RUN_SKIP_ANC: if constexpr (skips) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_SKIP_ANC>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, a), b, b.models, a, st); else return hipErrorInvalidValue; break;
+            case RUN_NO_MAX:      // a launch's level only (host/run_plan.hpp: launch_level): level 3 that leaves and reads no running maximum
+                if (!LLPF_SKIP_MAX) return hipErrorInvalidValue;
+                [[fallthrough]];
             case RUN_LEAN:
                 if constexpr (lean) {
                     ResArgs al = a;
@@ -64,6 +67,10 @@ static hipError_t launch_resprop_t(const BankDev& b, const ResArgs& a, const Ste
                     // 33 fraction bits (N <= 2^29, which the 32-bit byte offsets of the planes ask for anyway)
                     if ((LLPF_LR_BITS & LLPF_LR_NOPAD) && (int64_t)a.M != b.N) return hipErrorInvalidValue;
                     if ((LLPF_LR_BITS & LLPF_LR_QFIX) && (st.K < 33 || st.K > 62)) return hipErrorInvalidValue;
+#if LLPF_SKIP_MAX
+                    if (a.level == RUN_NO_MAX) hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_NO_MAX>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, al), b, b.models, al, st);
+                    else
+#endif
                     hipLaunchKernelGGL((k_resprop<Model, NX, NY, true, true, false, false, RUN_LEAN>), g, dim3(BLOCK), 0, s, LLPF_HOT_ARGS(b, al), b, b.models, al, st);
                 } else return hipErrorInvalidValue;
                 break;

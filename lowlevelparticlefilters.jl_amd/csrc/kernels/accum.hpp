@@ -147,6 +147,45 @@ DEV void block_flush(uint64_t* acc, int slot, double bmax, bool bad, const Weigh
     }
 }
 
+#ifdef LLPF_DEVTOOLS
+// LLPF_ABLATE bit 7: the three limbs of a block's sum on 32 lines each instead of NSHARD — lines 24 .. 119 of the filter's 192, whatever the
+// slot, never cleared.  What more shards could save at most; the head takes the sums as they are (results invalid).
+DEV void ablated_acc_add_u128_wide(uint64_t* acc, llpf_u128 v) {
+    const uint64_t limb[3] = {v.lo & M43, ((v.lo >> 43) | (v.hi << 21)) & M43, v.hi >> 22};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (limb[k]) atomicAdd(reinterpret_cast<unsigned long long*>(acc + (size_t)(24 + 32 * k + (int)(blockIdx.x & 31u)) * ACC_STRIDE), (unsigned long long)limb[k]);
+}
+static_assert(24 + 32 * 3 <= ACC_NWORDS * NSHARD, "the lines of LLPF_ABLATE bit 7 lie inside one filter's accumulators");
+#endif
+
+// block_flush of a launch that leaves no running maximum (k_resprop<..., LEVEL = 4>: the head behind it does not read one, kernels/resample.hpp:
+// NOMAX): the exp-sums and the count of NaN exp-weights alone, in the same one barrier — no wave_max, no NaN flag of the weights, no
+// atomicMax.  A NaN weight still stops the run: its exp-weight is NaN too (llpf_exp_core), so it is counted in ACC_BAD, which is what the
+// next head's bound test reads.  The sums are the integers block_flush adds, to the same lines.
+// (`ablate`: LLPF_ABLATE of a DEVTOOLS build, bit 5 no atomics, bit 7 the sums on 32 lines; results invalid)
+DEV void block_flush_sums(uint64_t* acc, int slot, const WeightAcc& wa, uint64_t (*sm)[8], int ablate = 0) {
+    const llpf_u128 s = wave_sum_u128(wa.S);
+    const uint64_t bd = (uint64_t)__builtin_popcountll(__ballot(wa.bad != 0));
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { sm[wv][0] = s.lo; sm[wv][1] = s.hi; sm[wv][2] = bd; }
+    __syncthreads();
+    if (threadIdx.x == 0 && !(ablate & 32)) {
+        llpf_u128 ts = {sm[0][0], sm[0][1]};
+        uint64_t tb = sm[0][2];
+        for (int k = 1; k < BLOCK / 64; ++k) {
+            llpf_u128 a1 = {sm[k][0], sm[k][1]};
+            ts = llpf_u128_add(ts, a1);
+            tb += sm[k][2];
+        }
+#ifdef LLPF_DEVTOOLS
+        if (ablate & 128) { ablated_acc_add_u128_wide(acc, ts); return; }
+#endif
+        acc_add_u128(acc, ACC_S(slot), ts);
+        if (tb) atomicAdd(reinterpret_cast<unsigned long long*>(acc_slot(acc, ACC_BAD(slot), blockIdx.x & (NSHARD - 1))), (unsigned long long)tb);
+    }
+}
+
 // fixed-order fp64 block sum of the per-thread partial sums e_i x_i (weighted-mean output only; never fed back)
 template <int NX>
 DEV void block_store_xm(const double* xm, double* dst /* [MAXD] */, double (*smx)[MAXD]) {

@@ -146,7 +146,11 @@ struct NoOverlap { DEV void operator()() const {} };
 // `LEAN`: the head of a level-3 launch (k_resprop<..., LEVEL >= 3>) with what host/run_plan.hpp and host/run.hpp fix for it compiled in —
 // no weighted means, keep_norm = 0, force = 0, accumulate = 1; launch_resprop_t refuses such a launch with any other value.  What tile 0
 // publishes is what the general head publishes for these values.
-template <int SRC, bool COH = false, class Overlap = NoOverlap, bool NO_TOT0 = false, bool LEAN = false>
+// `NOMAX`: the head of a level-3 launch whose slot holds no running maximum (k_resprop<..., LEVEL = 4>; host/run_plan.hpp: launch_level):
+// the eight ACC_PM lines are not requested, and tile 0 publishes the quiet NaN 0x7ff8000000000000 in FilterScal::mtrue and ::wmax.
+// Nothing reads either before the next head overwrites them; a reader that was forgotten would meet a NaN, not a
+// plausible number.
+template <int SRC, bool COH = false, class Overlap = NoOverlap, bool NO_TOT0 = false, bool LEAN = false, bool NOMAX = false>
 DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResShared& sh,
                      bool defer_skip = false, uint32_t stop_flag = 0, int fb_flag = 0, Overlap&& overlap = NoOverlap()) {
     FilterScal* sc = b.scal + f;
@@ -166,7 +170,7 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
     // loads.  wave 0: lane group g (8 lanes = 8 shards) fetches word g of this slot's accumulator set
     uint64_t accv = 0;
     const int grp = threadIdx.x / NSHARD, shard = threadIdx.x % NSHARD;
-    if (fin && threadIdx.x < 64) accv = Mem<COH>::ld(acc_slot(acc, acc_word_of_group(grp, a.parity), shard));
+    if (fin && threadIdx.x < 64 && !(NOMAX && grp == 0)) accv = Mem<COH>::ld(acc_slot(acc, acc_word_of_group(grp, a.parity), shard));
     uint64_t pre = 0, all = 0;
     const bool want_tq = (a.mode & RES_RESAMPLE) && !unif0;
     const bool tq_small = b.P2 <= 4 * BLOCK;   // up to 1024 tiles: four INDEPENDENT loads per thread (a loop waits for every one in turn)
@@ -242,15 +246,16 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
     }
     if (fin) {
         h.fast = a.fast_head && !exact_pre;            // a one-tile filter may have redone its sums in exact form already
-        h.mtrue = max_unkey(sh.accw[0]);
+        if constexpr (NOMAX) h.mtrue = llpf_u2d(0x7ff8000000000000ULL);
+        else h.mtrue = max_unkey(sh.accw[0]);
         const llpf_u128 s128 = acc_combine_u128(sh.accw[1], sh.accw[2], sh.accw[3]);
         const llpf_u128 e128 = acc_combine_u128(sh.accw[4], sh.accw[5], sh.accw[6]);
         const bool bad = sh.accw[7] != 0;
         if (h.fast) {
             h.a = off_pre;                                        // published by the weighting kernel that filled this slot
             bool fails = bad || s128.hi < ((uint64_t)1 << 22) || (NO_TOT0 && h.tot == 0);      // sum exp(w - bound) < 2^-10, or NaN weights
-#ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 5: the tail in front of this head left the accumulator atomics out; the run goes on (results invalid) */
-            if (a.ablate & 32) fails = false;
+#ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 5: the tail in front of this head left the accumulator atomics out (bit 7: put its sums elsewhere); the run goes on (results invalid) */
+            if (a.ablate & (32 | 128)) fails = false;
 #endif
             if (fails) {
                 h.status = RES_STATUS_FALLBACK;
@@ -289,7 +294,8 @@ DEV ResHead res_head(const BankDev& b, const ResArgs& a, int f, int tile, ResSha
                 }
                 sc->m = h.a; sc->mtrue = h.mtrue; sc->s = h.s; sc->stot = h.stot; sc->l = l; sc->inv = inv; sc->ll = ll;
                 sc->ess = ess; sc->e2 = h.e2; sc->fast = h.fast; sc->e2_valid = e2v;
-                sc->wmax = (h.mtrue - h.a) - l;                   // normalised weight of the best particle
+                if constexpr (NOMAX) sc->wmax = h.mtrue;          // no maximum in the slot: the same NaN
+                else sc->wmax = (h.mtrue - h.a) - l;              // normalised weight of the best particle
                 sc->K = a.K;
                 sc->uniform = 0;
                 sc->norm_pending = (!LEAN && a.keep_norm) ? 0 : 1;

@@ -58,6 +58,12 @@ template <class T> DEV void st_off(T* base, uint32_t byte_off, T v) {
 #define LLPF_LEAN_ROUND_ITEMS (LLPF_LR_QFIX | LLPF_LR_BZ | LLPF_LR_NOPAD | LLPF_LR_POW2)
 #endif
 #define LLPF_LR_BITS (LLPF_LEAN_ROUND ? (LLPF_LEAN_ROUND_ITEMS) : 0)
+#define LLPF_LR_NOMAX  64      /* no NaN flag of the weights in the round (k_resprop<..., LEVEL = 4>: the launch leaves no running maximum); not one of LLPF_LEAN_ROUND's items, set by the level alone */
+// a level-3 launch that another one follows leaves no running maximum behind (LEVEL = 4; EXPERIMENTS: the tail's accumulators): LLPF_SKIP_MAX=0
+// compiles neither the kernel nor the plan's use of it (host/run_plan.hpp), and every launch is the code as it was
+#ifndef LLPF_SKIP_MAX
+#define LLPF_SKIP_MAX 1
+#endif
 #define LLPF_RB_PLAIN_ST (Model::RB && !(model_lean<Model>::value && LLPF_RBX_WT))
 // store policy of the output loop (Mem<>::st): 1 = write-through (sc1), 0 = plain, 2 = nontemporal
 #ifndef LLPF_RESPROP_ST
@@ -174,7 +180,7 @@ struct PropCtx {
                 wv = wv + gauss_logpdf_c<NY>((gauss_cptr)&md->dg, v);
             }
             if constexpr (!(LR & LLPF_LR_NOPAD)) { if (o >= (uint32_t)b.N) wv = -LLPF_INF; }
-            bad = bad || (wv != wv);
+            if constexpr (!(LR & LLPF_LR_NOMAX)) bad = bad || (wv != wv);
 #ifdef LLPF_DEVTOOLS
             if (!(ablate & 8))
 #endif
@@ -262,13 +268,21 @@ static_assert(TILE == 1024, "TileSum assumes 1024-particle tiles");
 // Its head and scan hold the argument values of such a launch as constants (res_head / res_counts<..., LEAN>; launch_resprop_t refuses a
 // level-3 launch with others), and its tail is block_flush's one barrier: all blocks of a 10^6-particle filter are resident together and
 // pass head, scan and tail in lockstep, so nothing hides a barrier or an argument test there.
+// NOMAX (LEVEL = 4, a launch's level only: the plan's stays 3, and launch_level gives 4 to the level-3 launches that another launch with
+// a weighting phase follows): the launch leaves no running maximum of its weights and reads none.  The head behind it is a level-3 or
+// level-4 head, whose offset is the bound and whose bound test reads the integer sums and the NaN count; the maximum such a head combines
+// goes only into FilterScal::mtrue and ::wmax, which the head after it overwrites unread (DESIGN.md §4 lists every reader).  So the rounds
+// keep no bmax and no NaN flag of the weights, the tail is block_flush_sums (no wave_max, no atomicMax), and the launch's own head requests
+// no ACC_PM line and publishes NaN in both fields (res_head<..., NOMAX>).  The run's last weighting launch stays level 3: the head behind
+// it is the general one of the run's last launch, and what that head publishes is what the run leaves.
 template <class Model, int NX, int NY, bool WEIGHT, bool ACC, bool AUX = false, bool ONE = false, int LEVEL = 0>
 // amdgpu_waves_per_eu(4): the ~3.8 blocks per CU of a 10^6-particle filter must be resident together (<= 128 VGPRs); the
 // larger state dimensions would spill under that cap and keep the compiler's choice; the Rao-Blackwellized propagate uses
 // 130-156 VGPRs and is pinned to three waves per SIMD (<= 168): twice in this round an unrelated change pushed it past 170 and
 // cost it 28 %
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model::RB || (model_lean<Model>::value && LLPF_RBX_W4)) && NX <= 2 && NY <= 2 && !ONE) ? 4 : (Model::RB ? 3 : 1)))) void k_resprop(LLPF_HOT_PARAMS, BankDev b_in, const ModelD* __restrict__ models, ResArgs a_in, StepArgs st) {
-    constexpr bool SKIPW = LEVEL >= 1, SKIPA = LEVEL >= 2, LEAN = LEVEL >= 3;
+    constexpr bool SKIPW = LEVEL >= 1, SKIPA = LEVEL >= 2, LEAN = LEVEL >= 3, NOMAX = LEVEL >= 4;
+    static_assert(!NOMAX || (LLPF_SKIP_MAX && LLPF_LEAN_TAIL && LLPF_LEAN_HEAD), "level 4 is level 3's head and tail without the maximum");
     // what the head's first loads are addressed with arrives in SGPRs with the wave (kernarg preload) instead of through a
     // scalar load of the argument block: one memory round trip less at the start of every launch
     BankDev b = b_in;
@@ -345,7 +359,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     constexpr bool ALWAYS_RES = SKIPW;
     static_assert(!ALWAYS_RES || (WEIGHT && ACC && !AUX), "a launch that always resamples: the merged schedule's weighting form, never forced");
     constexpr bool LEAN_HEAD = LEAN && LLPF_LEAN_HEAD, LEAN_TAIL = LEAN && LLPF_LEAN_TAIL;
-    const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW, LEAN_HEAD>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
+    const ResHead h = res_head<SRC_FILTER, false, decltype(prepare)&, SKIPW, LEAN_HEAD, NOMAX>(b, a, f, tile, sh, true, stop_flag, fb_flag, prepare);
     if (h.status) return;
     // Values of FilterScal fetched above with the head's loads but wanted only from here on.  FilterScal is written by this
     // kernel, so they are vector loads made uniform with v_readfirstlane — which the compiler otherwise places right behind the
@@ -362,7 +376,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(((!Model:
     }
     LLPF_STAMP(1);
     // the items of the level-3 round (every other form: 0, its code untouched)
-    constexpr int LR = (LEAN && WEIGHT && ACC && !RBFAT) ? LLPF_LR_BITS : 0;
+    constexpr int LR = ((LEAN && WEIGHT && ACC && !RBFAT) ? LLPF_LR_BITS : 0) | (NOMAX ? LLPF_LR_NOMAX : 0);
     // lean_acc_add forms no sum of squares and hands out no e: only where neither is wanted (LEAN: always resamples, no weighted means)
     constexpr int LR_ACC = LR & (LLPF_LR_QFIX | LLPF_LR_NANFLAG | LLPF_LR_CARRY);
     static_assert(LR == 0 || (LEAN && SKIPW), "the items of the lean round are level 3's");
@@ -530,7 +544,7 @@ _Pragma("unroll 1") \
         } \
         double xs[NX]; \
         const double wv = pc.template one<LLPF_RESPROP_ST, NTLX>(src, o, wprev, bad, xs); \
-        bmax = llpf_fmax(bmax, wv); \
+        if constexpr (!NOMAX) bmax = llpf_fmax(bmax, wv); \
         LLPF_OUTPUT_ACC(o, wv, xs) \
     }
 #ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 6, level 3 only (K >= 33 there: launch_resprop_t): one shift for the quantum and no NaN count (what items 1 and 2 of the lean round can save at most; results invalid) */
@@ -665,8 +679,10 @@ _Pragma("unroll") \
     LLPF_STAMP(3);
 #ifdef LLPF_DEVTOOLS   /* LLPF_ABLATE bit 5: the tail without its accumulator atomics (acc_max, acc_add_u128): what they cost at most; results invalid */
 #define LLPF_NO_TAIL_ATOMICS ((a.ablate & 32) != 0)
+#define LLPF_TAIL_ABLATE a.ablate      /* level 4: bit 5 the same, bit 7 its sums on 32 lines (block_flush_sums) */
 #else
 #define LLPF_NO_TAIL_ATOMICS false
+#define LLPF_TAIL_ABLATE 0
 #endif
     if constexpr ((LR & LLPF_LR_NANFLAG) != 0) wacc.bad = wnan ? 1u : 0u;
     if constexpr (LEAN_TAIL) {
@@ -674,7 +690,8 @@ _Pragma("unroll") \
         // one LDS row; the threads' tile sums went to sh_tq in front of it (ts.flush above); behind the barrier thread 0 combines the rows and
         // issues the accumulator atomics while threads 0..7 add sh_tq to the global tile sums.  A block that owns no outputs (first == last:
         // a tile behind a very heavy one) contributes the maximum -Inf, no NaN flag and no sum, as in the levels below.
-        block_flush(b.acc + (size_t)f * ACC_WORDS, st.parity, bmax, bad, wacc, true, false, sm_fl, LLPF_NO_TAIL_ATOMICS);
+        if constexpr (NOMAX) block_flush_sums(b.acc + (size_t)f * ACC_WORDS, st.parity, wacc, sm_fl, LLPF_TAIL_ABLATE);
+        else block_flush(b.acc + (size_t)f * ACC_WORDS, st.parity, bmax, bad, wacc, true, false, sm_fl, LLPF_NO_TAIL_ATOMICS);
         if (threadIdx.x < 8 && sh_tq[threadIdx.x])
             atomicAdd(reinterpret_cast<unsigned long long*>(tq_next + tbase + threadIdx.x), (unsigned long long)sh_tq[threadIdx.x]);
         if (tile == 0 && threadIdx.x == 0) {
@@ -751,6 +768,7 @@ _Pragma("unroll") \
     LLPF_STAMP(4);
 #undef LLPF_STAMP
 #undef LLPF_NO_TAIL_ATOMICS
+#undef LLPF_TAIL_ABLATE
 #undef LLPF_NEED_E2
 #undef LLPF_WANT_XM
     if (tile == b.P2 - 1 && threadIdx.x == 0) {        // bookkeeping of this predict! (by the only block that reads anc_ident)
