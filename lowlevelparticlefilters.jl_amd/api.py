@@ -1550,19 +1550,29 @@ def metropolis(ll, R, theta0, draw=None, rng=None):
     return params, np.array(lls)
 
 
-def _spec_builds(spec_from_parameters, theta):
-    """does this candidate give a model the library accepts? (densities positive definite, dimensions as declared)"""
+def _build_spec(spec_from_parameters, theta, Ts):
+    """the llpf_model of a candidate; ValueError / TypeError / LinAlgError if the library would not accept it (densities positive definite,
+    dimensions as declared).  A model's own densities (UserNoise, UserInitial) carry no covariance: the Gaussian that stands in for them
+    in the descriptor is checked where one was given (UserNoise.gaussian)."""
+    dy, me, df, dg, d0 = spec_from_parameters(theta)
+    model = _build_model(dy, me, df, dg, d0, Ts)
+    for d in (df.gaussian if isinstance(df, UserNoise) else df, dg, None if isinstance(d0, UserInitial) else d0):
+        if d is None:
+            continue
+        c = np.asarray(d.cov, dtype=np.float64)      # what the library's gauss_prepare (csrc/host/densities.hpp:23) asks of a covariance
+        if not np.all(np.isfinite(c)) or not np.all(np.diag(c) > 0.0):
+            raise ValueError("covariance not finite or not positive")
+        np.linalg.cholesky(c)
+    return model
+
+
+def _spec_builds(spec_from_parameters, theta, Ts=1.0):
+    """the model of this candidate, or None if it is one the library would refuse.  Only what a bad PARAMETER VALUE raises is caught: an error
+    of the caller's spec_from_parameters itself (AttributeError, KeyError, ...) is a bug to be seen, not a rejected proposal."""
     try:
-        dy, me, df, dg, d0 = spec_from_parameters(theta)
-        _build_model(dy, me, df, dg, d0, 1.0)
-        for d in (df, dg, d0):                       # what the library's gauss_prepare (csrc/host/densities.hpp:23) asks of a covariance
-            c = np.asarray(d.cov, dtype=np.float64)
-            if not np.all(np.isfinite(c)) or not np.all(np.diag(c) > 0.0):
-                return False
-            np.linalg.cholesky(c)
-        return True
-    except Exception:
-        return False
+        return _build_spec(spec_from_parameters, theta, Ts)
+    except (ValueError, TypeError, np.linalg.LinAlgError):
+        return None
 
 
 def metropolis_bank(bank, spec_from_parameters, priors, u, y, R, theta0s, draw=None, burnin=0, rng=None):
@@ -1580,7 +1590,7 @@ def metropolis_bank(bank, spec_from_parameters, priors, u, y, R, theta0s, draw=N
 
     import re
 
-    def lls_of(thetas):
+    def lls_of(thetas, prebuilt=None):
         lp = np.array([sum(np.float64(priors[i].logpdf(th[i])) for i in range(th.size)) for th in thetas])
         ok = np.isfinite(lp)
         # Chains whose candidate lies outside the priors' support keep a valid model in their slot; its likelihood is not used.  A chain
@@ -1591,13 +1601,18 @@ def metropolis_bank(bank, spec_from_parameters, priors, u, y, R, theta0s, draw=N
         # rerun is a filter that degenerates on the device or a density that only the library refuses (a variance that underflowed to
         # zero passes the host's shape checks); the library names the first such filter.  An error that names no filter (bad shapes of
         # u / y, a lost device) is nobody's candidate and propagates at once.
+        built = list(cur_models)
         for k in range(n):
-            if ok[k] and not _spec_builds(spec_from_parameters, thetas[k]):
-                ok[k] = False
+            if ok[k]:
+                m = prebuilt[k] if prebuilt is not None else _spec_builds(spec_from_parameters, thetas[k], bank.Ts)
+                if m is None:
+                    ok[k] = False
+                else:
+                    built[k] = m
         ll = None
         for _ in range(n + 1):
             try:
-                bank.set_parameters([spec_from_parameters(thetas[k] if ok[k] else cur[k]) for k in range(n)])
+                bank.set_models([built[k] if ok[k] else cur_models[k] for k in range(n)])      # the models built above, not built again
                 ll = bank.loglik(u, y)
                 break
             except _capi.LLPFError as e:                 # DegenerateWeights is one
@@ -1609,17 +1624,26 @@ def metropolis_bank(bank, spec_from_parameters, priors, u, y, R, theta0s, draw=N
         if ll is None:
             raise RuntimeError("metropolis_bank: the bank fails with every chain on its current parameters")
         out = np.where(ok, lp + ll, -np.inf)
-        return np.where(np.isnan(out), -np.inf, out)
+        return np.where(np.isnan(out), -np.inf, out), built
 
+    # The starting parameters have nothing to fall back on: one that cannot be built is an error of the call (and says why), not a chain
+    # that scores -inf for ever.
     cur = theta0s.copy()
-    ll_cur = lls_of(cur)
+    cur_models = []
+    for k in range(n):
+        try:
+            cur_models.append(_build_spec(spec_from_parameters, cur[k], bank.Ts))
+        except (ValueError, TypeError, np.linalg.LinAlgError) as e:
+            raise ValueError("metropolis_bank: the starting parameters of chain %d cannot be built: %s" % (k, e)) from e
+    ll_cur, _ = lls_of(cur, cur_models)
     chain = np.empty((int(R), n, theta0s.shape[1] + 1))
     chain[0, :, :-1], chain[0, :, -1] = cur, ll_cur
     for i in range(1, int(R)):
         cand = np.stack([np.asarray(draw(cur[k]), dtype=np.float64) for k in range(n)])
-        ll_c = lls_of(cand)
+        ll_c, built = lls_of(cand)
         acc = rng.random(n) < np.exp(ll_c - ll_cur)
         cur = np.where(acc[:, None], cand, cur)
+        cur_models = [built[k] if acc[k] else cur_models[k] for k in range(n)]
         ll_cur = np.where(acc, ll_c, ll_cur)
         chain[i, :, :-1], chain[i, :, -1] = cur, ll_cur
     return np.concatenate([chain[int(burnin):, k, :] for k in range(n)], axis=0)
@@ -1997,8 +2021,13 @@ class FilterBank:
 
     def set_parameters(self, filters_spec):
         """new (dynamics, measurement, df, dg, d0) for every filter of the bank, nothing reallocated (llpf_bank_set_models)"""
-        self._models = [_build_model(dy, me, df, dg, d0, self.Ts) for (dy, me, df, dg, d0) in filters_spec]
-        self._h.set_models(self._models)
+        self.set_models([_build_model(dy, me, df, dg, d0, self.Ts) for (dy, me, df, dg, d0) in filters_spec])
+
+    def set_models(self, models):
+        """the same with llpf_model structs already built (metropolis_bank checks every candidate by building it, and hands that model on)"""
+        models = list(models)
+        self._h.set_models(models)
+        self._models = models
 
     def loglik(self, u, y):
         """[loglik(pf_k, u, y) for k] — reference src/smoothing.jl:227-230 applied to every filter."""

@@ -69,6 +69,90 @@ def test_log_likelihood_fun_host_logic(monkeypatch):
     assert np.isfinite(ll1([0.5, 2.0]))
 
 
+class _StubBank:
+    """what metropolis_bank asks of a FilterBank, without a device: the log-likelihood is a function of the models it was last given"""
+    Ts = 1.0
+
+    def __init__(self, n):
+        self.n_filters, self.models, self.runs = n, None, 0
+
+    def set_models(self, models):
+        self.models = list(models)
+
+    def set_parameters(self, filters_spec):
+        self.set_models([api._build_model(dy, me, df, dg, d0, self.Ts) for (dy, me, df, dg, d0) in filters_spec])
+
+    def loglik(self, u, y):
+        self.runs += 1
+        return np.array([-0.5 * (np.log(m["dg"]) - 1.0) ** 2 / 0.09 for m in self.models])
+
+
+def _stub_build(monkeypatch):
+    """_build_model replaced by a record of what it was handed (the real one compiles the snippet of a UserDynamics for the device)"""
+    built = []
+
+    def fake(dy, me, df, dg, d0, Ts, user_likelihood=False):
+        built.append({"df": df, "dg": float(dg.cov[0, 0]), "d0": d0})
+        return built[-1]
+    monkeypatch.setattr(api, "_build_model", fake)
+    return built
+
+
+def test_metropolis_bank_host_logic(monkeypatch):
+    """A model with densities of its own (UserNoise, UserInitial: no covariance to check) scores finite values and its chains move; every
+    candidate is built once and that model is what the bank is given; an error of spec_from_parameters itself is not a rejected proposal; and
+    starting parameters that cannot be built are an error of the call, not chains at -inf for ever.  (Before: the covariance check read
+    `.cov` on UserNoise, `except Exception` swallowed the AttributeError, every chain scored -inf — the starting parameters included —
+    and nothing moved or was raised.)"""
+    built = _stub_build(monkeypatch)
+    n, R = 3, 40
+    dyn, meas = object(), llpf_amd.UserMeasurement()
+    spec = lambda th: (dyn, meas, llpf_amd.UserNoise(), llpf_amd.MvNormal(np.zeros(1), float(np.exp(2 * th[0]))), llpf_amd.UserInitial())
+    priors = [_Normal(0.0, 10.0)]
+    th0 = np.array([[0.0], [0.3], [0.8]])
+    rng = np.random.default_rng(5)
+    bank = _StubBank(n)
+    out = llpf_amd.metropolis_bank(bank, spec, priors, None, None, R, th0, draw=lambda th: th + 0.2 * rng.standard_normal(1), rng=rng)
+    assert out.shape == (R * n, 2) and np.all(np.isfinite(out))
+    ch = out.reshape(n, R, 2)
+    assert np.array_equal(ch[:, 0, 0], th0[:, 0])
+    for k in range(n):
+        assert len(np.unique(ch[k, :, 0])) > 5, "chain %d did not move" % k
+    assert len(built) == n * R and bank.runs == R                  # one build per candidate, one bank run per iteration
+    assert all(any(m is b for b in built) for m in bank.models)    # ... and the bank is given those models, not rebuilt ones
+    # a Gaussian given with the model's own noise IS checked; such a candidate is rejected alone
+    bad_from = {"i": 0}
+
+    def spec_g(th):
+        bad_from["i"] += 1
+        cov = -1.0 if bad_from["i"] > n and bad_from["i"] % n == 2 else 0.04          # chain 1's proposals, never its starting parameters
+        return (dyn, meas, llpf_amd.UserNoise(llpf_amd.MvNormal(np.zeros(2), cov)), llpf_amd.MvNormal(np.zeros(1), float(np.exp(2 * th[0]))), llpf_amd.UserInitial())
+    out = llpf_amd.metropolis_bank(_StubBank(n), spec_g, priors, None, None, 10, th0, draw=lambda th: th + 0.2 * rng.standard_normal(1), rng=rng)
+    ch = out.reshape(n, 10, 2)
+    assert np.all(np.isfinite(out)) and np.all(ch[1, :, 0] == th0[1, 0]) and len(np.unique(ch[0, :, 0])) > 1
+    # an AttributeError of the caller's function propagates
+    def broken(th):
+        return (dyn, meas, llpf_amd.UserNoise().no_such_field, None, None)
+    with pytest.raises(AttributeError):
+        llpf_amd.metropolis_bank(_StubBank(n), broken, priors, None, None, 5, th0, draw=lambda th: th + 0.1, rng=rng)
+    # so does one that shows only in a proposal
+    calls = {"i": 0}
+
+    def breaks_later(th):
+        calls["i"] += 1
+        if calls["i"] > n:
+            raise AttributeError("a bug in spec_from_parameters")
+        return spec(th)
+    with pytest.raises(AttributeError):
+        llpf_amd.metropolis_bank(_StubBank(n), breaks_later, priors, None, None, 5, th0, draw=lambda th: th + 0.1, rng=rng)
+    # starting parameters that cannot be built (a negative variance in chain 2)
+    spec_neg = lambda th: (dyn, meas, llpf_amd.UserNoise(), llpf_amd.MvNormal(np.zeros(1), float(th[0])), llpf_amd.UserInitial())
+    stub = _StubBank(n)
+    with pytest.raises(ValueError, match="chain 2"):
+        llpf_amd.metropolis_bank(stub, spec_neg, priors, None, None, 5, np.array([[1.0], [0.5], [-0.5]]), draw=lambda th: th + 0.1, rng=rng)
+    assert stub.runs == 0
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _run_bits(h, U, Y):
     h.seed(77); h.reset()
@@ -230,3 +314,32 @@ def test_metropolis_bank_isolates_a_failing_chain():
     ch = out.reshape(n_chains, 6, 3)
     assert np.all(np.abs(ch[1, :, 1]) < 10) and np.all(np.abs(ch[2, :, 1]) < 10)      # chains 1 and 2 never accepted the wild values
     assert len({tuple(r) for r in ch[0, :, :2]}) > 1                                   # and the healthy chains kept moving
+
+
+@pytest.mark.gpu
+def test_metropolis_bank_on_a_model_with_densities_of_its_own():
+    """the chains of a UserDynamics snippet with UserNoise and UserInitial (user_models.MULT_NOISE_BOX_SRC): theta = log of the additive part
+    of the process noise and log standard deviation of the measurement noise.  Every chain used to score -inf from the start (see
+    test_metropolis_bank_host_logic); now every retained log-likelihood is finite and the chains move."""
+    import user_models as UM
+    lg = M.lg_test_model(0.1)
+    nx, nu, ny = lg.nx, lg.nu, lg.ny
+    A, B, Cm = (np.array(v[:r * c]).reshape(r, c) for v, r, c in ((lg.A, nx, nx), (lg.B, nx, nu), (lg.C, ny, nx)))
+    _, u, y = M.simulate_lg(lg, 40, seed=3)
+    meas = llpf_amd.UserMeasurement()
+
+    def spec(th):
+        dyn = llpf_amd.UserDynamics(UM.MULT_NOISE_BOX_SRC, nx, nu, ny, A=A, B=B, C=Cm, qt=[float(np.exp(th[0])), 0.05, -2.0, -2.0, 2.0, 2.0])
+        return (dyn, meas, llpf_amd.UserNoise(), llpf_amd.MvNormal(np.zeros(1), float(np.exp(2 * th[1]))), llpf_amd.UserInitial())
+    priors = [_Normal(np.log(0.1), 1.0), _Normal(0.0, 1.0)]
+    n_chains, R = 4, 20
+    rng = np.random.default_rng(4)
+    th0 = np.log([0.3, 0.5]) + 0.1 * rng.standard_normal((n_chains, 2))
+    bank = llpf_amd.FilterBank(1000, [spec(t) for t in th0], resample_threshold=0.1, rng=1)
+    out = llpf_amd.metropolis_bank(bank, spec, priors, u, y, R, th0, draw=lambda th: th + 0.15 * rng.standard_normal(2), rng=rng)
+    assert out.shape == (R * n_chains, 3) and np.all(np.isfinite(out))
+    ch = out.reshape(n_chains, R, 3)
+    assert np.array_equal(ch[:, 0, :2], th0)
+    moved = [len({tuple(r) for r in ch[k, :, :2]}) for k in range(n_chains)]
+    print("distinct parameter values per chain:", moved)
+    assert max(moved) > 1, moved                     # before the fix every chain stayed on its starting parameters, at -inf
